@@ -1,7 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- CHOMP iterations/sec on MI355X for the BASELINE.json workloads.
 
-  python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+  python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps of the headline workload and prints the result line.  Everything
+else moves behind `--full`: the strictly serial leg (`value_serial`), the parity spot check against the oracle (and
+its non-zero exit code), the CPU baseline, the N > 1 gather timing, the other configurations, the batch sweep, the
+stage breakdown and the full record (`--full-out`).  `--dump-outputs DIR` writes what the last timed step computed
+(trajectories, costs, status and iterations made, float64 .npy) after the timed steps; the inputs are seeded, so two
+builds can be compared output for output.
 
 With N > 1 and no WORLD_SIZE in the environment the command starts its own N ranks (`python -m
 torch.distributed.run`, a child process created before anything here touches the GPU) and exits with
@@ -16,8 +23,8 @@ iteration, final cost pass included).  The workload:
                     N, no data-path collective); the trajectories of step 0 are gathered on the host
                     of rank 0 afterwards and that time is reported separately (`gather`)
   --config 4 / 5    the other two single-GPU configurations as bench lines of their own; the default
-                    run (N = 1, config 2) appends both as `other_configs` (5 steps each, with their own
-                    `roofline`, counter traffic and `cpu_baseline`) so that they sit under the same clock
+                    run with --full (N = 1, config 2) appends both as `other_configs` (16 steps each, with their
+                    own `roofline`, counter traffic and `cpu_baseline`) so that they sit under the same clock
 
 Every step works on its own freshly created batch (created before the timed region; the
 trajectories are resident in HBM when it starts).  `value` = iterations the runs actually made
@@ -25,14 +32,14 @@ trajectories are resident in HBM when it starts).  `value` = iterations the runs
 as the reference throws) / wall time of the K steps, which are issued round-robin on `--streams`
 HIP streams (default 2: two launches overlap, so that the tail of one -- a few slow runs -- is filled by
 the next; more streams give the same throughput and longer launches) .
-`value_serial` is the same workload with strictly serial launches on one stream.
+`value_serial` (--full) is the same workload with strictly serial launches on one stream.
 
 `roofline`: the contract's yardstick -- ALGORITHMIC bytes of SURVEY.md 8(d) per launch / the fused
 kernel's average duration (HIP events on the launch stream) against the 8 TB/s HBM peak -- plus what
 the counters say actually binds the kernel (`bound`, `valu_issue`, from profiles/counters_latest.json).
-`cpu_baseline` times the oracle (oracle/, a CPU restatement of the reference) on the host cores over
-a bounded sample of the same workload.  The process exits non-zero when the parity spot check
-against the oracle exceeds its bound.
+`cpu_baseline` (--full) times the oracle (oracle/, a CPU restatement of the reference) on the host cores
+over a bounded sample of the same workload.  With --full the process exits non-zero when the parity spot
+check against the oracle exceeds its bound.
 """
 import argparse
 import json
@@ -341,8 +348,35 @@ def launch_ranks(args, argv):
     sys.exit(subprocess.call(cmd, env=env))
 
 
-def run_workload(config, args, rank, world, device, dist, steps, warmup, serial_steps, batch=0, want_gather=True, want_cpu=True):
-    """one bench line: K steps of one BASELINE configuration on this rank's GPU; returns (line or None, exit code)"""
+DUMP_LIMIT_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, mod, leg, rank, world):
+    """--dump-outputs: what a caller of the timed path receives from its LAST step (batch_sync's costs and status,
+    batch_iterations_done, batch_gettraj) as float64 DIR/<name>.npy; N > 1: every rank its own block as rank<r>_<name>.npy.
+    Beyond 64 MB in all, a fixed seeded sample of the runs (their indices in runs.npy)."""
+    costs, status = leg["results"][-1]
+    arrays = {"trajectories": mod.batch_gettraj(leg["ids"][-1]), "costs": costs, "status": status,
+              "iterations": leg["iters"][-1]}
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n_runs = len(status)
+    budget = DUMP_LIMIT_BYTES // world - 4096                      # (less the .npy headers)
+    per_run = sum(a.nbytes for a in arrays.values()) // n_runs
+    if per_run * n_runs > budget:
+        keep = budget // (per_run + 8)
+        runs = np.sort(np.random.default_rng(20250601).choice(n_runs, keep, replace=False))
+        arrays = {k: v[runs] for k, v in arrays.items()}
+        arrays["runs"] = runs.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    prefix = "" if world == 1 else "rank%d_" % rank
+    for k, v in arrays.items():
+        np.save(os.path.join(path, prefix + k + ".npy"), v)
+
+
+def run_workload(config, args, rank, world, device, dist, steps, warmup, serial_steps, batch=0, want_gather=True, want_cpu=True,
+                 dump=None):
+    """one bench line: K steps of one BASELINE configuration on this rank's GPU; returns (line or None, exit code).
+    The parity spot check and the CPU baseline are made with --full only; `dump`: the directory of --dump-outputs."""
     import torch
     import or_cdchomp_amd
     from or_cdchomp_amd import sharding
@@ -405,6 +439,8 @@ def run_workload(config, args, rank, world, device, dist, steps, warmup, serial_
     main_leg = timed_leg(steps, warmup, args.streams)
     timed = main_leg["ids"]
     elapsed = main_leg["elapsed"]
+    if dump:
+        dump_outputs(dump, mod, main_leg, rank, world)
 
     # iterations actually made, all ranks (host-side gather, gloo; no RCCL data path)
     local = {"status": np.concatenate([st for _, st in main_leg["results"]]),
@@ -417,7 +453,7 @@ def run_workload(config, args, rank, world, device, dist, steps, warmup, serial_
 
     # ---- N > 1: the host-side gather of the trajectories of step 0, timed on its own -----
     gather = None
-    if world > 1 and want_gather:
+    if world > 1 and want_gather and (args.full or args.dump_gather):
         barrier()
         g0 = time.perf_counter()
         traj_local = mod.batch_gettraj(timed[0])                         # device -> host of this rank
@@ -441,7 +477,7 @@ def run_workload(config, args, rank, world, device, dist, steps, warmup, serial_
     cpu = None
     parity_bound = 1e-3 if wl.precision == 32 else 1e-6
     rc = 0
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import oracle_py as O
         O.build(ref=False)
         wl.oracle_setup(O)
@@ -731,7 +767,13 @@ def main():
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams the steps are issued on round-robin: consecutive steps are independent batches, "
                          "so the tail of one launch (a few slow runs) is filled by the next; 1 = strictly serial launches")
-    ap.add_argument("--serial-steps", type=int, default=-1, help="steps of the strictly serial leg (value_serial); default min(steps, 10)")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline: the serial leg, the parity spot check, the CPU baseline, the N > 1 gather timing, "
+                         "the other configurations, the batch sweep, the stage breakdown and the full record")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--serial-steps", type=int, default=-1, help="steps of the strictly serial leg (value_serial); "
+                                                                 "default min(steps, 10) with --full, else 0")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-runs", type=int, default=0, help="override the cpu baseline sample size")
     ap.add_argument("--backend", default="gloo", help="torch.distributed backend for N>1.  The path has no data-path collective "
@@ -742,14 +784,15 @@ def main():
     ap.add_argument("--workgroup-threads", type=int, default=-1, help="workgroup shape of the batches (orc_set_workgroup_threads): 0, 128, 192, 256 or 512; "
                                                                       "default: the leg's own choice")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run only (N = 1, config 2): do not append the config 4 and config 5 lines")
+                    help="default run with --full only (N = 1, config 2): do not append the config 4 and config 5 lines")
     ap.add_argument("--other-steps", type=int, default=16, help="steps of each `other_configs` line (even: the steps alternate between two streams; "
                                                                "the first and the last step of a stream overlap with nothing: 16 steps are within 2 %% of 40)")
-    ap.add_argument("--no-sweep", action="store_true", help="default run only: do not append `batch_sweep`, `tsr1`, `tsr3` and `stages`")
+    ap.add_argument("--no-sweep", action="store_true", help="default run with --full only: do not append `batch_sweep`, `tsr1`, `tsr3` and `stages`")
     ap.add_argument("--sweep-batches", default="1,64,4096,8192,16384,65536", help="batch sizes of `batch_sweep` (8192 = one block of config 3: "
                                                                                   "the N = 1 point of the multi-GPU curve, like for like)")
-    ap.add_argument("--full-out", default=os.path.join(ROOT, "bench_full.json"),
-                    help="rank 0 writes the FULL record here (every line, sweep, stages, notes); stdout's last line is the compact one")
+    ap.add_argument("--full-out", default="",
+                    help="rank 0 writes the FULL record here (every line, sweep, stages, notes; default with --full: bench_full.json "
+                         "beside bench.py); stdout's last line is the compact one")
     ap.add_argument("--print-full", action="store_true", help="also print the full record as an EARLIER stdout line")
     ap.add_argument("--dump-gather", default="", help="N > 1: rank 0 saves the gathered step-0 trajectories here (.npy)")
     args = ap.parse_args()
@@ -783,9 +826,10 @@ def main():
         else:
             dist.init_process_group(backend=args.backend)
 
-    serial_steps = args.serial_steps if args.serial_steps >= 0 else min(args.steps, 10)
-    out, rc = run_workload(config, args, rank, world, device, dist, args.steps, args.warmup, serial_steps, batch=args.batch)
-    if world == 1 and not args.config and not args.batch and not args.no_other_configs:
+    serial_steps = args.serial_steps if args.serial_steps >= 0 else (min(args.steps, 10) if args.full else 0)
+    out, rc = run_workload(config, args, rank, world, device, dist, args.steps, args.warmup, serial_steps, batch=args.batch,
+                           dump=args.dump_outputs or None)
+    if args.full and world == 1 and not args.config and not args.batch and not args.no_other_configs:
         # the other two single-GPU configurations under the same clock (a few steps each)
         others = []
         for c in (4, 5):
@@ -826,7 +870,7 @@ def main():
             summ["sweep"] = {str(e["batch"]): r3(e["value"] / 1e6) for e in out["batch_sweep"]["sweep"]}
         out["summary"] = summ
     if rank == 0:
-        full_path = args.full_out or None
+        full_path = args.full_out or (os.path.join(ROOT, "bench_full.json") if args.full else None)
         if full_path:
             try:
                 with open(full_path, "w") as f:

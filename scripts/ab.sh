@@ -8,7 +8,7 @@ TAG=${3:-ab}
 OUT=$ROOT/gpurun_out/ab_$TAG.txt
 : > $OUT
 for c in $2; do
-  case $c in 2) ARGS="--steps 20 --warmup 2 --serial-steps 6";; 4) ARGS="--steps 6 --warmup 1 --serial-steps 3";; 5) ARGS="--steps 4 --warmup 1 --serial-steps 2";; *) ARGS="";; esac
+  case $c in 2) ARGS="--full --steps 20 --warmup 2 --serial-steps 6";; 4) ARGS="--full --steps 6 --warmup 1 --serial-steps 3";; 5) ARGS="--full --steps 4 --warmup 1 --serial-steps 2";; *) ARGS="--full";; esac
   for v in $1; do
     if [ $v = product ]; then unset ORC_LIB; else export ORC_LIB=$ROOT/or_cdchomp_amd/liborcdchomp_var_$v.so; fi
     python3 bench.py --config $c --no-cpu-baseline --no-other-configs $ARGS $AB_EXTRA > $ROOT/gpurun_out/ab_${TAG}_${v}_c$c.log 2>&1

@@ -15,7 +15,7 @@ for a in "$@"; do
   case $a in
     tests)   mode=""; timeout -k 10 900 python -m pytest tests -m gpu -q > $OUT/tests.txt 2>&1; rc=$?; tail -n 3 $OUT/tests.txt; [ $rc = 0 ] || exit $rc;;
     smoke)   mode=""; timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.txt 2>&1; rc=$?; tail -n 1 $OUT/smoke.txt | cut -c1-300; [ $rc = 0 ] || exit $rc;;
-    bench)   mode=""; timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default.json 2> $OUT/bench_default.err; rc=$?
+    bench)   mode=""; timeout -k 10 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench_default.json 2> $OUT/bench_default.err; rc=$?
              tail -c 1200 $OUT/bench_default.json; echo; cp -f bench_full.json $OUT/bench_full.json 2>/dev/null; [ $rc = 0 ] || exit $rc;;
     toggles) mode=""; timeout -k 10 1100 bash scripts/test_toggles.sh > $OUT/test_toggles.txt 2>&1; rc=$?; grep -c passed $OUT/test_toggles.txt; grep -c failed $OUT/test_toggles.txt; [ $rc = 0 ] || exit $rc;;
     wide)    mode=""; ORC_RANDOM_ROBOTS=${WIDE:-2000} timeout -k 10 1100 python -m pytest tests/test_gpu_random_robots.py -q > $OUT/random_robots_wide.txt 2>&1; rc=$?

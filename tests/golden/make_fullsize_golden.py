@@ -1,4 +1,5 @@
-"""Writes tests/golden/fullsize_config{3,4,5}.npz: oracle outputs for a fixed sample of the runs of
+"""Writes tests/golden/fullsize_config{3,4,5}.npz (and fullsize_config5_traj_b.npz, the second half of config 5's
+trajectories, so that no file exceeds 1 MiB): oracle outputs for a fixed sample of the runs of
 the BASELINE.json configurations at their FULL size, so that the -m gpu tests can hold
 the HIP path to the oracle at full size without a long oracle run on the GPU box.
 
@@ -49,7 +50,7 @@ def run_wam(goals, kw, basegoals=None, seeds=None):
     return out
 
 
-def pack(name, idx, res, extra=None):
+def pack(name, idx, res, extra=None, split_traj=False):
     (traj, costs, status, _), (ptraj, _, pstatus, _), (mtraj, _, mstatus, _) = res
     amp = np.array([max(common.rel_l2(ptraj[k], traj[k]), common.rel_l2(mtraj[k], traj[k])) for k in range(len(idx))])
     d = dict(index=idx, traj=traj, costs=costs, status=status, self_amp=amp, status_goal_plus_one_ulp=pstatus,
@@ -57,6 +58,11 @@ def pack(name, idx, res, extra=None):
     if extra:
         d.update(extra)
     path = os.path.join(HERE, name)
+    if split_traj:
+        # the second half of the trajectories goes to <name>_traj_b.npz: each committed file stays under 1 MiB
+        h = len(traj) // 2
+        d["traj"] = traj[:h]
+        np.savez_compressed(path.replace(".npz", "_traj_b.npz"), traj=traj[h:])
     np.savez_compressed(path, **d)
     print("%s: %d runs, status %s, self_amp max %.2e, %d bytes" % (name, len(idx), np.unique(status).tolist(), amp.max(),
                                                                   os.path.getsize(path)))
@@ -92,7 +98,7 @@ def main():
         # a checksum of the oracle's field: sum and sum of squares of the finite cells in a fixed order
         f = grids[k].data.ravel()
         extra["sdf_checksum_%d" % k] = np.array([f.sum(), np.square(f).sum(), f.min(), f.max()])
-    pack("fullsize_config5.npz", idx, res, extra)
+    pack("fullsize_config5.npz", idx, res, extra, split_traj=True)
 
 
 if __name__ == "__main__":

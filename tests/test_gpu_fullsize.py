@@ -186,7 +186,10 @@ def test_config4_floating_base_momentum_hmc_4096():
 
 
 def test_config5_tree30_four_fields_fp32_4096(oracle):
-    gold = np.load(os.path.join(GOLDEN, "fullsize_config5.npz"))
+    # (the sample's trajectories are split over two files: each committed file stays under 1 MiB)
+    gold = dict(np.load(os.path.join(GOLDEN, "fullsize_config5.npz")))
+    gold["traj"] = np.concatenate([gold["traj"], np.load(os.path.join(GOLDEN, "fullsize_config5_traj_b.npz"))["traj"]])
+    assert gold["traj"].shape == (len(gold["index"]), 200, 30)
     mod = _module()
     model = common.setup_product_tree30(mod)
     # the product's fields (voxelizer + flood fill + distance transform, on the GPU for grids of this

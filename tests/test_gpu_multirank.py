@@ -33,7 +33,7 @@ def _run_bench(extra, tmp_path, timeout=900):
 def test_bench_starts_its_own_two_ranks_and_gathers(tmp_path):
     dump = str(tmp_path / "gathered.npy")
     full_path = str(tmp_path / "full.json")
-    r = _run_bench(["--gpus", "2", "--backend", "gloo", "--batch", "512", "--steps", "2", "--warmup", "1",
+    r = _run_bench(["--gpus", "2", "--full", "--backend", "gloo", "--batch", "512", "--steps", "2", "--warmup", "1",
                     "--no-cpu-baseline", "--dump-gather", dump, "--full-out", full_path], tmp_path)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -66,7 +66,7 @@ def test_bench_starts_its_own_two_ranks_and_gathers(tmp_path):
     keep = os.path.join(ROOT, "gpurun_out")
     if os.path.isdir(keep):
         with open(os.path.join(keep, "r06_rehearsal_2ranks_gloo.json"), "w") as f:
-            json.dump({"command": "python bench.py --gpus 2 --backend gloo --batch 512 --steps 2 --warmup 1 --no-cpu-baseline",
+            json.dump({"command": "python bench.py --gpus 2 --full --backend gloo --batch 512 --steps 2 --warmup 1 --no-cpu-baseline",
                        "line": line, "gathered_equals_single_process_batch": True}, f, indent=1)
 
 

@@ -2,10 +2,22 @@
 string builders emit the reference's grammar; the product refuses to run without a GPU."""
 import os
 import re
+import subprocess
+import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _gpu_present():
+    """torch's answer in a fresh process: torch carries its own copy of the HIP runtime, and in a process where the
+    product's runtime has already opened the device (a -m gpu test that ran before in the same session) torch's copy
+    reports none"""
+    r = subprocess.run([sys.executable, "-c", "import torch; print(int(torch.cuda.is_available()))"], capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return r.stdout.strip().splitlines()[-1] == "1"
 
 
 def test_capi_exports_every_declared_symbol():
@@ -22,8 +34,7 @@ def test_capi_exports_every_declared_symbol():
 
 def test_no_cpu_fallback():
     """without a HIP device the module refuses loudly instead of computing on the CPU"""
-    import torch
-    if torch.cuda.is_available():
+    if _gpu_present():
         pytest.skip("a GPU is present")
     import or_cdchomp_amd
     with pytest.raises(RuntimeError, match="no HIP device available"):
@@ -107,8 +118,7 @@ def test_bench_gpus_n_starts_its_own_ranks():
     """`bench.py --gpus 2` with no WORLD_SIZE starts two child ranks itself and exits with their code: without a
     GPU every rank refuses ("needs an MI355X"), so the command must fail -- through the launcher it started
     (the launcher ends the other rank as soon as one has failed: at least one of them has said so)"""
-    import torch
-    if torch.cuda.is_available():
+    if _gpu_present():
         pytest.skip("a GPU is present: tests/test_gpu_multirank.py runs the real thing")
     r = _bench(["--gpus", "2", "--backend", "gloo", "--steps", "1", "--warmup", "0"])
     assert r.returncode != 0
