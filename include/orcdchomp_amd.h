@@ -218,6 +218,25 @@ void orc_batch_params_default(orc_batch_params * p);
 int orc_batch_create(orc_module * mod, const char * robot, const orc_batch_params * params, int n_runs,
    const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
    int * batch_id);
+/* orc_batch_create with obstacles per run: a scene is an ordered list of at most ORC_MAX_SDFS (8) field
+ * placements, and every run is optimized against the scene scene_of_run[run] names.  A placement is a
+ * kinbody whose field exists in the module (computedistancefield, addfield_fromobsarray,
+ * orc_scene_add_sdf) and the kinbody's world pose to use for it: the field then stands at
+ * pose_world_kinbody o (the field's pose in the kinbody frame).  Scenes are given in CSR form: scene s
+ * holds the placements [scene_begin[s], scene_begin[s+1]) of field_kinbodies / field_poses, in the
+ * order of the best-of-N field loop (a tie goes to the earlier field).  A scene may be empty (no
+ * obstacle cost) and may place one kinbody's field more than once; the scenes share the device
+ * copies of the grids.  field_poses [scene_begin[n_scenes]][7] (x y z qx qy qz qw) or NULL: every
+ * kinbody where it stands now.  The rest of the batch API works unchanged; the collision verdict
+ * (orc_batch_collision_verdict, gettrajbatch ... verdict, the re-check of gettraj) tests every run
+ * against its own scene, and a reported field index is the placement's position in that scene.
+ * A malformed table (n_scenes < 1, scene_begin not starting at 0 or decreasing, a scene of more
+ * than ORC_MAX_SDFS fields, an unknown kinbody or one without a field, a scene_of_run entry outside
+ * [0, n_scenes)) is rejected with a nonzero return; the module stays usable. */
+int orc_batch_create_scenes(orc_module * mod, const char * robot, const orc_batch_params * params, int n_runs,
+   const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
+   int n_scenes, const int * scene_begin, const char * const * field_kinbodies, const double * field_poses,
+   const int * scene_of_run, int * batch_id);
 /* replaces mod::iterate (src/orcdchomp_mod.cpp:2690-2852): n_iter iterations of
  * cd_chomp_iterate (src/libcd/chomp.c:430-683) for every run, then the final
  * cost evaluation.  costs_out [n_runs][3] = total, obs, smooth (may be NULL);

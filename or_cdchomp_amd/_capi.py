@@ -68,6 +68,9 @@ SYMBOLS = [
     ("orc_batch_params_default", None, [C.POINTER(BatchParams)]),
     ("orc_batch_create", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(BatchParams), C.c_int, c_double_p,
                                    c_double_p, c_double_p, c_uint_p, c_int_p]),
+    ("orc_batch_create_scenes", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(BatchParams), C.c_int, c_double_p,
+                                          c_double_p, c_double_p, c_uint_p, C.c_int, c_int_p, C.POINTER(C.c_char_p),
+                                          c_double_p, c_int_p, c_int_p]),
     ("orc_batch_iterate", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_int_p]),
     ("orc_batch_iterate_async", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("orc_batch_sync", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_int_p]),

@@ -256,8 +256,9 @@ hipError_t launch_typed(const DevBatch<float> & b, size_t lds, hipStream_t s, in
 } // namespace
 
 BatchShard::BatchShard(Module * mod, int dev, hipStream_t stream, const Robot & robot, const BatchParams & p, int nruns,
-   const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds)
-   : n_runs(nruns), params(p), device(dev), mod_(mod), stream_(stream)
+   const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
+   std::shared_ptr<const SceneTable> scenes, int run0)
+   : n_runs(nruns), params(p), device(dev), mod_(mod), stream_(stream), scenes_(std::move(scenes)), run0_(run0)
 {
    DeviceGuard guard(device);
    try { construct(robot, starts, goals, basegoals, seeds); }
@@ -393,7 +394,8 @@ void BatchShard::release()
    void ** all[] = { &d_model_, &d_sdfs_, &d_sdfc_, &d_traj_, &d_AG_, &d_G_, (void **) &d_mt_, (void **) &d_mt_bak_, (void **) &d_hmc_next_,
                      (void **) &d_hmc_next_bak_, (void **) &d_overflow_, (void **) &d_costs_, (void **) &d_trace_, (void **) &d_status_,
                      (void **) &d_iters_done_, (void **) &d_leap_, &d_Aband_, &d_beta_s_, &d_beta_g_, &d_metric64_, &d_pcr_, &d_Ainv_, &d_jl_lo_, &d_jl_hi_,
-                     (void **) &d_hmc_iters_, &d_noise_, (void **) &d_phase_, &d_Gcost_, &d_tsrs_, &d_tsr_ws_, (void **) &d_tsr_err_ };
+                     (void **) &d_hmc_iters_, &d_noise_, (void **) &d_phase_, &d_Gcost_, &d_tsrs_, &d_tsr_ws_, (void **) &d_tsr_err_,
+                     (void **) &d_scene_of_run_, (void **) &d_scene_nsdf_ };
    for (void ** p : all) { dev_free(*p); *p = nullptr; }
    sdf_refs_.clear();
    for (int k=0; k<2; k++) if (ev_plan_[k]) { (void) hipEventDestroy(ev_plan_[k]); ev_plan_[k] = nullptr; }
@@ -892,16 +894,35 @@ void BatchShard::build_device(const Robot & robot)
    hip_check(hipStreamSynchronize(st), "model sync");
    d_model_ = dm;
 
-   // rooted fields (mod.cpp:2348-2369)
-   n_sdfs_ = (int) mod_->sdfs.size();
+   // rooted fields (mod.cpp:2348-2369), scene by scene: descriptors [n_scenes][F] (F: the fields of the largest scene, what
+   // the LDS carve-up holds), the same in cell units [n_scenes][sdfc_stride_], every scene's slice padded to whole batches of
+   // four plus four and zeroed (the many-sphere cost path loads a batch unconditionally), the field count of every scene
+   const SceneTable & table = *scenes_;
+   n_scenes_ = (int) table.scenes.size();
+   n_sdfs_ = table.max_fields();
    if (n_sdfs_ > ORC_MAX_SDFS) throw std::runtime_error("too many signed distance fields for this build!");
-   std::vector<DevSdf<real>> hs(n_sdfs_);
-   std::vector<DevSdfCell<real>> hc((size_t)((n_sdfs_ + 3) / 4) * 4 + 4);      // (padded to whole batches of four: the many-sphere cost path loads a batch unconditionally)
+   sdfc_stride_ = ((n_sdfs_ + 3) / 4) * 4 + 4;
+   std::vector<DevSdf<real>> hs((size_t) n_scenes_ * n_sdfs_);
+   std::vector<DevSdfCell<real>> hc((size_t) n_scenes_ * sdfc_stride_);
    std::memset(hc.data(), 0, hc.size() * sizeof(DevSdfCell<real>));
-   for (int i=0; i<n_sdfs_; i++)
+   std::vector<int> scene_nsdf(n_scenes_);
+   // the grids of the scenes this shard's runs are in come to its device (once per device: the copies are shared)
+   std::vector<unsigned char> used(n_scenes_, 0);
+   for (int k=0; k<n_runs; k++) used[table.scene_of_run[run0_ + k]] = 1;
+   bool one_aligned = n_scenes_ > 0;      // every scene: one field with the world's axes
+   for (int sc=0; sc<n_scenes_; sc++)
    {
-      Sdf & s = *mod_->sdfs[i];
+   const std::vector<ScenePlacement> & fields = table.scenes[sc];
+   scene_nsdf[sc] = (int) fields.size();
+   if (fields.size() != 1) one_aligned = false;
+   for (int f=0; f<(int) fields.size(); f++)
+   {
+      Sdf & s = *fields[f].sdf;
+      DevSdf<real> & hsi = hs[(size_t) sc * n_sdfs_ + f];
+      DevSdfCell<real> & hci = hc[(size_t) sc * sdfc_stride_ + f];
       const size_t nc = s.grid.ncells();
+      if (used[sc])
+      {
       std::lock_guard<std::recursive_mutex> env_lock(mod_->env_mutex);      // (the device copies are shared by the shards)
       if (sizeof(real) == 8)
       {
@@ -911,7 +932,7 @@ void BatchShard::build_device(const Robot & robot)
             buf = device_buffer(device, nc*sizeof(double));
             hip_check(hipMemcpy(buf.get(), s.grid.data.data(), nc*sizeof(double), hipMemcpyHostToDevice), "sdf upload");
          }
-         hs[i].data = (const real *) buf.get();
+         hsi.data = (const real *) buf.get();
          sdf_refs_.push_back(buf);
       }
       else
@@ -923,25 +944,27 @@ void BatchShard::build_device(const Robot & robot)
             buf = device_buffer(device, nc*sizeof(float));
             hip_check(hipMemcpy(buf.get(), tmp.data(), nc*sizeof(float), hipMemcpyHostToDevice), "sdf upload");
          }
-         hs[i].data = (const real *) buf.get();
+         hsi.data = (const real *) buf.get();
          sdf_refs_.push_back(buf);
       }
-      const Pose pose_world_gsdf = pose_compose(mod_->body_transform(s.kinbody_name), s.pose);
+      }
+      const Pose pose_world_gsdf = pose_compose(fields[f].pose_world_kinbody, s.pose);
       const Pose pose_gsdf_world = pose_invert(pose_world_gsdf);
       const Mat3 Rgw = pose_rotation_expanded(pose_gsdf_world);
       const Mat3 Rwg = pose_rotation_expanded(pose_world_gsdf);
-      for (int q=0; q<9; q++) { hs[i].Rgw[q] = (real) Rgw.m[q]; hs[i].Rwg[q] = (real) Rwg.m[q]; }
-      hs[i].rot_identity = 1;
+      for (int q=0; q<9; q++) { hsi.Rgw[q] = (real) Rgw.m[q]; hsi.Rwg[q] = (real) Rwg.m[q]; }
+      hsi.rot_identity = 1;
       for (int q=0; q<9; q++)
-         if (Rgw.m[q] != ((q % 4 == 0) ? 1.0 : 0.0) || Rwg.m[q] != ((q % 4 == 0) ? 1.0 : 0.0)) hs[i].rot_identity = 0;
+         if (Rgw.m[q] != ((q % 4 == 0) ? 1.0 : 0.0) || Rwg.m[q] != ((q % 4 == 0) ? 1.0 : 0.0)) hsi.rot_identity = 0;
+      if (!hsi.rot_identity) one_aligned = false;
       for (int q=0; q<3; q++)
       {
-         hs[i].tgw[q] = (real) pose_gsdf_world.v[q];
-         hs[i].size[q] = s.grid.sizes[q];
-         hs[i].length[q] = (real) s.grid.lengths[q];
-         hs[i].inv_length[q] = (real)(1.0 / s.grid.lengths[q]);
-         hs[i].cell[q] = (real)(s.grid.lengths[q] / s.grid.sizes[q]);
-         hs[i].size_over_len[q] = (real)(s.grid.sizes[q] / s.grid.lengths[q]);
+         hsi.tgw[q] = (real) pose_gsdf_world.v[q];
+         hsi.size[q] = s.grid.sizes[q];
+         hsi.length[q] = (real) s.grid.lengths[q];
+         hsi.inv_length[q] = (real)(1.0 / s.grid.lengths[q]);
+         hsi.cell[q] = (real)(s.grid.lengths[q] / s.grid.sizes[q]);
+         hsi.size_over_len[q] = (real)(s.grid.sizes[q] / s.grid.lengths[q]);
       }
       // the field in cell units (DevSdfCell), folded in double precision
       for (int r=0; r<3; r++)
@@ -949,29 +972,35 @@ void BatchShard::build_device(const Robot & robot)
          const double sol = s.grid.sizes[r] / s.grid.lengths[r];
          for (int c=0; c<3; c++)
          {
-            hc[i].M[r*3+c] = (real)(sol * Rgw.m[r*3+c]);
-            hc[i].W[c*3+r] = (real)(Rwg.m[c*3+r] * sol);
+            hci.M[r*3+c] = (real)(sol * Rgw.m[r*3+c]);
+            hci.W[c*3+r] = (real)(Rwg.m[c*3+r] * sol);
          }
-         hc[i].t[r] = (real)(sol * pose_gsdf_world.v[r]);
-         hc[i].fsize[r] = (real) s.grid.sizes[r];
-         hc[i].fsize_m1[r] = (real)(s.grid.sizes[r] - 1);
+         hci.t[r] = (real)(sol * pose_gsdf_world.v[r]);
+         hci.fsize[r] = (real) s.grid.sizes[r];
+         hci.fsize_m1[r] = (real)(s.grid.sizes[r] - 1);
       }
-      hc[i].stride_b[0] = s.grid.sizes[1] * s.grid.sizes[2] * (int) sizeof(real);
-      hc[i].stride_b[1] = s.grid.sizes[2] * (int) sizeof(real);
-      hc[i].stride_r[0] = (real) hc[i].stride_b[0]; hc[i].stride_r[1] = (real) hc[i].stride_b[1]; hc[i].stride_r[2] = (real) sizeof(real);
-      hc[i].data = hs[i].data;
+      hci.stride_b[0] = s.grid.sizes[1] * s.grid.sizes[2] * (int) sizeof(real);
+      hci.stride_b[1] = s.grid.sizes[2] * (int) sizeof(real);
+      hci.stride_r[0] = (real) hci.stride_b[0]; hci.stride_r[1] = (real) hci.stride_b[1]; hci.stride_r[2] = (real) sizeof(real);
+      hci.data = hsi.data;
       if (nc * sizeof(real) >= (size_t) 1 << 31) throw std::runtime_error("signed distance field too large for this build!");
       // the many-sphere pass forms its cell offsets with 24-bit multiplies (cost_generic.h: signed, both operands below 2^23)
-      if (GS_ != 16 && !(tree_ & 512) && (hc[i].stride_b[0] >= (1 << 23) || std::max(s.grid.sizes[0], std::max(s.grid.sizes[1], s.grid.sizes[2])) >= (1 << 23)))
+      if (GS_ != 16 && !(tree_ & 512) && (hci.stride_b[0] >= (1 << 23) || std::max(s.grid.sizes[0], std::max(s.grid.sizes[1], s.grid.sizes[2])) >= (1 << 23)))
          throw std::runtime_error("signed distance field too large for this build (a y-z plane of 8 MB or more with a robot of more than 16 active spheres)!");
+   }
    }
    DevSdfCell<real> * dc = dev_alloc<DevSdfCell<real>>(hc.size());
    hip_check(hipMemcpy(dc, hc.data(), hc.size()*sizeof(DevSdfCell<real>), hipMemcpyHostToDevice), "sdfs (cell units)");
    d_sdfc_ = dc;
-   DevSdf<real> * ds = dev_alloc<DevSdf<real>>(n_sdfs_);
+   DevSdf<real> * ds = dev_alloc<DevSdf<real>>(hs.size());
    hip_check(hipMemcpy(ds, hs.data(), hs.size()*sizeof(DevSdf<real>), hipMemcpyHostToDevice), "sdfs");
    d_sdfs_ = ds;
-   if ((tree_ & (16 | 512)) && n_sdfs_ == 1 && hs[0].rot_identity) tree_ |= 32 | ((S_ == Sa_) ? 128 : 0);      // one field with the world's axes: known at compile time (phase_cost KIND)
+   d_scene_nsdf_ = dev_alloc<int>(n_scenes_);
+   hip_check(hipMemcpy(d_scene_nsdf_, scene_nsdf.data(), n_scenes_*sizeof(int), hipMemcpyHostToDevice), "scene field counts");
+   d_scene_of_run_ = dev_alloc<int>(n_runs);
+   hip_check(hipMemcpy(d_scene_of_run_, table.scene_of_run.data() + run0_, n_runs*sizeof(int), hipMemcpyHostToDevice), "scene of run");
+   // one field with the world's axes in every scene: known at compile time (phase_cost KIND)
+   if ((tree_ & (16 | 512)) && one_aligned) tree_ |= 32 | ((S_ == Sa_) ? 128 : 0);
 
    // metric tables
    d_Aband_ = upload<real>(metric_.Aband, st);
@@ -1248,6 +1277,7 @@ void BatchShard::collision_verdict(const std::vector<int> & offs, const std::vec
       d_u = upload<double>(u, st); d_rsum = upload<double>(pair_rsum, st); d_inact = upload<double>(inact_pos, st);
       DevVerdict<double> v;
       v.model = (const DevModel<double> *) d_model_; v.sdfs = (const DevSdf<double> *) d_sdfs_; v.n_sdfs = n_sdfs_;
+      v.scene_of_run = d_scene_of_run_; v.scene_nsdf = d_scene_nsdf_;
       v.n_runs = n_runs; v.n_points = n_points; v.n = n; v.chunk = chunk; v.traj = (const double *) d_traj_;
       v.offs = d_offs; v.seg = d_seg; v.u = (const double *) d_u; v.slot_xml = d_xml; v.key_out = d_key; v.depth_out = d_depth;
       v.n_pairs = n_pairs; v.pairs = d_pairs; v.pair_rsum = (const double *) d_rsum; v.inact_pos = (const double *) d_inact;
@@ -1258,6 +1288,7 @@ void BatchShard::collision_verdict(const std::vector<int> & offs, const std::vec
       d_u = upload<float>(u, st); d_rsum = upload<float>(pair_rsum, st); d_inact = upload<float>(inact_pos, st);
       DevVerdict<float> v;
       v.model = (const DevModel<float> *) d_model_; v.sdfs = (const DevSdf<float> *) d_sdfs_; v.n_sdfs = n_sdfs_;
+      v.scene_of_run = d_scene_of_run_; v.scene_nsdf = d_scene_nsdf_;
       v.n_runs = n_runs; v.n_points = n_points; v.n = n; v.chunk = chunk; v.traj = (const float *) d_traj_;
       v.offs = d_offs; v.seg = d_seg; v.u = (const float *) d_u; v.slot_xml = d_xml; v.key_out = d_key; v.depth_out = d_depth;
       v.n_pairs = n_pairs; v.pairs = d_pairs; v.pair_rsum = (const float *) d_rsum; v.inact_pos = (const float *) d_inact;
@@ -1441,6 +1472,7 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    b.sdfs = (const DevSdf<real> *) d_sdfs_;
    b.sdfc = (const DevSdfCell<real> *) d_sdfc_;
    b.n_sdfs = n_sdfs_;
+   b.scene_of_run = d_scene_of_run_; b.scene_nsdf = d_scene_nsdf_; b.n_scenes = n_scenes_; b.sdfc_stride = sdfc_stride_;
    b.n_runs = n_runs; b.n_points = m + 2; b.np_global = n_points; b.free_start = params.free_start; b.m = m; b.n = n;
    if (params.free_start && tile_first_ < 2)
       throw std::runtime_error("start_tsr: the first tile must hold the two points after the start point!");
@@ -1670,8 +1702,9 @@ template void BatchShard::build_device<float>(const Robot &);
 // the runs of a batch in contiguous blocks over the module's devices: no collective,
 // every shard copies its block straight into the caller's arrays (the host-side gather)
 Batch::Batch(Module * mod, const std::vector<int> & devices, const Robot & robot, const BatchParams & p, int nruns,
-   const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds)
-   : n_runs(nruns), params(p)
+   const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
+   std::shared_ptr<const SceneTable> scene_table)
+   : n_runs(nruns), params(p), scenes(std::move(scene_table))
 {
    const int n_adof = (int) robot.active_dofs.size();
    int world = (int) devices.size();
@@ -1698,7 +1731,7 @@ Batch::Batch(Module * mod, const std::vector<int> & devices, const Robot & robot
       const size_t lo = (size_t) offs[r];
       shards[r].reset(new BatchShard(mod, devices[r], streams[r], robot, p, offs[r+1] - offs[r],
          starts ? starts + lo * n_adof : nullptr, goals + lo * n_adof, basegoals ? basegoals + lo * 7 : nullptr,
-         seeds ? seeds + lo : nullptr));
+         seeds ? seeds + lo : nullptr, scenes, (int) lo));
    }, true);
    const BatchShard & s0 = *shards[0];
    n_points = s0.n_points; n = s0.n; m = s0.m;

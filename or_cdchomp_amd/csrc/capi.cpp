@@ -420,6 +420,57 @@ int orc_batch_create(orc_module * mod, const char * robot, const orc_batch_param
    });
 }
 
+int orc_batch_create_scenes(orc_module * mod, const char * robot, const orc_batch_params * p, int n_runs,
+   const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
+   int n_scenes, const int * scene_begin, const char * const * field_kinbodies, const double * field_poses,
+   const int * scene_of_run, int * batch_id)
+{
+   return guarded(mod, [&] {
+      need(robot, "robot"); need(p, "params"); need(batch_id, "batch_id");
+      orc::BatchParams q;
+      q.n_points = p->n_points; q.floating_base = p->floating_base; q.lambda = p->lambda;
+      q.derivative = p->derivative; q.use_momentum = p->use_momentum; q.use_hmc = p->use_hmc;
+      q.hmc_resample_lambda = p->hmc_resample_lambda; q.epsilon = p->epsilon; q.epsilon_self = p->epsilon_self;
+      q.obs_factor = p->obs_factor; q.obs_factor_self = p->obs_factor_self; q.precision = p->precision;
+      if (!goals) throw std::runtime_error("Did not pass either adofgoal or starttraj!");
+      if (q.floating_base && !basegoals) throw std::runtime_error("Passed floating_base with no basegoal!");
+      if (!q.floating_base && basegoals) throw std::runtime_error("Passed basegoal with no floating_base!");
+      if (q.lambda < 0.01) throw std::runtime_error("lambda must be >=0.01!");
+      if (q.n_points < 3) throw std::runtime_error("n_points must be >=3!");
+      if (n_runs < 1) throw std::runtime_error("n_runs must be >=1!");
+      // the scene table
+      if (n_scenes < 1) throw std::runtime_error("n_scenes must be >=1!");
+      need(scene_begin, "scene_begin"); need(scene_of_run, "scene_of_run");
+      if (scene_begin[0] != 0) throw std::runtime_error("scene_begin[0] must be 0!");
+      for (int sc=0; sc<n_scenes; sc++)
+      {
+         if (scene_begin[sc+1] < scene_begin[sc]) throw std::runtime_error("scene_begin must be non-decreasing!");
+         if (scene_begin[sc+1] - scene_begin[sc] > ORC_MAX_SDFS) throw std::runtime_error("too many signed distance fields for this build!");
+      }
+      const int n_fields = scene_begin[n_scenes];
+      if (n_fields > 0) need(field_kinbodies, "field_kinbodies");
+      std::shared_ptr<orc::SceneTable> t = std::make_shared<orc::SceneTable>();
+      t->scenes.resize(n_scenes);
+      for (int sc=0; sc<n_scenes; sc++)
+         for (int k=scene_begin[sc]; k<scene_begin[sc+1]; k++)
+         {
+            const std::string name = str(field_kinbodies[k], "field_kinbodies entry");
+            if (!mod->impl->has_body(name)) throw std::runtime_error("Kinbody " + name + " of a scene does not exist!");
+            std::shared_ptr<orc::Sdf> field;
+            for (const auto & f : mod->impl->sdfs) if (f->kinbody_name == name) field = f;
+            if (!field) throw std::runtime_error("Kinbody " + name + " of a scene has no signed distance field!");
+            orc::Pose pose;
+            if (field_poses) for (int j=0; j<7; j++) pose.v[j] = field_poses[(size_t) k*7 + j];
+            else pose = mod->impl->body_transform(name);
+            t->scenes[sc].push_back({ field, pose });
+         }
+      t->scene_of_run.assign(scene_of_run, scene_of_run + n_runs);
+      for (int sc : t->scene_of_run)
+         if (sc < 0 || sc >= n_scenes) throw std::runtime_error("scene_of_run entries must lie in [0, n_scenes)!");
+      *batch_id = mod->impl->create_batch(robot, q, n_runs, starts, goals, basegoals, seeds, nullptr, t);
+   });
+}
+
 int orc_batch_iterate(orc_module * mod, int id, int n_iter, double * costs_out, int * status_out)
 {
    return guarded(mod, [&] {

@@ -1418,6 +1418,12 @@ __device__ __forceinline__ KArg<real> * uniform_kernarg(const void * p)
    return (KArg<real> *)(((unsigned long long) hi << 32) | lo);
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// the scene of this workgroup's run (wave-uniform; DevBatch::scene_of_run)
+template <typename BT>
+__device__ __forceinline__ int run_scene(const BT & b)
+{
+   return (b.n_scenes > 1) ? uni(((const __attribute__((address_space(4))) int *) b.scene_of_run)[blockIdx.x]) : 0;
+}
 
 // the LDS carve-up and the views derived from it (everything here is wave-uniform)
 template <typename real>
@@ -1494,6 +1500,12 @@ __device__ __forceinline__ Env<real> make_env(const BT & b, unsigned char * smem
    mod.empty_mask = b.ms.placed ? (unsigned int)(~(b.ms.live_mask | b.ms.static_mask) & 0xFFFFull) : 0u;
    mod.static_slot_c = (const __attribute__((address_space(4))) int *) b.model->static_slot;
    mod.static_pos_c = (const __attribute__((address_space(4))) real (*)[3]) b.model->static_pos;
+   {
+      // the run's scene: its index and field count by scalar loads (one scene: scene 0 with all the batch's fields)
+      const int scene = run_scene(b);
+      mod.n_sdfs = (b.n_scenes > 1) ? uni(((const __attribute__((address_space(4))) int *) b.scene_nsdf)[scene]) : b.n_sdfs;
+      mod.sdfc = (const __attribute__((address_space(4))) DevSdfCell<real> *) b.sdfc + (size_t) scene * b.sdfc_stride;
+   }
    E.AG_g = b.AG + (size_t) run * mn;
    // momentum: in LDS for the launch, or in place in global memory (every entry is read and written
    // by the same thread, e = tid + k BLOCK, in all loops that touch it)
@@ -1552,13 +1564,13 @@ __device__ __attribute__((noinline)) void phase_setup(const void * kp)
    for (int e=tid; e<Sa; e+=BLOCK) E.saff_s[e] = gmod.sph_affects[e];
    for (int e=tid; e<12; e+=BLOCK) E.base_s[e] = (e < 9) ? gmod.base_R[e] : gmod.base_t[e-9];
    {
-      // word-wise copy of the field descriptors
-      const int * src2 = (const int *) b.sdfs; int * dst2 = (int *) E.sdfs_s;
-      for (int e=tid; e<b.n_sdfs*(int)(sizeof(DevSdf<real>)/4); e+=BLOCK) dst2[e] = src2[e];
+      // word-wise copy of the run's scene's field descriptors
+      const int * src2 = (const int *)(b.sdfs + (size_t) run_scene(b) * b.n_sdfs); int * dst2 = (int *) E.sdfs_s;
+      for (int e=tid; e<E.mod.n_sdfs*(int)(sizeof(DevSdf<real>)/4); e+=BLOCK) dst2[e] = src2[e];
    }
 #ifdef ORC_ABLATE_SDFLDS
    __syncthreads();
-   if (tid < b.n_sdfs) E.sdfs_s[tid].data = E.pos_s;
+   if (tid < E.mod.n_sdfs) E.sdfs_s[tid].data = E.pos_s;
 #endif
    for (int e=tid; e<n; e+=BLOCK) { E.jl_s[e] = b.jl_lo[e]; E.jl_s[n+e] = b.jl_hi[e]; }
    if (!GS16)
@@ -2393,6 +2405,10 @@ void collision_verdict_kernel(DevVerdict<real> v)
    const int run = blockIdx.x, tid = threadIdx.x;
    const int n = v.n, np = v.n_points, nj = gmod.nj, Sa = gmod.Sa;
    const int pstr = (Sa*3) | 1, astr = (nj*6) | 1, chunk = v.chunk;
+   // the run's scene: its slice of the descriptors and its field count
+   const int scene = v.scene_of_run ? v.scene_of_run[run] : 0;
+   const int n_fields = v.scene_nsdf ? v.scene_nsdf[scene] : v.n_sdfs;
+   const DevSdf<real> * sdfs = v.sdfs + (size_t) scene * v.n_sdfs;
    unsigned long long * key_s = (unsigned long long *) smem_raw;     // [2]: the first contact's key (sample << 32 | pair bit << 31 | sphere << 16 | field or partner)
    real * lds = (real *)(smem_raw + 16);
    real * rows_s = lds;                                              // [chunk][n]
@@ -2463,9 +2479,9 @@ void collision_verdict_kernel(DevVerdict<real> v)
          if (!((mod.live_mask >> slot) & 1ull)) continue;
          const real * p = pos_s + s*pstr + slot*3;
          const real radius = srad_s[slot];
-         for (int i=0; i<v.n_sdfs; i++)
+         for (int i=0; i<n_fields; i++)
          {
-            const DevSdf<real> & F = v.sdfs[i];
+            const DevSdf<real> & F = sdfs[i];
             real gp[3], gg[3], val;
 #pragma unroll
             for (int k=0; k<3; k++)

@@ -107,7 +107,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
       // four fields are issued before any is used (a field per trip would wait for its four reads, an L2
       // round trip, before the next field's addresses are formed).
       typedef const __attribute__((address_space(4))) DevSdfCell<real> CellDesc;
-      CellDesc * fc = (CellDesc *) b.sdfc;
+      CellDesc * fc = (CellDesc *) mod.sdfc;
       constexpr int NB = ORC_SDF_BATCH;      // fields in flight together
       real v0[NB], vn[NB][3], fr[NB][3];      // (of the batch of up to four fields in flight)
       bool prev[NB][3], inbq[NB];
@@ -137,7 +137,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
             for (int k=0; k<9; k++) __asm__ volatile("" : "+s"(Mq[k]));
 #pragma unroll
             for (int k=0; k<3; k++) { __asm__ volatile("" : "+s"(tq[k])); __asm__ volatile("" : "+s"(fsq[k])); }
-            bool inb = live & (i0 + q < b.n_sdfs);
+            bool inb = live & (i0 + q < mod.n_sdfs);
 #pragma unroll
             for (int k=0; k<3; k++)
             {
@@ -145,7 +145,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
                inb = inb & !(gx[q][k] < (real)0) & !(gx[q][k] > fsq[k]);      // the reference's x < 0 || x > 1 (grid.c:196-199)
             }
 #else
-            bool inb = live && (i0 + q < b.n_sdfs);
+            bool inb = live && (i0 + q < mod.n_sdfs);
 #pragma unroll
             for (int k=0; k<3; k++)
             {
@@ -223,7 +223,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
 #pragma unroll
          for (int q=0; q<NB; q++)
          {
-            if (i0 + q >= b.n_sdfs || !use[q]) continue;
+            if (i0 + q >= mod.n_sdfs || !use[q]) continue;
             bool poisoned = (v0[q] == inf);
             real val = v0[q], df[3];
 #pragma unroll
@@ -438,7 +438,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
 #if ORC_SDF_DEFER
       sdf_finish(0);
 #endif
-      for (int i0=ORC_SDF_BATCH; i0<b.n_sdfs; i0+=ORC_SDF_BATCH) { sdf_issue(i0); sdf_finish(i0); }      // (more fields than a batch holds: the rest one batch at a time)
+      for (int i0=ORC_SDF_BATCH; i0<mod.n_sdfs; i0+=ORC_SDF_BATCH) { sdf_issue(i0); sdf_finish(i0); }      // (more fields than a batch holds: the rest one batch at a time)
 #endif
       {
          const bool on = live && has;

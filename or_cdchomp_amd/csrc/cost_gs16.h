@@ -485,7 +485,7 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
       if constexpr (ONEF)
       {
          typedef const __attribute__((address_space(4))) DevSdfCell<real> CellDesc;
-         CellDesc & F = *((CellDesc *) b.sdfc);
+         CellDesc & F = *((CellDesc *) mod.sdfc);
 #pragma unroll
          for (int u=0; u<U; u++)
          {
@@ -506,9 +506,9 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
       else if (ORC_GS16_CELL > 1)
       {
          typedef const __attribute__((address_space(4))) DevSdfCell<real> CellDesc;
-         for (int i=0; i<b.n_sdfs; i++)
+         for (int i=0; i<mod.n_sdfs; i++)
          {
-            CellDesc & F = ((CellDesc *) b.sdfc)[i];
+            CellDesc & F = ((CellDesc *) mod.sdfc)[i];
 #pragma unroll
             for (int u=0; u<U; u++)
             {
@@ -524,7 +524,7 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
       }
       else
 #endif
-      for (int i=0; i<(ONEF ? 1 : b.n_sdfs); i++)
+      for (int i=0; i<(ONEF ? 1 : mod.n_sdfs); i++)
       {
          const DevSdf<real> & F = sdfs[i];
 #pragma unroll

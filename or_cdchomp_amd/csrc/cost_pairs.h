@@ -140,7 +140,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
 #ifndef ORC_ABLATE_SDF
          if constexpr (ONEF)
          {
-            CellDesc & F = *((CellDesc *) b.sdfc);
+            CellDesc & F = *((CellDesc *) mod.sdfc);
             real gw[3], val;
             bool inb;
             if constexpr (sizeof(real) == 8) inb = sdf_lookup_cell_aligned_lean(F, p, val, gw);
@@ -152,9 +152,9 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
             for (int k=0; k<3; k++) bgrad[k] = better ? gw[k] : bgrad[k];
          }
          else
-            for (int i=0; i<b.n_sdfs; i++)
+            for (int i=0; i<mod.n_sdfs; i++)
             {
-               CellDesc & F = ((CellDesc *) b.sdfc)[i];
+               CellDesc & F = ((CellDesc *) mod.sdfc)[i];
                real gw[3], val;
                const bool inb = sdf_lookup_cell<real>(F, p, val, gw);
                const bool better = inb && (val < best);           // strict <: HUGE_VAL never wins

@@ -200,7 +200,13 @@ struct DevBatch
    const DevModel<real> * model;
    const DevSdf<real> * sdfs;
    const DevSdfCell<real> * sdfc;      // [n_sdfs] the same fields in cell units (many-sphere cost path)
-   int n_sdfs;
+   int n_sdfs;             // fields of the largest scene (what the LDS carve-up holds)
+   // per-run scenes (orc_batch_create_scenes): sdfs is [n_scenes][n_sdfs], sdfc [n_scenes][sdfc_stride] (every scene's slice
+   // padded to whole groups of four plus four, zeroed), scene_nsdf [n_scenes] the fields of a scene, scene_of_run [n_runs] of
+   // this shard.  n_scenes == 1: every run has scene 0 with n_sdfs fields (the kernels read neither array)
+   const int * scene_of_run;
+   const int * scene_nsdf;
+   int n_scenes, sdfc_stride;
    int n_runs, n_points, m, n;
    int tile_m;             // moving waypoints per tile (the largest tile: what the LDS carve-up holds)
    int n_tiles;            // tiles of an iteration: the first holds tile_first moving waypoints, the others tile_rest (the last what is left)
@@ -285,8 +291,10 @@ template <typename real>
 struct DevVerdict
 {
    const DevModel<real> * model;
-   const DevSdf<real> * sdfs;
-   int n_sdfs;
+   const DevSdf<real> * sdfs;  // [n_scenes][n_sdfs]
+   int n_sdfs;                 // fields of the largest scene
+   const int * scene_of_run;   // [n_runs] (DevBatch::scene_of_run)
+   const int * scene_nsdf;     // [n_scenes]
    int n_runs, n_points, n;
    int chunk;                  // samples walked at a time (<= 64: as many as the CU's LDS holds of this robot)
    const real * traj;          // [n_runs][n_points][n]
@@ -333,6 +341,9 @@ struct ModelView
    const __attribute__((address_space(4))) DevFkJoint<real> * fkj;     // DevModel::fkj (scalar loads: one record per joint)
    const __attribute__((address_space(4))) int * static_slot_c;         // DevModel::static_slot / static_pos (FK writes them into every row)
    const __attribute__((address_space(4))) real (* static_pos_c)[3];
+   // the run's scene (make_env): its field count and its slice of DevBatch::sdfc (scalar loads)
+   int n_sdfs;
+   const __attribute__((address_space(4))) DevSdfCell<real> * sdfc;
 };
 #if defined(__HIPCC__)
 __host__ __device__

@@ -500,17 +500,36 @@ void Module::add_sdf(const std::string & kb, const Grid & g, const Pose & pose)
    if (find_sdf(kb)) throw std::runtime_error("We already have an sdf for this kinbody!");
    for (int d=0; d<3; d++)
       if (g.sizes[d] < 2) throw std::runtime_error("sdf grids need at least 2 cells per dimension!");
-   std::unique_ptr<Sdf> s(new Sdf);
+   std::shared_ptr<Sdf> s = std::make_shared<Sdf>();
    s->kinbody_name = kb;
    s->pose = pose;
    s->grid = g;
    sdfs.push_back(std::move(s));
 }
 
+int SceneTable::max_fields() const
+{
+   size_t f = 0;
+   for (const auto & sc : scenes) f = std::max(f, sc.size());
+   return (int) f;
+}
+
+std::shared_ptr<SceneTable> Module::current_scene(int n_runs)
+{
+   std::shared_ptr<SceneTable> t = std::make_shared<SceneTable>();
+   t->scenes.resize(1);
+   for (const auto & s : sdfs) t->scenes[0].push_back({ s, body_transform(s->kinbody_name) });
+   t->scene_of_run.assign(std::max(n_runs, 0), 0);
+   return t;
+}
+
 int Module::create_batch(const std::string & rname, const BatchParams & p, int n_runs,
    const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
-   const std::vector<int> * devices_override)
+   const std::vector<int> * devices_override, std::shared_ptr<const SceneTable> scenes)
 {
+   const bool per_run_scenes = scenes != nullptr;
+   if (!scenes) scenes = current_scene(n_runs);
+   if ((int) scenes->scene_of_run.size() != n_runs) throw std::runtime_error("scene_of_run must have an entry for every run!");
    const Robot r = robot_for_run(rname);
    if (devices_override)
    {
@@ -518,7 +537,8 @@ int Module::create_batch(const std::string & rname, const BatchParams & p, int n
       hip_check(hipGetDeviceCount(&count), "hipGetDeviceCount");
       for (int d : *devices_override) if (d < 0 || d >= count) throw std::runtime_error("orcdchomp_amd: bad device ordinal");
    }
-   std::unique_ptr<Batch> b(new Batch(this, devices_override ? *devices_override : devices, r, p, n_runs, starts, goals, basegoals, seeds));
+   std::unique_ptr<Batch> b(new Batch(this, devices_override ? *devices_override : devices, r, p, n_runs, starts, goals, basegoals, seeds, scenes));
+   b->per_run_scenes = per_run_scenes;
    b->run_spheres = r.spheres;
    b->run_self_excl = r.run_self_pairs_excluded((int) robot(rname).spheres.size());
    const int id = next_batch_id_++;
@@ -1466,17 +1486,21 @@ std::string Module::cmd_gettraj(const std::vector<std::string> & argv, bool batc
             double pw[3];
             mat3_vec(frames[sp.link].R, sp.pos, pw);
             for (int k=0; k<3; k++) pw[k] += frames[sp.link].t[k];
-            for (auto & f : sdfs)
+            // the module's fields where their kinbodies stand now; a batch with per-run scenes: the placements of run 0's scene
+            const size_t n_fields = b.per_run_scenes ? b.scenes->scenes[b.scenes->scene_of_run[0]].size() : sdfs.size();
+            for (size_t fi=0; fi<n_fields; fi++)
             {
-               const Pose pose_world_gsdf = pose_compose(body_transform(f->kinbody_name), f->pose);
+               const ScenePlacement * pl = b.per_run_scenes ? &b.scenes->scenes[b.scenes->scene_of_run[0]][fi] : nullptr;
+               const Sdf & f = pl ? *pl->sdf : *sdfs[fi];
+               const Pose pose_world_gsdf = pose_compose(pl ? pl->pose_world_kinbody : body_transform(f.kinbody_name), f.pose);
                double pg[3], val;
                pose_apply(pose_invert(pose_world_gsdf), pw, pg);
-               if (grid_interp(f->grid, pg, &val)) continue;
+               if (grid_interp(f.grid, pg, &val)) continue;
                if (val - sp.radius < 0.0)
                {
                   collides = true;
                   details << "Collision at t=" << time << ": sphere " << si << " of " << b.robot_name
-                          << " is " << (sp.radius - val) << " m inside the field of " << f->kinbody_name << "\n";
+                          << " is " << (sp.radius - val) << " m inside the field of " << f.kinbody_name << "\n";
                   break;
                }
             }

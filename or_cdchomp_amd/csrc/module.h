@@ -104,6 +104,21 @@ struct Sdf                        // struct sdf, src/orcdchomp_mod.cpp:148-153
    std::map<int, std::shared_ptr<void>> dev64, dev32;
 };
 
+// The obstacles of a batch's runs (orc_batch_create_scenes): scenes of at most ORC_MAX_SDFS field placements, every run
+// in one of them.  orc_batch_create is the one-scene case: the module's fields where their kinbodies stand, every run in
+// scene 0 (Module::current_scene).
+struct ScenePlacement
+{
+   std::shared_ptr<Sdf> sdf;      // the module's field (shared: removefield does not pull it from under a batch)
+   Pose pose_world_kinbody;       // where its kinbody stands for this scene: the field is at pose_world_kinbody o sdf->pose
+};
+struct SceneTable
+{
+   std::vector<std::vector<ScenePlacement>> scenes;   // in the order of the best-of-N loop: a tie goes to the earlier field
+   std::vector<int> scene_of_run;                     // [n_runs]
+   int max_fields() const;                            // fields of the largest scene
+};
+
 // a TSR hard constraint on every moving point (`con_tsr all ...` or `everyn_tsr`; struct tsr,
 // src/orcdchomp_mod.h:80-87, struct run_contsr, src/orcdchomp_mod.cpp:873-885)
 struct TsrSpec
@@ -140,7 +155,8 @@ class BatchShard
 {
 public:
    BatchShard(Module * mod, int device, hipStream_t stream, const Robot & robot, const BatchParams & p, int n_runs,
-      const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds);
+      const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
+      std::shared_ptr<const SceneTable> scenes, int run0);
    ~BatchShard();
    BatchShard(const BatchShard &) = delete;
    BatchShard & operator=(const BatchShard &) = delete;
@@ -184,6 +200,10 @@ private:
    Module * mod_;
    hipStream_t stream_ = nullptr;   // the stream all work of this shard is issued on
    std::vector<std::shared_ptr<void>> sdf_refs_;   // the field copies the device descriptors point at
+   std::shared_ptr<const SceneTable> scenes_;      // the batch's scenes; this shard holds runs [run0_, run0_ + n_runs) of its scene_of_run
+   int run0_ = 0;
+   int * d_scene_of_run_ = nullptr; int * d_scene_nsdf_ = nullptr;
+   int n_scenes_ = 1, sdfc_stride_ = 0;
    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_events_;
    Metric metric_;
    // device buffers (typed by params.precision)
@@ -237,7 +257,8 @@ class Batch
 {
 public:
    Batch(Module * mod, const std::vector<int> & devices, const Robot & robot, const BatchParams & p, int n_runs,
-      const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds);
+      const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
+      std::shared_ptr<const SceneTable> scenes);
    ~Batch();
    void iterate_async(int n_iter, int iter_begin = 0, bool final_eval = true, bool carry = false);
    void sync(double * costs_out, int * status_out, int * iters_out = nullptr);
@@ -266,6 +287,8 @@ public:
    std::vector<unsigned char> run_self_excl; // [n][n] pairs of them the re-check's self-collision leg never tests (Robot::run_self_pairs_excluded, taken at create)
    std::vector<std::unique_ptr<BatchShard>> shards;
    std::vector<int> offs;            // first run of every shard, then n_runs
+   std::shared_ptr<const SceneTable> scenes;   // the runs' obstacles as create placed them
+   bool per_run_scenes = false;      // created with a scene table (orc_batch_create_scenes): gettraj's re-check walks the run's scene
    bool has_dat() const { return !dat_.empty(); }
 private:
    void for_shards(const std::function<void(size_t)> & body, bool threads);
@@ -303,7 +326,9 @@ public:
    // fields
    void add_sdf(const std::string & kinbody, const Grid & sdf, const Pose & pose_kinbody_gsdf);
    Sdf * find_sdf(const std::string & kinbody);
-   std::vector<std::unique_ptr<Sdf>> sdfs;
+   std::vector<std::shared_ptr<Sdf>> sdfs;
+   // the module's fields where their kinbodies stand now, every one of `n_runs` runs in it (what orc_batch_create plans with)
+   std::shared_ptr<SceneTable> current_scene(int n_runs);
 
    // lane placement of a robot's active spheres (place_spheres_on_row): a pure function of the robot
    // (geometry, limits, frozen dof values), the active dofs, floating base and epsilon_self
@@ -315,7 +340,7 @@ public:
    // batches
    int create_batch(const std::string & robot, const BatchParams & p, int n_runs,
       const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
-      const std::vector<int> * devices_override = nullptr);
+      const std::vector<int> * devices_override = nullptr, std::shared_ptr<const SceneTable> scenes = nullptr);
    Batch & batch(int id);
    void destroy_batch(int id);
    // collision verdict of all runs of a batch (gettraj's re-check, batched on the device): per run

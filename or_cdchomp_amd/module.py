@@ -25,6 +25,33 @@ def _f64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.float64))
 
 
+def scenes_to_csr(scenes):
+    """A list of scenes, each a list of (kinbody, pose7 or None), as the scene table of orc_batch_create_scenes:
+    (scene_begin int32 [n_scenes + 1], kinbody names [n_fields], poses float64 [n_fields][7] with NaN rows where the
+    pose is None -- or None when every pose is None).  Pure: no library call."""
+    begin = [0]
+    names, poses = [], []
+    for sc in scenes:
+        for kinbody, pose in sc:
+            names.append(str(kinbody))
+            if pose is None:
+                poses.append(None)
+            else:
+                pv = np.asarray(pose, dtype=np.float64).reshape(-1)
+                if pv.size != 7:
+                    raise ValueError("a field placement's pose has 7 entries (x y z qx qy qz qw), not %d" % pv.size)
+                poses.append(pv)
+        begin.append(len(names))
+    begin = np.asarray(begin, dtype=np.int32)
+    if all(p is None for p in poses):
+        return begin, names, None
+    out = np.full((len(names), 7), np.nan)
+    for k, pv in enumerate(poses):
+        if pv is not None:
+            out[k] = pv
+    return begin, names, out
+
+
 class Module:
     def __init__(self, device=0):
         """device: one HIP ordinal, or a list of them (batches are then sharded over the list inside
@@ -215,7 +242,10 @@ class Module:
                 setattr(p, k, v)
         return p
 
-    def batch_create(self, robot, goals, starts=None, basegoals=None, seeds=None, **params):
+    def batch_create(self, robot, goals, starts=None, basegoals=None, seeds=None, scenes=None, scene_of_run=None, **params):
+        """scenes: obstacles per run (orc_batch_create_scenes) -- a list of scenes, each a list of (kinbody, pose7 or None:
+        where the kinbody stands now), and scene_of_run [n_runs] the scene of every run; without them every run sees the
+        module's fields where their kinbodies stand."""
         p = self.batch_params(**params)
         goals = _f64(goals)
         goals = goals.reshape(1, -1) if goals.ndim == 1 else goals
@@ -224,6 +254,25 @@ class Module:
         bg = None if basegoals is None else _f64(basegoals)
         sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint32)
         bid = C.c_int(0)
+        if scenes is not None or scene_of_run is not None:
+            if scenes is None or scene_of_run is None:
+                raise ValueError("scenes and scene_of_run go together")
+            begin, names, poses = scenes_to_csr(scenes)
+            if poses is not None:
+                for k in range(len(names)):
+                    if np.isnan(poses[k, 0]):
+                        poses[k] = self.body_transform(names[k])
+                poses = np.ascontiguousarray(poses)
+            sor = np.ascontiguousarray(scene_of_run, dtype=np.int32).reshape(-1)
+            if sor.size != n_runs:
+                raise ValueError("scene_of_run has %d entries for %d runs" % (sor.size, n_runs))
+            cnames = (C.c_char_p * max(len(names), 1))(*[nm.encode() for nm in names])
+            self._check(self._lib.orc_batch_create_scenes(
+                self._h, robot.encode(), C.byref(p), n_runs,
+                None if st is None else _dp(st), _dp(goals), None if bg is None else _dp(bg),
+                None if sd is None else sd.ctypes.data_as(_capi.c_uint_p),
+                len(begin) - 1, _ip(begin), cnames, None if poses is None else _dp(poses), _ip(sor), C.byref(bid)))
+            return bid.value
         self._check(self._lib.orc_batch_create(
             self._h, robot.encode(), C.byref(p), n_runs,
             None if st is None else _dp(st), _dp(goals), None if bg is None else _dp(bg),
