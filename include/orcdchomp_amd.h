@@ -273,7 +273,7 @@ int orc_batch_collision_verdict(orc_module * mod, int batch_id, int * collides_o
 /* optimizer state read-back for tests: which = "G", "AG", "T" ([n_runs][m][n]); "phase" ([n_runs][8] cycle counters with
  * ORC_PHASE_TIMERS=1); "plan" (8 numbers: kernel variant bits -- 512 = the dense pair-list family, 1 = a tree --, threads per
  * workgroup, LDS bytes per workgroup, tile, solve mode (2 closed-form scans, 3 band-inverse generators, 1 dense), workgroups
- * per CU, tiles, lanes per waypoint) */
+ * per CU, tiles, lanes per waypoint; a ninth, the moving waypoints of the first tile, when cap_doubles >= 9) */
 int orc_batch_get_state(orc_module * mod, int batch_id, const char * which, double * out, size_t cap_doubles);
 int orc_batch_dims(orc_module * mod, int batch_id, int * n_runs, int * n_points, int * n);
 /* overwrite the trajectories of a batch (warm start; what `create starttraj` does for one run,

@@ -1638,10 +1638,11 @@ void BatchShard::gettraj(double * out)
    download(d_traj_, (size_t) n_runs * n_points * n, params.precision, out, stream_);
 }
 
-void BatchShard::get_plan(double out[8]) const
+void BatchShard::get_plan(double out[9]) const
 {
    out[0] = tree_; out[1] = block_; out[2] = (double) lds_bytes_; out[3] = tile_m_; out[4] = solve_mode_;
    out[5] = (double)((160*1024) / ((lds_bytes_ + 1279) / 1280 * 1280)); out[6] = n_tiles_; out[7] = GS_;
+   out[8] = tile_first_;
 }
 
 void BatchShard::get_state(const std::string & which, double * out)
@@ -1779,7 +1780,7 @@ void Batch::gettraj(double * out)
    for_shards([&](size_t k) { shards[k]->gettraj(out + (size_t) offs[k] * n_points * n); }, true);
 }
 
-void Batch::get_plan(double out[8]) { shards[0]->get_plan(out); }
+void Batch::get_plan(double out[9]) { shards[0]->get_plan(out); }
 
 void Batch::get_state(const std::string & which, double * out)
 {

@@ -548,7 +548,9 @@ int orc_batch_get_state(orc_module * mod, int id, const char * which, double * o
       if (std::string(which) == "plan")
       {
          if (cap < 8) throw std::runtime_error("buffer too small!");
-         b.get_plan(out);
+         double plan[9];
+         b.get_plan(plan);
+         std::copy(plan, plan + (cap < 9 ? 8 : 9), out);      // (the first tile's size: appended, read when there is room)
          return;
       }
       if (cap < (size_t) b.n_runs * b.m * b.n) throw std::runtime_error("buffer too small!");

@@ -1431,7 +1431,7 @@ struct Env
 {
    double * red; int * redi; unsigned int * colmask_s;
    long long * phc_s;                      // [8] per-phase cycle counters (diagnostics), thread 0
-   real * T_s, * G_s, * Gc, * W_s, * pos_s, * ax_s, * srad_s, * sinact_s, * jl_s, * r2_s, * pcr_s, * sphpos_s, * base_s;
+   real * T_s, * G_s, * Gc, * W_s, * pos_s, * ax_s, * srad_s, * sinact_s, * jl_s, * r2_s, * pcr_s, * base_s;
    real * T_u;                             // the trajectory as the update phase and the cost sums see it: T_s, or its staged copy (DevBatch::t_staged)
    int * slink_s, * jtype_s, * jcol_s, * slot_s;
    int * jctl_s; DevSdf<real> * sdfs_s; unsigned long long * saff_s, * sallow_s;
@@ -1476,8 +1476,7 @@ __device__ __forceinline__ Env<real> make_env(const BT & b, unsigned char * smem
    E.jtype_s = E.slink_s + S;                              // [nj]
    E.jcol_s = E.jtype_s + nj;                              // [nj]
    E.slot_s = E.jcol_s + nj;                               // [Sa_real] slot of the k-th active sphere (sorted order)
-   E.sphpos_s = E.pcr_s + (((b.pcr_in_lds ? b.pcr_rows : 0)*m + 3) & ~3);   // [Sa][3] + base frame [12]
-   E.base_s = E.sphpos_s + Sa*3;
+   E.base_s = E.pcr_s + (((b.pcr_in_lds ? b.pcr_rows : 0)*m + 3) & ~3);     // base frame [12]
    E.jctl_s = (int *)(smem_raw + L.joints_bytes);
    E.sdfs_s = (DevSdf<real> *)(smem_raw + L.sdfs_bytes);
    E.saff_s = (unsigned long long *)(smem_raw + L.saff_bytes);
@@ -1489,7 +1488,7 @@ __device__ __forceinline__ Env<real> make_env(const BT & b, unsigned char * smem
    mod.Sa_real = b.ms.Sa_real; mod.placed = b.ms.placed; mod.live_mask = b.ms.live_mask; mod.slot_of = E.slot_s;
    mod.base_sph_begin = b.ms.base_sph_begin; mod.base_sph_end = b.ms.base_sph_end;
    mod.base_R = E.base_s; mod.base_t = E.base_s + 9;
-   mod.jctl = E.jctl_s; mod.sph_pos = (const real (*)[3]) E.sphpos_s; mod.sph_affects = E.saff_s; mod.sph_allowed = E.sallow_s;
+   mod.jctl = E.jctl_s; mod.sph_affects = E.saff_s; mod.sph_allowed = E.sallow_s;
    mod.jpk = (const __attribute__((address_space(4))) int *) b.model->jpacked;
    mod.jpk2 = (const __attribute__((address_space(4))) int *) b.model->jpacked2;
    mod.sph_pos_c = (const __attribute__((address_space(4))) real (*)[3]) b.model->sph_pos;
@@ -1559,7 +1558,6 @@ __device__ __attribute__((noinline)) void phase_setup(const void * kp)
       E.jctl_s[2*e] = J.packed;
       E.jctl_s[2*e+1] = (J.aff_begin & 255) | ((J.aff_end & 255) << 8) | ((J.type & 255) << 16) | ((J.col & 255) << 24);
    }
-   for (int e=tid; e<Sa*3; e+=BLOCK) E.sphpos_s[e] = gmod.sph_pos[e/3][e%3];
    for (int e=tid; e<(E.mod.placed ? E.mod.Sa : E.mod.Sa_real); e+=BLOCK) E.slot_s[e] = gmod.slot_of[e];      // (placed: all 16 entries, see DevModel::slot_of)
    for (int e=tid; e<Sa; e+=BLOCK) E.saff_s[e] = gmod.sph_affects[e];
    for (int e=tid; e<12; e+=BLOCK) E.base_s[e] = (e < 9) ? gmod.base_R[e] : gmod.base_t[e-9];
@@ -2414,13 +2412,11 @@ void collision_verdict_kernel(DevVerdict<real> v)
    real * rows_s = lds;                                              // [chunk][n]
    real * pos_s = rows_s + ((chunk*n + 3) & ~3);                        // [chunk][pstr]
    real * ax_s = pos_s + ((chunk*pstr + 3) & ~3);                       // [chunk][astr]
-   real * sphpos_s = ax_s + ((chunk*astr + 3) & ~3);                    // [Sa][3]
-   real * base_s = sphpos_s + ((Sa*3 + 3) & ~3);                     // [12]
+   real * base_s = ax_s + ((chunk*astr + 3) & ~3);                      // [12]
    real * srad_s = base_s + 12;                                      // [Sa]
    int * slot_s = (int *)(srad_s + ((Sa + 3) & ~3));                 // [Sa_real]
    int * xml_s = slot_s + ((gmod.Sa_real + 3) & ~3);                 // [Sa]
    int * jctl_s = xml_s + ((Sa + 3) & ~3);                            // [nj][2]
-   for (int e=tid; e<Sa*3; e+=ORC_BLOCK) sphpos_s[e] = gmod.sph_pos[e/3][e%3];
    for (int e=tid; e<12; e+=ORC_BLOCK) base_s[e] = (e < 9) ? gmod.base_R[e] : gmod.base_t[e-9];
    for (int e=tid; e<Sa; e+=ORC_BLOCK) { srad_s[e] = gmod.sph_radius[e]; xml_s[e] = v.slot_xml[e]; }
    for (int e=tid; e<gmod.Sa_real; e+=ORC_BLOCK) slot_s[e] = gmod.slot_of[e];
@@ -2431,7 +2427,7 @@ void collision_verdict_kernel(DevVerdict<real> v)
    mod.base_sph_begin = gmod.base_sph_begin; mod.base_sph_end = gmod.base_sph_end; mod.jt_scan = 0;
    mod.Sa_real = gmod.Sa_real; mod.placed = gmod.placed; mod.live_mask = gmod.live_mask; mod.slot_of = slot_s;
    mod.base_R = base_s; mod.base_t = base_s + 9;
-   mod.jctl = jctl_s; mod.sph_pos = (const real (*)[3]) sphpos_s; mod.sph_affects = nullptr; mod.n_static = 0; mod.empty_mask = 0u;
+   mod.jctl = jctl_s; mod.sph_affects = nullptr; mod.n_static = 0; mod.empty_mask = 0u;
    mod.jpk = (const __attribute__((address_space(4))) int *) gmod.jpacked;
    mod.jpk2 = (const __attribute__((address_space(4))) int *) gmod.jpacked2;
    mod.sph_pos_c = (const __attribute__((address_space(4))) real (*)[3]) gmod.sph_pos;
@@ -2752,7 +2748,7 @@ size_t orc_verdict_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_siz
 {
    const int pstr = (Sa*3) | 1, astr = (nj*6) | 1;
    auto r4 = [](int x) { return (x + 3) & ~3; };
-   size_t reals = (size_t) r4(chunk*n) + r4(chunk*pstr) + r4(chunk*astr) + r4(Sa*3) + 12 + r4(Sa);
+   size_t reals = (size_t) r4(chunk*n) + r4(chunk*pstr) + r4(chunk*astr) + 12 + r4(Sa);
    size_t ints = (size_t) r4(Sa_real) + r4(Sa);
    return 16 + reals * real_size + ints * 4 + (size_t) nj * 8 + 64;
 }

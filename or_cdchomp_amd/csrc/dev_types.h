@@ -330,7 +330,6 @@ struct ModelView
    const real * base_R;                    // [9]
    const real * base_t;                    // [3]
    const int * jctl;                       // [nj][2] control words of a joint: DevJoint::packed, and aff_begin | aff_end << 8 | type << 16 | col << 24
-   const real (* sph_pos)[3];              // [Sa][3]
    const unsigned long long * sph_affects; // [Sa]
    const unsigned long long * sph_allowed; // [64] bit o of entry s: sphere o is active and rides on another link than sphere s (many-sphere path)
    const __attribute__((address_space(4))) int * jpk;    // [nj] DevModel::jpacked (global memory, scalar loads)
@@ -387,7 +386,7 @@ inline LdsLayout lds_layout(int np, int n, int Sa, int S, int nj, int tile_m, in
    L.jl = take(2*n);
    L.r2 = take(8*16);                      // squared ranges of the self-collision row rotations [8][16]
    L.pcr = take(pcr_rows*m);
-   (void) take(Sa*3 + 12);                 // staged sphere local positions + base frame (after pcr)
+   (void) take(12);                        // staged base frame (after pcr; the sphere tables are read by scalar loads)
    L.end_reals = o;
    L.ints_bytes = ORC_LDS_HEADER + o*real_size;
    int bytes = L.ints_bytes + (S + 2*nj + 4 + Sa) * (int) sizeof(int);     // slink, jtype, jcol, slot_of

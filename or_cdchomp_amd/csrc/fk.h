@@ -201,7 +201,7 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
       if (first)
          for (int s=mod.base_sph_begin; s<mod.base_sph_end; s++)
          {
-            const real * lp = mod.sph_pos[s];
+            const __attribute__((address_space(4))) real * lp = mod.sph_pos_c[s];      // (s is uniform: scalar loads)
             const real o = base.r[0]*lp[0] + base.r[1]*lp[1] + base.r[2]*lp[2] + base.t;
             if (valid) pos_k[mod.slot_of[s]*3] = o;
          }

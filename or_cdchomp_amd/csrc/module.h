@@ -167,7 +167,7 @@ public:
    void sync_begin(double * costs_out, int * status_out, int * iters_out);   // enqueue the copies
    void sync_end();                                                          // wait for them
    void gettraj(double * out);
-   void get_plan(double out[8]) const;      // kernel variant bits, threads per workgroup, LDS bytes, tile, solve mode, workgroups per CU, tiles, lanes per waypoint
+   void get_plan(double out[9]) const;      // kernel variant bits, threads per workgroup, LDS bytes, tile, solve mode, workgroups per CU, tiles, lanes per waypoint, first tile
    void get_state(const std::string & which, double * out);
    void get_trace(double * out);
    void set_noise(const double * noise, int n_blocks);
@@ -263,7 +263,7 @@ public:
    void iterate_async(int n_iter, int iter_begin = 0, bool final_eval = true, bool carry = false);
    void sync(double * costs_out, int * status_out, int * iters_out = nullptr);
    void gettraj(double * out);
-   void get_plan(double out[8]);            // the plan of the first shard (all shards of a batch plan alike)
+   void get_plan(double out[9]);            // the plan of the first shard (all shards of a batch plan alike)
    void get_state(const std::string & which, double * out);
    void get_trace(double * out);
    void set_noise(const double * noise, int n_blocks);

@@ -337,9 +337,10 @@ class Module:
 
     def batch_plan(self, bid):
         """what the planner chose for this batch (orc_batch_get_state "plan")"""
-        out = np.zeros(8)
+        out = np.zeros(9)
         self._check(self._lib.orc_batch_get_state(self._h, bid, b"plan", _dp(out), out.size))
-        keys = ("variant", "threads", "lds_bytes", "tile_m", "solve_mode", "workgroups_per_cu", "tiles", "lanes_per_waypoint")
+        keys = ("variant", "threads", "lds_bytes", "tile_m", "solve_mode", "workgroups_per_cu", "tiles", "lanes_per_waypoint",
+                "tile_first")
         return {k: int(v) for k, v in zip(keys, out)}
 
     def batch_state(self, bid, which):
