@@ -62,7 +62,10 @@ int orc_set_num_streams(orc_module * mod, int n);
  * (iteration, seconds, cost_total, cost_obs, cost_smooth; mod.cpp:2306-2310, 2811-2818); the seconds
  * are wall seconds since the iterate call began (the reference: thread CPU seconds), a fused launch's
  * interval divided evenly over its iterations.  createbatch takes a pattern with %d = run index, and
- * `devices 'i j ...'` to shard one batch over GPUs (see orc_module_new_multi). */
+ * `devices 'i j ...'` to shard one batch over GPUs (see orc_module_new_multi).  iterate / iteratebatch
+ * take `converge_rtol F`, `converge_patience N` and `converge_obs F`: the convergence stop of
+ * orc_batch_set_convergence for that call only (tokens not given keep the batch's setting, patience
+ * defaults to 1); a run that converges reports status 1, and only status -1 throws. */
 int orc_send_command(orc_module * mod, const char * cmd, char * out, size_t out_cap);
 /* size in bytes (without NUL) of the full reply of the last successful command */
 size_t orc_last_reply_size(const orc_module * mod);
@@ -240,18 +243,34 @@ int orc_batch_create_scenes(orc_module * mod, const char * robot, const orc_batc
 /* replaces mod::iterate (src/orcdchomp_mod.cpp:2690-2852): n_iter iterations of
  * cd_chomp_iterate (src/libcd/chomp.c:430-683) for every run, then the final
  * cost evaluation.  costs_out [n_runs][3] = total, obs, smooth (may be NULL);
- * status_out [n_runs]: 0 ok, -1 "Resulting trajectory is outside of joint limits!". */
+ * status_out [n_runs]: 0 ok, -1 "Resulting trajectory is outside of joint limits!", 1 the run
+ * converged and stopped early (orc_batch_set_convergence; not an error). */
 int orc_batch_iterate(orc_module * mod, int batch_id, int n_iter, double * costs_out, int * status_out);
 /* A run that leaves its joint limits stops iterating for the rest of THAT call (the reference throws
  * out of mod::iterate, src/orcdchomp_mod.cpp:2799-2803) and reports status -1 and the costs of its
  * last complete iteration; the run stays usable and a later call iterates it again, as in the
- * reference.  Iterations each run completed in the last call: iters_out [n_runs]. */
+ * reference.  A run that converged (status 1) made k+1 <= n_iter iterations and reports the final
+ * costs of a call of k+1 iterations.  Iterations each run completed in the last call: iters_out [n_runs]. */
 int orc_batch_iterations_done(orc_module * mod, int batch_id, int * iters_out);
+/* Convergence stop for the batch's later iterate calls (orc_batch_iterate, _iterate_async, the
+ * iterate / iteratebatch commands), on the device, per run.  With tot_k = obs_k + smooth_k the costs
+ * of iteration k (the trace's row k), iteration k is settled when it has a predecessor k-1 in the
+ * same call, |tot_{k-1} - tot_k| <= rtol |tot_{k-1}| and obs_k <= obs_max.  A streak counter starts
+ * at 0 in every call, counts settled iterations and drops to 0 on an unsettled one; the run stops
+ * after completing the first iteration at which it reaches patience, with status 1.  A stopped run
+ * is exactly a run whose call had n_iter = k+1 (trajectory, final costs, "AG", iterations done); its
+ * trace rows from k+1 on are NaN.  A run that leaves its joint limits first reports -1 as before.
+ * patience <= 0 switches the stop off (the default).  A NaN or non-positive rtol or a NaN obs_max
+ * is rejected with a nonzero return; the batch keeps its previous setting.  obs_max: +inf for none.
+ * HMC runs: the call's momentum resamples are planned for all n_iter iterations, so after a stop the
+ * random stream is where a full-length call leaves it (as after a run that left its limits). */
+int orc_batch_set_convergence(orc_module * mod, int batch_id, double rtol, int patience, double obs_max);
 /* asynchronous form for measurement: enqueue only, results stay on the device */
 int orc_batch_iterate_async(orc_module * mod, int batch_id, int n_iter);
 int orc_batch_sync(orc_module * mod, int batch_id, double * costs_out, int * status_out);
 /* per-iteration cost trace of the last iterate call: [n_runs][n_iter][3] (total, obs, smooth as the
- * reference logs them, mod.cpp:2798); rows of iterations an aborted run did not complete are NaN */
+ * reference logs them, mod.cpp:2798); rows of iterations an aborted (status -1) or converged
+ * (status 1) run did not make are NaN */
 int orc_batch_get_trace(orc_module * mod, int batch_id, double * trace_out, size_t cap_doubles);
 /* momentum noise for HMC resampling supplied by the caller instead of the module's
  * own mt19937 stream: noise [n_runs][n_blocks][m][n] (used in resample order) */

@@ -77,6 +77,7 @@ SYMBOLS = [
     ("orc_batch_iterations_done", C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     ("orc_batch_get_trace", C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_size_t]),
     ("orc_batch_set_noise", C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int]),
+    ("orc_batch_set_convergence", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double]),
     ("orc_batch_gettraj", C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_size_t]),
     ("orc_batch_collision_verdict", C.c_int, [C.c_void_p, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p]),
     ("orc_batch_get_state", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, c_double_p, C.c_size_t]),

@@ -334,6 +334,10 @@ void BatchShard::construct(const Robot & robot, const double * starts, const dou
    d_status_ = dev_alloc<int>(n_runs);
    d_iters_done_ = dev_alloc<int>(n_runs);
    d_leap_ = dev_alloc<int>(n_runs);
+   d_conv_prev_ = dev_alloc<double>(n_runs);
+   d_conv_streak_ = dev_alloc<int>(n_runs);
+   hip_check(hipMemsetAsync(d_conv_prev_, 0, n_runs*sizeof(double), st), "memset");
+   hip_check(hipMemsetAsync(d_conv_streak_, 0, n_runs*sizeof(int), st), "memset");
    hip_check(hipMemsetAsync(d_costs_, 0, (size_t) n_runs*3*sizeof(double), st), "memset");
    hip_check(hipMemsetAsync(d_status_, 0, n_runs*sizeof(int), st), "memset");
    hip_check(hipMemsetAsync(d_iters_done_, 0, n_runs*sizeof(int), st), "memset");
@@ -395,7 +399,7 @@ void BatchShard::release()
                      (void **) &d_hmc_next_bak_, (void **) &d_overflow_, (void **) &d_costs_, (void **) &d_trace_, (void **) &d_status_,
                      (void **) &d_iters_done_, (void **) &d_leap_, &d_Aband_, &d_beta_s_, &d_beta_g_, &d_metric64_, &d_pcr_, &d_Ainv_, &d_jl_lo_, &d_jl_hi_,
                      (void **) &d_hmc_iters_, &d_noise_, (void **) &d_phase_, &d_Gcost_, &d_tsrs_, &d_tsr_ws_, (void **) &d_tsr_err_,
-                     (void **) &d_scene_of_run_, (void **) &d_scene_nsdf_ };
+                     (void **) &d_scene_of_run_, (void **) &d_scene_nsdf_, (void **) &d_conv_prev_, (void **) &d_conv_streak_ };
    for (void ** p : all) { dev_free(*p); *p = nullptr; }
    sdf_refs_.clear();
    for (int k=0; k<2; k++) if (ev_plan_[k]) { (void) hipEventDestroy(ev_plan_[k]); ev_plan_[k] = nullptr; }
@@ -1504,6 +1508,9 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    b.jl_lo = (const real *) d_jl_lo_; b.jl_hi = (const real *) d_jl_hi_;
    b.hmc_iters = d_hmc_iters_; b.noise = (const real *) d_noise_; b.max_resamples = max_resamples_;
    b.n_iter = n_iter; b.final_eval = final_eval ? 1 : 0; b.carry_status = carry ? 1 : 0;
+   b.conv_patience = conv.patience > 0 ? conv.patience : 0;
+   b.conv_rtol = conv.rtol; b.conv_obs_max = conv.obs_max;
+   b.conv_prev = d_conv_prev_; b.conv_streak = d_conv_streak_;      // (a launch that starts a call does not read them)
    b.phase_cycles = d_phase_;
    b.pcr_in_lds = pcr_in_lds_; b.pcr_sym = pcr_sym_; b.pcr_rows = pcr_rows_; b.ag_in_lds = ag_in_lds_;
    b.stagger_mode = stagger_mode_; b.stagger_sleeps = stagger_sleeps_; b.lim_generic = lim_generic_;
@@ -1763,6 +1770,21 @@ void Batch::iterate_async(int n_iter, int iter_begin, bool final_eval, bool carr
    last_n_iter = n_iter;
    // one host thread per shard: each asserts its device and launches there (the hmc plan of a shard may wait for its device)
    for_shards([&](size_t k) { shards[k]->iterate_async(n_iter, iter_begin, final_eval, carry); }, true);
+}
+
+void ConvergenceSpec::validate() const
+{
+   if (patience <= 0) return;
+   if (!(rtol > 0.0)) throw std::runtime_error("convergence: rtol must be a number > 0!");
+   if (std::isnan(obs_max)) throw std::runtime_error("convergence: obs_max must not be NaN!");
+}
+
+void Batch::set_convergence(const ConvergenceSpec & c)
+{
+   c.validate();
+   ConvergenceSpec v = c;
+   if (v.patience <= 0) v = ConvergenceSpec();
+   for (auto & s : shards) s->conv = v;
 }
 
 void Batch::sync(double * costs_out, int * status_out, int * iters_out)

@@ -480,6 +480,15 @@ int orc_batch_iterate(orc_module * mod, int id, int n_iter, double * costs_out, 
    });
 }
 
+int orc_batch_set_convergence(orc_module * mod, int id, double rtol, int patience, double obs_max)
+{
+   return guarded(mod, [&] {
+      orc::ConvergenceSpec c;
+      c.rtol = rtol; c.patience = patience; c.obs_max = obs_max;
+      mod->impl->batch(id).set_convergence(c);
+   });
+}
+
 int orc_batch_iterate_async(orc_module * mod, int id, int n_iter)
 {
    return guarded(mod, [&] { mod->impl->batch(id).iterate_async(n_iter); });

@@ -1515,6 +1515,46 @@ __device__ __forceinline__ Env<real> make_env(const BT & b, unsigned char * smem
 
 extern __shared__ __align__(16) unsigned char orc_smem[];
 
+// ---- convergence stop (orc_batch_set_convergence) ----
+// Its state lives in free bytes of the LDS header, and the phase functions keep it (not the kernel's loop: the loop's
+// scalars are held across the phase calls, and one more of them spills on the headline kernel): the previous iteration's
+// total cost in this call (NaN: none yet, so that the call's first iteration is never settled), the settled iterations in
+// a row, and the stop flag the loop reads.  A launch that continues a call (carry_status) picks up where the last one left
+// it (DevBatch::conv_prev / conv_streak, written back by phase_finish).
+#define ORC_LDS_CONV 176      // bytes [176, 192) of the header: after the timer mark, before the phase counters
+struct ConvState { double prev; int streak, stop; };
+static_assert(ORC_LDS_CONV + sizeof(ConvState) <= ORC_LDS_HEADER - 64, "the convergence state overlaps the phase counters");
+__device__ __forceinline__ ConvState * conv_state() { return (ConvState *)(orc_smem + ORC_LDS_CONV); }
+
+// phase_setup, thread 0 (a barrier follows): the stop flag is clear in every launch
+template <typename real>
+__device__ __forceinline__ void conv_begin(KArg<real> & b, int run)
+{
+   ConvState * cs = conv_state();
+   cs->stop = 0;
+   if (b.conv_patience)
+   {
+      cs->prev = b.carry_status ? b.conv_prev[run] : __longlong_as_double(0x7ff8000000000000LL);
+      cs->streak = b.carry_status ? b.conv_streak[run] : 0;
+   }
+}
+
+// phase_costs, after a complete iteration with costs (obs, smooth) (workgroup-uniform): the rule of convergence_stop
+// (or_cdchomp_amd/module.py); raises the stop flag when the streak reaches the patience
+template <typename real>
+__device__ __forceinline__ void conv_step(KArg<real> & b, double obs_in, double smooth_in)
+{
+   ConvState * cs = conv_state();
+   const double obs = unir(obs_in), smooth = unir(smooth_in);
+   const double tot = obs + smooth;                  // (the trace's column 0)
+   const double prev = unir(cs->prev);
+   const bool settled = ::fabs(prev - tot) <= b.conv_rtol * ::fabs(prev) && obs <= b.conv_obs_max;
+   const int streak = settled ? uni(cs->streak) + 1 : 0;
+   __syncthreads();                                  // (every wavefront has read the state)
+   if (threadIdx.x == 0) { cs->prev = tot; cs->streak = streak; cs->stop = (streak >= b.conv_patience) ? 1 : 0; }
+   __syncthreads();
+}
+
 #include "tsr.h"
 
 // per-phase cycle counters (diagnostics: b.phase_cycles == null in production), kept in the LDS header
@@ -1583,6 +1623,7 @@ __device__ __attribute__((noinline)) void phase_setup(const void * kp)
    if (b.use_momentum && b.ag_in_lds) for (int e=tid; e<mn; e+=BLOCK) E.AG_s[e] = E.AG_g[e];
    if (tid < 2) E.colmask_s[tid] = 0u;
    if (tid < 8) E.phc_s[tid] = 0;
+   if (tid == 0) conv_begin<real>(b, blockIdx.x);
    __syncthreads();
 
    if (!GS16 && b.ms.pr_rounds == 0 && tid < 64)
@@ -1893,7 +1934,8 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    else if (!b.use_momentum)
    {
       // AG = X is not carried between iterations: keep only the last one (read-back state)
-      const bool keep = (it == b.n_iter - 1) || (!LEAN && b.Gdbg != nullptr);
+      // (with the convergence stop on, every iteration may be the run's last: AG is kept every time)
+      const bool keep = (it == b.n_iter - 1) || (!LEAN && b.Gdbg != nullptr) || b.conv_patience != 0;
       for (int e=tid; e<mn; e+=BLOCK)
       {
          const real x = X[e];
@@ -2197,6 +2239,7 @@ __device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int 
       }
       __syncthreads();
    }
+   if (b.conv_patience && do_iteration) conv_step<real>(b, pc.obs, pc.smooth);
    return pc;
 }
 
@@ -2206,11 +2249,19 @@ __device__ __attribute__((noinline)) void phase_finish(const void * kp, int stat
    double done_obs, double done_smooth)
 {
    KArg<real> & b = *uniform_kernarg<real>(kp);
-   const int status = uni(status_in), iters_done = uni(iters_done_in), leapfrog_first = uni(leapfrog_first_in), have_costs = uni(have_costs_in);
+   int status = uni(status_in);
+   const int iters_done = uni(iters_done_in), leapfrog_first = uni(leapfrog_first_in), have_costs = uni(have_costs_in);
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
    const int run = blockIdx.x, tid = threadIdx.x;
    const int n = b.n, m = b.m, np = b.n_points, mn = m*n;
    __syncthreads();
+   // a run the convergence stop ended (in this launch, or in an earlier one of the call) reports status 1
+   if (b.conv_patience)
+   {
+      const ConvState * cs = conv_state();
+      if (status == 0 && uni(cs->streak) >= b.conv_patience) status = 1;
+      if (tid == 0) { b.conv_prev[run] = cs->prev; b.conv_streak[run] = cs->streak; }
+   }
    if (b.t_in_lds)
    {
       const int skip = b.free_start ? n : 0;
@@ -2255,8 +2306,9 @@ void chomp_iterate_kernel(const DevBatch<real> b)
    const int tid = threadIdx.x;
 
    // a launch that continues an iterate call: the run left its joint limits in an earlier launch of the call, the
-   // reference has thrown out of the call by now (workgroup-uniform)
-   if (b.carry_status && b.status[run] != 0) return;
+   // reference has thrown out of the call by now (workgroup-uniform).  A run that converged in an earlier launch of the
+   // call (status 1) makes no more iterations, but takes the call's final cost-only pass (n_iter == 0)
+   if (b.carry_status && b.status[run] != 0 && (b.status[run] != 1 || b.n_iter != 0)) return;
 
    phase_setup<real, TREE, GS16, BLOCK, WGS>(kp);
 
@@ -2283,6 +2335,11 @@ void chomp_iterate_kernel(const DevBatch<real> b)
    for (int it=0; it<total_passes; it++)
    {
       const bool do_iteration = (it < b.n_iter);
+      // the convergence stop (orc_batch_set_convergence): phase_costs raised the flag after the run's last complete
+      // iteration; its remaining iterations are passed over, on to the final cost-only pass, so that the run ends exactly
+      // where a call of that many iterations leaves it.  (Passing over rather than leaving the loop: a loop exit or a jump
+      // of `it` costs the headline kernel 16 bytes of scratch, this an LDS read per iteration)
+      if (do_iteration && uni(conv_state()->stop)) continue;
 
       // ---- hmc momentum resample (src/orcdchomp_mod.cpp:2755-2768) ----------
       if (do_iteration && b.use_hmc && b.use_momentum && next_resample < b.max_resamples
@@ -2352,6 +2409,7 @@ void chomp_iterate_kernel(const DevBatch<real> b)
       }
       done_obs = pc.obs; done_smooth = pc.smooth; have_costs = 1;
       if (do_iteration) iters_done++;
+
    }
 
    phase_finish<real, GS16, BLOCK, WGS>(kp, status, iters_done, leapfrog_first, have_costs, done_obs, done_smooth);

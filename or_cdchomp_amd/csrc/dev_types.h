@@ -218,8 +218,8 @@ struct DevBatch
    real * Gcost;           // [n_runs][m][n]: where the cost phase puts its gradient rows when !g_in_lds
    double * costs;         // [n_runs][3] total, obs, smooth
    double * trace;         // [n_runs][n_iter][3] or null
-   int * status;           // [n_runs] of this launch: 0, or -1 "outside of joint limits"
-   int * iters_done;       // [n_runs] iterations this launch completed (n_iter unless the run aborted)
+   int * status;           // [n_runs] of this launch: 0, -1 "outside of joint limits", or 1 converged (conv_patience)
+   int * iters_done;       // [n_runs] iterations this launch completed (n_iter unless the run aborted or converged)
    int * leapfrog_first;   // [n_runs]
    // run parameters
    real dt, inv_2dt, inv_dt2, lambda, inv_m;
@@ -246,6 +246,7 @@ struct DevBatch
    int n_iter;
    int final_eval;
    int carry_status;       // this launch continues an iterate call (one launch per iteration: max_time, trajs_fileformstr): a run that left its joint limits in an earlier launch of the call stays out, iters_done accumulates
+                           // (a run that converged stays out of the iteration launches but takes the final cost-only launch, n_iter == 0)
    long long * phase_cycles; // [n_runs][8] or null: diagnostics (cycles per phase, wave 0)
    real a_diag, a_off;     // D == 1: A = tridiag(a_off, a_diag, a_off), B couples the end rows with a_off
    int pcr_in_lds;         // the cyclic-reduction tables are staged in LDS
@@ -283,6 +284,13 @@ struct DevBatch
    real band_c[ORC_SS_MAX_RANK + 1];
    double band_c64[ORC_SS_MAX_RANK + 1];
    int ss_rank;
+   // convergence stop (orc_batch_set_convergence): iteration k of a call is settled when it has a predecessor k-1 in the call,
+   // |tot_{k-1} - tot_k| <= conv_rtol |tot_{k-1}| and obs_k <= conv_obs_max (tot = obs + smooth, the trace's doubles); the run
+   // stops with status 1 after the iteration at which conv_patience settled iterations follow one another.  0: off
+   int conv_patience;
+   double conv_rtol, conv_obs_max;
+   double * conv_prev;        // [n_runs] tot of the run's last iteration in this call (NaN: none yet): carried between the launches of a call
+   int * conv_streak;         // [n_runs] settled iterations in a row (carry_status launches continue it)
 };
 
 // Collision verdict of the trajectories of a batch (the step after the path: gettraj's re-check,

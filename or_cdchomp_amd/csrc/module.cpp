@@ -1,6 +1,7 @@
 // module.cpp -- environment stand-ins, SDF commands, command grammar.
 // Reference: src/orcdchomp_mod.cpp (commands), src/orcwrap.cpp (argv adaptor).
 #include "module.h"
+#include <algorithm>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -1197,6 +1198,23 @@ int parse_run(const std::vector<std::string> & argv, int & i, int & run, const c
    run = v;
    return v;
 }
+
+double parse_conv_double(const std::string & s, const char * what)
+{
+   char * end = nullptr;
+   const double v = std::strtod(s.c_str(), &end);
+   if (end == s.c_str() || *end) throw std::runtime_error(std::string("Could not parse ") + what + "!");
+   return v;
+}
+
+// puts a batch's convergence stop back as it was when the iterate call began (converge_* tokens hold for one call)
+struct ConvergenceRestore
+{
+   Batch & b;
+   ConvergenceSpec saved;
+   explicit ConvergenceRestore(Batch & batch) : b(batch), saved(batch.convergence()) {}
+   ~ConvergenceRestore() { try { b.set_convergence(saved); } catch (...) {} }
+};
 }
 
 // src/orcdchomp_mod.cpp:2690-2852
@@ -1207,12 +1225,25 @@ std::string Module::cmd_iterate(const std::vector<std::string> & argv, bool batc
    std::string fileform;
    bool have_fileform = false;
    double * costs_ptr = nullptr; int * status_ptr = nullptr;
+   // the convergence stop for this call only (converge_*: the batch's own setting, overridden token by token)
+   bool have_rtol = false, have_obs = false, have_patience = false;
+   ConvergenceSpec call_conv;
    const int argc = (int) argv.size();
    int i;
    for (i=1; i<argc; i++)
    {
       if (argv[i] == "run" && i+1 < argc) parse_run(argv, i, run, "Only one r can be passed!");
       else if (argv[i] == "n_iter" && i+1 < argc) n_iter = std::atoi(argv[++i].c_str());
+      else if (argv[i] == "converge_rtol" && i+1 < argc) { call_conv.rtol = parse_conv_double(argv[++i], "converge_rtol"); have_rtol = true; }
+      else if (argv[i] == "converge_obs" && i+1 < argc) { call_conv.obs_max = parse_conv_double(argv[++i], "converge_obs"); have_obs = true; }
+      else if (argv[i] == "converge_patience" && i+1 < argc)
+      {
+         char * end = nullptr;
+         const long v = std::strtol(argv[++i].c_str(), &end, 10);
+         if (end == argv[i].c_str() || *end) throw std::runtime_error("Could not parse converge_patience!");
+         call_conv.patience = (int) std::max(-1L, std::min(v, 1L << 30));
+         have_patience = true;
+      }
       else if (argv[i] == "max_time" && i+1 < argc) max_time = std::atof(argv[++i].c_str());
       else if (argv[i] == "trajs_fileformstr" && i+1 < argc) { fileform = argv[++i]; have_fileform = true; }
       else if (batchmode && argv[i] == "costs" && i+1 < argc) costs_ptr = (double *) parse_pointer(argv[++i]);
@@ -1223,6 +1254,19 @@ std::string Module::cmd_iterate(const std::vector<std::string> & argv, bool batc
    if (!run) throw std::runtime_error("you must pass a created run!");
    if (n_iter < 0) throw std::runtime_error("n_iter must be >=0!");
    Batch & b = batch(run);
+   std::unique_ptr<ConvergenceRestore> conv_restore;
+   if (have_rtol || have_obs || have_patience)
+   {
+      // tokens not given keep the batch's setting; the stop is on (patience 1) unless converge_patience says otherwise
+      const ConvergenceSpec cur = b.convergence();
+      ConvergenceSpec c = cur;
+      if (have_rtol) c.rtol = call_conv.rtol;
+      if (have_obs) c.obs_max = call_conv.obs_max;
+      c.patience = have_patience ? call_conv.patience : (cur.patience > 0 ? cur.patience : 1);
+      conv_restore.reset(new ConvergenceRestore(b));
+      b.set_convergence(c);
+   }
+   const bool conv_on = b.convergence().patience > 0;
    std::vector<double> costs((size_t) b.n_runs * 3, 0.0);
    std::vector<int> status(b.n_runs, 0), iters(b.n_runs, 0);
    if (have_fileform && b.params.floating_base)
@@ -1288,10 +1332,12 @@ std::string Module::cmd_iterate(const std::vector<std::string> & argv, bool batc
             for (int k=0; k<b.n_runs; k++) made[k] = iters[k] - before[k];
             b.write_dat(it, 1, made.data(), t_begin, t_end);
          }
-         for (int k=0; k<b.n_runs; k++) if (st1[k] != 0) { status[k] = st1[k]; aborted = true; }
+         // status 1: the run converged (it makes no more iterations in this call but takes the final cost-only pass)
+         for (int k=0; k<b.n_runs; k++) if (st1[k] != 0) { status[k] = st1[k]; if (st1[k] == -1) aborted = true; }
          // a single run stops where the reference throws; a batch goes on for its other runs
          if (aborted && b.n_runs == 1) break;
          if (t_end > max_time) break;
+         if (conv_on && std::all_of(status.begin(), status.end(), [](int v) { return v != 0; })) break;      // nothing left to iterate
       }
       if (!(aborted && b.n_runs == 1))
       {

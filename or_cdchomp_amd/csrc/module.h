@@ -6,6 +6,7 @@
 // third party; the pieces of it the hot path reads are held here explicitly.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <functional>
@@ -147,6 +148,16 @@ struct BatchParams
    int workgroups_per_cu = 0;   // 0: the module's setting (orc_set_workgroups_per_cu)
 };
 
+// the convergence stop of a batch's runs (orc_batch_set_convergence; dev_types.h DevBatch::conv_*): patience 0 is off
+struct ConvergenceSpec
+{
+   double rtol = 0.0;
+   int patience = 0;
+   double obs_max = HUGE_VAL;
+   // rejects a NaN or non-positive rtol and a NaN obs_max when the stop is on (throws)
+   void validate() const;
+};
+
 class Module;
 
 // a contiguous block of the runs of a batch on ONE device: n_runs independent runs sharing robot,
@@ -182,6 +193,7 @@ public:
 
    int n_runs, n_points, n, m;
    BatchParams params;
+   ConvergenceSpec conv;           // sticky for the later iterate calls (Batch::set_convergence)
    int last_n_iter = 0;
    int device;
    std::string robot_name;
@@ -210,6 +222,7 @@ private:
    void * d_model_ = nullptr; void * d_sdfs_ = nullptr; void * d_sdfc_ = nullptr;
    void * d_traj_ = nullptr; void * d_AG_ = nullptr; void * d_G_ = nullptr; void * d_Gcost_ = nullptr;
    double * d_costs_ = nullptr; double * d_trace_ = nullptr; size_t trace_cap_ = 0;
+   double * d_conv_prev_ = nullptr; int * d_conv_streak_ = nullptr;      // [n_runs] the convergence stop's state between the launches of a call
    int * d_status_ = nullptr; int * d_iters_done_ = nullptr; int * d_leap_ = nullptr; long long * d_phase_ = nullptr;
    void * d_Aband_ = nullptr; void * d_beta_s_ = nullptr; void * d_beta_g_ = nullptr; void * d_metric64_ = nullptr;
    void * d_pcr_ = nullptr; void * d_Ainv_ = nullptr; void * d_jl_lo_ = nullptr; void * d_jl_hi_ = nullptr;
@@ -272,6 +285,9 @@ public:
                           const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
                           unsigned long long * key_out, double * depth_out);
    void get_phase_cycles(long long * out);
+   // the convergence stop of every shard's runs for the later iterate calls (validated: throws and changes nothing on a bad spec)
+   void set_convergence(const ConvergenceSpec & c);
+   const ConvergenceSpec & convergence() const { return shards[0]->conv; }
    // the per-iteration log of create's dat_filename (src/orcdchomp_mod.cpp:2306-2310, 2811-2818)
    void open_dat(const std::string & pattern);
    void write_dat(int iter_begin, int n_iter, const int * iters_done, double t_begin, double t_end);

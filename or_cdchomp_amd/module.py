@@ -52,6 +52,50 @@ def scenes_to_csr(scenes):
     return begin, names, out
 
 
+def convergence_stop(trace, rtol, patience, obs_max=float("inf")):
+    """The convergence stop of orc_batch_set_convergence, applied to the cost trace of an iterate call made without it.
+
+    trace: [n_iter][3] or [n_runs][n_iter][3] rows (total, obs, smooth) as orc_batch_get_trace returns them, NaN rows
+    for iterations a run did not make.  With tot_k = obs_k + smooth_k, iteration k is settled when k > 0 (the call's first
+    iteration has no predecessor), |tot_{k-1} - tot_k| <= rtol |tot_{k-1}| and obs_k <= obs_max.  The streak of settled
+    iterations starts at 0 and drops to 0 on an unsettled one; the run stops after the first iteration k at which it
+    reaches patience.  Returns (iters, stopped): iters = k+1 where the run stops, else the rows it made (those before its
+    first NaN row); stopped True where it stops.  Arrays of n_runs entries for a 3-d trace, scalars for a 2-d one.
+    Pure: no library call."""
+    tr = np.asarray(trace, dtype=np.float64)
+    if tr.ndim == 2:
+        it, st = convergence_stop(tr[None], rtol, patience, obs_max)
+        return int(it[0]), bool(st[0])
+    if tr.ndim != 3 or tr.shape[2] != 3:
+        raise ValueError("a trace has rows of 3 costs (total, obs, smooth)")
+    if not rtol > 0 or not patience >= 1 or np.isnan(obs_max):
+        raise ValueError("the criterion needs rtol > 0, patience >= 1 and obs_max not NaN")
+    n_runs, n_iter = tr.shape[:2]
+    iters = np.zeros(n_runs, dtype=np.int32)
+    stopped = np.zeros(n_runs, dtype=bool)
+    for r in range(n_runs):
+        made = n_iter
+        for k in range(n_iter):
+            if np.isnan(tr[r, k]).all():
+                made = k
+                break
+        iters[r] = made
+        streak = 0
+        for k in range(made):
+            obs = float(tr[r, k, 1])
+            tot = obs + float(tr[r, k, 2])     # (the kernel's pc.obs + pc.smooth: the same double as the trace's column 0)
+            settled = False
+            if k > 0:
+                prev = float(tr[r, k - 1, 1]) + float(tr[r, k - 1, 2])
+                settled = bool(abs(prev - tot) <= rtol * abs(prev)) and bool(obs <= obs_max)
+            streak = streak + 1 if settled else 0
+            if streak >= patience:
+                iters[r] = k + 1
+                stopped[r] = True
+                break
+    return iters, stopped
+
+
 class Module:
     def __init__(self, device=0):
         """device: one HIP ordinal, or a list of them (batches are then sharded over the list inside
@@ -303,7 +347,7 @@ class Module:
         return costs, status
 
     def batch_iterations_done(self, bid):
-        """iterations every run completed in the last iterate call (n_iter unless it left its joint limits)"""
+        """iterations every run completed in the last iterate call (n_iter unless it left its joint limits or converged)"""
         n_runs = self.batch_dims(bid)[0]
         it = np.zeros(n_runs, dtype=np.int32)
         self._check(self._lib.orc_batch_iterations_done(self._h, bid, _ip(it)))
@@ -314,6 +358,12 @@ class Module:
         tr = np.zeros((n_runs, n_iter, 3))
         self._check(self._lib.orc_batch_get_trace(self._h, bid, _dp(tr), tr.size))
         return tr
+
+    def batch_set_convergence(self, bid, rtol, patience=1, obs_max=float("inf")):
+        """Stop each run of the batch on the device once its cost has settled (orc_batch_set_convergence; the rule is
+        convergence_stop's).  Sticky for the batch's later iterate calls; patience <= 0 switches it off.  A run that
+        stops reports status 1."""
+        self._check(self._lib.orc_batch_set_convergence(self._h, bid, float(rtol), int(patience), float(obs_max)))
 
     def batch_set_noise(self, bid, noise):
         noise = _f64(noise)
