@@ -15,8 +15,8 @@
 // launch wrappers implemented in chomp_kernel.hip
 size_t orc_chomp_lds_bytes(int n_points, int n, int Sa, int S, int nj, int tile_m, int pcr_rows, size_t real_size,
    int use_momentum, int n_sdfs, int flags, int pair_entries);
-hipError_t orc_launch_iterate_f64(const DevBatch<double> & b, size_t lds, hipStream_t stream, int tree);
-hipError_t orc_launch_iterate_f32(const DevBatch<float> & b, size_t lds, hipStream_t stream, int tree);
+hipError_t orc_launch_iterate_f64(const DevBatch<double> & b, size_t lds, hipStream_t stream, int variant);
+hipError_t orc_launch_iterate_f32(const DevBatch<float> & b, size_t lds, hipStream_t stream, int variant);
 hipError_t orc_launch_verdict_f64(const DevVerdict<double> & v, size_t lds, hipStream_t stream, int tree);
 hipError_t orc_launch_verdict_f32(const DevVerdict<float> & v, size_t lds, hipStream_t stream, int tree);
 size_t orc_verdict_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);
@@ -250,8 +250,8 @@ std::vector<int> place_spheres_on_row(const Robot & robot, double eps_self, cons
    return (c_best < c_ident - 0.25) ? best : ident;
 }
 
-hipError_t launch_typed(const DevBatch<double> & b, size_t lds, hipStream_t s, int tree) { return orc_launch_iterate_f64(b, lds, s, tree); }
-hipError_t launch_typed(const DevBatch<float> & b, size_t lds, hipStream_t s, int tree) { return orc_launch_iterate_f32(b, lds, s, tree); }
+hipError_t launch_typed(const DevBatch<double> & b, size_t lds, hipStream_t s, int variant) { return orc_launch_iterate_f64(b, lds, s, variant); }
+hipError_t launch_typed(const DevBatch<float> & b, size_t lds, hipStream_t s, int variant) { return orc_launch_iterate_f32(b, lds, s, variant); }
 
 } // namespace
 
@@ -663,15 +663,13 @@ void BatchShard::build_device(const Robot & robot)
    // self-collision pair list (cost_pairs.h).  The spheres keep their sorted order; inactive ones ride on the free lanes.
    bool pairs = false;
    PairTable ptab;
-   const int n_tsrs_in = (int) params.tsrs.size();
    const int asked_block = mod_->workgroup_threads ? mod_->workgroup_threads : params.workgroup_threads;
-   // (ORC_PAIRS16=1: the robots of the 16-lane family too, an experiment: profiles/r05_ab_experiments.txt)
    // Round 6: trees whose joints move contiguous ranges of the sorted spheres (jt_scan 2: a WAM with its finger dofs active) and
    // fp32 runs take the family too (256-thread workgroups; the latency shape stays an fp64 chain's)
    const bool pair_chain64 = sizeof(real) == 8 && !M.tree && M.jt_scan == 1;
    const bool pair_other = M.GS == 32 && ((M.tree && M.jt_scan == 2) || (!M.tree && M.jt_scan == 1)) && !getenv("ORC_PAIRS_CHAIN64_ONLY");
-   if ((pair_chain64 || pair_other) && (M.GS == 32 || (sizeof(real) == 8 && M.GS == 16 && getenv("ORC_PAIRS16") && !M.floating && nj <= 16 && n_tsrs_in == 0)) && !params.free_start
-       && (asked_block == 0 || asked_block == 256 || (asked_block == 512 && M.GS == 32))
+   if ((pair_chain64 || pair_other) && M.GS == 32 && !params.free_start
+       && (asked_block == 0 || asked_block == 256 || asked_block == 512)
        && !getenv("ORC_NO_PAIRS") && !getenv("ORC_NO_KIND") && !getenv("ORC_BLOCK_THREADS"))
    {
       const int ns = getenv("ORC_NO_STATIC_LANES") ? 0 : std::min((int) inact.size(), M.GS - Sa);
@@ -810,12 +808,12 @@ void BatchShard::build_device(const Robot & robot)
          if (best > 0 && 4 * best_len <= 3 * nj) { M.fk_split = 1; M.fk_nanc = c + 1; M.fk_b_begin = best; }
       }
    }
-   nj_ = nj; Sa_ = lanes; S_ = lanes + (int) inact.size() - n_static; GS_ = M.GS; tree_ = M.tree | ((M.GS == 16) ? 2 : 0);     // kernel variant bits
+   nj_ = nj; Sa_ = lanes; S_ = lanes + (int) inact.size() - n_static; GS_ = M.GS; variant_ = (M.tree ? ORC_VAR_TREE : 0) | ((M.GS == 16) ? ORC_VAR_GS16 : 0);
    if (M.GS == 16 && !M.tree && M.jt_scan == 1 && M.placed && nj <= 16 && !getenv("ORC_NO_KIND"))
-      tree_ |= 16 | (M.floating ? 64 : 0);      // the variants that know all this at compile time (chomp_kernel.hip phase_cost KIND)
+      variant_ |= ORC_VAR_KIND | (M.floating ? ORC_VAR_FLOATING : 0);      // the variants that know all this at compile time (chomp_kernel.hip phase_cost KIND)
    if (M.GS != 16 && !M.floating && M.jt_scan == (M.tree ? 2 : 1) && !getenv("ORC_NO_KIND") && !pairs)
-      tree_ |= 16;                              // many-sphere path: the J^T form is known
-   if (pairs) tree_ |= 512 | (M.floating ? 64 : 0);      // the 32-lane family with the dense pair list
+      variant_ |= ORC_VAR_KIND;                    // many-sphere path: the J^T form is known
+   if (pairs) variant_ |= ORC_VAR_PAIRS | (M.floating ? ORC_VAR_FLOATING : 0);      // the 32-lane family with the dense pair list
    // (the family is a function of the robot and the run, not of the shape asked for: the latency shape -- 512 threads, what the
    // single-run `create` asks for -- exists for the fp64 chain only; a tree or an fp32 run keeps the family at 256 threads, so
    // that a run alone has the bits it has inside a batch)
@@ -989,7 +987,7 @@ void BatchShard::build_device(const Robot & robot)
       hci.data = hsi.data;
       if (nc * sizeof(real) >= (size_t) 1 << 31) throw std::runtime_error("signed distance field too large for this build!");
       // the many-sphere pass forms its cell offsets with 24-bit multiplies (cost_generic.h: signed, both operands below 2^23)
-      if (GS_ != 16 && !(tree_ & 512) && (hci.stride_b[0] >= (1 << 23) || std::max(s.grid.sizes[0], std::max(s.grid.sizes[1], s.grid.sizes[2])) >= (1 << 23)))
+      if (GS_ != 16 && !(variant_ & ORC_VAR_PAIRS) && (hci.stride_b[0] >= (1 << 23) || std::max(s.grid.sizes[0], std::max(s.grid.sizes[1], s.grid.sizes[2])) >= (1 << 23)))
          throw std::runtime_error("signed distance field too large for this build (a y-z plane of 8 MB or more with a robot of more than 16 active spheres)!");
    }
    }
@@ -1004,7 +1002,7 @@ void BatchShard::build_device(const Robot & robot)
    d_scene_of_run_ = dev_alloc<int>(n_runs);
    hip_check(hipMemcpy(d_scene_of_run_, table.scene_of_run.data() + run0_, n_runs*sizeof(int), hipMemcpyHostToDevice), "scene of run");
    // one field with the world's axes in every scene: known at compile time (phase_cost KIND)
-   if ((tree_ & (16 | 512)) && one_aligned) tree_ |= 32 | ((S_ == Sa_) ? 128 : 0);
+   if ((variant_ & (ORC_VAR_KIND | ORC_VAR_PAIRS)) && one_aligned) variant_ |= ORC_VAR_ONE_FIELD | ((S_ == Sa_) ? ORC_VAR_NO_INACT : 0);
 
    // metric tables
    d_Aband_ = upload<real>(metric_.Aband, st);
@@ -1107,7 +1105,7 @@ void BatchShard::build_device(const Robot & robot)
    // can ask for the 192-thread shape for the whole module: orc_set_workgroup_threads (measured, one
    // launch of 1024 WAM runs: 9.3 M it/s against 8.4 M; from 4096 runs on the order is reversed).
    force_block = mod_->workgroup_threads ? mod_->workgroup_threads : params.workgroup_threads;
-   if ((tree_ & 512) && force_block == 512 && !pairs_latency_shape_) force_block = 0;
+   if ((variant_ & ORC_VAR_PAIRS) && force_block == 512 && !pairs_latency_shape_) force_block = 0;
    // orc_set_workgroups_per_cu(4): the fp64 16-lane kernels of a fixed-base chain also exist at 128 VGPRs, four 256-thread
    // workgroups per CU (three tiles instead of two for the WAM): +3 % when launches overlap, -3 % one launch at a time
    int want_wgs = mod_->workgroups_per_cu ? mod_->workgroups_per_cu : params.workgroups_per_cu;
@@ -1118,8 +1116,8 @@ void BatchShard::build_device(const Robot & robot)
    // constrained runs, the 128-thread shape (eight runs per CU: +18 %).  One launch of <= 1024 unconstrained runs at a time
    // is 3 % faster with the kernels' own budget, which is the default there.  3 = "the kernels' own budget", said explicitly.
    const bool overlapping = mod_->num_streams >= 2;
-   const bool can128 = sizeof(real) == 8 && (tree_ & 16) && (tree_ & 2) && !(tree_ & (1 | 64));
-   if (want_wgs == 0 && ((n_tsrs_ > 0 && !(tree_ & 64)) || (tree_ & 512) || (overlapping && !(tree_ & 64)))) want_wgs = 4;
+   const bool can128 = sizeof(real) == 8 && (variant_ & ORC_VAR_KIND) && (variant_ & ORC_VAR_GS16) && !(variant_ & (ORC_VAR_TREE | ORC_VAR_FLOATING));
+   if (want_wgs == 0 && ((n_tsrs_ > 0 && !(variant_ & ORC_VAR_FLOATING)) || (variant_ & ORC_VAR_PAIRS) || (overlapping && !(variant_ & ORC_VAR_FLOATING)))) want_wgs = 4;
    if (want_wgs == 3) want_wgs = 0;
    // (the planner's own 128 is a preference, tried in a pass of its own: a long constrained trajectory that has no 128-thread plan --
    // 40 KB of LDS at four per CU -- is planned like any other run afterwards; a caller's orc_set_workgroup_threads stays binding)
@@ -1140,7 +1138,7 @@ void BatchShard::build_device(const Robot & robot)
    const bool relax = (pass == 2);
    max_wgs = relax ? max_wgs_budget : max_wgs_default; force_block = (pass == -1) ? 128 : force_block_asked;
    if (relax) { force_t = 0; force_pcr = -1; force_ag = -1; }
-   budget4 = (pass == 0) && (want_wgs == 4) && sizeof(real) == 8 && (((tree_ & 16) && (tree_ & 2) && (!(tree_ & 64) || (tree_ & 160) == 160)) || (tree_ & 512)) && (force_block == 0 || force_block == 256)
+   budget4 = (pass == 0) && (want_wgs == 4) && sizeof(real) == 8 && (((variant_ & ORC_VAR_KIND) && (variant_ & ORC_VAR_GS16) && (!(variant_ & ORC_VAR_FLOATING) || (variant_ & (ORC_VAR_ONE_FIELD | ORC_VAR_NO_INACT)) == (ORC_VAR_ONE_FIELD | ORC_VAR_NO_INACT))) || (variant_ & ORC_VAR_PAIRS)) && (force_block == 0 || force_block == 256)
                         && !getenv("ORC_BLOCK_THREADS") && !getenv("ORC_WGS") && !getenv("ORC_TILE_M");      // (the experiments' switches come first)
    if (budget4) { max_wgs = 4; force_block = 256; }
    if (const char * e = getenv("ORC_BLOCK_THREADS")) if (!relax) force_block = atoi(e);
@@ -1156,7 +1154,7 @@ void BatchShard::build_device(const Robot & robot)
    struct Shape { int block, wgs; };
    std::vector<Shape> shapes;
    for (int wgs=max_wgs; wgs>=(budget4 ? 4 : 1); wgs--) shapes.push_back({ 256, wgs });
-   if (max_wgs >= 3 && !(tree_ & 512)) shapes.push_back({ 192, 4 });      // (the pair-list family is built for 256-thread workgroups)
+   if (max_wgs >= 3 && !(variant_ & ORC_VAR_PAIRS)) shapes.push_back({ 192, 4 });      // (the pair-list family is built for 256-thread workgroups)
    // a caller that asked for the 192-thread shape gets it for runs that do not fit four to a CU as well
    if (force_block == 192) for (int wgs=3; wgs>=1; wgs--) shapes.push_back({ 192, wgs });
    // the latency shape: eight wavefronts on one run, one run per CU (a lone wavefront issues a vector
@@ -1211,7 +1209,7 @@ void BatchShard::build_device(const Robot & robot)
                const double rounds = tiles * std::ceil(t * (double) lanes_per_wp / block);
                // measured: an FK pass costs ~1.7k cycles per joint, a round of the 16-lane cost phase ~11k,
                // of the generic one ~350 per active sphere (WAM / 30-dof tree, scripts/phase_profile*.py)
-               const double fk_pass = 1.7e3 * nj, round_cycles = (GS_ == 16) ? 11e3 : ((tree_ & 512) ? 9e3 : 350.0 * Sa_);
+               const double fk_pass = 1.7e3 * nj, round_cycles = (GS_ == 16) ? 11e3 : ((variant_ & ORC_VAR_PAIRS) ? 9e3 : 350.0 * Sa_);
                const double cycles = fk_pass * fk_passes + round_cycles * rounds + 30e3 * (256.0 / block) + (with_pcr ? 0.0 : 1e3) + (ag_lds ? 0.0 : 2e3)
                                    + (g_lds ? 0.0 : 2e3) + (t_lds ? 0.0 : ((flags & ORC_LDS_T_STAGED) ? 4e3 : 12e3));
                const double waves_per_simd = wgs * block / 256.0;
@@ -1228,7 +1226,7 @@ void BatchShard::build_device(const Robot & robot)
    }
    }
    if (!tile_m_) throw std::runtime_error("run does not fit the LDS of one CU!");
-   if (budget4) tree_ |= 256;
+   if (budget4) variant_ |= ORC_VAR_WGS4;
    // Tile boundaries.  A tile of s moving waypoints costs ceil(s * lanes per waypoint / threads) rounds of
    // the workgroup in the cost phase; equal tiles of the largest size are not always the cheapest cut
    // (98 waypoints in tiles of at most 34 at 16 per round: 33 + 33 + 32 is 3 + 3 + 2 rounds, 34 + 32 + 32
@@ -1285,7 +1283,7 @@ void BatchShard::collision_verdict(const std::vector<int> & offs, const std::vec
       v.n_runs = n_runs; v.n_points = n_points; v.n = n; v.chunk = chunk; v.traj = (const double *) d_traj_;
       v.offs = d_offs; v.seg = d_seg; v.u = (const double *) d_u; v.slot_xml = d_xml; v.key_out = d_key; v.depth_out = d_depth;
       v.n_pairs = n_pairs; v.pairs = d_pairs; v.pair_rsum = (const double *) d_rsum; v.inact_pos = (const double *) d_inact;
-      e = orc_launch_verdict_f64(v, orc_verdict_lds_bytes(n, Sa_, Sa_real_, nj_, 8, chunk), st, tree_ & 1);
+      e = orc_launch_verdict_f64(v, orc_verdict_lds_bytes(n, Sa_, Sa_real_, nj_, 8, chunk), st, variant_ & ORC_VAR_TREE);
    }
    else
    {
@@ -1296,7 +1294,7 @@ void BatchShard::collision_verdict(const std::vector<int> & offs, const std::vec
       v.n_runs = n_runs; v.n_points = n_points; v.n = n; v.chunk = chunk; v.traj = (const float *) d_traj_;
       v.offs = d_offs; v.seg = d_seg; v.u = (const float *) d_u; v.slot_xml = d_xml; v.key_out = d_key; v.depth_out = d_depth;
       v.n_pairs = n_pairs; v.pairs = d_pairs; v.pair_rsum = (const float *) d_rsum; v.inact_pos = (const float *) d_inact;
-      e = orc_launch_verdict_f32(v, orc_verdict_lds_bytes(n, Sa_, Sa_real_, nj_, 4, chunk), st, tree_ & 1);
+      e = orc_launch_verdict_f32(v, orc_verdict_lds_bytes(n, Sa_, Sa_real_, nj_, 4, chunk), st, variant_ & ORC_VAR_TREE);
    }
    hip_check(e, "collision_verdict_kernel launch");
    hip_check(hipMemcpyAsync(key_out, d_key, n_runs*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "verdict keys");
@@ -1564,7 +1562,7 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    }
    hipEvent_t ev[2] = { mod_->acquire_event(device), mod_->acquire_event(device) };
    hip_check(hipEventRecord(ev[0], stream_), "hipEventRecord");
-   hipError_t e = launch_typed(b, lds_bytes_, stream_, tree_ | (block_ == 192 ? 4 : 0) | (block_ == 512 ? 8 : 0) | (block_ == 128 ? 1024 : 0));
+   hipError_t e = launch_typed(b, lds_bytes_, stream_, variant_ | (block_ == 192 ? ORC_VAR_T192 : 0) | (block_ == 512 ? ORC_VAR_T512 : 0) | (block_ == 128 ? ORC_VAR_T128 : 0));
    hip_check(e, "chomp_iterate_kernel launch");
    hip_check(hipEventRecord(ev[1], stream_), "hipEventRecord");
    pending_events_.push_back(std::make_pair(ev[0], ev[1]));
@@ -1647,7 +1645,7 @@ void BatchShard::gettraj(double * out)
 
 void BatchShard::get_plan(double out[9]) const
 {
-   out[0] = tree_; out[1] = block_; out[2] = (double) lds_bytes_; out[3] = tile_m_; out[4] = solve_mode_;
+   out[0] = variant_; out[1] = block_; out[2] = (double) lds_bytes_; out[3] = tile_m_; out[4] = solve_mode_;
    out[5] = (double)((160*1024) / ((lds_bytes_ + 1279) / 1280 * 1280)); out[6] = n_tiles_; out[7] = GS_;
    out[8] = tile_first_;
 }

@@ -740,329 +740,15 @@ __device__ __attribute__((noinline)) int limit_rounds_semisep_call(real * T_gen,
 }
 
 
-#ifndef ORC_LIM_SPARSE
-#define ORC_LIM_SPARSE 0       // violated entries up to which a round takes the entry-by-entry form; 0 (default): one or two by the round-2 closed form, more by wave scans.  Measured at 12 on BASELINE configs[3]: +1 % (profiles/r05_ab_experiments.txt), different last bits: not taken
-#endif
-#ifndef ORC_LIM_MASKS
-#define ORC_LIM_MASKS 1        // the register form that looks at lane masks first (limit_regs.h); 0: every slot evaluated in every round (round 2-4)
-#endif
 #include "limit_regs.h"
-// The joint-limit rounds with the violated columns held in REGISTERS.  A round only changes the
-// columns that have a violated entry (Gjlimit, and with it A^-1 Gjlimit, is zero in every other
-// column), so no column can join the set found after the step, and the rounds need nothing but
-// those columns: lane = RPL consecutive waypoints of each of the NC columns.  A round is then
-// violations -> wave arg-max (ties to the first row-major index, as the reference's scan) -> the
-// closed-form A^-1 by one prefix and one suffix wave scan per column -> T += 1.01 Gjl[l]/GA[l] GA,
-// without a single LDS access.  Same operations on the same values as limit_rounds_wave.
-// cols: the columns (ascending); returns the number of rounds made (1000: the caller sets the status).
+// (A forwarding level of its own, on purpose: with the two folded into one function the rounds inline one level less deep, and the
+// compiled limit_rounds_call* functions come out different -- other registers, another schedule.  To be folded by a change that is
+// timed on the card anyway.)
 template <typename real, int NC, int RPL, typename PT, typename PJ>
 __device__ __forceinline__ int limit_rounds_regs(PT T_s, PJ jl_s, int m, int n, real kinv, unsigned long long cols, long long * dbg)
 {
-#if ORC_LIM_MASKS
-   if (!ORC_LIM_SPARSE) return limit_rounds_regs_masks<real, NC, RPL>(T_s, jl_s, m, n, kinv, cols, dbg);
-#endif
-   const int lane = threadIdx.x & 63;
-   int col[NC]; real lo[NC], hi[NC];
-   {
-      unsigned long long rest = cols;
-#pragma unroll
-      for (int ci=0; ci<NC; ci++)
-      {
-         col[ci] = __builtin_ctzll(rest); rest &= rest - 1;
-         lo[ci] = jl_s[col[ci]]; hi[ci] = jl_s[n + col[ci]];
-      }
-   }
-   real T[NC][RPL], wp[RPL], wq[RPL];
-   bool valid[RPL];
-#pragma unroll
-   for (int r=0; r<RPL; r++)
-   {
-      const int row = lane*RPL + r;
-      valid[r] = row < m;
-      wp[r] = (real)(row + 1); wq[r] = (real)(m - row);
-#pragma unroll
-      for (int ci=0; ci<NC; ci++) T[ci][r] = valid[r] ? T_s[n + row*n + col[ci]] : (real)0;
-   }
-   // A round only changes the columns it applies A^-1 Gjlimit to -- those with a violated entry --, so a column that is back
-   // inside its limits stays there for the rest of the call: it is not looked at again (bit c of `open`, wave-uniform)
-   unsigned int open = (1u << NC) - 1u;
-   int rounds;
-   for (rounds=0; rounds<1000; rounds++)
-   {
-      real g[NC][RPL];
-      // violations, and which lanes hold one (per register slot: scalar masks)
-      unsigned long long mk[NC][RPL];
-      int total = 0;
-#pragma unroll
-      for (int ci=0; ci<NC; ci++)
-      {
-         if (!((open >> ci) & 1u))
-         {
-#pragma unroll
-            for (int r=0; r<RPL; r++) { g[ci][r] = 0; mk[ci][r] = 0ull; }
-            continue;
-         }
-         int cnt = 0;
-#pragma unroll
-         for (int r=0; r<RPL; r++)
-         {
-            const real t = T[ci][r];
-            real v = M<real>::max_(lo[ci] - t, (real)0) + M<real>::min_(hi[ci] - t, (real)0);
-            v = valid[r] ? v : (real)0;
-            g[ci][r] = v;
-            mk[ci][r] = __ballot(v != (real)0);
-            cnt += __popcll(mk[ci][r]);
-         }
-         if (cnt == 0) open &= ~(1u << ci);
-         total += cnt;
-      }
-      if (total == 0) break;                          // nothing violated
-#if ORC_LIM_SPARSE
-      if (dbg) *dbg += (total <= ORC_LIM_SPARSE) ? 1LL : (1LL << 20);       // diagnostics: sparse rounds | scan rounds << 20 | general-loop rounds << 40
-      if (total <= ORC_LIM_SPARSE)
-      {
-         // A few violated entries (nearly every round: a run of neighbouring waypoints of one or two columns): A^-1 Gjlimit from
-         // the closed form of the inverse's columns, x_i = kinv (wq_i P_i + wp_i Q_i) with P_i / Q_i the sums of g wp / g wq over
-         // the violated rows at or before / after row i -- what the wave scans compute, entry by entry instead: the entries are
-         // read out of their lanes (the masks are scalar, the register slot of an entry a compile-time index) and every lane adds
-         // each of them to its rows' sums.  A third of the instructions of a scan round for five entries in two columns.
-         // pass 1: the largest violation; ties to the first row-major index (chomp.c:621-638)
-         real best = 0, best_g = 0; int best_e = 0x7fffffff;
-#pragma unroll
-         for (int ci=0; ci<NC; ci++)
-         {
-            if (!((open >> ci) & 1u)) continue;
-#pragma unroll
-            for (int r=0; r<RPL; r++)
-            {
-               unsigned long long mm = mk[ci][r];
-               while (mm)
-               {
-                  const int ln = __builtin_ctzll(mm); mm &= mm - 1;
-                  const real gk = read_lane(g[ci][r], ln);
-                  const real a = M<real>::fabs_(gk);
-                  const int e = (ln*RPL + r)*n + col[ci];
-                  const bool better = (a > best) || (a == best && e < best_e);
-                  best = better ? a : best; best_g = better ? gk : best_g; best_e = better ? e : best_e;
-               }
-            }
-         }
-         const int ge = __builtin_amdgcn_readfirstlane(best_e);
-         const int gi = ge / n, gc = ge - gi*n;
-         const int owner = gi / RPL, gr = gi - owner*RPL;
-         const real gl = read_lane(best_g, 0);            // (the same in every lane)
-         auto sparse_column = [&](const real (& gc_)[RPL], const unsigned long long (& mc_)[RPL], real (& xo)[RPL])
-         {
-            real P[RPL], Q[RPL];
-#pragma unroll
-            for (int rr=0; rr<RPL; rr++) { P[rr] = 0; Q[rr] = 0; }
-#pragma unroll
-            for (int r=0; r<RPL; r++)
-            {
-               unsigned long long mm = mc_[r];
-               while (mm)
-               {
-                  const int ln = __builtin_ctzll(mm); mm &= mm - 1;
-                  const real gk = read_lane(gc_[r], ln);
-                  const int rowk = ln*RPL + r;
-                  const real gp = gk * (real)(rowk + 1), gq = gk * (real)(m - rowk);
-#pragma unroll
-                  for (int rr=0; rr<RPL; rr++)
-                  {
-                     const bool before = rowk <= lane*RPL + rr;
-                     P[rr] += before ? gp : (real)0;
-                     Q[rr] += before ? (real)0 : gq;
-                  }
-               }
-            }
-#pragma unroll
-            for (int rr=0; rr<RPL; rr++) xo[rr] = kinv * (wq[rr] * P[rr] + wp[rr] * Q[rr]);
-         };
-         // the winner's column first: its entry at the winner is the scale of the round
-         real xw[RPL];
-#pragma unroll
-         for (int rr=0; rr<RPL; rr++) xw[rr] = 0;
-#pragma unroll
-         for (int ci=0; ci<NC; ci++)
-         {
-            if (col[ci] != gc) continue;                  // wave-uniform
-            sparse_column(g[ci], mk[ci], xw);
-         }
-         real ga_sel = 0;
-#pragma unroll
-         for (int rr=0; rr<RPL; rr++) ga_sel = (rr == gr) ? xw[rr] : ga_sel;
-         const real ga = read_lane(ga_sel, owner);
-         const real sc = ((real)1.01 * gl) * rcp_fast(ga);
-#pragma unroll
-         for (int ci=0; ci<NC; ci++)
-         {
-            if (!((open >> ci) & 1u)) continue;           // (a column without a violated entry: A^-1 Gjlimit is zero there)
-            unsigned long long anyc = 0ull;
-#pragma unroll
-            for (int r=0; r<RPL; r++) anyc |= mk[ci][r];
-            if (anyc == 0ull) continue;
-            if (col[ci] == gc)
-            {
-#pragma unroll
-               for (int r=0; r<RPL; r++) T[ci][r] += sc * xw[r];
-            }
-            else
-            {
-               real xc[RPL];
-               sparse_column(g[ci], mk[ci], xc);
-#pragma unroll
-               for (int r=0; r<RPL; r++) T[ci][r] += sc * xc[r];
-            }
-         }
-         continue;
-      }
-#else
-      if (dbg) *dbg += (total <= 2) ? 1LL : (1LL << 20);       // diagnostics: closed-form rounds | scan rounds << 20 | general-loop rounds << 40
-#endif
-      if (!ORC_LIM_SPARSE && total <= 2)
-      {
-         // One or two violated entries (nearly every round): A^-1 Gjlimit from the closed form of the
-         // inverse's columns, x_i = kinv (wq_i P_i + wp_i Q_i) with P_i / Q_i the sums of g wp / g wq over
-         // the violated rows at or before / after row i -- what the scans compute, without the scans.
-         int e_lane[2] = {0, 0}, e_r[2] = {0, 0}, e_ci[2] = {0, 0}, cnt = 0;
-#pragma unroll
-         for (int r=0; r<RPL; r++)
-#pragma unroll
-            for (int ci=0; ci<NC; ci++)
-            {
-               unsigned long long mm = mk[ci][r];
-               while (mm && cnt < 2)
-               {
-                  e_lane[cnt] = __builtin_ctzll(mm); e_r[cnt] = r; e_ci[cnt] = ci; cnt++;
-                  mm &= mm - 1;
-               }
-            }
-         real gk[2], wpk[2], wqk[2]; int rowk[2], ek[2];
-#pragma unroll
-         for (int k=0; k<2; k++)
-         {
-            real sel = 0;
-#pragma unroll
-            for (int r=0; r<RPL; r++)
-#pragma unroll
-               for (int ci=0; ci<NC; ci++) sel = (ci == e_ci[k] && r == e_r[k]) ? g[ci][r] : sel;
-            gk[k] = (k < total) ? read_lane(sel, e_lane[k]) : (real)0;
-            rowk[k] = e_lane[k]*RPL + e_r[k];
-            int ck = 0;
-#pragma unroll
-            for (int ci=0; ci<NC; ci++) ck = (ci == e_ci[k]) ? col[ci] : ck;
-            ek[k] = rowk[k]*n + ck;
-            wpk[k] = (real)(rowk[k] + 1); wqk[k] = (real)(m - rowk[k]);
-         }
-         // the largest violation; ties to the first row-major index (chomp.c:621-638)
-         const real a0 = M<real>::fabs_(gk[0]), a1 = M<real>::fabs_(gk[1]);
-         const bool second = (total == 2) && (a1 > a0 || (a1 == a0 && ek[1] < ek[0]));
-         const int w = second ? 1 : 0;
-         const real gl = second ? gk[1] : gk[0];
-         const int roww = second ? rowk[1] : rowk[0];
-         const int ciw = second ? e_ci[1] : e_ci[0];
-         const real gp0 = gk[0] * wpk[0], gq0 = gk[0] * wqk[0], gp1 = gk[1] * wpk[1], gq1 = gk[1] * wqk[1];
-         // GA at the winner
-         real Pw = 0, Qw = 0;
-         {
-            const bool same0 = (e_ci[0] == ciw), same1 = (total == 2) && (e_ci[1] == ciw);
-            Pw += (same0 && rowk[0] <= roww) ? gp0 : (real)0;  Qw += (same0 && rowk[0] > roww) ? gq0 : (real)0;
-            Pw += (same1 && rowk[1] <= roww) ? gp1 : (real)0;  Qw += (same1 && rowk[1] > roww) ? gq1 : (real)0;
-         }
-         const real ga = kinv * ((real)(m - roww) * Pw + (real)(roww + 1) * Qw);
-         const real sc = ((real)1.01 * gl) * rcp_fast(ga);
-         (void) w;
-#pragma unroll
-         for (int ci=0; ci<NC; ci++)
-         {
-            const bool in0 = (e_ci[0] == ci), in1 = (total == 2) && (e_ci[1] == ci);
-            if (!(in0 || in1)) continue;                 // wave-uniform: this column has no violated entry
-#pragma unroll
-            for (int r=0; r<RPL; r++)
-            {
-               const int row = lane*RPL + r;
-               real P = 0, Q = 0;
-               P += (in0 && rowk[0] <= row) ? gp0 : (real)0;  Q += (in0 && rowk[0] > row) ? gq0 : (real)0;
-               P += (in1 && rowk[1] <= row) ? gp1 : (real)0;  Q += (in1 && rowk[1] > row) ? gq1 : (real)0;
-               const real x = kinv * (wq[r] * P + wp[r] * Q);
-               T[ci][r] += sc * x;
-            }
-         }
-         continue;
-      }
-      real best = 0, best_g = 0; int best_e = 0x7fffffff;
-#pragma unroll
-      for (int r=0; r<RPL; r++)
-#pragma unroll
-         for (int ci=0; ci<NC; ci++)
-         {
-            const real v = g[ci][r];
-            const real a = M<real>::fabs_(v);
-            const int e = (lane*RPL + r)*n + col[ci];                 // row-major index: ascending in (r, ci)
-            const bool better = a > best;                              // later entries of the lane win only when strictly larger
-            best = better ? a : best; best_g = better ? v : best_g; best_e = better ? e : best_e;
-         }
-      wave_argmax(best, best_e);
-      const int ge = __builtin_amdgcn_readfirstlane(best_e);
-      const int gi = ge / n, gc = ge - gi*n;
-      const int owner = gi / RPL;
-      // the owner's own best is the winner (its key is the global one), so its signed value is Gjlimit[largest]
-      const real gl = read_lane(best_g, owner);
-      // GA = A^-1 Gjlimit by one prefix and one suffix wave scan per column.  The winner's column comes
-      // first: its entry at the winner is the scale of the round; then every column with a violated entry
-      // is solved and applied at once (nothing of GA is kept: registers for up to 8 columns x 4 rows)
-      auto scan_column = [&](const real (& gc_)[RPL], real (& xo)[RPL])
-      {
-         real sp = 0, sq = 0;
-#pragma unroll
-         for (int r=0; r<RPL; r++) { sp += gc_[r] * wp[r]; sq += gc_[r] * wq[r]; }
-         const real ip = wave_prefix_incl(sp), is = wave_suffix_incl(sq);
-         real run_p = __shfl_up(ip, 1, 64);   if (lane == 0) run_p = 0;
-         real run_q = __shfl_down(is, 1, 64); if (lane == 63) run_q = 0;
-         real q[RPL];
-#pragma unroll
-         for (int r=RPL-1; r>=0; r--) { q[r] = run_q; run_q += gc_[r] * wq[r]; }
-#pragma unroll
-         for (int r=0; r<RPL; r++)
-         {
-            run_p += gc_[r] * wp[r];
-            xo[r] = kinv * (wq[r] * run_p + wp[r] * q[r]);
-         }
-      };
-      real ga_mine = 0;
-#pragma unroll
-      for (int ci=0; ci<NC; ci++)
-      {
-         if (col[ci] != gc) continue;                  // wave-uniform
-         real xw[RPL];
-         scan_column(g[ci], xw);
-#pragma unroll
-         for (int r=0; r<RPL; r++) ga_mine = (lane*RPL + r == gi) ? xw[r] : ga_mine;
-      }
-      const real ga = read_lane(ga_mine, owner);
-      const real sc = ((real)1.01 * gl) * rcp_fast(ga);
-#pragma unroll
-      for (int ci=0; ci<NC; ci++)
-      {
-         // a column without a violated entry in this round: A^-1 Gjlimit is zero there (wave-uniform)
-         unsigned long long anyc = 0ull;
-#pragma unroll
-         for (int r=0; r<RPL; r++) anyc |= mk[ci][r];
-         if (anyc == 0ull) continue;
-         real xc[RPL];
-         scan_column(g[ci], xc);
-#pragma unroll
-         for (int r=0; r<RPL; r++) T[ci][r] += sc * xc[r];
-      }
-   }
-#pragma unroll
-   for (int r=0; r<RPL; r++)
-#pragma unroll
-      for (int ci=0; ci<NC; ci++)
-         if (valid[r]) T_s[n + (lane*RPL + r)*n + col[ci]] = T[ci][r];
-   return rounds;
+   return limit_rounds_regs_masks<real, NC, RPL>(T_s, jl_s, m, n, kinv, cols, dbg);
 }
-
 template <typename real, int NC, typename PT, typename PJ>
 __device__ __forceinline__ int limit_rounds_regs_rpl(PT T_s, PJ jl_s, int m, int n, real kinv, unsigned long long cols, long long * dbg)
 {
@@ -1083,10 +769,8 @@ __device__ __forceinline__ int limit_rounds_regs_rpl(PT T_s, PJ jl_s, int m, int
 // precision serves every kernel variant.  T_s / G_s / jl_s are LDS addresses.
 struct LimResult { int rounds; long long kinds; };      // kinds: closed-form | register scans << 20 | general loop << 40
 
-#ifndef ORC_LIM_SPLIT
-#define ORC_LIM_SPLIT 1        // the rounds of one or two columns are a function of their own (its register appetite, and with it the callee-saved registers a call saves and restores, is a third of the large cases')
-#endif
-// PART: 0 every case; 1 one or two columns only; 2 three columns and more
+// PART: 1 one or two columns only; 2 three columns and more.  The rounds of one or two columns are a function of their own: its
+// register appetite, and with it the callee-saved registers a call saves and restores, is a third of the large cases'
 template <typename real, int PART, typename PT>
 __device__ __forceinline__ LimResult limit_rounds_body(PT T_s, real * G_gen, const real * jl_gen, int m_in, int n_in, real kinv_in,
    unsigned long long viol_cols_in)
@@ -1117,8 +801,7 @@ __device__ __forceinline__ LimResult limit_rounds_body(PT T_s, real * G_gen, con
    }
    switch (nc)
    {
-   case 1: if (PART == 0) res.rounds = limit_rounds_regs_rpl<real, 1>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;      // (PART 2 is never called with one or two)
-   case 2: if (PART == 0) res.rounds = limit_rounds_regs_rpl<real, 2>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
+   case 1: case 2: break;      // (PART 2 is never called with one or two)
    case 3: res.rounds = limit_rounds_regs_rpl<real, 3>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
    default:
       // four to eight columns (a trajectory that is leaving its limits for good, the 1000-round
@@ -1158,13 +841,13 @@ __device__ __attribute__((noinline)) LimResult limit_rounds_call(real * T_gen, r
    unsigned long long viol_cols)
 {
    typedef __attribute__((address_space(3))) real * lds_ptr;
-   return limit_rounds_body<real, ORC_LIM_SPLIT ? 2 : 0>((lds_ptr) T_gen, G_gen, jl_gen, m, n, kinv, viol_cols);
+   return limit_rounds_body<real, 2>((lds_ptr) T_gen, G_gen, jl_gen, m, n, kinv, viol_cols);
 }
 template <typename real, int SHAPE>
 __device__ __attribute__((noinline)) LimResult limit_rounds_call_global(real * T_gen, real * G_gen, const real * jl_gen, int m, int n, real kinv,
    unsigned long long viol_cols)
 {
-   return limit_rounds_body<real, ORC_LIM_SPLIT ? 2 : 0>(T_gen, G_gen, jl_gen, m, n, kinv, viol_cols);
+   return limit_rounds_body<real, 2>(T_gen, G_gen, jl_gen, m, n, kinv, viol_cols);
 }
 // ... and the same for one or two columns (nearly every call of a 7-dof arm)
 template <typename real, int SHAPE>
@@ -1366,32 +1049,13 @@ __device__ __attribute__((noinline)) double band_cost_pass(const void * kp, cons
    return acc;
 }
 
-// 1: the many-sphere cost pass of an iteration is part of the kernel function itself (see the kernel's tile loop);
-// 2: the 16-lane pass as well (no gain measured: it saves 2 callee-saved registers per call); 0: every pass is a call
-#ifndef ORC_UPDATE_BATCH
-#define ORC_UPDATE_BATCH 4     // entries of a thread whose gradient / momentum rows the update phase reads ahead where they live in global memory and a thread has more than four (0: never)
-#endif
-#ifndef ORC_INLINE_COST
-#define ORC_INLINE_COST 1
-#endif
-
-#ifndef ORC_U
-#define ORC_U 1          // waypoints per lane in the 16-sphere cost phase (1: registers go to a third workgroup per CU instead)
-#endif
-
+// entries of a thread whose gradient / momentum rows the update phase reads ahead where they live in global memory and a thread has more than four
+constexpr int UPDATE_BATCH = 4;
+// waypoints per lane in the 16-sphere cost phase (1: registers go to a third workgroup per CU instead)
+constexpr int GS16_U = 1;
 // wave priorities of the phases (s_setprio): the latency-bound ones go first when they have something to issue
-#ifndef ORC_PRIO_FK
-#define ORC_PRIO_FK 3
-#endif
-#ifndef ORC_PRIO_COST
-#define ORC_PRIO_COST 0
-#endif
-#ifndef ORC_PRIO_COST_LAST
-#define ORC_PRIO_COST_LAST 2      // the last round of a tile: it is what the tile's barrier waits for
-#endif
-#ifndef ORC_PRIO_UPDATE
-#define ORC_PRIO_UPDATE 3
-#endif
+constexpr int PRIO_FK = 3, PRIO_COST = 0, PRIO_UPDATE = 3;
+constexpr int PRIO_COST_LAST = 2;      // the last round of a tile: it is what the tile's barrier waits for
 
 #include "cost_gs16.h"
 #include "cost_pairs.h"
@@ -1692,12 +1356,6 @@ __device__ __forceinline__ void copy_batched(real * dst, const real * src, int c
 }
 
 // ---- FK phase of one tile: lane = (waypoint, world axis) (sphere_cost_pre, src/orcdchomp_mod.cpp:988-1093) ----
-#ifndef ORC_FK_SKIP_IDLE
-#define ORC_FK_SKIP_IDLE 1    // wavefronts without a waypoint in a tile skip the FK phase's call (they join its barrier)
-#endif
-#ifndef ORC_INLINE_FK
-#define ORC_INLINE_FK 0      // 1: the FK phase of the fp64 16-lane kernels inside the kernel function (no callee-saved registers to preserve, 37 scalar registers through v_writelane and back per call otherwise) -- but the loop invariants it hoists across the other phases' calls are spilled to scratch and reloaded inside the joint loop: measured slower, kept for A/B
-#endif
 template <typename real, bool TREE, bool GS16, int BLOCK, int WGS = 0>
 __device__ __forceinline__ void phase_fk_body(const void * kp, int ts_in, int te_in)
 {
@@ -1706,7 +1364,7 @@ __device__ __forceinline__ void phase_fk_body(const void * kp, int ts_in, int te
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
    const int tid = threadIdx.x, n = b.n;
    const int nfk = te - ts + 2;          // waypoints ts .. te+1 (global index)
-   __builtin_amdgcn_s_setprio(ORC_PRIO_FK);          // latency-bound phases go first when they have something to issue
+   __builtin_amdgcn_s_setprio(PRIO_FK);          // latency-bound phases go first when they have something to issue
    // a wavefront walks 20 waypoints: five triads of lanes (x, y, z rows) in each of its four rows of 16.  A robot whose
    // joint tree is a chain that then branches (DevModel::fk_split) is walked by PAIRS of wavefronts: one takes the
    // joints up to fk_b_begin, the other the chain (without storing) and the joints from fk_b_begin on
@@ -1746,7 +1404,7 @@ __device__ __attribute__((noinline)) double phase_cost_start(const void * kp, in
    E.mod.live_mask |= b.ms.static_mask;
    const real inv_eps = (real)1 / b.epsilon, inv_eps_self = (real)1 / b.epsilon_self;
    if constexpr (GS16)
-      cost_tile_gs16<real, ORC_U, BLOCK, KArg<real>, true>(b, E.mod, E.sdfs_s, 0, 1, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s, E.r2_s,
+      cost_tile_gs16<real, GS16_U, BLOCK, KArg<real>, true>(b, E.mod, 0, 1, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s, E.r2_s,
                                                           E.slink_s, E.jtype_s, E.jcol_s, inv_eps, inv_eps_self, cost_lane);
    else
       cost_tile_generic<real, BLOCK, KArg<real>, true>(b, E.mod, E.sdfs_s, 0, 1, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s,
@@ -1778,16 +1436,16 @@ __device__ __forceinline__ double phase_cost_body(const void * kp, int ts_in, in
    if constexpr (!GS16 && (KIND & 1) != 0) { E.mod.floating = 0; E.mod.jt_scan = TREE ? 2 : 1; }
    E.mod.live_mask |= b.ms.static_mask;      // the static spheres' lanes take part in the row's pairs
    const real inv_eps = (real)1 / b.epsilon, inv_eps_self = (real)1 / b.epsilon_self;
-   __builtin_amdgcn_s_setprio(ORC_PRIO_COST);
+   __builtin_amdgcn_s_setprio(PRIO_COST);
    if constexpr (GS16)
-      cost_tile_gs16<real, ORC_U, BLOCK, KArg<real>, false, (KIND & 2) != 0, (KIND & 1) != 0, (KIND & 8) != 0>(b, E.mod, E.sdfs_s, ts, te, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s, E.r2_s,
+      cost_tile_gs16<real, GS16_U, BLOCK, KArg<real>, false, (KIND & 2) != 0, (KIND & 1) != 0, (KIND & 8) != 0>(b, E.mod, ts, te, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s, E.r2_s,
                                          E.slink_s, E.jtype_s, E.jcol_s, inv_eps, inv_eps_self, cost_lane);
    else if constexpr ((KIND & 16) != 0)
    {
       // 17 .. 32 active spheres on a chain: the dense pair list (KIND 16; 16 | 2 | 8: one field with the world's axes, a fixed
       // base, no inactive sphere left for the loop over them)
       if constexpr ((KIND & 2) != 0) E.mod.floating = 0;
-      cost_tile_pairs<real, (KIND & 32) ? 16 : 32, BLOCK, KArg<real>, (KIND & 2) != 0, (KIND & 8) != 0>(b, E.mod, ts, te, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s,
+      cost_tile_pairs<real, BLOCK, KArg<real>, (KIND & 2) != 0, (KIND & 8) != 0>(b, E.mod, ts, te, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s,
                                          E.slink_s, E.pent_s, E.pgat_s, inv_eps, inv_eps_self, cost_lane);
    }
    else
@@ -1823,9 +1481,8 @@ __device__ __attribute__((noinline)) double phase_cost(const void * kp, int ts_i
 
 // ---- update phase (cd_chomp_iterate, src/libcd/chomp.c:490-655): G/m + A T + B, A^-1 G, the step,
 // the joint-limit rounds.  Returns the number of limit rounds made (1000: "ran too many joint limit fixes").
-#ifndef ORC_UPDATE_LEAN
-#define ORC_UPDATE_LEAN 1      // runs of the common kind (tridiagonal Toeplitz metric by the scan solve, no TSR constraint, at most 64 dofs, no debug read-back) take a copy of the update phase compiled without the other paths: fewer live scalars, fewer registers saved and restored per call
-#endif
+// Runs of the common kind (tridiagonal Toeplitz metric by the scan solve, at most 64 dofs, no debug read-back) take a copy of the update
+// phase compiled without the other paths: fewer live scalars, fewer registers saved and restored per call.
 // LEAN 1 / 2: the caller has checked solve_mode == 2, n <= 64, no lim_generic, no Gdbg, and no TSR constraint (1) or some (2) (the kernel's loop)
 template <typename real, bool TREE, bool GS16, int BLOCK, int WGS = 0, int LEAN = 0>
 __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in, int leapfrog_first_in)
@@ -1849,25 +1506,24 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
       __syncthreads();
    }
 
-   __builtin_amdgcn_s_setprio(ORC_PRIO_UPDATE);
+   __builtin_amdgcn_s_setprio(PRIO_UPDATE);
    if (tid < 2) colmask_s[tid] = 0u;       // read last after the previous step's barrier, set again after the next one
    // G = G/m + A T + B   (chomp.c:492, 515-522)
    const bool band = !LEAN && b.D != 1;      // (a metric that is not the tridiagonal Toeplitz one: its pass is a function of its own)
    if (band) band_gradient_pass<real, BLOCK>(kp, pcr_tab, T_s, Gc, G_s);
-#if ORC_UPDATE_BATCH
    // (four entries of a thread per trip, their gradient rows read first: where the plan keeps the rows in global memory a plain
    // loop made one round trip through L2 per entry, eleven in a row for a 200-waypoint run of 14 dofs: BASELINE configs[3] +2 %;
    // for the three entries per thread of a 7 x 100 run it costs 0.7 %: those take the plain loop)
-   const bool batched = ORC_UPDATE_BATCH && mn > 4*BLOCK;      // (workgroup-uniform)
+   const bool batched = mn > 4*BLOCK;      // (workgroup-uniform)
    if (band) {}
    else if (batched && !b.g_in_lds)
-   for (int e0=tid; e0<mn; e0+=ORC_UPDATE_BATCH*BLOCK)
+   for (int e0=tid; e0<mn; e0+=UPDATE_BATCH*BLOCK)
    {
-      real gq[ORC_UPDATE_BATCH];
+      real gq[UPDATE_BATCH];
 #pragma unroll
-      for (int q=0; q<ORC_UPDATE_BATCH; q++) { const int e = e0 + q*BLOCK; gq[q] = (e < mn) ? Gc[e] : (real)0; }
+      for (int q=0; q<UPDATE_BATCH; q++) { const int e = e0 + q*BLOCK; gq[q] = (e < mn) ? Gc[e] : (real)0; }
 #pragma unroll
-      for (int q=0; q<ORC_UPDATE_BATCH; q++)
+      for (int q=0; q<UPDATE_BATCH; q++)
       {
          int e = e0 + q*BLOCK;
          if (e >= mn) break;
@@ -1884,10 +1540,6 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
       }
    }
    else
-#else
-   const bool batched = false;
-   if (!band)
-#endif
    for (int e=tid; e<mn; e+=BLOCK)
    {
       const int i = div_n(e, rn_f), c = e - i*n;
@@ -1949,16 +1601,15 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    else
    {
       const real sc = (leapfrog_first ? (real)0.5 : (real)1) / b.lambda;
-#if ORC_UPDATE_BATCH
       // (the momentum rows likewise: read four entries ahead where they live in global memory)
       if (batched && !b.ag_in_lds)
-      for (int e0=tid; e0<mn; e0+=ORC_UPDATE_BATCH*BLOCK)
+      for (int e0=tid; e0<mn; e0+=UPDATE_BATCH*BLOCK)
       {
-         real aq[ORC_UPDATE_BATCH];
+         real aq[UPDATE_BATCH];
 #pragma unroll
-         for (int q=0; q<ORC_UPDATE_BATCH; q++) { const int e = e0 + q*BLOCK; aq[q] = (e < mn) ? AG_s[e] : (real)0; }
+         for (int q=0; q<UPDATE_BATCH; q++) { const int e = e0 + q*BLOCK; aq[q] = (e < mn) ? AG_s[e] : (real)0; }
 #pragma unroll
-         for (int q=0; q<ORC_UPDATE_BATCH; q++)
+         for (int q=0; q<UPDATE_BATCH; q++)
          {
             int e = e0 + q*BLOCK;
             if (e >= mn) break;
@@ -1972,7 +1623,6 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
          }
       }
       else
-#endif
       for (int e=tid; e<mn; e+=BLOCK)
       {
          const real ag = AG_s[e] + sc * X[e];
@@ -2009,7 +1659,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
          {
             const real kinv = (real)(-1) / ((real)(m + 1) * b.a_off);      // 1/((m+1) ca), ca = -a_off
             constexpr int SH = (BLOCK == 512) ? 1 : (WGS ? 2 : 0);
-            const bool few = ORC_LIM_SPLIT && __popcll(viol_cols) <= 2;      // (workgroup-uniform)
+            const bool few = __popcll(viol_cols) <= 2;      // (workgroup-uniform)
             const LimResult lr = (b.t_in_lds || staged)
                ? (few ? limit_rounds_call_small<real, SH>(T_s, G_s, jl_s, m, n, kinv, viol_cols) : limit_rounds_call<real, SH>(T_s, G_s, jl_s, m, n, kinv, viol_cols))
                : (few ? limit_rounds_call_global_small<real, SH>(T_s, G_s, jl_s, m, n, kinv, viol_cols) : limit_rounds_call_global<real, SH>(T_s, G_s, jl_s, m, n, kinv, viol_cols));
@@ -2188,7 +1838,7 @@ __device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int 
       __syncthreads();
    }
    PassCosts pc;
-   __builtin_amdgcn_s_setprio(ORC_PRIO_UPDATE);
+   __builtin_amdgcn_s_setprio(PRIO_UPDATE);
    {
       double acc = 0.0;
       if (b.D != 1) acc = band_cost_pass<real, BLOCK>(kp, E.pcr_tab, T_s);
@@ -2360,25 +2010,22 @@ void chomp_iterate_kernel(const DevBatch<real> b)
          // (scripts/single_run_latency.py, profiles/r04_single_run_ceiling.txt)
          if (b.stagger_mode == 9 && tk > 0) { if (tk == 1) for (int k=0; k<b.stagger_sleeps; k++) __builtin_amdgcn_s_sleep(10); continue; }
 #ifndef ORC_ABLATE_FK
-         if constexpr (ORC_INLINE_FK && GS16 && sizeof(real) == 8) phase_fk_body<real, TREE, GS16, BLOCK, WGS>(kp, ts, te);
-#if ORC_FK_SKIP_IDLE
          // a wavefront without a waypoint in the tile (20 per wavefront: the second of a 128-thread workgroup in each of its tiles of 14)
          // only joins the phase's barrier: it saves the call's ~120 scalar registers moved through the vector pipe
-         else if (!b.ms.fk_split && uni(tid >> 6) * 20 >= te - ts + 2) __syncthreads();
-#endif
+         if (!b.ms.fk_split && uni(tid >> 6) * 20 >= te - ts + 2) __syncthreads();
          else phase_fk<real, TREE, GS16, BLOCK, WGS>(kp, ts, te);      // (skipping the call for the wavefronts without a waypoint in the tile -- their share of the callee-saved registers -- measured nothing: profiles/r04_ab_experiments.txt)
 #ifdef ORC_ABLATE_FKTWICE      // timing experiments: the FK phase twice (what a 2x slower FK would cost)
          phase_fk<real, TREE, GS16, BLOCK, WGS>(kp, ts, te);
 #endif
 #endif
 #ifndef ORC_ABLATE_COST
-#if ORC_INLINE_COST
          // the pass of an iteration inside the kernel function itself: a kernel has no callee-saved registers to
          // preserve (as a call the many-sphere pass saved and restored 67 of them per tile and wavefront: 2 x 198 GB
          // of scratch traffic per launch of BASELINE configs[4], most of what the HBM counters saw)
-         if (do_iteration && (!GS16 || ORC_INLINE_COST > 1)) cost_lane = phase_cost_body<real, TREE, GS16, BLOCK, KIND, true>(kp, ts, te, cost_lane);
+         // The 16-lane pass and the FK phase stay calls: inside the kernel function they measured slower (the FK phase's hoisted loop
+         // invariants spill to scratch; profiles/r04_ab_experiments.txt, profiles/r05_ab_experiments.txt)
+         if (do_iteration && !GS16) cost_lane = phase_cost_body<real, TREE, GS16, BLOCK, KIND, true>(kp, ts, te, cost_lane);
          else
-#endif
          cost_lane = do_iteration ? phase_cost<real, TREE, GS16, BLOCK, KIND, true, WGS>(kp, ts, te, cost_lane)
                                   : phase_cost<real, TREE, GS16, BLOCK, KIND, false, WGS>(kp, ts, te, cost_lane);
          if (tk == 0 && b.free_start) cost_lane = phase_cost_start<real, TREE, GS16, BLOCK, WGS>(kp, do_iteration ? 1 : 0, cost_lane);
@@ -2387,7 +2034,7 @@ void chomp_iterate_kernel(const DevBatch<real> b)
 
       if (do_iteration)
       {
-         const bool lean = ORC_UPDATE_LEAN && b.solve_mode == 2 && b.n <= 64 && !b.lim_generic && b.Gdbg == nullptr;      // (workgroup-uniform)
+         const bool lean = b.solve_mode == 2 && b.n <= 64 && !b.lim_generic && b.Gdbg == nullptr;      // (workgroup-uniform)
          const int num_limadjs = !lean ? uni(phase_update<real, TREE, GS16, BLOCK, WGS, 0>(kp, it, leapfrog_first))
                                : (b.n_tsrs == 0 ? uni(phase_update<real, TREE, GS16, BLOCK, WGS, 1>(kp, it, leapfrog_first))
                                                 : uni(phase_update<real, TREE, GS16, BLOCK, WGS, 2>(kp, it, leapfrog_first)));
@@ -2605,62 +2252,54 @@ static hipError_t launch_iterate_tt(const DevBatch<real> & b, size_t lds, hipStr
    return hipGetLastError();
 }
 
-// variant: bit 0 the joint tree branches, bit 1 the robot has <= 16 active spheres (DPP-row cost
-// phase), bit 2 workgroups of 192 threads (three wavefronts, four workgroups per CU) instead of 256,
-// bit 3 workgroups of 512 threads (eight wavefronts, one workgroup per CU: the latency shape),
-// bit 4 the robot is a fixed-base chain with its spheres placed on the row (with bit 1, without bit 0),
-// bit 5 (with bit 4) there is one field and its axes are the world's, bit 6 (with bit 4) the base floats,
-// bit 7 (with bits 4 and 5) no inactive sphere is left for the loop over them
+// variant: the ORC_VAR_ bits of dev_types.h
 template <typename real>
 static hipError_t launch_iterate_t(const DevBatch<real> & b, size_t lds, hipStream_t stream, int variant)
 {
+   constexpr int ONEF_NOINACT = ORC_VAR_ONE_FIELD | ORC_VAR_NO_INACT;
 #ifdef ORC_FAST_BUILD
    // experiment builds (make var DEFS=-DORC_FAST_BUILD=2): only the kernels of the config-2 bench legs are compiled (the fp64
    // fixed-base chain with placed spheres, one aligned field, no inactive sphere left: KIND 11), half a minute instead of three
 #if ORC_FAST_BUILD == 5      // -DORC_FAST_BUILD=5: BASELINE configs[4] (fp32, the many-sphere pass of a tree with its J^T form known)
    if constexpr (sizeof(real) == 4)
-      if ((variant & 16) && !(variant & 2) && (variant & 1) && !(variant & (4 | 8))) return launch_iterate_tt<real, true, false, 256, 1>(b, lds, stream);
+      if ((variant & ORC_VAR_KIND) && !(variant & ORC_VAR_GS16) && (variant & ORC_VAR_TREE) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, true, false, 256, 1>(b, lds, stream);
 #endif
    if constexpr (sizeof(real) == 8)
    {
-#if ORC_FAST_BUILD == 8      // -DORC_FAST_BUILD=8: config 2 with the pair list on 16-lane groups (ORC_PAIRS16=1) beside the row rotations, both budgets
-      if ((variant & 512) && (variant & 2) && (variant & 32) && (variant & 128) && !(variant & 64))
-         return (variant & 256) ? launch_iterate_tt<real, false, false, 256, 58, 4>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 58>(b, lds, stream);
-#endif
 #if ORC_FAST_BUILD == 7      // -DORC_FAST_BUILD=7: the TSR-constrained WAM (KIND 11) at four 256-thread and eight 128-thread workgroups per CU
-      if ((variant & (16 | 2 | 1 | 64)) == (16 | 2) && (variant & 160) == 160)
+      if ((variant & (ORC_VAR_TREE | ORC_VAR_GS16 | ORC_VAR_KIND | ORC_VAR_FLOATING)) == (ORC_VAR_GS16 | ORC_VAR_KIND) && (variant & ONEF_NOINACT) == ONEF_NOINACT)
       {
-         if (variant & 1024) return launch_iterate_tt<real, false, true, 128, 11, 4>(b, lds, stream);
-         if ((variant & 256) && !(variant & (4 | 8))) return launch_iterate_tt<real, false, true, 256, 11, 4>(b, lds, stream);
-         if (!(variant & (4 | 8))) return launch_iterate_tt<real, false, true, 256, 11>(b, lds, stream);
+         if (variant & ORC_VAR_T128) return launch_iterate_tt<real, false, true, 128, 11, 4>(b, lds, stream);
+         if ((variant & ORC_VAR_WGS4) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 11, 4>(b, lds, stream);
+         if (!(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 11>(b, lds, stream);
       }
       return hipErrorInvalidValue;
 #endif
 #if ORC_FAST_BUILD == 6      // -DORC_FAST_BUILD=6: the WAM that holds a box (the dense pair list, one aligned field) at both budgets
-      if ((variant & 512) && (variant & 32) && (variant & 128) && !(variant & 64))
-         return (variant & 256) ? launch_iterate_tt<real, false, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 26>(b, lds, stream);
+      if ((variant & ORC_VAR_PAIRS) && (variant & ORC_VAR_ONE_FIELD) && (variant & ORC_VAR_NO_INACT) && !(variant & ORC_VAR_FLOATING))
+         return (variant & ORC_VAR_WGS4) ? launch_iterate_tt<real, false, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 26>(b, lds, stream);
 #endif
-      const int kind = 1 | ((variant & 32) ? 2 : 0) | ((variant & 64) ? 4 : 0) | (((variant & 160) == 160) ? 8 : 0);
-      if ((variant & (16 | 2 | 1)) == (16 | 2))
+      const int kind = 1 | ((variant & ORC_VAR_ONE_FIELD) ? 2 : 0) | ((variant & ORC_VAR_FLOATING) ? 4 : 0) | (((variant & ONEF_NOINACT) == ONEF_NOINACT) ? 8 : 0);
+      if ((variant & (ORC_VAR_TREE | ORC_VAR_GS16 | ORC_VAR_KIND)) == (ORC_VAR_GS16 | ORC_VAR_KIND))
       {
 #if ORC_FAST_BUILD == 5 || ORC_FAST_BUILD == 6
 #elif ORC_FAST_BUILD == 4      // -DORC_FAST_BUILD=4: BASELINE configs[3] (floating base, KIND 15) at the default shape and at four workgroups per CU
-         if (kind == 15 && (variant & 256) && !(variant & (4 | 8))) return launch_iterate_tt<real, false, true, 256, 15, 4>(b, lds, stream);
-         if (kind == 15 && !(variant & (4 | 8))) return launch_iterate_tt<real, false, true, 256, 15>(b, lds, stream);
+         if (kind == 15 && (variant & ORC_VAR_WGS4) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 15, 4>(b, lds, stream);
+         if (kind == 15 && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 15>(b, lds, stream);
 #else
-         if (kind == 11 && (variant & 256) && !(variant & (4 | 8))) return launch_iterate_tt<real, false, true, 256, 11, 4>(b, lds, stream);
-         if (kind == 11 && (variant & 4)) return launch_iterate_tt<real, false, true, 192, 11>(b, lds, stream);
-         if (kind == 11 && !(variant & 8)) return launch_iterate_tt<real, false, true, 256, 11>(b, lds, stream);
+         if (kind == 11 && (variant & ORC_VAR_WGS4) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 11, 4>(b, lds, stream);
+         if (kind == 11 && (variant & ORC_VAR_T192)) return launch_iterate_tt<real, false, true, 192, 11>(b, lds, stream);
+         if (kind == 11 && !(variant & ORC_VAR_T512)) return launch_iterate_tt<real, false, true, 256, 11>(b, lds, stream);
 #endif
       }
    }
    return hipErrorInvalidValue;
 #else
-   if (variant & 1024)     // 128-thread workgroups, eight per CU at 128 registers: the fp64 16-lane family of a fixed-base chain (orc_set_workgroup_threads(128))
+   if (variant & ORC_VAR_T128)     // 128-thread workgroups, eight per CU at 128 registers: the fp64 16-lane family of a fixed-base chain (orc_set_workgroup_threads(128))
    {
       if constexpr (sizeof(real) == 8)
-         if ((variant & (16 | 2 | 1 | 64)) == (16 | 2))
-            switch (1 | ((variant & 32) ? 2 : 0) | (((variant & 160) == 160) ? 8 : 0))
+         if ((variant & (ORC_VAR_TREE | ORC_VAR_GS16 | ORC_VAR_KIND | ORC_VAR_FLOATING)) == (ORC_VAR_GS16 | ORC_VAR_KIND))
+            switch (1 | ((variant & ORC_VAR_ONE_FIELD) ? 2 : 0) | (((variant & ONEF_NOINACT) == ONEF_NOINACT) ? 8 : 0))
             {
             case 1: return launch_iterate_tt<real, false, true, 128, 1, 4>(b, lds, stream);
             case 3: return launch_iterate_tt<real, false, true, 128, 3, 4>(b, lds, stream);
@@ -2668,57 +2307,48 @@ static hipError_t launch_iterate_t(const DevBatch<real> & b, size_t lds, hipStre
             }
       return hipErrorInvalidValue;
    }
-   if (variant & 512)      // 17 .. 32 active spheres: the dense pair list (cost_pairs.h; phase_cost KIND 16)
+   if (variant & ORC_VAR_PAIRS)      // 17 .. 32 active spheres: the dense pair list (cost_pairs.h; phase_cost KIND 16)
    {
-      const bool lean = (variant & 32) && (variant & 128) && !(variant & 64);      // one aligned field, no inactive sphere left, fixed base
+      const bool lean = (variant & ORC_VAR_ONE_FIELD) && (variant & ORC_VAR_NO_INACT) && !(variant & ORC_VAR_FLOATING);      // one aligned field, no inactive sphere left, fixed base
       if constexpr (sizeof(real) == 8)
       {
-         if (variant & 2)      // 16 lanes per waypoint (ORC_PAIRS16=1: the experiment of profiles/r05_ab_experiments.txt; the lean kind only)
+         if (variant & (ORC_VAR_GS16 | ORC_VAR_T192)) return hipErrorInvalidValue;      // (no 16-lane form and no 192-thread shape: batch.cpp keeps such a module on the many-sphere family)
+         if (variant & ORC_VAR_TREE)      // a tree (round 6: the WAM with its finger dofs active that holds something); no latency shape
          {
-#ifdef ORC_PAIRS16_KERNELS      // (measured -24 % against the row rotations on BASELINE configs[1]: the kernels are not in the product build)
-            if (!lean || (variant & (4 | 8 | 1))) return hipErrorInvalidValue;
-            return (variant & 256) ? launch_iterate_tt<real, false, false, 256, 58, 4>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 58>(b, lds, stream);
-#else
-            return hipErrorInvalidValue;
-#endif
-         }
-         if (variant & 4) return hipErrorInvalidValue;      // (no 192-thread shape: batch.cpp keeps such a module on the many-sphere family)
-         if (variant & 1)      // a tree (round 6: the WAM with its finger dofs active that holds something); no latency shape
-         {
-            if (variant & 8) return hipErrorInvalidValue;
-            if (variant & 256) return lean ? launch_iterate_tt<real, true, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, true, false, 256, 16, 4>(b, lds, stream);
+            if (variant & ORC_VAR_T512) return hipErrorInvalidValue;
+            if (variant & ORC_VAR_WGS4) return lean ? launch_iterate_tt<real, true, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, true, false, 256, 16, 4>(b, lds, stream);
             return lean ? launch_iterate_tt<real, true, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, true, false, 256, 16>(b, lds, stream);
          }
-         if (variant & 8) return lean ? launch_iterate_tt<real, false, false, 512, 26>(b, lds, stream) : launch_iterate_tt<real, false, false, 512, 16>(b, lds, stream);
-         if (variant & 256) return lean ? launch_iterate_tt<real, false, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 16, 4>(b, lds, stream);
+         if (variant & ORC_VAR_T512) return lean ? launch_iterate_tt<real, false, false, 512, 26>(b, lds, stream) : launch_iterate_tt<real, false, false, 512, 16>(b, lds, stream);
+         if (variant & ORC_VAR_WGS4) return lean ? launch_iterate_tt<real, false, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 16, 4>(b, lds, stream);
          return lean ? launch_iterate_tt<real, false, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 16>(b, lds, stream);
       }
       else
       {
          // fp32 (round 6): 256-thread workgroups at the fp32 many-sphere budget (four per CU), chains and trees
-         if (variant & (2 | 4 | 8)) return hipErrorInvalidValue;
-         if (variant & 1) return lean ? launch_iterate_tt<real, true, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, true, false, 256, 16>(b, lds, stream);
+         if (variant & (ORC_VAR_GS16 | ORC_VAR_T192 | ORC_VAR_T512)) return hipErrorInvalidValue;
+         if (variant & ORC_VAR_TREE) return lean ? launch_iterate_tt<real, true, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, true, false, 256, 16>(b, lds, stream);
          return lean ? launch_iterate_tt<real, false, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 16>(b, lds, stream);
       }
    }
-   if ((variant & 16) && !(variant & 2))      // the many-sphere path with its J^T form known (phase_cost KIND 1)
+   if ((variant & ORC_VAR_KIND) && !(variant & ORC_VAR_GS16))      // the many-sphere path with its J^T form known (phase_cost KIND 1)
    {
-      if (variant & 1)
+      if (variant & ORC_VAR_TREE)
       {
-         if (variant & 8) return launch_iterate_tt<real, true, false, 512, 1>(b, lds, stream);
-         if (variant & 4) return launch_iterate_tt<real, true, false, 192, 1>(b, lds, stream);
+         if (variant & ORC_VAR_T512) return launch_iterate_tt<real, true, false, 512, 1>(b, lds, stream);
+         if (variant & ORC_VAR_T192) return launch_iterate_tt<real, true, false, 192, 1>(b, lds, stream);
          return launch_iterate_tt<real, true, false, 256, 1>(b, lds, stream);
       }
-      if (variant & 8) return launch_iterate_tt<real, false, false, 512, 1>(b, lds, stream);
-      if (variant & 4) return launch_iterate_tt<real, false, false, 192, 1>(b, lds, stream);
+      if (variant & ORC_VAR_T512) return launch_iterate_tt<real, false, false, 512, 1>(b, lds, stream);
+      if (variant & ORC_VAR_T192) return launch_iterate_tt<real, false, false, 192, 1>(b, lds, stream);
       return launch_iterate_tt<real, false, false, 256, 1>(b, lds, stream);
    }
-   if (variant & 16)      // phase_cost KIND: a chain with placed spheres (16), one field with the world's axes (32), floating base (64)
+   if (variant & ORC_VAR_KIND)      // phase_cost KIND: a chain with placed spheres, one field with the world's axes (2), floating base (4), no inactive sphere left (8)
    {
-      const int kind = 1 | ((variant & 32) ? 2 : 0) | ((variant & 64) ? 4 : 0) | (((variant & 160) == 160) ? 8 : 0);
-      // bit 8: the kernels built for four 256-thread workgroups per CU (orc_set_workgroups_per_cu; fp64 fixed-base chains)
+      const int kind = 1 | ((variant & ORC_VAR_ONE_FIELD) ? 2 : 0) | ((variant & ORC_VAR_FLOATING) ? 4 : 0) | (((variant & ONEF_NOINACT) == ONEF_NOINACT) ? 8 : 0);
+      // the kernels built for four 256-thread workgroups per CU (orc_set_workgroups_per_cu; fp64 fixed-base chains)
       if constexpr (sizeof(real) == 8)
-         if ((variant & 256) && !(variant & (4 | 8)))
+         if ((variant & ORC_VAR_WGS4) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512)))
             switch (kind)
             {
             case 1: return launch_iterate_tt<real, false, true, 256, 1, 4>(b, lds, stream);
@@ -2727,8 +2357,8 @@ static hipError_t launch_iterate_t(const DevBatch<real> & b, size_t lds, hipStre
             case 15: return launch_iterate_tt<real, false, true, 256, 15, 4>(b, lds, stream);      // (floating base, one aligned field: BASELINE configs[3])
             }
 #define ORC_KIND_CASE(K) case K: \
-         if (variant & 8) return launch_iterate_tt<real, false, true, 512, K>(b, lds, stream); \
-         if (variant & 4) return launch_iterate_tt<real, false, true, 192, K>(b, lds, stream); \
+         if (variant & ORC_VAR_T512) return launch_iterate_tt<real, false, true, 512, K>(b, lds, stream); \
+         if (variant & ORC_VAR_T192) return launch_iterate_tt<real, false, true, 192, K>(b, lds, stream); \
          return launch_iterate_tt<real, false, true, 256, K>(b, lds, stream);
       switch (kind)
       {
@@ -2736,23 +2366,23 @@ static hipError_t launch_iterate_t(const DevBatch<real> & b, size_t lds, hipStre
       }
 #undef ORC_KIND_CASE
    }
-   if (variant & 8)
-      switch (variant & 3)
+   if (variant & ORC_VAR_T512)
+      switch (variant & (ORC_VAR_TREE | ORC_VAR_GS16))
       {
       case 0: return launch_iterate_tt<real, false, false, 512>(b, lds, stream);
-      case 1: return launch_iterate_tt<real, true, false, 512>(b, lds, stream);
-      case 2: return launch_iterate_tt<real, false, true, 512>(b, lds, stream);
+      case ORC_VAR_TREE: return launch_iterate_tt<real, true, false, 512>(b, lds, stream);
+      case ORC_VAR_GS16: return launch_iterate_tt<real, false, true, 512>(b, lds, stream);
       default: return launch_iterate_tt<real, true, true, 512>(b, lds, stream);
       }
-   switch (variant & 7)
+   switch (variant & (ORC_VAR_TREE | ORC_VAR_GS16 | ORC_VAR_T192))
    {
    case 0: return launch_iterate_tt<real, false, false, 256>(b, lds, stream);
-   case 1: return launch_iterate_tt<real, true, false, 256>(b, lds, stream);
-   case 2: return launch_iterate_tt<real, false, true, 256>(b, lds, stream);
-   case 3: return launch_iterate_tt<real, true, true, 256>(b, lds, stream);
-   case 4: return launch_iterate_tt<real, false, false, 192>(b, lds, stream);
-   case 5: return launch_iterate_tt<real, true, false, 192>(b, lds, stream);
-   case 6: return launch_iterate_tt<real, false, true, 192>(b, lds, stream);
+   case ORC_VAR_TREE: return launch_iterate_tt<real, true, false, 256>(b, lds, stream);
+   case ORC_VAR_GS16: return launch_iterate_tt<real, false, true, 256>(b, lds, stream);
+   case ORC_VAR_TREE | ORC_VAR_GS16: return launch_iterate_tt<real, true, true, 256>(b, lds, stream);
+   case ORC_VAR_T192: return launch_iterate_tt<real, false, false, 192>(b, lds, stream);
+   case ORC_VAR_T192 | ORC_VAR_TREE: return launch_iterate_tt<real, true, false, 192>(b, lds, stream);
+   case ORC_VAR_T192 | ORC_VAR_GS16: return launch_iterate_tt<real, false, true, 192>(b, lds, stream);
    default: return launch_iterate_tt<real, true, true, 192>(b, lds, stream);
    }
 #endif

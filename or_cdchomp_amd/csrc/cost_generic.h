@@ -19,21 +19,6 @@
 //       a fixed summation order.
 #pragma once
 
-#ifndef ORC_SDF_SIGNS
-#define ORC_SDF_SIGNS 1      // 1: which side a one-sided difference looks at is kept as a factor +-1 in a vector register instead of a lane mask in a scalar pair (twelve masks live across the self-collision term spill through v_writelane / v_readlane)
-#endif
-#ifndef ORC_SDF_BATCH
-#define ORC_SDF_BATCH 1      // fields whose cell reads are in flight together (round 3: 4; round 5: 1 -- the first field's reads run under the self-collision term, the others one
-                             // after the other: the registers and lane masks four fields held across that term cost more than the round trips they hid: BASELINE
-                             // configs[4] 257 k -> 234 k vector instructions per run-iteration, 1.78 -> 1.91 M it/s, profiles/r05_ab_experiments.txt)
-#endif
-#ifndef ORC_SDF_BURST
-#define ORC_SDF_BURST 1      // a field's transform and sizes by one burst of scalar loads in front of the in-bounds test
-#endif
-#ifndef ORC_SDF_DEFER
-#define ORC_SDF_DEFER 1      // the fields' cell reads are used after the self-collision term (0: right after they are issued)
-#endif
-
 // START: the pass of the start point alone when it is a variable (`start_tsr`), see cost_gs16.h
 template <typename real, int BLOCK, typename BT, bool START = false>
 __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<real> & mod,
@@ -108,10 +93,13 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
       // round trip, before the next field's addresses are formed).
       typedef const __attribute__((address_space(4))) DevSdfCell<real> CellDesc;
       CellDesc * fc = (CellDesc *) mod.sdfc;
-      constexpr int NB = ORC_SDF_BATCH;      // fields in flight together
+      // fields whose cell reads are in flight together: one -- the first field's reads run under the self-collision term, the others one
+      // after the other (the registers and lane masks four fields held across that term cost more than the round trips they hid: BASELINE
+      // configs[4] 257 k -> 234 k vector instructions per run-iteration, 1.78 -> 1.91 M it/s, profiles/r05_ab_experiments.txt)
+      constexpr int NB = 1;
       real v0[NB], vn[NB][3], fr[NB][3];      // (of the batch of up to four fields in flight)
       bool prev[NB][3], inbq[NB];
-      real sg[NB][3];                        // (ORC_SDF_SIGNS: -1 towards the previous cell, +1 towards the next)
+      real sg[NB][3];                        // (which side a one-sided difference looks at, as a factor: -1 towards the previous cell, +1 towards the next; as lane masks in scalar pairs, twelve of them live across the self-collision term spilled through v_writelane / v_readlane)
       bool use[NB] = {};              // wave-uniform: some sphere of the wavefront is inside the field
       auto sdf_issue = [&](int i0)
       {
@@ -125,7 +113,6 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
          for (int q=0; q<NB; q++)
          {
             CellDesc & F = fc[i0 + q];
-#if ORC_SDF_BURST
             // the field's transform and sizes in ONE burst of scalar loads, before anything is tested (written as a chain of
             // `&&`, the in-bounds test became a ladder of branches with a scalar load and a wait for it on every rung)
             real Mq[9], tq[3], fsq[3];
@@ -144,15 +131,6 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
                gx[q][k] = Mq[k*3+0]*p[0] + Mq[k*3+1]*p[1] + Mq[k*3+2]*p[2] + tq[k];
                inb = inb & !(gx[q][k] < (real)0) & !(gx[q][k] > fsq[k]);      // the reference's x < 0 || x > 1 (grid.c:196-199)
             }
-#else
-            bool inb = live && (i0 + q < mod.n_sdfs);
-#pragma unroll
-            for (int k=0; k<3; k++)
-            {
-               gx[q][k] = F.M[k*3+0]*p[0] + F.M[k*3+1]*p[1] + F.M[k*3+2]*p[2] + F.t[k];
-               inb = inb && !(gx[q][k] < (real)0) && !(gx[q][k] > F.fsize[k]);      // the reference's x < 0 || x > 1 (grid.c:196-199)
-            }
-#endif
             // a field none of the wavefront's spheres is inside of contributes nothing (the reference
             // skips an out-of-bounds lookup, src/orcdchomp_mod.cpp:1176-1183): no cells, no reads
             inbq[q] = inb;
@@ -165,13 +143,6 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
             real m1[3] = { F.fsize_m1[0], F.fsize_m1[1], F.fsize_m1[2] };
             int sb3[3] = { F.stride_b[0], F.stride_b[1], (int) sizeof(real) };
             const char * base = (const char *) F.data;
-#if ORC_SDF_BURST > 1
-            // (issued with the first burst's wait still ahead, whether the field is used or not: no scalar-cache round trip behind the test)
-#pragma unroll
-            for (int k=0; k<3; k++) __asm__ volatile("" : "+s"(m1[k]));
-            __asm__ volatile("" : "+s"(sb3[0])); __asm__ volatile("" : "+s"(sb3[1]));
-            __asm__ volatile("" : "+s"(base));
-#endif
             if (!use[q]) continue;
             if (dbg) dbg[5]++;
             int off = 0;
@@ -184,27 +155,14 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
                fr[q][k] = (g - fl) - (real)0.5;                     // offset from the cell centre, in cells
                // one-sided difference towards the nearer neighbour, inwards at the faces (grid.c:372-389)
                prev[q][k] = (fl == (real)0) ? false : ((fl == m1[k]) ? true : (fr[q][k] < (real)0));
-#if ORC_SDF_SIGNS
                sg[q][k] = prev[q][k] ? (real)(-1) : (real)1;
-#endif
-#if ORC_LEAN
                off += __mul24((int) fl, sb3[k]);                     // (a full-rate SIGNED 24-bit multiply: cell index and byte stride are below 2^23, checked at create: batch.cpp build_device)
-#else
-               off += (int) fl * sb3[k];
-#endif
             }
-#if ORC_LEAN
             // (unsigned 32-bit offsets against the field's base in scalar registers: no sign extension, no 64-bit address add)
             v0[q] = *(const real *)(base + (unsigned int) off);
 #pragma unroll
             for (int k=0; k<3; k++)
                vn[q][k] = *(const real *)(base + (unsigned int)(off + (prev[q][k] ? -sb3[k] : sb3[k])));
-#else
-            v0[q] = *(const real *)(base + off);
-#pragma unroll
-            for (int k=0; k<3; k++)
-               vn[q][k] = *(const real *)(base + (off + (prev[q][k] ? -sb3[k] : sb3[k])));
-#endif
          }
       };
       auto sdf_finish = [&](int i0)
@@ -214,12 +172,6 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
          for (int q=0; q<NB; q++)
 #pragma unroll
             for (int k=0; k<9; k++) Wq[q][k] = fc[i0 + q].W[k];
-#if ORC_SDF_BURST > 2
-#pragma unroll
-         for (int q=0; q<NB; q++)
-#pragma unroll
-            for (int k=0; k<9; k++) __asm__ volatile("" : "+s"(Wq[q][k]));
-#endif
 #pragma unroll
          for (int q=0; q<NB; q++)
          {
@@ -231,11 +183,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
             {
                poisoned = poisoned || (vn[q][k] == inf);
                const real dd = vn[q][k] - v0[q];
-#if ORC_SDF_SIGNS
                df[k] = sg[q][k] * dd;                                // after - before (exact: the factor is +-1)
-#else
-               df[k] = prev[q][k] ? -dd : dd;                        // after - before
-#endif
                val += df[k] * fr[q][k];
             }
             val = poisoned ? inf : val;
@@ -255,9 +203,6 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
       };
 #ifndef ORC_ABLATE_SDF
       sdf_issue(0);
-#if !ORC_SDF_DEFER
-      sdf_finish(0);
-#endif
 #endif
       ORC_GMARK(0);
       // ---- self collision (src/orcdchomp_mod.cpp:1251-1317) ----
@@ -435,10 +380,8 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
       }
       // ---- the obstacle term's second half: values and gradients of the fields, the sphere's cost and force ----
 #ifndef ORC_ABLATE_SDF
-#if ORC_SDF_DEFER
       sdf_finish(0);
-#endif
-      for (int i0=ORC_SDF_BATCH; i0<mod.n_sdfs; i0+=ORC_SDF_BATCH) { sdf_issue(i0); sdf_finish(i0); }      // (more fields than a batch holds: the rest one batch at a time)
+      for (int i0=NB; i0<mod.n_sdfs; i0+=NB) { sdf_issue(i0); sdf_finish(i0); }      // (more fields than a batch holds: the rest one batch at a time)
 #endif
       {
          const bool on = live && has;
@@ -467,7 +410,6 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
             f[k] += push ? val : (real)0;
          }
       }
-
 
       ORC_GMARK(2);
       if (live) cost_lane += cost_sphere;

@@ -10,119 +10,9 @@
 // SDF lookup src/libcd/grid.c:191-209, 331-454.
 #pragma once
 
-#ifndef ORC_GS16_CELL
-#define ORC_GS16_CELL 2      // 1: the one-field variants look the field up in cell units with the descriptor in scalar registers; 2: the general 16-lane pass as well (two fields: +3 %)
-#endif
-
-#ifndef ORC_GS16_BURST
-#define ORC_GS16_BURST 1     // round 5: the lean lookup reads its descriptor's scalars in one burst in front of the in-bounds tests
-#endif
-#ifndef ORC_LEAN
-#define ORC_LEAN 1           // round 4: the pass with fewer issue slots (0: the round-3 forms, for A/B builds)
-#endif
-
 #ifdef ORC_COST_TIMERS
 __device__ long long orc_cost_dbg[8];   // [0] setup [1] obstacle [2] self collision [3] J^T [4] between rounds (thread 0 of every workgroup adds: use one run)
 #endif
-// SDF lookup without early exits: returns whether p is inside the field; value/grad are only
-// meaningful then (indices are clamped so that the loads stay inside the grid either way).
-template <typename real>
-__device__ __forceinline__ bool sdf_lookup_pred(const DevSdf<real> & f, const real p[3], real & value, real grad[3])
-{
-   int sub[3];
-   bool inb = true;
-#pragma unroll
-   for (int d=0; d<3; d++)
-   {
-      const real x = p[d] * f.inv_length[d];
-      inb = inb && !(x < (real)0) && !(x > (real)1);
-      int sb = (int) M<real>::floor_(x * (real) f.size[d]);
-      sb = sb < 0 ? 0 : sb;
-      sb = sb > f.size[d]-1 ? f.size[d]-1 : sb;           // also the reference's sub==size -> size-1
-      sub[d] = inb ? sb : 0;
-   }
-   const int stride[3] = { f.size[1] * f.size[2], f.size[2], 1 };
-   const int index = sub[0]*stride[0] + sub[1]*stride[1] + sub[2];
-   real center[3]; bool prev[3]; int nidx[3];
-#pragma unroll
-   for (int d=0; d<3; d++)
-   {
-      center[d] = ((real)0.5 + (real) sub[d]) * f.cell[d];
-      prev[d] = (sub[d] == 0) ? false : ((sub[d] == f.size[d]-1) ? true : (p[d] < center[d]));
-      nidx[d] = prev[d] ? index - stride[d] : index + stride[d];
-   }
-   const real v0 = f.data[ORC_SDF_IDX(index)];
-   const real vn0 = f.data[ORC_SDF_IDX(nidx[0])], vn1 = f.data[ORC_SDF_IDX(nidx[1])], vn2 = f.data[ORC_SDF_IDX(nidx[2])];
-   const real vn[3] = { vn0, vn1, vn2 };
-   const real inf = M<real>::inf();
-   real v = v0;
-   bool poisoned = (v0 == inf);
-#pragma unroll
-   for (int d=2; d>=0; d--)                     // the reference walks the axes z, y, x
-   {
-      poisoned = poisoned || (vn[d] == inf);
-      const real diff = prev[d] ? (v0 - vn[d]) : (vn[d] - v0);      // after - before
-      const real slope = diff * f.size_over_len[d];
-      grad[d] = slope;
-      v += slope * (p[d] - center[d]);
-   }
-   value = poisoned ? inf : v;
-   return inb;
-}
-
-// The same lookup in two halves, so that the cell reads of several fields are in flight together:
-// sdf_cells() finds the four cells, sdf_combine() forms value and gradient from their contents.
-template <typename real>
-struct SdfCells { int index, nidx[3]; real off[3]; bool prev[3]; bool inb; };
-
-template <typename real>
-__device__ __forceinline__ SdfCells<real> sdf_cells(const DevSdf<real> & f, const real p[3])
-{
-   SdfCells<real> c;
-   int sub[3];
-   bool inb = true;
-#pragma unroll
-   for (int d=0; d<3; d++)
-   {
-      const real x = p[d] * f.inv_length[d];
-      inb = inb && !(x < (real)0) && !(x > (real)1);
-      int sb = (int) M<real>::floor_(x * (real) f.size[d]);
-      sb = sb < 0 ? 0 : sb;
-      sb = sb > f.size[d]-1 ? f.size[d]-1 : sb;
-      sub[d] = inb ? sb : 0;
-   }
-   const int stride[3] = { f.size[1] * f.size[2], f.size[2], 1 };
-   c.index = sub[0]*stride[0] + sub[1]*stride[1] + sub[2];
-#pragma unroll
-   for (int d=0; d<3; d++)
-   {
-      const real center = ((real)0.5 + (real) sub[d]) * f.cell[d];
-      c.prev[d] = (sub[d] == 0) ? false : ((sub[d] == f.size[d]-1) ? true : (p[d] < center));
-      c.nidx[d] = c.prev[d] ? c.index - stride[d] : c.index + stride[d];
-      c.off[d] = p[d] - center;
-   }
-   c.inb = inb;
-   return c;
-}
-
-template <typename real>
-__device__ __forceinline__ void sdf_combine(const DevSdf<real> & f, const SdfCells<real> & c, real v0, const real vn[3], real & value, real grad[3])
-{
-   const real inf = M<real>::inf();
-   real v = v0;
-   bool poisoned = (v0 == inf);
-#pragma unroll
-   for (int d=2; d>=0; d--)                     // the reference walks the axes z, y, x
-   {
-      poisoned = poisoned || (vn[d] == inf);
-      const real diff = c.prev[d] ? (v0 - vn[d]) : (vn[d] - v0);      // after - before
-      const real slope = diff * f.size_over_len[d];
-      grad[d] = slope;
-      v += slope * c.off[d];
-   }
-   value = poisoned ? inf : v;
-}
-
 // The lookup for ONE field whose axes are the world's, in cell units (DevSdfCell), the descriptor in scalar registers:
 // g = sol p + t per axis, value = v0 + sum (after - before) (g - (sub + 0.5)), world gradient = sol (after - before).
 // Returns whether p is inside the field (value / gradient are only meaningful then).
@@ -168,7 +58,7 @@ __device__ __forceinline__ bool sdf_lookup_cell_aligned(const CD & F, const real
    return inb;
 }
 
-// The same lookup in fp64 with fewer issue slots (ORC_LEAN): which side the one-sided difference looks at is a SIGN (+-1.0: one
+// The same lookup in fp64 with fewer issue slots: which side the one-sided difference looks at is a SIGN (+-1.0: one
 // select of a high word) instead of a flag, so the neighbour's offset is one fused multiply-add, `after - before` one product
 // (exact: the factor is +-1), and the cell offset is formed in fp64 (exact below 2^53) and converted once: no quarter-rate
 // integer multiply, no 64-bit address arithmetic (unsigned 32-bit offsets against the field's base in scalar registers).
@@ -178,44 +68,25 @@ __device__ __forceinline__ bool sdf_lookup_cell_aligned_lean(const CD & F, const
 {
    double fr[3], sgn[3], fl[3];
    bool inb = true;
-#if ORC_GS16_BURST
    // the descriptor's scalars in one burst in front of the tests (a chain of `&&` makes a ladder of branches with a scalar load and a wait on
-   // every rung: cost_generic.h ORC_SDF_BURST)
+   // every rung, as in cost_generic.h)
    double Md[3], td[3], fsd[3], fmd[3];
 #pragma unroll
    for (int k=0; k<3; k++) { Md[k] = F.M[4*k]; td[k] = F.t[k]; fsd[k] = F.fsize[k]; fmd[k] = F.fsize_m1[k]; }
 #pragma unroll
    for (int k=0; k<3; k++) { __asm__ volatile("" : "+s"(Md[k])); __asm__ volatile("" : "+s"(td[k])); __asm__ volatile("" : "+s"(fsd[k])); __asm__ volatile("" : "+s"(fmd[k])); }
-#if ORC_GS16_BURST > 1
-   // ... the gradient's scale factors too (read where they are used, each was a scalar-cache round trip behind the cell reads)
-   double Wd[3];
-#pragma unroll
-   for (int k=0; k<3; k++) { Wd[k] = F.W[4*k]; __asm__ volatile("" : "+s"(Wd[k])); }
-#endif
-#endif
 #pragma unroll
    for (int k=0; k<3; k++)
    {
-#if ORC_GS16_BURST
       const double gx = Md[k] * p[k] + td[k];
       inb = inb & !(gx < 0.0) & !(gx > fsd[k]);
       double f0 = M<double>::floor_(gx);
       f0 = M<double>::max_(M<double>::min_(f0, fmd[k]), 0.0);
-#else
-      const double gx = F.M[4*k] * p[k] + F.t[k];
-      inb = inb && !(gx < 0.0) && !(gx > F.fsize[k]);
-      double f0 = M<double>::floor_(gx);
-      f0 = M<double>::max_(M<double>::min_(f0, F.fsize_m1[k]), 0.0);
-#endif
       fl[k] = f0;
       fr[k] = (gx - f0) - 0.5;
       // -1: the cell before (previous) is the other end of the difference; +1: the cell after
       const int hi_mid = (fr[k] < 0.0) ? (int) 0xBFF00000 : 0x3FF00000;
-#if ORC_GS16_BURST
       const int hi_end = (f0 == fmd[k]) ? (int) 0xBFF00000 : hi_mid;
-#else
-      const int hi_end = (f0 == F.fsize_m1[k]) ? (int) 0xBFF00000 : hi_mid;
-#endif
       sgn[k] = __hiloint2double((f0 == 0.0) ? 0x3FF00000 : hi_end, 0);
    }
    const double offr = fma(fl[0], F.stride_r[0], fma(fl[1], F.stride_r[1], fl[2] * F.stride_r[2]));
@@ -233,11 +104,7 @@ __device__ __forceinline__ bool sdf_lookup_cell_aligned_lean(const CD & F, const
    {
       poisoned = poisoned || (vn[k] == inf);
       const double df = sgn[k] * (vn[k] - v0);  // after - before
-#if ORC_GS16_BURST > 1
-      gw[k] = Wd[k] * df;
-#else
       gw[k] = F.W[4*k] * df;
-#endif
       v += df * fr[k];
    }
    value = poisoned ? inf : v;
@@ -311,19 +178,14 @@ __device__ __forceinline__ void self_sym_step16(const real * prow, const real * 
 {
    constexpr int F = 0x120 + K, B = 0x120 + (16 - K);     // row_ror:K and its inverse
    const int sp = dpp_move<F>(srow);
-#if ORC_LEAN
    // (LDS addresses are 32 bits: as a generic pointer the partner's address is a 64-bit multiply-add, a quarter-rate instruction)
    typedef const __attribute__((address_space(3))) real * lds_real_p;
    lds_real_p pp = (lds_real_p)((unsigned int)(unsigned long long) prow + __umul24((unsigned int) sp, (unsigned int)(3 * sizeof(real))));
-#else
-   const real * pp = prow + sp*3;
-#endif
    real d[3];
 #pragma unroll
    for (int k=0; k<3; k++) d[k] = p[k] - pp[k];
    const real d2 = d[0]*d[0] + d[1]*d[1] + d[2]*d[2];
    const real R2 = r2row[(K-1)*16 + srow];
-#if ORC_LEAN
    // the lane's own bit of the ballot IS the comparison's lane mask: no shift-and-test of the 64-bit mask per lane
    const bool near = (d2 <= R2) && live_lane;
    const unsigned long long near_lanes = __builtin_amdgcn_ballot_w64(d2 <= R2) & live_lanes;      // wave-uniform (scalar: and, compare, branch)
@@ -332,15 +194,6 @@ __device__ __forceinline__ void self_sym_step16(const real * prow, const real * 
    { __asm__ volatile("" :: "s"(near_lanes)); return; }      // timing experiments: range tests only
 #endif
    const real ro = srad[sp];                                // the partner's radius from the table in LDS (two DPP moves otherwise)
-#else
-   const unsigned long long near_lanes = __builtin_amdgcn_ballot_w64(d2 <= R2) & live_lanes;      // wave-uniform
-   if (near_lanes == 0ull) return;
-#ifdef ORC_ABLATE_ROTF
-   { __asm__ volatile("" :: "s"(near_lanes)); return; }      // timing experiments: range tests only
-#endif
-   const bool near = (near_lanes >> (threadIdx.x & 63)) & 1ull;
-   const real ro = dpp_move<F>(radius);
-#endif
    real uo[3];
 #pragma unroll
    for (int k=0; k<3; k++) uo[k] = dpp_move<F>(u[k]);
@@ -396,7 +249,7 @@ __device__ __forceinline__ void self_sym_step16(const real * prow, const real * 
 // NOINACT: no inactive sphere is left for the loop over them (none, or all on free lanes of the row).
 template <typename real, int U, int BLOCK, typename BT, bool START = false, bool ONEF = false, bool NJ16 = false, bool NOINACT = false>
 __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<real> & mod,
-   const DevSdf<real> * sdfs, int ts, int te, bool do_iteration, const real * T_s, real * G_s, const real * pos_s, const real * ax_s,
+   int ts, int te, bool do_iteration, const real * T_s, real * G_s, const real * pos_s, const real * ax_s,
    const real * srad_s, const real * sinact_s, const real * r2_s, const int * slink_s, const int * jtype_s, const int * jcol_s,
    real inv_eps, real inv_eps_self, double & cost_lane)
 {
@@ -419,7 +272,7 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
       if (base_item + (tid & ~63) >= items) continue;      // a wavefront without a waypoint in this round (wave-uniform)
       ORC_CMARK(4);
       // the last round of a tile goes first: it is what the tile's barrier waits for
-      if (base_item + BLOCK >= items) __builtin_amdgcn_s_setprio(ORC_PRIO_COST_LAST); else __builtin_amdgcn_s_setprio(ORC_PRIO_COST);
+      if (base_item + BLOCK >= items) __builtin_amdgcn_s_setprio(PRIO_COST_LAST); else __builtin_amdgcn_s_setprio(PRIO_COST);
       const int item = base_item + tid;
       const int g = item >> 4, s = item & 15;
       const bool lane_ok = (item < items) && (((mod.live_mask >> s) & 1ull) != 0);
@@ -481,7 +334,6 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
 #pragma unroll
       for (int u=0; u<U; u++) { best[u] = inf; has[u] = false; bgrad[u][0] = 0; bgrad[u][1] = 0; bgrad[u][2] = 0; }
 #ifndef ORC_ABLATE_SDF
-#if ORC_GS16_CELL
       if constexpr (ONEF)
       {
          typedef const __attribute__((address_space(4))) DevSdfCell<real> CellDesc;
@@ -491,10 +343,8 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
          {
             real gw[3], val;
             bool inb;
-#if ORC_LEAN
             if constexpr (sizeof(real) == 8) inb = sdf_lookup_cell_aligned_lean(F, p[u], val, gw);
             else
-#endif
             inb = sdf_lookup_cell_aligned<real>(F, p[u], val, gw);
             const bool better = inb && (val < best[u]);
             best[u] = better ? val : best[u];
@@ -503,7 +353,7 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
             for (int k=0; k<3; k++) bgrad[u][k] = better ? gw[k] : bgrad[u][k];
          }
       }
-      else if (ORC_GS16_CELL > 1)
+      else      // (the general 16-lane pass looks its fields up in cell units as well: two fields +3 %)
       {
          typedef const __attribute__((address_space(4))) DevSdfCell<real> CellDesc;
          for (int i=0; i<mod.n_sdfs; i++)
@@ -522,42 +372,6 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
             }
          }
       }
-      else
-#endif
-      for (int i=0; i<(ONEF ? 1 : mod.n_sdfs); i++)
-      {
-         const DevSdf<real> & F = sdfs[i];
-#pragma unroll
-         for (int u=0; u<U; u++)
-         {
-            real gp[3], gg[3], gw[3], val;
-            // field axes = world axes (the field is only translated): the products with 0 and 1 are exact
-            const bool aligned = ONEF || (__builtin_amdgcn_readfirstlane(F.rot_identity) != 0);
-            if (aligned)
-            {
-#pragma unroll
-               for (int k=0; k<3; k++) gp[k] = p[u][k] + F.tgw[k];
-            }
-            else
-            {
-#pragma unroll
-               for (int k=0; k<3; k++)
-                  gp[k] = F.Rgw[k*3+0]*p[u][0] + F.Rgw[k*3+1]*p[u][1] + F.Rgw[k*3+2]*p[u][2] + F.tgw[k];
-            }
-            const bool inb = sdf_lookup_pred(F, gp, val, gg);
-            const bool better = inb && (val < best[u]);           // strict <: HUGE_VAL never wins
-            best[u] = better ? val : best[u];
-            has[u] = has[u] || better;
-            if (aligned) { gw[0] = gg[0]; gw[1] = gg[1]; gw[2] = gg[2]; }
-            else
-            {
-#pragma unroll
-               for (int k=0; k<3; k++) gw[k] = F.Rwg[k*3+0]*gg[0] + F.Rwg[k*3+1]*gg[1] + F.Rwg[k*3+2]*gg[2];   // grid -> world
-            }
-#pragma unroll
-            for (int k=0; k<3; k++) bgrad[u][k] = better ? gw[k] : bgrad[u][k];
-         }
-      }
 #endif
 #pragma unroll
       for (int u=0; u<U; u++)
@@ -574,18 +388,12 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
          const real sc2 = scale * (vnorm[u] * b.obs_factor);
          real xg[3], xc[3];
 #pragma unroll
-#if ORC_LEAN
          // (the best field's gradient is finite -- a poisoned value never wins -- and zero without a field, so scale == 0 gives
          // an exact zero without a select; the guard of the two projections is one select of their common factor)
          for (int k=0; k<3; k++) { xg[k] = bgrad[u][k] * sc2; xc[k] = acc[u][k]; }
          const real ivm = moving[u] ? inv_vn2[u] : (real)0;
          const real pg = (xg[0]*vel[u][0] + xg[1]*vel[u][1] + xg[2]*vel[u][2]) * ivm;
          const real pc2 = (xc[0]*vel[u][0] + xc[1]*vel[u][1] + xc[2]*vel[u][2]) * ivm;
-#else
-         for (int k=0; k<3; k++) { xg[k] = (scale == (real)0) ? (real)0 : bgrad[u][k] * sc2; xc[k] = acc[u][k]; }
-         const real pg = moving[u] ? (xg[0]*vel[u][0] + xg[1]*vel[u][1] + xg[2]*vel[u][2]) * inv_vn2[u] : (real)0;
-         const real pc2 = moving[u] ? (xc[0]*vel[u][0] + xc[1]*vel[u][1] + xc[2]*vel[u][2]) * inv_vn2[u] : (real)0;
-#endif
          // x_grad -= cost * curvature, curvature = xc/|v|^2; then c_grad += |v| J^T x_grad.  |v| == 0:
          // the reference's dgemv(alpha=0) leaves c_grad untouched, so the sphere is skipped
          const real cw = cs * inv_vn2[u];
@@ -652,11 +460,7 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
 #endif
 
 #pragma unroll
-#if ORC_LEAN
       for (int u=0; u<U; u++) cost_lane += cost_sphere[u];      // (every term of it was masked where it was added)
-#else
-      for (int u=0; u<U; u++) cost_lane += live[u] ? cost_sphere[u] : 0.0;
-#endif
 
       ORC_CMARK(2);
       // ---- J^T contraction and reduction over the 16 spheres of a waypoint ----
@@ -676,7 +480,6 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
          //                      G_j = axis_j . sum f                          (prismatic)
          // which is sum_s axis_j . ((p_s - anchor_j) x f_s) of src/orcdchomp_mod.cpp:1040-1048,1323.
          real w6[U][6];
-#if ORC_LEAN
          if (mod.n_static)
          {
             const bool stat = ((b.ms.static_mask >> s) & 1ull) != 0;
@@ -685,7 +488,6 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
 #pragma unroll
                for (int k=0; k<3; k++) f[u][k] = stat ? (real)0 : f[u][k];
          }
-#endif
          if (mod.jt_scan || mod.floating)
          {
 #pragma unroll
@@ -695,11 +497,7 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
                w6[u][1] = p[u][2]*f[u][0] - p[u][0]*f[u][2];
                w6[u][2] = p[u][0]*f[u][1] - p[u][1]*f[u][0];
                w6[u][3] = f[u][0]; w6[u][4] = f[u][1]; w6[u][5] = f[u][2];
-#if !ORC_LEAN
-#pragma unroll
-               for (int k=0; k<6; k++) w6[u][k] = live[u] ? w6[u][k] : (real)0;
-#endif
-               // (ORC_LEAN: a lane that is not live holds f = 0 -- every addition to f is masked by the lane's own liveness or by a
+               // (a lane that is not live holds f = 0 -- every addition to f is masked by the lane's own liveness or by a
                // pair's range entry, -1 for lanes without a sphere -- and a finite position: its wrench is an exact zero already.
                // The one exception, a static lane (an inactive sphere riding on a free lane receives its pairs' reactions), is
                // taken out where the forces are final, below.)
@@ -712,22 +510,14 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
                // the scan runs over the spheres sorted by joint: lane i takes the wrench of the i-th of them
                int sl = s;
                __asm__ volatile("" : "+v"(sl));      // keeps the table read inside the pass (hoisted, it is spilled to scratch)
-#if ORC_LEAN
                const int src = mod.slot_of[sl];      // slot_of[i >= Sa_real]: a slot without an active sphere (batch.cpp), whose wrench is zero
-#else
-               const int src = (sl < mod.Sa_real) ? mod.slot_of[sl] : sl;
-#endif
 #pragma unroll
                for (int u=0; u<U; u++)
 #pragma unroll
                   for (int k=0; k<6; k++)
                   {
                      const real v = __shfl(w6[u][k], src, 16);
-#if ORC_LEAN
                      w6[u][k] = v;      // (lanes past the active spheres fetch a lane whose wrench is zero: `src` below)
-#else
-                     w6[u][k] = (s < mod.Sa_real) ? v : (real)0;
-#endif
                   }
             }
 #pragma unroll
@@ -758,11 +548,7 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
                   for (int k=0; k<6; k++)
                   {
                      const real hi = __shfl(w6[u][k], ab & 15, 16);
-#if ORC_LEAN
                      W[k] = hi;         // (a joint that moves no sphere: the result is selected to zero below, once)
-#else
-                     W[k] = (ab < 16) ? hi : (real)0;
-#endif
                   }
                   if (mod.jt_scan == 2)
                   {
@@ -779,7 +565,6 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
                   const real c2 = W[2] - (ax[3]*W[4] - ax[4]*W[3]);
                   const real crev = ax[0]*c0 + ax[1]*c1 + ax[2]*c2;
                   const real cpri = ax[0]*W[3] + ax[1]*W[4] + ax[2]*W[5];
-#if ORC_LEAN
                   const real gj = (ab < 16) ? (rev ? crev : cpri) : (real)0;      // (ab == 16: the joint moves no sphere)
                   if (jok && (item < items) && (wl[u] < nw))
                   {
@@ -789,9 +574,6 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
                      if (b.g_in_lds) ((lds_real_w)(unsigned int)(unsigned long long) G_s)[gi] = gj;
                      else G_s[gi] = gj;
                   }
-#else
-                  if (jok && (item < items) && (wl[u] < nw)) G_s[(ts + wl[u])*n + col] = rev ? crev : cpri;
-#endif
                }
             }
          }

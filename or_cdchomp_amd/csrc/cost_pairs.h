@@ -23,13 +23,6 @@
 // J^T as in cost_gs16.h: one suffix scan of the wrench over the waypoint's lanes, lane r finishes joint r.
 #pragma once
 
-#ifndef ORC_PAIR_HOT_EARLY
-#define ORC_PAIR_HOT_EARLY 0      // 1: the always-evaluated rounds fetch their spheres' velocity terms with the centres (more registers in flight)
-#endif
-#ifndef ORC_PAIR_GATHER_GROUP
-#define ORC_PAIR_GATHER_GROUP 2   // gather entries whose fetches are in flight together (1, 2 or 4: 6 registers each)
-#endif
-
 __device__ __forceinline__ double bperm(int addr4, double v)
 {
    const int lo = __builtin_amdgcn_ds_bpermute(addr4, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(addr4, __double2hiint(v));
@@ -56,9 +49,7 @@ __device__ __forceinline__ PairEnt<float> pair_entry(const __attribute__((addres
 
 // ONEF: there is one field and its axes are the world's, known at compile time.  NOINACT: no inactive sphere is left for
 // the loop over them (none, or all on free lanes of the group).
-// GSL: lanes per waypoint, 32 (two waypoints per wavefront) or 16 (four: the 16-lane family's robots with the pair list instead of
-// the row rotations, an experiment: ORC_PAIRS16=1, profiles/r05_ab_experiments.txt).
-template <typename real, int GSL, int BLOCK, typename BT, bool ONEF = false, bool NOINACT = false>
+template <typename real, int BLOCK, typename BT, bool ONEF = false, bool NOINACT = false>
 __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<real> & mod, int ts, int te, bool do_iteration,
    const real * T_s, real * G_s, const real * pos_s, const real * ax_s, const real * srad_s, const real * sinact_s, const int * slink_s,
    const real * pent_gen, const int * pgat_gen, real inv_eps, real inv_eps_self, double & cost_lane)
@@ -69,6 +60,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
    const int Sa = mod.Sa, S = mod.S, nj = mod.nj, n = b.n;
    const int pstr = (Sa*3) | 1, astr = (nj*6) | 1;   // padded waypoint strides (LdsLayout::pstr/astr)
    const int nw = te - ts;                      // moving waypoints of this tile
+   constexpr int GSL = 32;                      // lanes per waypoint (two waypoints per wavefront)
    const int items = nw * GSL;
    const real inf = M<real>::inf();
    const int rounds = b.ms.pr_rounds, n_hot = b.ms.pr_hot;
@@ -89,7 +81,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
       if (base_item + (tid & ~63) >= items) continue;      // a wavefront without a waypoint in this round (wave-uniform)
       ORC_PMARK(4);
       // the last round of a tile goes first: it is what the tile's barrier waits for
-      if (base_item + BLOCK >= items) __builtin_amdgcn_s_setprio(ORC_PRIO_COST_LAST); else __builtin_amdgcn_s_setprio(ORC_PRIO_COST);
+      if (base_item + BLOCK >= items) __builtin_amdgcn_s_setprio(PRIO_COST_LAST); else __builtin_amdgcn_s_setprio(PRIO_COST);
       const int item = base_item + tid;
       const int wl = item / GSL, s = item & (GSL - 1);
       const bool wp_ok = (item < items);
@@ -253,7 +245,6 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
                wa = bperm(la4, wself); wb = bperm(lb4, wself);
             };
             orc_v2i gat = { 0, 0 };
-            if (ORC_PAIR_HOT_EARLY && hot) { operands(); gat = pgat[r*GSL + s]; }
             // a round ahead: the centres; two rounds ahead: the entry (past the last round: the last round's again, unused)
             real d_n[3];
             centres(ent_n.ab, d_n);
@@ -269,7 +260,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
 #endif
             if (evaluate)
             {
-               if (!(ORC_PAIR_HOT_EARLY && hot)) { operands(); gat = pgat[r*GSL + s]; }
+               operands(); gat = pgat[r*GSL + s];
                real inv_d;
                real dist = sqrt_rsq_pos(near ? d2 : (real)1, &inv_d);
                dist -= rsum;
@@ -294,7 +285,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
                   // entry not in use names the round's last lane, whose force is an exact zero); a side's fetches in flight together
                   const int dg = (int)(((r < 8) ? deg0 : deg1) >> (8*(r & 7))) & 255;      // entries in use over the round: adding | subtracting << 4 (wave-uniform)
                   const int dp = dg & 15, dm = dg >> 4;
-                  constexpr int GG = ORC_PAIR_GATHER_GROUP;
+                  constexpr int GG = 2;      // gather entries whose fetches are in flight together (6 registers each)
 #pragma unroll
                   for (int q0=0; q0<4; q0+=GG)
                   {
@@ -373,11 +364,8 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
                v += dpp_move<0x102>(v);       // row_shl:2
                v += dpp_move<0x104>(v);       // row_shl:4
                v += dpp_move<0x108>(v);       // row_shl:8
-               if constexpr (GSL == 32)
-               {
-                  const real t16 = read_lane(v, 16), t48 = read_lane(v, 48);
-                  v += lower ? ((ln < 32) ? t16 : t48) : (real)0;
-               }
+               const real t16 = read_lane(v, 16), t48 = read_lane(v, 48);
+               v += lower ? ((ln < 32) ? t16 : t48) : (real)0;
                w6[k] = v;                     // sum over the spheres s .. GSL-1 of this waypoint
             }
          }

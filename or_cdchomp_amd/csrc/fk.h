@@ -66,16 +66,6 @@ __device__ __forceinline__ void sincos_joint(float x, float * sn, float * cs)
    *cs = ((q + 1) & 2) ? -ca : ca;
 }
 
-#ifndef ORC_FK_LAZY64
-#define ORC_FK_LAZY64 1      // fp64: the sphere part of a joint's record is fetched after the frame (0: the whole record, 59 words, in one burst: one scalar-cache round trip per joint instead of two)
-#endif
-#ifndef ORC_FK_QPRE
-#define ORC_FK_QPRE 3        // trips of the sin/cos loop whose joint values a lane reads ahead when the trajectory lives in global memory (3 cover 9 joints)
-#endif
-#ifndef ORC_FK_AHEAD
-#define ORC_FK_AHEAD 1
-#endif
-
 // one row of a frame: R[k][0..2] and t[k]
 template <typename real>
 struct FrameRow { real r[3]; real t; };
@@ -215,16 +205,16 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
    cur = base;
    if (TREE) { sv0 = base; sv1 = base; sv2 = base; sv3 = base; }
    // the triad's sin/cos of the joints it stores: lane k evaluates joints j_begin + k, + k + 3, ...
-#if ORC_FK_QPRE
    // (the lane's joint values of the first trips are read before any is used: with the trajectory in global memory every trip
    // of the loop below began with a round trip through L2)
-   int pk_pre[ORC_FK_QPRE]; real q_pre[ORC_FK_QPRE];
+   constexpr int QPRE = 3;      // trips of the loop whose joint values a lane reads ahead (3 cover 9 joints)
+   int pk_pre[QPRE]; real q_pre[QPRE];
 #pragma unroll
-   for (int tq=0; tq<ORC_FK_QPRE; tq++) { pk_pre[tq] = 0; q_pre[tq] = 0; }
+   for (int tq=0; tq<QPRE; tq++) { pk_pre[tq] = 0; q_pre[tq] = 0; }
    if (row_is_global)      // (wave-uniform)
    {
 #pragma unroll
-   for (int tq=0; tq<ORC_FK_QPRE; tq++)
+   for (int tq=0; tq<QPRE; tq++)
    {
       const int j = j_begin + 3*tq + kk;
       const int jm = (j < j_end) ? j : j_end - 1;
@@ -232,27 +222,21 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
       pk_pre[tq] = mod.jctl[2*jc];
    }
 #pragma unroll
-   for (int tq=0; tq<ORC_FK_QPRE; tq++) q_pre[tq] = row[(pk_pre[tq] >> 24) & 127];
+   for (int tq=0; tq<QPRE; tq++) q_pre[tq] = row[(pk_pre[tq] >> 24) & 127];
    }
-#endif
    for (int j0=j_begin; j0<j_end; j0+=3)
    {
       const int j = j0 + kk;
       const int jm = (j < j_end) ? j : j_end - 1;
-#if ORC_FK_QPRE
       const int tq_ = (j0 - j_begin) / 3;
       int pkm; real qm;
-      if (row_is_global && tq_ < ORC_FK_QPRE)
+      if (row_is_global && tq_ < QPRE)
       {
          pkm = pk_pre[0]; qm = q_pre[0];
 #pragma unroll
-         for (int tq=1; tq<ORC_FK_QPRE; tq++) { pkm = (tq_ == tq) ? pk_pre[tq] : pkm; qm = (tq_ == tq) ? q_pre[tq] : qm; }
+         for (int tq=1; tq<QPRE; tq++) { pkm = (tq_ == tq) ? pk_pre[tq] : pkm; qm = (tq_ == tq) ? q_pre[tq] : qm; }
       }
       else { pkm = mod.jctl[2*jm]; qm = row[(pkm >> 24) & 127]; }
-#else
-      const int pkm = mod.jctl[2*jm];
-      real qm = row[(pkm >> 24) & 127];
-#endif
       real snm, csm;
 #ifdef ORC_ABLATE_FKSIN
       snm = qm; csm = (real)1 - qm;
@@ -269,7 +253,7 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
    auto joint_of = [&](int idx) { return (idx < n_anc) ? idx : j_begin + (idx - n_anc); };
    // (fp32: 2 x 32 scalar registers hold this joint's record and the next; an fp64 record is 59 words, and two of
    // them cost more in scalar spills than the fetch ahead gains: measured on BASELINE configs[1] and [3])
-   constexpr bool AHEAD = ORC_FK_AHEAD && sizeof(real) == 4;
+   constexpr bool AHEAD = sizeof(real) == 4;
    DevFkJoint<real> nxt;
    if (AHEAD) nxt = fk_record<real, true>(mod.fkj + joint_of(0));
    for (int idx=0; idx<n_steps; idx++)
@@ -283,9 +267,6 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
       {
          const real * st = ax_wp + j*6;
          sn = st[0]; cs = st[1]; qp = st[2];
-#if ORC_FK_AHEAD > 1
-         __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
       }
       DevFkJoint<real> J;
       if (AHEAD)
@@ -293,7 +274,7 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
          J = nxt;
          nxt = fk_record<real, true>(mod.fkj + joint_of((idx + 1 < n_steps) ? idx + 1 : idx));      // the next joint's record, a step ahead
       }
-      else J = fk_record<real, ORC_FK_LAZY64 == 0>(mod.fkj + j);
+      else J = fk_record<real, false>(mod.fkj + j);      // (fp64: the sphere part of the record is fetched after the frame, by fk_joint_row)
       if (!own)
       {
          const bool revolute = ((J.ctl >> 24) & 1) != 0;
@@ -311,7 +292,7 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
          else if (load_slot == 2) cur = sv2;
          else if (load_slot == 3) cur = sv3;
       }
-      fk_joint_row<real, !AHEAD && (ORC_FK_LAZY64 != 0)>(mod, J, mod.fkj + j, cur, qp, sn, cs, valid && own, ax_wp + j*6 + kk, pos_k);
+      fk_joint_row<real, !AHEAD>(mod, J, mod.fkj + j, cur, qp, sn, cs, valid && own, ax_wp + j*6 + kk, pos_k);
       if (TREE)
       {
          const int save_slot = ((J.ctl >> 20) & 15) - 2;

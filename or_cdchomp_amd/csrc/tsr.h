@@ -530,7 +530,7 @@ __device__ void tsr_block_thomas(const BT & b, const Env<real> & E, const real *
 //   with F_i = f_i [I; 0] is f_i times the delta-delta corner of the inverse, so the columns of F need not ride along (until
 //   round 5 the block was [S | F | r]: 18 columns for a WAM point with three constrained rows, rows of 32 lanes, five registers
 //   and two ds_bpermute per register and step; now 11 columns, rows of 16 lanes, three registers, DPP for the multipliers
-//   and one ds_bpermute pair for the pivot row -- the v_permlane form of that measured slower, ORC_TSR_PRAW below).
+//   and one ds_bpermute pair for the pivot row -- the v_permlane form of that measured slower, see gauss_jordan_regs).
 //   What the next point takes of this one -- the corner of the inverse and r' -- sits in the SAME lanes and registers of the
 //   next block: nothing moves between lanes when a block is put together.  Only the rows of C' and r' the back pass needs go
 //   to memory.
@@ -558,48 +558,10 @@ __device__ __forceinline__ T * uniform_ptr(T * p)
    return (T *)(((unsigned long long) hi << 32) | lo);
 }
 
-#ifndef ORC_TSR_BIG_SHAPES
-#define ORC_TSR_BIG_SHAPES 1   // rows of 32 lanes with 10 and 12 registers (17 .. 24 rows per block); 0: such blocks take the LDS form
-#endif
-#ifndef ORC_TSR_PRAW
-#define ORC_TSR_PRAW 1      // the pivot row to every row-slot: 0 v_permlane16/32_swap, 1 ds_bpermute (kept: the step is bound by vector issue, profiles/r06_ab_experiments.txt)
-#endif
-#ifndef ORC_TSR_UNIT
-#define ORC_TSR_UNIT 1      // the unit column of the in-place inverse: 0 selects, 1 a multiply by 0 / 1 (kept)
-#endif
 template <int K> struct PivotIndex { static constexpr int value = K; };
 template <int... Ks, typename F>
 __device__ __forceinline__ void for_each_pivot(std::integer_sequence<int, Ks...>, F && f) { (f(PivotIndex<Ks>{}), ...); }
 
-// Row-slot J of the wavefront (one of its four 16-lane rows when WP == 16, one of its two 32-lane halves when WP == 32) to every
-// row-slot, lane by lane: v_permlane16_swap / v_permlane32_swap on (x, x) -- the swap of the odd rows of one operand with the even
-// rows of the other leaves (x0 x0 x2 x2) and (x1 x1 x3 x3), the swap of the halves (lo lo) and (hi hi); J is a compile-time constant,
-// so the choice between the two results costs nothing.  No LDS crossbar behind it (ds_bpermute: ~100 cycles in a dependent chain);
-// scripts/ubench/permlane_bcast.hip checks the lane pictures on the card.
-template <int WP, int J>
-__device__ __forceinline__ unsigned slot_bcast_u32(unsigned x)
-{
-   if constexpr (WP == 16)
-   {
-      const auto a = __builtin_amdgcn_permlane16_swap(x, x, false, false);
-      const unsigned y = (J & 1) ? a[1] : a[0];
-      const auto h = __builtin_amdgcn_permlane32_swap(y, y, false, false);
-      return (J & 2) ? h[1] : h[0];
-   }
-   else
-   {
-      const auto h = __builtin_amdgcn_permlane32_swap(x, x, false, false);
-      return J ? h[1] : h[0];
-   }
-}
-template <int WP, int J>
-__device__ __forceinline__ double slot_bcast(double v)
-{
-   const unsigned lo = slot_bcast_u32<WP, J>((unsigned) __double2loint(v)), hi = slot_bcast_u32<WP, J>((unsigned) __double2hiint(v));
-   return __hiloint2double((int) hi, (int) lo);
-}
-template <int WP, int J>
-__device__ __forceinline__ float slot_bcast(float v) { return __uint_as_float(slot_bcast_u32<WP, J>(__float_as_uint(v))); }
 // lane K of every row-slot to the whole slot: DPP row_newbcast inside the 16-lane rows; a 32-lane half takes the row that holds
 // lane K through one v_permlane16_swap
 template <int WP, int K>
@@ -626,7 +588,7 @@ __device__ __forceinline__ float lane_bcast(float v) { return __uint_as_float(la
 // t (64 / WP) + rsub), pivots 0 .. N-1, WP = 16 or 32.  Every step is written out: the pivot's register and the row-slot that holds it
 // are known at compile time, so a step selects nothing: the pivot by v_readlane, the lane's multipliers W[r][k] by lane_bcast
 // (DPP; round 6 for rows of 32 lanes, which took two ds_bpermute per register until then), the pivot row at this lane's column by
-// one ds_bpermute pair (ORC_TSR_PRAW 1) or by slot_bcast (0: v_permlane swaps, no LDS crossbar in the chain -- and 7 % slower on
+// one ds_bpermute pair (v_permlane16/32 swaps instead, with no LDS crossbar in the chain, measured 7 % slower on
 // the bench lines, whose steps are bound by vector issue: profiles/r06_ab_experiments.txt).  Steps k >= N are skipped (wave-uniform).
 // INPLACE: the block is S (N x N) with right-hand sides in further columns, and S is replaced by its INVERSE -- column k plays the
 // unit column e_k of the augmented form [S | I] in step k, the step it would become one in; a block then needs N + 1 columns
@@ -643,28 +605,18 @@ __device__ __forceinline__ bool gauss_jordan_regs(real (& w)[NREG], int N, int c
       if (k < N)
       {
          const real p = read_lane(w[tk], j * WP + k);
-#if ORC_TSR_PRAW == 1
          real praw = lane_fetch(w[tk], (j * WP + c) * 4);       // the pivot row at this lane's column: ds_bpermute (A/B: profiles/r06_ab_experiments.txt)
-#else
-         real praw = slot_bcast<WP, j>(w[tk]);                 // the pivot row at this lane's column
-#endif
          real f[NREG];
 #pragma unroll
          for (int t=0; t<NREG; t++) f[t] = lane_bcast<WP, k>(w[t]);      // W[r][k] of the lane's own rows
          const bool unit = INPLACE && (c == k);
          if (INPLACE) praw = unit ? (real)1 : praw;
          const real prow = praw * rcp_fast(p);
-#if ORC_TSR_UNIT == 1
          const real keep = unit ? (real)0 : (real)1;           // (one multiply per register instead of two 32-bit selects)
-#endif
 #pragma unroll
          for (int t=0; t<NREG; t++)
          {
-#if ORC_TSR_UNIT == 1
             const real from = INPLACE ? w[t] * keep : w[t];
-#else
-            const real from = (INPLACE && unit) ? (real)0 : w[t];
-#endif
             const real upd = from - f[t] * prow;
             w[t] = (t == tk) ? ((rsub == j) ? prow : upd) : upd;
          }
@@ -1285,13 +1237,11 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp)
       __syncthreads();
       const int Nm = b.tsr_nmax, wave = tid >> 6;
       int shape = 0;                             // the register form's padded width, 0: the LDS form (one wavefront)
-#ifndef ORC_TSR_LDS
       // a block [S | r] of N = n + (constrained rows of the point) rows needs N + 1 columns: rows of 16 lanes up to N = 15
       // (a 7-dof arm with up to eight constrained rows on a point), rows of 32 lanes up to N = 24
       if (BLOCK >= 128 && m >= 4 && n <= 23)
-         shape = (Nm <= 15) ? 16 : ((Nm <= (ORC_TSR_BIG_SHAPES ? 24 : 16)) ? 32 : 0);
+         shape = (Nm <= 15) ? 16 : ((Nm <= 24) ? 32 : 0);
       if (Nm - n > 16) shape = 0;      // (the row lists of a point hold 16 entries: more constrained rows on one point take the dense path)
-#endif
       if (!shape)
       {
          if (tid < 64) tsr_block_thomas<real>(b, E, hws, Jws, Cst, E.redi);
@@ -1313,10 +1263,8 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp)
             else if (shape == 16 && Nm <= 12) tsr_eliminate_regs<real, 16, 3, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);     // (a WAM point with up to five constrained rows)
             else if (shape == 16) tsr_eliminate_regs<real, 16, 4, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);
             else if (Nm <= 16) tsr_eliminate_regs<real, 32, 8, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);                    // (two rows per register)
-#if ORC_TSR_BIG_SHAPES
             else if (Nm <= 20) tsr_eliminate_regs<real, 32, 10, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);
             else tsr_eliminate_regs<real, 32, 12, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);
-#endif
          }
          else if (wave == 1)
          {
@@ -1325,10 +1273,8 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp)
             else if (shape == 16 && Nm <= 12) tsr_eliminate_regs<real, 16, 3, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
             else if (shape == 16) tsr_eliminate_regs<real, 16, 4, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
             else if (Nm <= 16) tsr_eliminate_regs<real, 32, 8, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
-#if ORC_TSR_BIG_SHAPES
             else if (Nm <= 20) tsr_eliminate_regs<real, 32, 10, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
             else tsr_eliminate_regs<real, 32, 12, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
-#endif
          }
          __threadfence_block();
          __syncthreads();
