@@ -298,6 +298,51 @@ int orc_batch_dims(orc_module * mod, int batch_id, int * n_runs, int * n_points,
 /* overwrite the trajectories of a batch (warm start; what `create starttraj` does for one run,
  * src/orcdchomp_mod.cpp:2375-2416): traj [n_runs][n_points][n] */
 int orc_batch_set_traj(orc_module * mod, int batch_id, const double * traj, size_t count_doubles);
+/* ---- multi-start: K runs per planning problem from different seed trajectories, the best one kept -----------------
+ * The reference has no multi-start (its seed is the straight line, src/orcdchomp_mod.cpp:2417-2464, so K runs of one
+ * problem without hmc are K identical runs); these three calls diversify the seeds, reduce the results and fetch the
+ * winners on the device.  They compose with per-run scenes and the convergence stop: one batch can hold P problems x K
+ * starts, each run stopping on its own, and hand back P trajectories. */
+/* Adds a smooth random displacement to the moving waypoints of every run; after create (or orc_batch_set_traj), before
+ * iterate.  For run r, with m moving waypoints and n columns:  xi = the first m n unit Gaussians of a fresh GSL stream
+ * seeded seeds[r], in [waypoint][dof] order -- exactly what orc_host_gsl_stream(seeds[r], 1.0, m n, ...) returns; seed 0
+ * is GSL's 4357; the stream is the call's own, the batch's hmc stream is not advanced.  delta = sigma c A^-1 xi, column
+ * by column, with A the batch's smoothness metric (what orc_host_metric(m, derivative, dt = 1/(n_points-1), ...)
+ * describes) and c = 1 / |row mid of A^-1|_2, mid = m / 2 (integer division, 0-based moving row): sigma is the standard
+ * deviation, in dof units, of the displacement of the middle waypoint, and the displacement tapers to zero at the fixed
+ * ends (the scale of A cancels).  Then T[moving] += delta and every entry is clamped to [limit_lower, limit_upper] of
+ * its dof.  The arithmetic is in double for precision 32 batches too; the result is stored in the batch's precision.
+ * A run's result depends on its seed, sigma and the batch's parameters only, never on its position in the batch or on
+ * the shard that holds it.  sigma == 0 on a batch the call accepts returns before any device work and changes no bit
+ * (the rejections below are checked first, so they do not depend on sigma).  The call leaves no other state behind: a
+ * perturbed batch is the same batch as one given those trajectories through orc_batch_set_traj.
+ * Rejected with a nonzero return and a message, the batch unchanged and the module usable: a NaN, negative or infinite
+ * sigma; seeds == NULL; an unknown batch; a floating-base batch (quaternion columns); a batch whose start point is free
+ * (start_tsr); derivative > 4 or any metric for which the device has only the dense inverse (orc_host_metric_semisep_rank
+ * gives 0 for a derivative >= 2); a run whose m n Gaussians (doubles) do not fit the LDS of one CU
+ * (m n > 20 136: 8 m n + 2496 bytes of generator state against 160 KB - 256). */
+int orc_batch_perturb(orc_module * mod, int batch_id, double sigma, const unsigned int * seeds);
+/* The best run of every group of a batch, after an iterate call.  group_of_run [n_runs] with entries in [0, n_groups)
+ * (anything else is rejected), or NULL: n_groups contiguous equal blocks of runs (n_runs % n_groups != 0 is then
+ * rejected).  A run is eligible when its status from the last iterate call is 0 or 1, its total cost (costs[run][0] of
+ * that call) is finite and, with require_collision_free != 0, the batch's collision verdict for its current trajectory
+ * says it does not collide -- the verdict orc_batch_collision_verdict gives, with the robot's self-check setting.  Per
+ * group the eligible run of lowest total cost wins, a tie goes to the lowest run index: best_run_out [n_groups] (-1 for a
+ * group without an eligible run), best_cost_out [n_groups] (+inf there), n_eligible_out [n_groups] the group's eligible
+ * runs; any output may be NULL.  A batch that has never been iterated is rejected (orc_batch_iterate with 0 iterations
+ * makes the costs valid).  The reduction is a segmented arg-min on the device over the costs and status an iterate call
+ * left there: only n_groups triples leave it (a module over several devices: every shard reduces its runs and the host
+ * merges n_shards x n_groups candidates by the same rule; groups may span shards).  What stays on the host: the
+ * verdict's retiming and sample planning, as in orc_batch_collision_verdict -- with require_collision_free that path
+ * still reads the trajectories back; without it no trajectory leaves the device.  The arguments are checked before the
+ * verdict is taken: a rejected call costs no read-back. */
+int orc_batch_select_best(orc_module * mod, int batch_id, int n_groups, const int * group_of_run, int require_collision_free,
+   int * best_run_out, double * best_cost_out, int * n_eligible_out);
+/* The rows runs[0 .. n_sel) of what orc_batch_gettraj returns, gathered on the device and copied as n_sel n_points n
+ * doubles: traj_out [n_sel][n_points][n].  An entry -1 (what orc_batch_select_best reports for a group without an
+ * eligible run) gives a row of NaN; duplicates are allowed; runs that live on different shards work.  Any other entry
+ * outside [0, n_runs), a NULL array or a short buffer is an error, found before anything is written to traj_out. */
+int orc_batch_gettraj_runs(orc_module * mod, int batch_id, const int * runs, int n_sel, double * traj_out, size_t cap_doubles);
 /* the collision report the last gettraj produced (the reference logs it, mod.cpp:3000) */
 const char * orc_last_collision_details(const orc_module * mod);
 /* replaces mod::destroy (src/orcdchomp_mod.cpp:3013-3066) */

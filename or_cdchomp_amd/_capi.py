@@ -83,6 +83,9 @@ SYMBOLS = [
     ("orc_batch_get_state", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, c_double_p, C.c_size_t]),
     ("orc_batch_dims", C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p]),
     ("orc_batch_set_traj", C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_size_t]),
+    ("orc_batch_perturb", C.c_int, [C.c_void_p, C.c_int, C.c_double, c_uint_p]),
+    ("orc_batch_select_best", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, c_double_p, c_int_p]),
+    ("orc_batch_gettraj_runs", C.c_int, [C.c_void_p, C.c_int, c_int_p, C.c_int, c_double_p, C.c_size_t]),
     ("orc_last_collision_details", C.c_char_p, [C.c_void_p]),
     ("orc_batch_destroy", C.c_int, [C.c_void_p, C.c_int]),
     ("orc_kernel_time", C.c_int, [C.c_void_p, c_double_p, c_int_p, C.c_int]),

@@ -25,6 +25,15 @@ hipError_t orc_launch_hmc_plan_f64(uint32_t * state, int * next, int n_runs, int
    double * noise, int * iters, int * overflow, hipStream_t stream);
 hipError_t orc_launch_hmc_plan_f32(uint32_t * state, int * next, int n_runs, int iter_begin, int iter_end, int cap, size_t mn, double lambda,
    float * noise, int * iters, int * overflow, hipStream_t stream);
+// multistart_kernels.hip
+size_t orc_perturb_lds_bytes(int m, int n);
+hipError_t orc_launch_perturb_f64(double * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
+   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream);
+hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
+   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream);
+hipError_t orc_launch_select_best(const double * costs, const int * status, const int * collides, const int * group, int n_runs,
+   unsigned long long * key, int * count, int * best, hipStream_t stream);
+hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);
 hipError_t orc_launch_seed_f64(double * traj, const double * starts, const double * goals,
    int n_runs, int n_points, int n, int floating, hipStream_t stream);
 hipError_t orc_launch_seed_f32(float * traj, const double * starts, const double * goals,
@@ -1694,6 +1703,80 @@ void BatchShard::set_traj(const double * traj)
    hip_check(hipStreamSynchronize(stream_), "set_traj sync");
 }
 
+// ---- multi-start ----------------------------------------------------------------------------------------------------
+void BatchShard::perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank)
+{
+   DeviceGuard guard(device);
+   hipStream_t st = stream_;
+   const size_t lds = orc_perturb_lds_bytes(m, n);
+   // one upload: the generators, then the limits of the columns
+   std::vector<double> host(gen);
+   host.insert(host.end(), jl_lo_.begin(), jl_lo_.end());
+   host.insert(host.end(), jl_hi_.begin(), jl_hi_.end());
+   double * d_gen = nullptr; unsigned int * d_seeds = nullptr;
+   try
+   {
+      d_gen = dev_alloc<double>(host.size());
+      d_seeds = dev_alloc<unsigned int>(n_runs);
+      hip_check(hipMemcpyAsync(d_gen, host.data(), host.size()*sizeof(double), hipMemcpyHostToDevice, st), "perturb generators");
+      hip_check(hipMemcpyAsync(d_seeds, seeds, n_runs*sizeof(unsigned int), hipMemcpyHostToDevice, st), "perturb seeds");
+      const double * U = d_gen, * V = d_gen + (size_t) rank * m, * lo = d_gen + (size_t) 2 * rank * m, * hi = lo + n;
+      hipError_t e;
+      if (params.precision == 64) e = orc_launch_perturb_f64((double *) d_traj_, n_runs, n_points, n, m, d_seeds, rank, U, V, scale, lo, hi, lds, st);
+      else e = orc_launch_perturb_f32((float *) d_traj_, n_runs, n_points, n, m, d_seeds, rank, U, V, scale, lo, hi, lds, st);
+      hip_check(e, "perturb_kernel launch");
+      hip_check(hipStreamSynchronize(st), "perturb sync");
+   }
+   catch (...) { dev_free(d_gen); dev_free(d_seeds); throw; }
+   dev_free(d_gen); dev_free(d_seeds);
+}
+
+void BatchShard::select_best(int n_groups, const int * group, const int * collides, unsigned long long * key_out, int * best_out, int * count_out)
+{
+   DeviceGuard guard(device);
+   hipStream_t st = stream_;
+   int * d_group = nullptr; int * d_col = nullptr; unsigned long long * d_key = nullptr; int * d_best = nullptr; int * d_count = nullptr;
+   try
+   {
+      d_group = dev_alloc<int>(n_runs); d_key = dev_alloc<unsigned long long>(n_groups); d_best = dev_alloc<int>(n_groups); d_count = dev_alloc<int>(n_groups);
+      hip_check(hipMemcpyAsync(d_group, group, n_runs*sizeof(int), hipMemcpyHostToDevice, st), "select groups");
+      if (collides)
+      {
+         d_col = dev_alloc<int>(n_runs);
+         hip_check(hipMemcpyAsync(d_col, collides, n_runs*sizeof(int), hipMemcpyHostToDevice, st), "select verdict");
+      }
+      hip_check(hipMemsetAsync(d_key, 0xff, n_groups*sizeof(unsigned long long), st), "select keys");
+      hip_check(hipMemsetAsync(d_best, 0x7f, n_groups*sizeof(int), st), "select runs");      // (0x7f7f7f7f: above every run index)
+      hip_check(hipMemsetAsync(d_count, 0, n_groups*sizeof(int), st), "select counts");
+      hip_check(orc_launch_select_best(d_costs_, d_status_, d_col, d_group, n_runs, d_key, d_count, d_best, st), "select_best kernels launch");
+      hip_check(hipMemcpyAsync(key_out, d_key, n_groups*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "select keys");
+      hip_check(hipMemcpyAsync(best_out, d_best, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select runs");
+      hip_check(hipMemcpyAsync(count_out, d_count, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select counts");
+      hip_check(hipStreamSynchronize(st), "select sync");
+   }
+   catch (...) { dev_free(d_group); dev_free(d_col); dev_free(d_key); dev_free(d_best); dev_free(d_count); throw; }
+   dev_free(d_group); dev_free(d_col); dev_free(d_key); dev_free(d_best); dev_free(d_count);
+}
+
+void BatchShard::gettraj_rows(const std::vector<int> & rows, double * out)
+{
+   if (rows.empty()) return;
+   DeviceGuard guard(device);
+   hipStream_t st = stream_;
+   const size_t row_len = (size_t) n_points * n;
+   int * d_rows = nullptr; double * d_out = nullptr;
+   try
+   {
+      d_rows = dev_alloc<int>(rows.size()); d_out = dev_alloc<double>(rows.size() * row_len);
+      hip_check(hipMemcpyAsync(d_rows, rows.data(), rows.size()*sizeof(int), hipMemcpyHostToDevice, st), "gather rows");
+      hip_check(orc_launch_gather_rows(d_traj_, params.precision, d_rows, (int) rows.size(), row_len, d_out, st), "gather_rows_kernel launch");
+      hip_check(hipMemcpyAsync(out, d_out, rows.size()*row_len*sizeof(double), hipMemcpyDeviceToHost, st), "gather download");
+      hip_check(hipStreamSynchronize(st), "gather sync");
+   }
+   catch (...) { dev_free(d_rows); dev_free(d_out); throw; }
+   dev_free(d_rows); dev_free(d_out);
+}
+
 void BatchShard::set_noise(const double * noise, int n_blocks)
 {
    if (hmc_on_device_) throw std::runtime_error("caller-supplied noise needs the host noise streams (ORC_HMC_HOST=1, or fewer than 256 runs)!");
@@ -1766,6 +1849,7 @@ void Batch::iterate_async(int n_iter, int iter_begin, bool final_eval, bool carr
 {
    if (n_iter < 0) throw std::runtime_error("n_iter must be >=0!");
    last_n_iter = n_iter;
+   iterated = true;
    // one host thread per shard: each asserts its device and launches there (the hmc plan of a shard may wait for its device)
    for_shards([&](size_t k) { shards[k]->iterate_async(n_iter, iter_begin, final_eval, carry); }, true);
 }
@@ -1820,6 +1904,130 @@ void Batch::set_noise(const double * noise, int n_blocks)
 void Batch::set_traj(const double * traj)
 {
    for_shards([&](size_t k) { shards[k]->set_traj(traj + (size_t) offs[k] * n_points * n); }, true);
+}
+
+// ---- multi-start ----------------------------------------------------------------------------------------------------
+void Batch::perturb(double sigma, const unsigned int * seeds)
+{
+   if (!(sigma >= 0.0) || !std::isfinite(sigma)) throw std::runtime_error("perturb: sigma must be a finite number >= 0!");
+   if (!seeds) throw std::runtime_error("null argument: seeds");
+   if (params.floating_base) throw std::runtime_error("perturb: floating-base batches (quaternion columns) are not supported!");
+   if (params.free_start) throw std::runtime_error("perturb: batches with a free start point (start_tsr) are not supported!");
+   const Metric & M = shards[0]->metric();
+   const int D = M.D;
+   if (D > ORC_SS_MAX_RANK || (D >= 2 && M.ss_rank != D))
+      throw std::runtime_error("perturb: the device has only the dense inverse of this batch's metric (derivative > 4, or too few waypoints for it)!");
+   if ((size_t) m * n > BatchShard::ORC_PERTURB_MAX_MN)
+      throw std::runtime_error("perturb: the run's m x n Gaussians do not fit the LDS of one CU (m n <= " + std::to_string(BatchShard::ORC_PERTURB_MAX_MN) + ")!");
+   if (sigma == 0.0) return;
+   // the generators of A^-1: U [D][m], then V [D][m]
+   std::vector<double> gen((size_t) 2 * D * m);
+   if (D == 1)
+   {
+      // A = a tridiag(-1, 2, -1) (both ends fixed): Ainv[i][j] = (i+1) (m-j) / ((m+1) a) for i <= j
+      const double a = M.Aband[(size_t) 1*m + 0] / 2.0;
+      for (int i=0; i<m; i++)
+      {
+         const double diag = M.Aband[(size_t) 1*m + i], lo = i > 0 ? M.Aband[(size_t) 0*m + i] : -a, hi = i < m-1 ? M.Aband[(size_t) 2*m + i] : -a;
+         if (!(a > 0.0) || std::fabs(diag - 2.0*a) > 1e-12*a || std::fabs(lo + a) > 1e-12*a || std::fabs(hi + a) > 1e-12*a)
+            throw std::runtime_error("perturb: the device has only the dense inverse of this batch's metric!");
+         gen[i] = (double)(i + 1);
+         gen[(size_t) m + i] = (double)(m - i) / ((double)(m + 1) * a);
+      }
+   }
+   else
+   {
+      std::copy(M.ssU.begin(), M.ssU.end(), gen.begin());
+      std::copy(M.ssV.begin(), M.ssV.end(), gen.begin() + (size_t) D * m);
+   }
+   // c = 1 / |row mid of A^-1|_2: sigma is the standard deviation of the middle waypoint's displacement
+   std::vector<double> e(m, 0.0), row(m, 0.0);
+   e[m / 2] = 1.0;
+   metric_solve(M, e.data(), 1, row.data());
+   double s2 = 0.0;
+   for (int i=0; i<m; i++) s2 += row[i] * row[i];
+   if (!(s2 > 0.0) || !std::isfinite(s2)) throw std::runtime_error("perturb: the metric's inverse has no middle row!");
+   const double c = 1.0 / std::sqrt(s2);
+   const double scale = sigma * c;
+   for_shards([&](size_t k) { shards[k]->perturb(scale, seeds + offs[k], gen, D); }, true);
+}
+
+std::vector<int> Batch::select_groups(int n_groups, const int * group_of_run) const
+{
+   if (!iterated) throw std::runtime_error("select_best: the batch has not been iterated (orc_batch_iterate with 0 iterations makes its costs valid)!");
+   if (n_groups < 1) throw std::runtime_error("select_best: n_groups must be >=1!");
+   std::vector<int> group(n_runs);
+   if (group_of_run)
+   {
+      for (int r=0; r<n_runs; r++)
+      {
+         if (group_of_run[r] < 0 || group_of_run[r] >= n_groups) throw std::runtime_error("select_best: group_of_run entries must lie in [0, n_groups)!");
+         group[r] = group_of_run[r];
+      }
+   }
+   else
+   {
+      if (n_runs % n_groups) throw std::runtime_error("select_best: n_runs is not a multiple of n_groups (pass group_of_run)!");
+      for (int r=0; r<n_runs; r++) group[r] = r / (n_runs / n_groups);
+   }
+   return group;
+}
+
+void Batch::select_best(int n_groups, const std::vector<int> & group, const int * collides, int * best_run_out, double * best_cost_out, int * n_eligible_out)
+{
+   const size_t S = shards.size();
+   std::vector<unsigned long long> key(S * n_groups);
+   std::vector<int> best(S * n_groups), count(S * n_groups);
+   for_shards([&](size_t k) {
+      shards[k]->select_best(n_groups, group.data() + offs[k], collides ? collides + offs[k] : nullptr,
+                             key.data() + k * n_groups, best.data() + k * n_groups, count.data() + k * n_groups);
+   }, true);
+   // the merge of n_shards x n_groups candidates: the lower cost, then the lower run (the shards hold ascending runs)
+   for (int g=0; g<n_groups; g++)
+   {
+      unsigned long long bk = ~0ull; int br = -1, cnt = 0;
+      for (size_t k=0; k<S; k++)
+      {
+         const size_t q = k * n_groups + g;
+         cnt += count[q];
+         if (count[q] > 0 && key[q] < bk) { bk = key[q]; br = offs[k] + best[q]; }
+      }
+      if (best_run_out) best_run_out[g] = br;
+      if (n_eligible_out) n_eligible_out[g] = cnt;
+      if (best_cost_out)
+      {
+         double cost = HUGE_VAL;
+         if (br >= 0)
+         {
+            const unsigned long long bits = (bk >> 63) ? (bk & 0x7fffffffffffffffull) : ~bk;      // (cost_key of multistart_kernels.hip, undone)
+            std::memcpy(&cost, &bits, sizeof(double));
+         }
+         best_cost_out[g] = cost;
+      }
+   }
+}
+
+void Batch::gettraj_runs(const int * runs, int n_sel, double * out)
+{
+   const size_t row_len = (size_t) n_points * n;
+   const size_t S = shards.size();
+   std::vector<std::vector<int>> rows(S), where(S);      // per shard: local runs, and the rows of `out` they go to
+   for (int q=0; q<n_sel; q++)      // (before anything is written: a rejected call leaves `out` alone)
+      if (runs[q] < -1 || runs[q] >= n_runs) throw std::runtime_error("gettraj_runs: a run index is out of range (-1: a row of NaN)!");
+   for (int q=0; q<n_sel; q++)
+   {
+      const int r = runs[q];
+      if (r == -1) { for (size_t e=0; e<row_len; e++) out[(size_t) q * row_len + e] = std::nan(""); continue; }
+      size_t k = 0;
+      while (r >= offs[k+1]) k++;
+      rows[k].push_back(r - offs[k]); where[k].push_back(q);
+   }
+   for_shards([&](size_t k) {
+      std::vector<double> tmp(rows[k].size() * row_len);
+      shards[k]->gettraj_rows(rows[k], tmp.data());
+      for (size_t j=0; j<rows[k].size(); j++)
+         std::memcpy(out + (size_t) where[k][j] * row_len, &tmp[j * row_len], row_len * sizeof(double));
+   }, true);
 }
 
 void Batch::get_phase_cycles(long long * out)

@@ -587,6 +587,38 @@ int orc_batch_set_traj(orc_module * mod, int id, const double * traj, size_t cou
    });
 }
 
+int orc_batch_perturb(orc_module * mod, int id, double sigma, const unsigned int * seeds)
+{
+   return guarded(mod, [&] { mod->impl->batch(id).perturb(sigma, seeds); });
+}
+
+int orc_batch_select_best(orc_module * mod, int id, int n_groups, const int * group_of_run, int require_collision_free,
+   int * best_run_out, double * best_cost_out, int * n_eligible_out)
+{
+   return guarded(mod, [&] {
+      orc::Batch & b = mod->impl->batch(id);
+      const std::vector<int> group = b.select_groups(n_groups, group_of_run);      // (the arguments first: the verdict below reads every trajectory back)
+      std::vector<int> collides;
+      if (require_collision_free)
+      {
+         collides.resize(b.n_runs);
+         mod->impl->batch_collision_verdict(id, collides.data(), nullptr, nullptr, nullptr, nullptr);
+      }
+      b.select_best(n_groups, group, require_collision_free ? collides.data() : nullptr, best_run_out, best_cost_out, n_eligible_out);
+   });
+}
+
+int orc_batch_gettraj_runs(orc_module * mod, int id, const int * runs, int n_sel, double * out, size_t cap)
+{
+   return guarded(mod, [&] {
+      orc::Batch & b = mod->impl->batch(id);
+      need(runs, "runs"); need(out, "out");
+      if (n_sel < 0) throw std::runtime_error("gettraj_runs: n_sel must be >=0!");
+      if (cap < (size_t) n_sel * b.n_points * b.n) throw std::runtime_error("buffer too small!");
+      b.gettraj_runs(runs, n_sel, out);
+   });
+}
+
 const char * orc_last_collision_details(const orc_module * mod)
 {
    return mod ? mod->impl->last_collision_details.c_str() : "";
@@ -695,40 +727,7 @@ static int host_metric_impl(bool free_start, int m, int derivative, double dt, d
       if (beta_s_out) std::memcpy(beta_s_out, M.beta_s.data(), m*sizeof(double));
       if (beta_g_out) std::memcpy(beta_g_out, M.beta_g.data(), m*sizeof(double));
       if (kappa_out) { kappa_out[0] = M.kss; kappa_out[1] = M.ksg; kappa_out[2] = M.kgg; }
-      if (rhs && solve_out)
-      {
-         const int n = ncols;
-         if (derivative == 1)
-         {
-            // the device's cyclic reduction, executed serially with the same tables
-            std::vector<double> cur(rhs, rhs + (size_t) m*n), nxt((size_t) m*n);
-            int stride = 1;
-            for (int l=0; l<M.pcr_levels; l++)
-            {
-               const double * ka = &M.pcr[(size_t)(2*l)*m]; const double * kc = ka + m;
-               for (int i=0; i<m; i++) for (int c=0; c<n; c++)
-               {
-                  double d = cur[(size_t) i*n+c];
-                  if (i-stride >= 0) d += ka[i] * cur[(size_t)(i-stride)*n+c];
-                  if (i+stride < m)  d += kc[i] * cur[(size_t)(i+stride)*n+c];
-                  nxt[(size_t) i*n+c] = d;
-               }
-               cur.swap(nxt);
-               stride <<= 1;
-            }
-            const double * invb = &M.pcr[(size_t)(2*M.pcr_levels)*m];
-            for (int i=0; i<m; i++) for (int c=0; c<n; c++) solve_out[(size_t) i*n+c] = cur[(size_t) i*n+c] * invb[i];
-         }
-         else if (M.ss_rank > 0)
-            orc::semisep_apply(M, rhs, n, solve_out);      // the device's scans over the band inverse's generators, serially
-         else
-            for (int i=0; i<m; i++) for (int c=0; c<n; c++)
-            {
-               double s = 0.0;
-               for (int k=0; k<m; k++) s += M.Ainv[(size_t) i*m+k] * rhs[(size_t) k*n+c];
-               solve_out[(size_t) i*n+c] = s;
-            }
-      }
+      if (rhs && solve_out) orc::metric_solve(M, rhs, ncols, solve_out);
       return 0;
    }
    catch (...) { return 1; }

@@ -10,6 +10,7 @@
 // A batch's stream lives either here or in the host's GslRng objects (batch.cpp picks at create).
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "mt_wave.h"
 
 namespace {
 
@@ -35,88 +36,11 @@ __global__ void hmc_seed_kernel(uint32_t * state, int * next, const unsigned int
 // k's momentum (written relative to iter_begin; the comparison of the reference is `iter ==
 // hmc_resample_iter` with iter restarting at 0 in every call), and the noise.
 //
-// One WAVEFRONT per run.  A run's stream is sequential in the reference, but every step of it is
-// either a whole-state operation or independent per pair of outputs:
-//   * the MT19937 twist of the 624-word state: lane i of a 64-lane step reads mt[i], mt[i+1],
-//     mt[i+397] and writes mt[i]; the steps run in order, which is exactly the recurrence's order of
-//     dependence (a step only reads words of later steps before they change, and new words of
-//     earlier steps);
-//   * polar Box-Muller (gsl_ran_gaussian): an attempt takes two outputs and is accepted or not on
-//     their own merit, so the k-th Gaussian is the k-th accepted PAIR of the stream: 64 pairs are
-//     tried at once, the accepted ones are compacted with a ballot, and the stream position moves
-//     to the end of the last pair used;
-//   * gsl_rng_uniform_pos skips an output word that is 0 (probability 2^-32 per word, i.e. about
-//     once per 50 launches of 4096 runs): a chunk that contains one is redone by a one-at-a-time walk.
+// One WAVEFRONT per run draws its stream (struct MtWave, mt_wave.h: the twist of the state 64 words at a time, 64 pairs of
+// polar Box-Muller tried at once and the accepted ones compacted with a ballot).
 // (One thread per run, the first version, took 48-115 ms per call for config 4's 4096 runs, as long as
 // the 100 iterations it planned: profiles/r02_config4_kernel_stats.csv.)
 #define ORC_HMC_WAVES 4
-struct MtWave
-{
-   uint32_t * mt;          // [624] in LDS, this run's state
-   int mti;                // next unread word of the state (624: none left)
-   int has_carry;          // the last word of the previous state is still unread ...
-   uint32_t carry;         // ... and this is its tempered value
-   static __device__ __forceinline__ uint32_t temper(uint32_t k)
-   {
-      k ^= (k >> 11);
-      k ^= (k << 7) & 0x9d2c5680U;
-      k ^= (k << 15) & 0xefc60000U;
-      k ^= (k >> 18);
-      return k;
-   }
-   __device__ __forceinline__ int avail() const { return has_carry + (624 - mti); }
-   // word j of the unread stream (j < avail()), tempered
-   __device__ __forceinline__ uint32_t peek(int j) const
-   {
-      if (j < has_carry) return carry;
-      return temper(mt[mti + j - has_carry]);
-   }
-   __device__ __forceinline__ void consume(int words)
-   {
-      mti += words - has_carry;      // (words >= 1 whenever a carry is pending)
-      has_carry = 0;
-   }
-   // the next 624 words; a single unread word of the old state is kept as the carry
-   __device__ __forceinline__ void twist()
-   {
-      const int lane = threadIdx.x & 63;
-      if (mti == 623) { carry = temper(mt[623]); has_carry = 1; }
-      for (int base=0; base<624; base+=64)
-      {
-         const int i = base + lane;
-         if (i < 624)
-         {
-            const uint32_t a = mt[i], b = mt[(i + 1 == 624) ? 0 : i + 1], c = mt[(i + 397 >= 624) ? i + 397 - 624 : i + 397];
-            const uint32_t y = (a & 0x80000000U) | (b & 0x7fffffffU);
-            mt[i] = c ^ (y >> 1) ^ ((y & 1U) ? 0x9908b0dfU : 0U);
-         }
-         __builtin_amdgcn_wave_barrier();
-      }
-      mti = 0;
-   }
-   // one word, one at a time (every lane computes the same): gsl_rng_get
-   __device__ __forceinline__ uint32_t get()
-   {
-      if (avail() == 0) twist();
-      const uint32_t k = peek(0);
-      consume(1);
-      return k;
-   }
-   __device__ __forceinline__ double uniform() { return get() / 4294967296.0; }
-   __device__ __forceinline__ double uniform_pos() { double x; do { x = uniform(); } while (x == 0); return x; }
-   __device__ double gaussian_one(double sigma)
-   {
-      double x, y, r2;
-      do
-      {
-         x = -1 + 2 * uniform_pos();
-         y = -1 + 2 * uniform_pos();
-         r2 = x*x + y*y;
-      }
-      while (r2 > 1.0 || r2 == 0);
-      return sigma * y * sqrt(-2.0 * log(r2) / r2);
-   }
-};
 
 template <typename real>
 __global__ __launch_bounds__(64 * ORC_HMC_WAVES)
@@ -139,42 +63,7 @@ void hmc_plan_kernel(uint32_t * state, int * next, int n_runs, int iter_begin, i
       const double alpha = 100.0 * exp(0.02 * nx);                 // src/orcdchomp_mod.cpp:2759-2762
       const double sigma = 1.0 / sqrt(alpha);
       real * out = noise + ((size_t) k * cap + r) * mn;
-      size_t done = 0;
-      while (done < mn)
-      {
-         if (g.avail() < 2) { g.twist(); }
-         const int pairs = (g.avail() / 2 < 64) ? g.avail() / 2 : 64;
-         const bool mine = (lane < pairs);
-         const uint32_t w1 = mine ? g.peek(2*lane) : 1u, w2 = mine ? g.peek(2*lane + 1) : 1u;
-#ifdef ORC_HMC_TEST_FALLBACK      // test builds: take the one-at-a-time walk often (it must give the same stream)
-         if (__builtin_amdgcn_ballot_w64((w1 & 0x1FFu) == 0u || w2 == 0u) != 0ull)
-#else
-         if (__builtin_amdgcn_ballot_w64(w1 == 0u || w2 == 0u) != 0ull)
-#endif
-         {
-            // an output word that uniform_pos skips: this Gaussian by the one-at-a-time walk
-            const double v = g.gaussian_one(sigma);
-            if (lane == 0) out[done] = (real) v;
-            done++;
-            continue;
-         }
-         const double x = -1 + 2 * (w1 / 4294967296.0), y = -1 + 2 * (w2 / 4294967296.0);
-         const double r2 = x*x + y*y;
-         const bool acc = mine && !(r2 > 1.0 || r2 == 0);
-         const unsigned long long accm = __builtin_amdgcn_ballot_w64(acc);
-         const int rank = __builtin_amdgcn_mbcnt_hi((unsigned)(accm >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) accm, 0u));
-         const size_t need = mn - done;
-         const int cnt = __popcll(accm);
-         if (acc && (size_t) rank < need) out[done + rank] = (real)(sigma * y * sqrt(-2.0 * log(r2) / r2));
-         if ((size_t) cnt >= need)
-         {
-            // the stream stops behind the pair of the last Gaussian wanted
-            const unsigned long long lastm = __builtin_amdgcn_ballot_w64(acc && (size_t) rank == need - 1);
-            g.consume(2 * (__builtin_ctzll(lastm) + 1));
-            done = mn;
-         }
-         else { g.consume(2 * pairs); done += cnt; }
-      }
+      g.gaussians(out, mn, sigma);
       if (lane == 0) iters[(size_t) k * cap + r] = nx - iter_begin;
       r++;
       nx += 1 + (int)(-log(g.uniform()) / lambda);

@@ -528,6 +528,41 @@ void semisep_apply(const Metric & M, const double * rhs, int n, double * out)
    }
 }
 
+void metric_solve(const Metric & M, const double * rhs, int n, double * solve_out)
+{
+   const int m = M.m;
+   if (M.D == 1)
+   {
+      // the device's cyclic reduction, executed serially with the same tables
+      std::vector<double> cur(rhs, rhs + (size_t) m*n), nxt((size_t) m*n);
+      int stride = 1;
+      for (int l=0; l<M.pcr_levels; l++)
+      {
+         const double * ka = &M.pcr[(size_t)(2*l)*m]; const double * kc = ka + m;
+         for (int i=0; i<m; i++) for (int c=0; c<n; c++)
+         {
+            double d = cur[(size_t) i*n+c];
+            if (i-stride >= 0) d += ka[i] * cur[(size_t)(i-stride)*n+c];
+            if (i+stride < m)  d += kc[i] * cur[(size_t)(i+stride)*n+c];
+            nxt[(size_t) i*n+c] = d;
+         }
+         cur.swap(nxt);
+         stride <<= 1;
+      }
+      const double * invb = &M.pcr[(size_t)(2*M.pcr_levels)*m];
+      for (int i=0; i<m; i++) for (int c=0; c<n; c++) solve_out[(size_t) i*n+c] = cur[(size_t) i*n+c] * invb[i];
+   }
+   else if (M.ss_rank > 0)
+      semisep_apply(M, rhs, n, solve_out);      // the device's scans over the band inverse's generators, serially
+   else
+      for (int i=0; i<m; i++) for (int c=0; c<n; c++)
+      {
+         double s = 0.0;
+         for (int k=0; k<m; k++) s += M.Ainv[(size_t) i*m+k] * rhs[(size_t) k*n+c];
+         solve_out[(size_t) i*n+c] = s;
+      }
+}
+
 void build_metric(int m, int D, double dt, Metric & out, bool free_start)
 {
    if (D < 1) throw std::runtime_error("derivative must be >=1!");

@@ -104,6 +104,9 @@ struct Metric
 #endif
 // x = A^-1 rhs ([m][n], row-major) through the generators, in the device's order of operations (serially)
 void semisep_apply(const Metric & M, const double * rhs, int n, double * out);
+// x = A^-1 rhs ([m][n]) by what the device applies for this metric, serially: the cyclic-reduction tables (D = 1), the
+// generators (ss_rank > 0) or the dense inverse -- the solve of orc_host_metric
+void metric_solve(const Metric & M, const double * rhs, int n, double * out);
 void build_metric(int m, int D, double dt, Metric & out, bool free_start = false);   // free_start: no start boundary (`start_tsr`)
 
 // ------------------------------------------------------------------ rng ---

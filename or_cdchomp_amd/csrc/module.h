@@ -183,6 +183,17 @@ public:
    void get_trace(double * out);
    void set_noise(const double * noise, int n_blocks);
    void set_traj(const double * traj);          // [n_runs][n_points][n] host -> device (warm start)
+   // multi-start (multistart_kernels.hip).  m n of a run perturb stages in LDS: 8 m n + 2496 (the mt19937 state) <= 160 KB - 256
+   static constexpr size_t ORC_PERTURB_MAX_MN = 20136;
+   // perturb: T[moving] += scale * A^-1 xi(seed of the run), clamped to the limits;
+   // gen = the generators of A^-1, U [rank][m] then V [rank][m] (Batch::perturb builds them once for all shards)
+   void perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank);
+   // per group the lowest cost key among this shard's eligible runs, the lowest LOCAL run that has it, the eligible runs;
+   // group [n_runs] and collides [n_runs] (or NULL: not asked for) are this shard's slices
+   void select_best(int n_groups, const int * group, const int * collides, unsigned long long * key_out, int * best_out, int * count_out);
+   // rows[k] (local runs) of the trajectory array as doubles: out [rows.size()][n_points][n]
+   void gettraj_rows(const std::vector<int> & rows, double * out);
+   const Metric & metric() const { return metric_; }
    // first contact of every run's trajectory with a field, on the device (Module::batch_collision_verdict plans the samples)
    void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
                           const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
@@ -281,6 +292,12 @@ public:
    void get_trace(double * out);
    void set_noise(const double * noise, int n_blocks);
    void set_traj(const double * traj);
+   // multi-start: orc_batch_perturb / _select_best / _gettraj_runs (include/orcdchomp_amd.h has the contract)
+   void perturb(double sigma, const unsigned int * seeds);
+   std::vector<int> select_groups(int n_groups, const int * group_of_run) const;   // the validated group of every run (NULL: contiguous equal blocks); throws
+   void select_best(int n_groups, const std::vector<int> & group, const int * collides, int * best_run_out, double * best_cost_out, int * n_eligible_out);
+   void gettraj_runs(const int * runs, int n_sel, double * out);
+   bool iterated = false;            // an iterate call has been made: the device's costs and status are a call's results
    void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
                           const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
                           unsigned long long * key_out, double * depth_out);

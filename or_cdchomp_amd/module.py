@@ -96,6 +96,77 @@ def convergence_stop(trace, rtol, patience, obs_max=float("inf")):
     return iters, stopped
 
 
+def seed_perturbation(m, n, derivative, dt, sigma, seed, lower, upper, base):
+    """The seed perturbation of orc_batch_perturb for one run, from the library's host utilities (no GPU).
+
+    base: the run's m moving rows [m][n]; lower, upper: the limits of the n columns.  xi is the first m n unit Gaussians of
+    a fresh GSL stream seeded `seed` (orc_host_gsl_stream; 0 is GSL's 4357) in [waypoint][dof] order; delta = sigma c A^-1 xi
+    column by column with A the smoothness metric of orc_host_metric(m, derivative, dt) and c = 1 / |row m // 2 of A^-1|_2,
+    so that sigma is the standard deviation of the displacement of the middle waypoint.  Returns clip(base + delta, lower,
+    upper) [m][n]; sigma == 0 returns base as it is."""
+    m = int(m); n = int(n)
+    base = np.array(base, dtype=np.float64).reshape(m, n)
+    if not (sigma >= 0 and np.isfinite(sigma)):
+        raise ValueError("sigma must be a finite number >= 0")
+    if sigma == 0:
+        return base
+    lib = _capi.lib()
+    xi = np.zeros(m * n)
+    lib.orc_host_gsl_stream(int(seed), 1.0, m * n, _dp(xi), None)
+    mid = np.zeros((m, 1))
+    mid[m // 2, 0] = 1.0
+    row = np.zeros((m, 1))
+    sol = np.zeros((m, n))
+    xi = np.ascontiguousarray(xi.reshape(m, n))
+    if lib.orc_host_metric(m, int(derivative), float(dt), None, None, None, None, _dp(mid), 1, _dp(row)) != 0 or \
+       lib.orc_host_metric(m, int(derivative), float(dt), None, None, None, None, _dp(xi), n, _dp(sol)) != 0:
+        raise ValueError("no smoothness metric for m %d, derivative %d" % (m, derivative))
+    c = 1.0 / float(np.sqrt(np.sum(row * row)))
+    lo = np.broadcast_to(np.asarray(lower, dtype=np.float64), (n,))
+    hi = np.broadcast_to(np.asarray(upper, dtype=np.float64), (n,))
+    return np.minimum(np.maximum(base + (float(sigma) * c) * sol, lo), hi)
+
+
+def select_best(costs, status, collides, group_of_run, n_groups):
+    """The rule of orc_batch_select_best.  costs [n_runs] total costs (or [n_runs][3] rows as batch_iterate returns them),
+    status [n_runs], collides [n_runs] (None: the collision verdict is not asked for), group_of_run [n_runs] with entries
+    in [0, n_groups).  A run is eligible when its status is 0 or 1, its cost is finite and it does not collide; per group
+    the eligible run of lowest cost wins, a tie goes to the lowest run index.  Returns (best_run int32 [n_groups], -1 for a
+    group without an eligible run; best_cost [n_groups], +inf there; n_eligible int32 [n_groups]).  Pure numpy."""
+    costs = np.asarray(costs, dtype=np.float64)
+    if costs.ndim == 2:
+        costs = costs[:, 0]
+    status = np.asarray(status).reshape(-1)
+    group = np.asarray(group_of_run).reshape(-1)
+    n_runs = costs.shape[0]
+    if status.shape[0] != n_runs or group.shape[0] != n_runs:
+        raise ValueError("costs, status and group_of_run have one entry per run")
+    if n_groups < 1 or (n_runs and (group.min() < 0 or group.max() >= n_groups)):
+        raise ValueError("group_of_run entries must lie in [0, n_groups)")
+    ok = ((status == 0) | (status == 1)) & np.isfinite(costs)
+    if collides is not None:
+        ok &= np.asarray(collides).reshape(-1) == 0
+    best_run = np.full(n_groups, -1, dtype=np.int32)
+    best_cost = np.full(n_groups, np.inf)
+    n_eligible = np.zeros(n_groups, dtype=np.int32)
+    for r in range(n_runs):
+        if not ok[r]:
+            continue
+        g = int(group[r])
+        n_eligible[g] += 1
+        if costs[r] < best_cost[g]:      # (strictly: an equal cost later in the batch does not take over)
+            best_run[g] = r
+            best_cost[g] = costs[r]
+    return best_run, best_cost, n_eligible
+
+
+def contiguous_groups(n_runs, n_groups):
+    """group_of_run of n_groups contiguous equal blocks: what orc_batch_select_best takes a NULL group_of_run for"""
+    if n_groups < 1 or n_runs % n_groups:
+        raise ValueError("%d runs do not divide into %d equal groups" % (n_runs, n_groups))
+    return np.repeat(np.arange(n_groups, dtype=np.int32), n_runs // n_groups)
+
+
 class Module:
     def __init__(self, device=0):
         """device: one HIP ordinal, or a list of them (batches are then sharded over the list inside
@@ -373,6 +444,48 @@ class Module:
         n_runs, n_points, n = self.batch_dims(bid)
         out = np.zeros((n_runs, n_points, n))
         self._check(self._lib.orc_batch_gettraj(self._h, bid, _dp(out), out.size))
+        return out
+
+    # ---- multi-start: perturbed seeds, the best run per problem, its trajectory ----------------------------------
+    def batch_perturb(self, bid, sigma, seeds):
+        """Add a smooth random displacement to the moving waypoints of every run, on the device (orc_batch_perturb; the
+        rule is seed_perturbation's): sigma is the standard deviation at the middle waypoint in dof units, seeds [n_runs]
+        the GSL seed of every run's displacement.  After batch_create / batch_set_traj, before batch_iterate."""
+        n_runs = self.batch_dims(bid)[0]
+        sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+        if sd.size != n_runs:
+            raise ValueError("seeds has %d entries for %d runs" % (sd.size, n_runs))
+        self._check(self._lib.orc_batch_perturb(self._h, bid, float(sigma), sd.ctypes.data_as(_capi.c_uint_p)))
+
+    def batch_select_best(self, bid, groups=None, n_groups=None, collision_free=True):
+        """The best run of every group after an iterate call, reduced on the device (orc_batch_select_best; the rule is
+        select_best's).  groups: group_of_run [n_runs] (n_groups defaults to its maximum + 1), or None for n_groups
+        contiguous equal blocks (one group when n_groups is None too).  Returns (best_run int32 [n_groups], -1 for a
+        group without an eligible run; best_cost [n_groups], +inf there; n_eligible int32 [n_groups])."""
+        n_runs = self.batch_dims(bid)[0]
+        gp = None
+        if groups is not None:
+            gp = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+            if gp.size != n_runs:
+                raise ValueError("groups has %d entries for %d runs" % (gp.size, n_runs))
+            if n_groups is None:
+                n_groups = int(gp.max()) + 1
+        elif n_groups is None:
+            n_groups = 1
+        n_groups = int(n_groups)
+        size = max(n_groups, 1)
+        best = np.zeros(size, dtype=np.int32); cost = np.zeros(size); cnt = np.zeros(size, dtype=np.int32)
+        self._check(self._lib.orc_batch_select_best(self._h, bid, n_groups, None if gp is None else _ip(gp),
+                                                    1 if collision_free else 0, _ip(best), _dp(cost), _ip(cnt)))
+        return best[:n_groups], cost[:n_groups], cnt[:n_groups]
+
+    def batch_gettraj_runs(self, bid, runs):
+        """The rows `runs` of batch_gettraj, gathered on the device (orc_batch_gettraj_runs): [len(runs)][n_points][n];
+        an entry -1 (select_best's "no eligible run") gives a row of NaN, duplicates are allowed."""
+        _, n_points, n = self.batch_dims(bid)
+        rs = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1)
+        out = np.zeros((rs.size, n_points, n))
+        self._check(self._lib.orc_batch_gettraj_runs(self._h, bid, _ip(rs), rs.size, _dp(out), out.size))
         return out
 
     def batch_collision_verdict(self, bid):
