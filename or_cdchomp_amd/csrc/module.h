@@ -15,54 +15,9 @@
 #include <mutex>
 #include <string>
 #include <vector>
-#include "dev_types.h"
-#include "host_math.h"
+#include "stages.h"      // Robot, Sdf, SceneTable, TsrSpec, BatchParams; the stages of `create`
 
 namespace orc {
-
-struct Robot                      // what the path reads from an OpenRAVE::RobotBase
-{
-   std::string name;
-   int n_links = 0;
-   std::vector<int> parent;
-   std::vector<Pose> pose_parent_joint;
-   std::vector<int> joint_type;
-   std::vector<double> axis;      // [n_links][3]
-   std::vector<int> dof_index;
-   int n_dof = 0;
-   std::vector<double> limit_lower, limit_upper;
-   std::vector<double> limit_vel;   // GetDOFVelocityLimits, used by the retimer of gettraj (default 1)
-   struct Sphere { int link; double pos[3]; double radius; int body = 0; };   // struct sphere, src/orcdchomp_kdata.h:33-39; body: 0 the robot's own, 1 + k a sphere of the k-th grabbed body (robot_for_run)
-   std::vector<Sphere> spheres;   // XML order
-   // what the TSR constraints address (`con_tsr 'all link NAME'`, `'all manipee NAME'`, src/orcdchomp_mod.cpp:1957-1976)
-   std::vector<std::string> link_names;        // GetLink(name); empty: links are addressed as "link<i>"
-   struct Manip { std::string name; int link; Pose tool; };   // GetEndEffectorTransform = link transform o tool
-   std::vector<Manip> manips;
-   int active_manip = 0;                       // GetActiveManipulator
-   std::vector<std::pair<int, int>> adjacent;  // link pairs the robot description declares adjacent (<adjacent> tags)
-   bool self_check = true;                     // the sphere-pair stand-in for CheckSelfCollision in gettraj's re-check (orc_robot_set_self_check)
-   // kinbodies the robot holds, in the order they were grabbed (RobotBase::Grab / GetGrabbed, src/orcdchomp_mod.cpp:2168-2171):
-   // the body is rigid with `link` from the moment of the grab, `rel` = T_w_link^-1 o T_w_body at that moment
-   // touch_link / touch_body: what the body's spheres overlapped AT THE MOMENT OF THE GRAB (Module::grab; taken anew when
-   // set_kinbody_transform re-anchors it): links of the robot, by its own spheres, and bodies the robot held already.
-   // OpenRAVE's CheckSelfCollision leaves a grabbed body out against exactly those (and against the grabbing link).
-   struct Grab { std::string body; int link; Xform rel; std::vector<unsigned char> touch_link; std::vector<std::string> touch_body; };
-   std::vector<Grab> grabbed;
-   // state
-   Pose transform;
-   std::vector<double> dof_values;
-   std::vector<int> active_dofs;
-   bool does_affect(int dof, int link) const;
-   // link pairs a self-collision check skips [n_links][n_links]: the same link, parent and child, the pairs the robot
-   // description declares adjacent, and links whose spheres already overlap with all dofs at zero (KinBody computes
-   // its non-adjacent links from the initial configuration the same way)
-   std::vector<unsigned char> self_pairs_excluded() const;
-   // ... sphere by sphere for a run's list (the robot's spheres, then those of the bodies it holds, `spheres` as robot_for_run
-   // leaves them, the robot in the configuration of `create`): [n][n], 1 = the pair is never tested
-   std::vector<unsigned char> run_self_pairs_excluded(int n_own) const;
-   // world frames of all links for the given state
-   void fk(const Pose & base, const std::vector<double> & q, std::vector<Xform> & frames) const;
-};
 
 struct KinBody                    // a kinbody of oriented boxes (InitFromBoxes style) and / or triangles (a mesh: KinBody::InitFromTrimesh, the .iv files of the reference's scene)
 {
@@ -95,57 +50,21 @@ private:
 // device memory released on the device it was allocated on
 std::shared_ptr<void> device_buffer(int device, size_t bytes);
 
-struct Sdf                        // struct sdf, src/orcdchomp_mod.cpp:148-153
+// Device memory with one owner: what the handle holds is freed when it is reset or destroyed, on the device that was current
+// when the handle took it (the device of the allocation).
+class DevBuf
 {
-   std::string kinbody_name;
-   Pose pose;                     // grid wrt kinbody frame
-   Grid grid;
-   // device copies per device ordinal, created on demand; batches that read a copy share its
-   // ownership, so removefield while a run exists does not pull the cells from under it
-   std::map<int, std::shared_ptr<void>> dev64, dev32;
-};
-
-// The obstacles of a batch's runs (orc_batch_create_scenes): scenes of at most ORC_MAX_SDFS field placements, every run
-// in one of them.  orc_batch_create is the one-scene case: the module's fields where their kinbodies stand, every run in
-// scene 0 (Module::current_scene).
-struct ScenePlacement
-{
-   std::shared_ptr<Sdf> sdf;      // the module's field (shared: removefield does not pull it from under a batch)
-   Pose pose_world_kinbody;       // where its kinbody stands for this scene: the field is at pose_world_kinbody o sdf->pose
-};
-struct SceneTable
-{
-   std::vector<std::vector<ScenePlacement>> scenes;   // in the order of the best-of-N loop: a tie goes to the earlier field
-   std::vector<int> scene_of_run;                     // [n_runs]
-   int max_fields() const;                            // fields of the largest scene
-};
-
-// a TSR hard constraint on every moving point (`con_tsr all ...` or `everyn_tsr`; struct tsr,
-// src/orcdchomp_mod.h:80-87, struct run_contsr, src/orcdchomp_mod.cpp:873-885)
-struct TsrSpec
-{
-   int ee_link = -1;
-   Pose tool;                 // end effector in the link frame (identity for `link NAME`)
-   Pose T0w, Twe;
-   double Bw[6][2];
-   int point = -1;            // -1: every moving point (`con_tsr all`, `everyn_tsr`); >= 0: that moving point only (`start_tsr`: 0)
-};
-
-struct BatchParams
-{
-   std::vector<TsrSpec> tsrs; // in the reference's order of addition: start_tsr, everyn_tsr, then the con_tsrs (mod.cpp:2570-2612)
-   int free_start = 0;        // `start_tsr`: the start point is a variable (m = n_points - 1, no start boundary in the metric)
-   int n_points = 101;
-   int floating_base = 0;
-   double lambda = 10.0;
-   int derivative = 1;
-   int use_momentum = 0;
-   int use_hmc = 0;
-   double hmc_resample_lambda = 0.02;
-   double epsilon = 0.1, epsilon_self = 0.04, obs_factor = 200.0, obs_factor_self = 10.0;
-   int precision = 64;
-   int workgroup_threads = 0;   // 0: the module's setting (orc_set_workgroup_threads); `create` asks for 512 for its single run
-   int workgroups_per_cu = 0;   // 0: the module's setting (orc_set_workgroups_per_cu)
+public:
+   DevBuf() = default;
+   ~DevBuf() { reset(); }
+   DevBuf(const DevBuf &) = delete;
+   DevBuf & operator=(const DevBuf &) = delete;
+   void reset(void * p = nullptr);
+   template <typename T> T * as() const { return static_cast<T *>(p_); }
+   explicit operator bool() const { return p_ != nullptr; }
+private:
+   void * p_ = nullptr;
+   int device_ = -1;
 };
 
 // the convergence stop of a batch's runs (orc_batch_set_convergence; dev_types.h DevBatch::conv_*): patience 0 is off
@@ -212,66 +131,60 @@ public:
    std::vector<int> device_sphere_order;    // XML index of device sphere k
    std::vector<int> slot_xml;               // XML index of the sphere in lane/slot q of the active block, -1: empty
 private:
-   template <typename real> void build_device(const Robot & robot);
+   template <typename real> void build_device(const Robot & robot);     // the stages of stages.h, and the uploads of what they return
+   template <typename real> std::shared_ptr<void> grid_on_device(Sdf & s);      // the device's copy of a field's grid, shared by the shards
+   template <typename real> void seed_runs(const Robot & robot, const double * starts, const double * goals, const double * basegoals);
+   void start_hmc(const unsigned int * seeds);
    template <typename real> void launch(int n_iter, bool final_eval, bool carry);
+   template <typename real> void collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
+      const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+      unsigned long long * key_out, double * depth_out);
    void plan_hmc(int iter_begin, int iter_end);
-   int hmc_room(int n_iter) const;
+   int hmc_room(int n_iter, const Switches & now) const;
    void hmc_reserve(int cap, bool pending_work);
    void construct(const Robot & robot, const double * starts, const double * goals, const double * basegoals,
       const unsigned int * seeds);
-   void release();                  // frees every device buffer (destructor and failed construction)
    Module * mod_;
    hipStream_t stream_ = nullptr;   // the stream all work of this shard is issued on
+   Switches sw_;                    // the environment's switches as `create` found them
    std::vector<std::shared_ptr<void>> sdf_refs_;   // the field copies the device descriptors point at
    std::shared_ptr<const SceneTable> scenes_;      // the batch's scenes; this shard holds runs [run0_, run0_ + n_runs) of its scene_of_run
    int run0_ = 0;
-   int * d_scene_of_run_ = nullptr; int * d_scene_nsdf_ = nullptr;
-   int n_scenes_ = 1, sdfc_stride_ = 0;
    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_events_;
    Metric metric_;
-   // device buffers (typed by params.precision)
-   void * d_model_ = nullptr; void * d_sdfs_ = nullptr; void * d_sdfc_ = nullptr;
-   void * d_traj_ = nullptr; void * d_AG_ = nullptr; void * d_G_ = nullptr; void * d_Gcost_ = nullptr;
-   double * d_costs_ = nullptr; double * d_trace_ = nullptr; size_t trace_cap_ = 0;
-   double * d_conv_prev_ = nullptr; int * d_conv_streak_ = nullptr;      // [n_runs] the convergence stop's state between the launches of a call
-   int * d_status_ = nullptr; int * d_iters_done_ = nullptr; int * d_leap_ = nullptr; long long * d_phase_ = nullptr;
-   void * d_Aband_ = nullptr; void * d_beta_s_ = nullptr; void * d_beta_g_ = nullptr; void * d_metric64_ = nullptr;
-   void * d_pcr_ = nullptr; void * d_Ainv_ = nullptr; void * d_jl_lo_ = nullptr; void * d_jl_hi_ = nullptr;
+   // what the stages of `create` left (stages.h)
+   ModelScalars ms_ = {};           // the device model's scalars (carried in the kernarg block)
+   TsrDims tsr_;
+   SceneDims scn_;
+   MetricDims met_;
+   IteratePlan plan_;
+   // device buffers of the shard (typed by params.precision: a cast where they are used)
+   DevBuf d_model_, d_sdfs_, d_sdfc_, d_scene_of_run_, d_scene_nsdf_;
+   DevBuf d_traj_, d_AG_, d_G_, d_Gcost_;
+   DevBuf d_costs_, d_trace_; size_t trace_cap_ = 0;
+   DevBuf d_conv_prev_, d_conv_streak_;      // [n_runs] the convergence stop's state between the launches of a call
+   DevBuf d_status_, d_iters_done_, d_leap_, d_phase_;
+   DevBuf d_Aband_, d_beta_s_, d_beta_g_, d_metric64_, d_pcr_, d_Ainv_, d_jl_lo_, d_jl_hi_;
    // TSR hard constraints (csrc/tsr.h): the device copies of the constraints, the per-run workspace
-   void * d_tsrs_ = nullptr; void * d_tsr_ws_ = nullptr; int * d_tsr_err_ = nullptr;
-   int n_tsrs_ = 0, cons_k_ = 0; size_t tsr_ws_stride_ = 0;
+   DevBuf d_tsrs_, d_tsr_ws_, d_tsr_err_;
+   // The momentum resamples of a call: iterations [n_runs][cap] and noise [n_runs][cap][m n].  NOT owned: they point at the
+   // module's buffers of this shard's stream (plan_shared_, Module::plan_buffers) or at own_* below
    int * d_hmc_iters_ = nullptr; void * d_noise_ = nullptr; size_t hmc_cap_iters_ = 0, noise_cap_ = 0;
+   bool plan_shared_ = false;
+   DevBuf own_hmc_iters_, own_noise_;
    int max_resamples_ = 0;
    hipEvent_t ev_plan_[2] = { nullptr, nullptr };   // iterate stream -> plan stream -> iterate stream
    int overflow_host_ = 0; bool overflow_armed_ = false;   // the plan's overflow flag, read (and cleared) with the results of a call
-   bool plan_shared_ = false;                               // d_noise_ / d_hmc_iters_ are the module's buffers of this shard's stream
    bool unusable_ = false;                                  // set by an overflow: the runs' schedules were cut short, the batch has to be created again
-   bool debug_state_ = false;   // ORC_DEBUG_STATE=1: keep the last gradient readable (get_state "G")
-   int n_sdfs_ = 0;
-   int n_tiles_ = 1, tile_first_ = 0, tile_rest_ = 0;   // tiles of an iteration: the first of tile_first_ moving waypoints, the others of tile_rest_
-   ModelScalars ms_ = {};             // the device model's scalars (carried in the kernarg block)
-   int Sa_real_ = 0;                  // active spheres
-   int tsr_blocks_ = 0;               // (constraint, point) blocks of the TSR system
-   int tsr_kmax_ = 0;                 // most constrained rows on one point
-   int nj_ = 0, Sa_ = 0, S_ = 0;      // optimized joints; lanes of the active sphere block; lanes + inactive spheres
-   int tile_m_ = 0;
-   int block_ = 256;                  // threads per workgroup of the iterate kernel (256 or 192)
-   int pcr_in_lds_ = 0;
-   int variant_ = 0;      // the kernel variant mask (ORC_VAR_ bits of dev_types.h)
-   bool pairs_latency_shape_ = false;      // the pair-list family's 512-thread kernels exist for this robot and precision (fp64 chains)
-   int pair_entries_ = 0;             // entries of the staged self-collision pair list (rounds x 32; 0: the kernel family does not use one)
-   int pcr_rows_ = 0, pcr_sym_ = 0, solve_mode_ = 0, ag_in_lds_ = 1, g_in_lds_ = 1, t_in_lds_ = 1, lds_flags_ = 0, GS_ = 0;
-   size_t lds_bytes_ = 0;
    std::vector<double> jl_lo_, jl_hi_;
    // hmc host state per run (src/orcdchomp_mod.cpp:948-952)
    std::vector<GslRng> rng_;
    // ... or, for large batches, on the device (hmc_kernels.hip): mt19937 state [625][n_runs], next resample iteration [n_runs]
    bool hmc_on_device_ = false;
-   uint32_t * d_mt_ = nullptr; uint32_t * d_mt_bak_ = nullptr; int * d_hmc_next_ = nullptr; int * d_hmc_next_bak_ = nullptr; int * d_overflow_ = nullptr;
+   DevBuf d_mt_, d_mt_bak_, d_hmc_next_, d_hmc_next_bak_, d_overflow_;
    std::vector<int> hmc_resample_iter_;
    std::vector<double> ext_noise_; int ext_noise_blocks_ = 0;
    std::vector<int> ext_noise_used_;   // caller-supplied blocks consumed by the current iterate call, per run
-   int stagger_mode_ = 0, stagger_sleeps_ = 10, lim_generic_ = 0;
 };
 
 // A batch as the boundary sees it: its runs are cut into contiguous blocks, one BatchShard per

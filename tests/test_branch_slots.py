@@ -1,8 +1,8 @@
-"""The bound behind `ORC_MAX_SAVE` (csrc/dev_types.h, the planner in csrc/batch.cpp `build_device`): a branch point's
+"""The bound behind `ORC_MAX_SAVE` (csrc/dev_types.h; `fold_joint_tree` in csrc/fold.cpp orders the walk by `slots_needed`): a branch point's
 frame is kept in a slot while all of its subtrees but the last are walked; with the subtree that needs most slots walked
 last, a joint tree of n joints needs at most floor(log2(n + 1)) slots, and no more than four up to the 32 joints the build accepts
 (the complete binary tree of 31 joints needs exactly four).
-The recurrence of the planner, restated, over random and worst-case trees."""
+The recurrence of `fold_joint_tree`, restated, over random and worst-case trees."""
 import math
 
 import numpy as np
