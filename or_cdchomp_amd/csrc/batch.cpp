@@ -3,6 +3,8 @@
 // src/libcd/chomp.h:38-101): uploads what the stages of `create` fold and plan (stages.h), keeps
 // the per-run state in HBM (run-major), plans the hmc resamples, launches the fused kernel.
 #include "module.h"
+#include "kernel_table.h"
+#include "launch.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -12,12 +14,7 @@
 #include <exception>
 #include <cstdlib>
 
-// launch wrappers implemented in chomp_kernel.hip
-hipError_t orc_launch_iterate_f64(const DevBatch<double> & b, size_t lds, hipStream_t stream, int variant);
-hipError_t orc_launch_iterate_f32(const DevBatch<float> & b, size_t lds, hipStream_t stream, int variant);
-hipError_t orc_launch_verdict_f64(const DevVerdict<double> & v, size_t lds, hipStream_t stream, int tree);
-hipError_t orc_launch_verdict_f32(const DevVerdict<float> & v, size_t lds, hipStream_t stream, int tree);
-size_t orc_verdict_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);
+// launch wrappers implemented in hmc_kernels.hip
 hipError_t orc_launch_hmc_seed(uint32_t * state, int * next, const unsigned int * seeds, int n_runs, hipStream_t stream);
 hipError_t orc_launch_hmc_plan_f64(uint32_t * state, int * next, int n_runs, int iter_begin, int iter_end, int cap, size_t mn, double lambda,
    double * noise, int * iters, int * overflow, hipStream_t stream);
@@ -32,10 +29,6 @@ hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n,
 hipError_t orc_launch_select_best(const double * costs, const int * status, const int * collides, const int * group, int n_runs,
    unsigned long long * key, int * count, int * best, hipStream_t stream);
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);
-hipError_t orc_launch_seed_f64(double * traj, const double * starts, const double * goals,
-   int n_runs, int n_points, int n, int floating, hipStream_t stream);
-hipError_t orc_launch_seed_f32(float * traj, const double * starts, const double * goals,
-   int n_runs, int n_points, int n, int floating, hipStream_t stream);
 
 namespace orc {
 
@@ -67,16 +60,6 @@ real * upload(const std::vector<double> & v, hipStream_t s)
 }
 
 void dev_free(void * p) { if (p) (void) hipFree(p); }
-
-// the kernels' launch wrappers by precision
-hipError_t launch_typed(const DevBatch<double> & b, size_t lds, hipStream_t s, int variant) { return orc_launch_iterate_f64(b, lds, s, variant); }
-hipError_t launch_typed(const DevBatch<float> & b, size_t lds, hipStream_t s, int variant) { return orc_launch_iterate_f32(b, lds, s, variant); }
-hipError_t launch_typed(const DevVerdict<double> & v, size_t lds, hipStream_t s, int tree) { return orc_launch_verdict_f64(v, lds, s, tree); }
-hipError_t launch_typed(const DevVerdict<float> & v, size_t lds, hipStream_t s, int tree) { return orc_launch_verdict_f32(v, lds, s, tree); }
-hipError_t launch_seed(double * traj, const double * s, const double * g, int n_runs, int n_points, int n, int floating, hipStream_t st)
-{ return orc_launch_seed_f64(traj, s, g, n_runs, n_points, n, floating, st); }
-hipError_t launch_seed(float * traj, const double * s, const double * g, int n_runs, int n_points, int n, int floating, hipStream_t st)
-{ return orc_launch_seed_f32(traj, s, g, n_runs, n_points, n, floating, st); }
 
 } // namespace
 
@@ -152,7 +135,7 @@ void BatchShard::seed_runs(const Robot & robot, const double * starts, const dou
    d_traj_.reset(dev_alloc<real>(tcount)); d_AG_.reset(dev_alloc<real>(mcount)); d_G_.reset(dev_alloc<real>(mcount));
    hip_check(hipMemsetAsync(d_AG_.as<void>(), 0, mcount*sizeof(real), st), "memset");       // zero momentum, chomp.c:114-115
    hip_check(hipMemsetAsync(d_G_.as<void>(), 0, mcount*sizeof(real), st), "memset");
-   hip_check(launch_seed(d_traj_.as<real>(), d_s.as<double>(), d_g.as<double>(), n_runs, n_points, n, p.floating_base, st), "seed");
+   hip_check(orc_launch_seed(d_traj_.as<real>(), d_s.as<double>(), d_g.as<double>(), n_runs, n_points, n, p.floating_base, st), "seed");
    d_costs_.reset(dev_alloc<double>((size_t) n_runs * 3));
    d_status_.reset(dev_alloc<int>(n_runs));
    d_iters_done_.reset(dev_alloc<int>(n_runs));
@@ -318,10 +301,8 @@ void BatchShard::build_device(const Robot & robot)
    d_jl_hi_.reset(upload<real>(jl_hi_, st));
 
    PlanInput in;
-   in.variant = fm.variant;
    // one field with the world's axes in every scene: known at compile time (phase_cost KIND)
-   if ((in.variant & (ORC_VAR_KIND | ORC_VAR_PAIRS)) && fs.one_aligned) in.variant |= ORC_VAR_ONE_FIELD | ((ms_.S == ms_.Sa) ? ORC_VAR_NO_INACT : 0);
-   in.pairs_latency_shape = fm.pairs_latency_shape;
+   in.variant = scene_variant(fm.variant, fs.one_aligned, ms_.S == ms_.Sa);
    in.m = m; in.n = n; in.nj = ms_.nj; in.Sa = ms_.Sa; in.S = ms_.S; in.GS = ms_.GS;
    in.n_sdfs = scn_.n_sdfs; in.n_tsrs = tsr_.n_tsrs; in.tsr_kmax = tsr_.kmax; in.pcr_rows = met_.pcr_rows; in.pair_entries = fm.pair_entries;
    in.use_momentum = params.use_momentum; in.free_start = params.free_start; in.derivative = params.derivative; in.solve_mode = met_.solve_mode;
@@ -361,7 +342,7 @@ void BatchShard::collision_verdict_typed(const std::vector<int> & offs, const st
    v.offs = d_offs.as<int>(); v.seg = d_seg.as<int>(); v.u = d_u.as<const real>(); v.slot_xml = d_xml.as<int>();
    v.key_out = d_key.as<unsigned long long>(); v.depth_out = d_depth.as<double>();
    v.n_pairs = (int) pair_rsum.size(); v.pairs = d_pairs.as<int>(); v.pair_rsum = d_rsum.as<const real>(); v.inact_pos = d_inact.as<const real>();
-   hip_check(launch_typed(v, orc_verdict_lds_bytes(n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk), st, plan_.variant & ORC_VAR_TREE),
+   hip_check(orc_launch_verdict(v, orc_verdict_lds_bytes(n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk), st, plan_.variant & ORC_VAR_TREE),
              "collision_verdict_kernel launch");
    hip_check(hipMemcpyAsync(key_out, d_key.as<void>(), n_runs*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "verdict keys");
    hip_check(hipMemcpyAsync(depth_out, d_depth.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict depth");
@@ -607,7 +588,7 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    b.tsr_ws = d_tsr_ws_.as<real>(); b.tsr_ws_stride = tsr_.ws_stride; b.tsr_err = d_tsr_err_.as<int>();
    hipEvent_t ev[2] = { mod_->acquire_event(device), mod_->acquire_event(device) };
    hip_check(hipEventRecord(ev[0], stream_), "hipEventRecord");
-   hipError_t e = launch_typed(b, P.lds_bytes, stream_, P.variant | (P.block == 192 ? ORC_VAR_T192 : 0) | (P.block == 512 ? ORC_VAR_T512 : 0) | (P.block == 128 ? ORC_VAR_T128 : 0));
+   hipError_t e = orc_launch_iterate(b, P.lds_bytes, stream_, P.variant, P.block);
    hip_check(e, "chomp_iterate_kernel launch");
    hip_check(hipEventRecord(ev[1], stream_), "hipEventRecord");
    pending_events_.push_back(std::make_pair(ev[0], ev[1]));

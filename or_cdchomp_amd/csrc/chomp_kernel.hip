@@ -28,6 +28,8 @@
 #include <type_traits>
 #include <utility>
 #include "dev_types.h"
+#include "kernel_table.h"
+#include "launch.h"
 
 // the device arithmetic may fuse a*b+c (the host files are built with -ffp-contract=off so that
 // the SDF build stays bit-identical to the reference; the kernels are held to a tolerance)
@@ -1941,14 +1943,9 @@ __device__ __attribute__((noinline)) void phase_finish(const void * kp, int stat
 // ---------------------------------------------------------------------------
 // The kernel: one workgroup = one run for all iterations of the launch; the loop below only
 // sequences the phase functions and carries the few scalars that cross iterations.
-// second argument of the launch bounds: wavefronts per SIMD = the register budget (3: 168 VGPRs, 12 wavefronts per CU as 3 x 256 or
-// 4 x 192 threads; 2 for the one-run-per-CU shape of 512).  The fp32 many-sphere kernels are built for FOUR (128 VGPRs, four
-// 256-thread workgroups per CU, smaller tiles): measured on BASELINE configs[4] 1.61 -> 1.74 M it/s; the fp64 16-lane kernels
-// at four gain 3 % with overlapping launches and lose 3 % one launch at a time (config 2), lose 5 % on config 4: left at three
-template <typename real, bool GS16, int BLOCK>
-struct WavesPerSimd { static constexpr int value = (BLOCK == 512) ? 2 : ((sizeof(real) == 4 && !GS16) ? ORC_WGS_PER_CU_FP32_MANY : ORC_WGS_PER_CU); };
+// second argument of the launch bounds: wavefronts per SIMD = the register budget of the family (kernel_table.h waves_per_simd)
 template <typename real, bool TREE, bool GS16, int BLOCK, int KIND = 0, int WGS = 0>      // WGS: 0 the family's own budget, 4: four workgroups of 256 per CU (128 VGPRs)
-__global__ __launch_bounds__(BLOCK, (WGS ? WGS : WavesPerSimd<real, GS16, BLOCK>::value))
+__global__ __launch_bounds__(BLOCK, (WGS ? WGS : orc::waves_per_simd(sizeof(real), GS16, BLOCK)))
 void chomp_iterate_kernel(const DevBatch<real> b)
 {
    const void * kp = (const void *) __builtin_amdgcn_kernarg_segment_ptr();      // DevBatch b is the kernel's only argument
@@ -2226,14 +2223,7 @@ void collision_verdict_kernel(DevVerdict<real> v)
 } // namespace
 
 // ---------------------------------------------------------------------------
-// host-side launch wrappers (called from module.cpp)
-size_t orc_chomp_lds_bytes(int n_points, int n, int Sa, int S, int nj, int tile_m, int pcr_rows, size_t real_size,
-   int use_momentum, int n_sdfs, int flags, int pair_entries)
-{
-   const int ss = real_size == 8 ? (int) sizeof(DevSdf<double>) : (int) sizeof(DevSdf<float>);
-   return (size_t) lds_layout(n_points, n, Sa, S, nj, tile_m, pcr_rows, (int) real_size, use_momentum, n_sdfs, ss, flags, pair_entries).total_bytes;
-}
-
+// host-side launch wrappers (launch.h)
 template <typename real, bool TREE, bool GS16, int BLOCK, int KIND = 0, int WGS = 0>
 static hipError_t launch_iterate_tt(const DevBatch<real> & b, size_t lds, hipStream_t stream)
 {
@@ -2252,163 +2242,35 @@ static hipError_t launch_iterate_tt(const DevBatch<real> & b, size_t lds, hipStr
    return hipGetLastError();
 }
 
-// variant: the ORC_VAR_ bits of dev_types.h
+// The row of kernel_table.h that the plan names (its variant mask -- the ORC_VAR_ bits of dev_types.h --, its block size, the
+// precision) launches; a plan that names no row of this build is refused.
 template <typename real>
-static hipError_t launch_iterate_t(const DevBatch<real> & b, size_t lds, hipStream_t stream, int variant)
+static hipError_t launch_iterate_t(const DevBatch<real> & b, size_t lds, hipStream_t stream, int variant, int block)
 {
-   constexpr int ONEF_NOINACT = ORC_VAR_ONE_FIELD | ORC_VAR_NO_INACT;
-#ifdef ORC_FAST_BUILD
-   // experiment builds (make var DEFS=-DORC_FAST_BUILD=2): only the kernels of the config-2 bench legs are compiled (the fp64
-   // fixed-base chain with placed spheres, one aligned field, no inactive sphere left: KIND 11), half a minute instead of three
-#if ORC_FAST_BUILD == 5      // -DORC_FAST_BUILD=5: BASELINE configs[4] (fp32, the many-sphere pass of a tree with its J^T form known)
-   if constexpr (sizeof(real) == 4)
-      if ((variant & ORC_VAR_KIND) && !(variant & ORC_VAR_GS16) && (variant & ORC_VAR_TREE) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, true, false, 256, 1>(b, lds, stream);
-#endif
-   if constexpr (sizeof(real) == 8)
-   {
-#if ORC_FAST_BUILD == 7      // -DORC_FAST_BUILD=7: the TSR-constrained WAM (KIND 11) at four 256-thread and eight 128-thread workgroups per CU
-      if ((variant & (ORC_VAR_TREE | ORC_VAR_GS16 | ORC_VAR_KIND | ORC_VAR_FLOATING)) == (ORC_VAR_GS16 | ORC_VAR_KIND) && (variant & ONEF_NOINACT) == ONEF_NOINACT)
-      {
-         if (variant & ORC_VAR_T128) return launch_iterate_tt<real, false, true, 128, 11, 4>(b, lds, stream);
-         if ((variant & ORC_VAR_WGS4) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 11, 4>(b, lds, stream);
-         if (!(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 11>(b, lds, stream);
-      }
-      return hipErrorInvalidValue;
-#endif
-#if ORC_FAST_BUILD == 6      // -DORC_FAST_BUILD=6: the WAM that holds a box (the dense pair list, one aligned field) at both budgets
-      if ((variant & ORC_VAR_PAIRS) && (variant & ORC_VAR_ONE_FIELD) && (variant & ORC_VAR_NO_INACT) && !(variant & ORC_VAR_FLOATING))
-         return (variant & ORC_VAR_WGS4) ? launch_iterate_tt<real, false, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 26>(b, lds, stream);
-#endif
-      const int kind = 1 | ((variant & ORC_VAR_ONE_FIELD) ? 2 : 0) | ((variant & ORC_VAR_FLOATING) ? 4 : 0) | (((variant & ONEF_NOINACT) == ONEF_NOINACT) ? 8 : 0);
-      if ((variant & (ORC_VAR_TREE | ORC_VAR_GS16 | ORC_VAR_KIND)) == (ORC_VAR_GS16 | ORC_VAR_KIND))
-      {
-#if ORC_FAST_BUILD == 5 || ORC_FAST_BUILD == 6
-#elif ORC_FAST_BUILD == 4      // -DORC_FAST_BUILD=4: BASELINE configs[3] (floating base, KIND 15) at the default shape and at four workgroups per CU
-         if (kind == 15 && (variant & ORC_VAR_WGS4) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 15, 4>(b, lds, stream);
-         if (kind == 15 && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 15>(b, lds, stream);
-#else
-         if (kind == 11 && (variant & ORC_VAR_WGS4) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512))) return launch_iterate_tt<real, false, true, 256, 11, 4>(b, lds, stream);
-         if (kind == 11 && (variant & ORC_VAR_T192)) return launch_iterate_tt<real, false, true, 192, 11>(b, lds, stream);
-         if (kind == 11 && !(variant & ORC_VAR_T512)) return launch_iterate_tt<real, false, true, 256, 11>(b, lds, stream);
-#endif
-      }
-   }
+   const orc::KernelKey key = orc::kernel_of(variant, block, (int) sizeof(real));
+#define ORC_LAUNCH_ROW(BYTES, TREE, GS16, BLOCK, KIND, WGS) \
+   if constexpr (sizeof(real) == BYTES && orc::kernel_compiled(orc::KernelKey{ BYTES, TREE, GS16, BLOCK, KIND, WGS })) \
+      if (key == orc::KernelKey{ BYTES, TREE, GS16, BLOCK, KIND, WGS }) return launch_iterate_tt<real, TREE, GS16, BLOCK, KIND, WGS>(b, lds, stream);
+   ORC_ITERATE_KERNELS(ORC_LAUNCH_ROW)
+#undef ORC_LAUNCH_ROW
    return hipErrorInvalidValue;
-#else
-   if (variant & ORC_VAR_T128)     // 128-thread workgroups, eight per CU at 128 registers: the fp64 16-lane family of a fixed-base chain (orc_set_workgroup_threads(128))
-   {
-      if constexpr (sizeof(real) == 8)
-         if ((variant & (ORC_VAR_TREE | ORC_VAR_GS16 | ORC_VAR_KIND | ORC_VAR_FLOATING)) == (ORC_VAR_GS16 | ORC_VAR_KIND))
-            switch (1 | ((variant & ORC_VAR_ONE_FIELD) ? 2 : 0) | (((variant & ONEF_NOINACT) == ONEF_NOINACT) ? 8 : 0))
-            {
-            case 1: return launch_iterate_tt<real, false, true, 128, 1, 4>(b, lds, stream);
-            case 3: return launch_iterate_tt<real, false, true, 128, 3, 4>(b, lds, stream);
-            case 11: return launch_iterate_tt<real, false, true, 128, 11, 4>(b, lds, stream);
-            }
-      return hipErrorInvalidValue;
-   }
-   if (variant & ORC_VAR_PAIRS)      // 17 .. 32 active spheres: the dense pair list (cost_pairs.h; phase_cost KIND 16)
-   {
-      const bool lean = (variant & ORC_VAR_ONE_FIELD) && (variant & ORC_VAR_NO_INACT) && !(variant & ORC_VAR_FLOATING);      // one aligned field, no inactive sphere left, fixed base
-      if constexpr (sizeof(real) == 8)
-      {
-         if (variant & (ORC_VAR_GS16 | ORC_VAR_T192)) return hipErrorInvalidValue;      // (no 16-lane form and no 192-thread shape: batch.cpp keeps such a module on the many-sphere family)
-         if (variant & ORC_VAR_TREE)      // a tree (round 6: the WAM with its finger dofs active that holds something); no latency shape
-         {
-            if (variant & ORC_VAR_T512) return hipErrorInvalidValue;
-            if (variant & ORC_VAR_WGS4) return lean ? launch_iterate_tt<real, true, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, true, false, 256, 16, 4>(b, lds, stream);
-            return lean ? launch_iterate_tt<real, true, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, true, false, 256, 16>(b, lds, stream);
-         }
-         if (variant & ORC_VAR_T512) return lean ? launch_iterate_tt<real, false, false, 512, 26>(b, lds, stream) : launch_iterate_tt<real, false, false, 512, 16>(b, lds, stream);
-         if (variant & ORC_VAR_WGS4) return lean ? launch_iterate_tt<real, false, false, 256, 26, 4>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 16, 4>(b, lds, stream);
-         return lean ? launch_iterate_tt<real, false, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 16>(b, lds, stream);
-      }
-      else
-      {
-         // fp32 (round 6): 256-thread workgroups at the fp32 many-sphere budget (four per CU), chains and trees
-         if (variant & (ORC_VAR_GS16 | ORC_VAR_T192 | ORC_VAR_T512)) return hipErrorInvalidValue;
-         if (variant & ORC_VAR_TREE) return lean ? launch_iterate_tt<real, true, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, true, false, 256, 16>(b, lds, stream);
-         return lean ? launch_iterate_tt<real, false, false, 256, 26>(b, lds, stream) : launch_iterate_tt<real, false, false, 256, 16>(b, lds, stream);
-      }
-   }
-   if ((variant & ORC_VAR_KIND) && !(variant & ORC_VAR_GS16))      // the many-sphere path with its J^T form known (phase_cost KIND 1)
-   {
-      if (variant & ORC_VAR_TREE)
-      {
-         if (variant & ORC_VAR_T512) return launch_iterate_tt<real, true, false, 512, 1>(b, lds, stream);
-         if (variant & ORC_VAR_T192) return launch_iterate_tt<real, true, false, 192, 1>(b, lds, stream);
-         return launch_iterate_tt<real, true, false, 256, 1>(b, lds, stream);
-      }
-      if (variant & ORC_VAR_T512) return launch_iterate_tt<real, false, false, 512, 1>(b, lds, stream);
-      if (variant & ORC_VAR_T192) return launch_iterate_tt<real, false, false, 192, 1>(b, lds, stream);
-      return launch_iterate_tt<real, false, false, 256, 1>(b, lds, stream);
-   }
-   if (variant & ORC_VAR_KIND)      // phase_cost KIND: a chain with placed spheres, one field with the world's axes (2), floating base (4), no inactive sphere left (8)
-   {
-      const int kind = 1 | ((variant & ORC_VAR_ONE_FIELD) ? 2 : 0) | ((variant & ORC_VAR_FLOATING) ? 4 : 0) | (((variant & ONEF_NOINACT) == ONEF_NOINACT) ? 8 : 0);
-      // the kernels built for four 256-thread workgroups per CU (orc_set_workgroups_per_cu; fp64 fixed-base chains)
-      if constexpr (sizeof(real) == 8)
-         if ((variant & ORC_VAR_WGS4) && !(variant & (ORC_VAR_T192 | ORC_VAR_T512)))
-            switch (kind)
-            {
-            case 1: return launch_iterate_tt<real, false, true, 256, 1, 4>(b, lds, stream);
-            case 3: return launch_iterate_tt<real, false, true, 256, 3, 4>(b, lds, stream);
-            case 11: return launch_iterate_tt<real, false, true, 256, 11, 4>(b, lds, stream);
-            case 15: return launch_iterate_tt<real, false, true, 256, 15, 4>(b, lds, stream);      // (floating base, one aligned field: BASELINE configs[3])
-            }
-#define ORC_KIND_CASE(K) case K: \
-         if (variant & ORC_VAR_T512) return launch_iterate_tt<real, false, true, 512, K>(b, lds, stream); \
-         if (variant & ORC_VAR_T192) return launch_iterate_tt<real, false, true, 192, K>(b, lds, stream); \
-         return launch_iterate_tt<real, false, true, 256, K>(b, lds, stream);
-      switch (kind)
-      {
-      ORC_KIND_CASE(1) ORC_KIND_CASE(3) ORC_KIND_CASE(5) ORC_KIND_CASE(7) ORC_KIND_CASE(11) ORC_KIND_CASE(15)
-      }
-#undef ORC_KIND_CASE
-   }
-   if (variant & ORC_VAR_T512)
-      switch (variant & (ORC_VAR_TREE | ORC_VAR_GS16))
-      {
-      case 0: return launch_iterate_tt<real, false, false, 512>(b, lds, stream);
-      case ORC_VAR_TREE: return launch_iterate_tt<real, true, false, 512>(b, lds, stream);
-      case ORC_VAR_GS16: return launch_iterate_tt<real, false, true, 512>(b, lds, stream);
-      default: return launch_iterate_tt<real, true, true, 512>(b, lds, stream);
-      }
-   switch (variant & (ORC_VAR_TREE | ORC_VAR_GS16 | ORC_VAR_T192))
-   {
-   case 0: return launch_iterate_tt<real, false, false, 256>(b, lds, stream);
-   case ORC_VAR_TREE: return launch_iterate_tt<real, true, false, 256>(b, lds, stream);
-   case ORC_VAR_GS16: return launch_iterate_tt<real, false, true, 256>(b, lds, stream);
-   case ORC_VAR_TREE | ORC_VAR_GS16: return launch_iterate_tt<real, true, true, 256>(b, lds, stream);
-   case ORC_VAR_T192: return launch_iterate_tt<real, false, false, 192>(b, lds, stream);
-   case ORC_VAR_T192 | ORC_VAR_TREE: return launch_iterate_tt<real, true, false, 192>(b, lds, stream);
-   case ORC_VAR_T192 | ORC_VAR_GS16: return launch_iterate_tt<real, false, true, 192>(b, lds, stream);
-   default: return launch_iterate_tt<real, true, true, 192>(b, lds, stream);
-   }
-#endif
 }
 
-hipError_t orc_launch_iterate_f64(const DevBatch<double> & b, size_t lds, hipStream_t stream, int variant)
-{ return launch_iterate_t<double>(b, lds, stream, variant); }
-hipError_t orc_launch_iterate_f32(const DevBatch<float> & b, size_t lds, hipStream_t stream, int variant)
-{ return launch_iterate_t<float>(b, lds, stream, variant); }
+hipError_t orc_launch_iterate(const DevBatch<double> & b, size_t lds, hipStream_t stream, int variant, int block)
+{ return launch_iterate_t<double>(b, lds, stream, variant, block); }
+hipError_t orc_launch_iterate(const DevBatch<float> & b, size_t lds, hipStream_t stream, int variant, int block)
+{ return launch_iterate_t<float>(b, lds, stream, variant, block); }
 
-hipError_t orc_launch_seed_f64(double * traj, const double * starts, const double * goals,
-   int n_runs, int n_points, int n, int floating, hipStream_t stream)
+template <typename real>
+hipError_t orc_launch_seed(real * traj, const double * starts, const double * goals, int n_runs, int n_points, int n, int floating, hipStream_t stream)
 {
    const long total = (long) n_runs * n_points;
    int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-   hipLaunchKernelGGL(seed_traj_kernel<double>, dim3(blocks), dim3(256), 0, stream, traj, starts, goals, n_runs, n_points, n, floating);
+   hipLaunchKernelGGL(seed_traj_kernel<real>, dim3(blocks), dim3(256), 0, stream, traj, starts, goals, n_runs, n_points, n, floating);
    return hipGetLastError();
 }
-hipError_t orc_launch_seed_f32(float * traj, const double * starts, const double * goals,
-   int n_runs, int n_points, int n, int floating, hipStream_t stream)
-{
-   const long total = (long) n_runs * n_points;
-   int blocks = (int)((total + 255) / 256); if (blocks > 4096) blocks = 4096; if (blocks < 1) blocks = 1;
-   hipLaunchKernelGGL(seed_traj_kernel<float>, dim3(blocks), dim3(256), 0, stream, traj, starts, goals, n_runs, n_points, n, floating);
-   return hipGetLastError();
-}
+template hipError_t orc_launch_seed<double>(double *, const double *, const double *, int, int, int, int, hipStream_t);
+template hipError_t orc_launch_seed<float>(float *, const double *, const double *, int, int, int, int, hipStream_t);
 
 template <typename real>
 static hipError_t launch_verdict_t(const DevVerdict<real> & v, size_t lds, hipStream_t stream, int tree)
@@ -2428,8 +2290,8 @@ static hipError_t launch_verdict_t(const DevVerdict<real> & v, size_t lds, hipSt
    else hipLaunchKernelGGL((collision_verdict_kernel<real, false>), dim3(v.n_runs), dim3(ORC_BLOCK), lds, stream, v);
    return hipGetLastError();
 }
-hipError_t orc_launch_verdict_f64(const DevVerdict<double> & v, size_t lds, hipStream_t stream, int tree) { return launch_verdict_t<double>(v, lds, stream, tree); }
-hipError_t orc_launch_verdict_f32(const DevVerdict<float> & v, size_t lds, hipStream_t stream, int tree) { return launch_verdict_t<float>(v, lds, stream, tree); }
+hipError_t orc_launch_verdict(const DevVerdict<double> & v, size_t lds, hipStream_t stream, int tree) { return launch_verdict_t<double>(v, lds, stream, tree); }
+hipError_t orc_launch_verdict(const DevVerdict<float> & v, size_t lds, hipStream_t stream, int tree) { return launch_verdict_t<float>(v, lds, stream, tree); }
 
 // dynamic LDS of collision_verdict_kernel (the carve-up at its top)
 size_t orc_verdict_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk)

@@ -156,7 +156,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
                // one-sided difference towards the nearer neighbour, inwards at the faces (grid.c:372-389)
                prev[q][k] = (fl == (real)0) ? false : ((fl == m1[k]) ? true : (fr[q][k] < (real)0));
                sg[q][k] = prev[q][k] ? (real)(-1) : (real)1;
-               off += __mul24((int) fl, sb3[k]);                     // (a full-rate SIGNED 24-bit multiply: cell index and byte stride are below 2^23, checked at create: batch.cpp build_device)
+               off += __mul24((int) fl, sb3[k]);                     // (a full-rate SIGNED 24-bit multiply: cell index and byte stride are below 2^23, checked at create: fold.cpp fold_field)
             }
             // (unsigned 32-bit offsets against the field's base in scalar registers: no sign extension, no 64-bit address add)
             v0[q] = *(const real *)(base + (unsigned int) off);

@@ -9,7 +9,7 @@
 // The lanes of a waypoint's group play two parts in turn:
 //   (1) lane = sphere (cost_gs16.h's part: velocity, acceleration, field lookup, obstacle force);
 //   (2) lane = PAIR: round r, lane k evaluates entry r*32 + k of the robot's pair list (DevModel::pr_*, built at create:
-//       batch.cpp build_pair_table) for the group's waypoint -- centres from the tile's position buffer, range test, and when
+//       fold.cpp build_pair_table) for the group's waypoint -- centres from the tile's position buffer, range test, and when
 //       some lane of the wavefront has its pair within range, both spheres' velocity terms through ds_bpermute and the net
 //       force of the pair on its first sphere, x_ab - x_ba = s/|d| ((w_a + w_b) d - (d.u_a) u_a - (d.u_b) u_b) (cost_gs16.h
 //       has the derivation; a sphere that stands still has w = 0, u = 0: exactly the other side's visit of the pair);

@@ -5,6 +5,7 @@
 //   struct run_rsdf   src/orcdchomp_mod.cpp:850-855
 //   struct cd_chomp   src/libcd/chomp.h:38-101
 #pragma once
+#include <cstddef>
 
 #define ORC_MAX_JOINTS   32      // active (optimized) joints of one robot
 #define ORC_MAX_SPHERES  64      // spheres of one robot (active + inactive)
@@ -27,22 +28,20 @@
 #define ORC_PAIR_ROUNDS   16      // rounds of the dense self-collision pair list at most (cost_pairs.h): 16 x 32 lanes hold every pair of 32 spheres
 #define ORC_PAIR_DEG      4       // pairs of one round that add to (and that subtract from) one sphere at most
 
-// The kernel variant mask: batch.cpp assembles it (Batch::variant_, reported by get_plan), launch_iterate_t in chomp_kernel.hip
-// picks the instantiation of the iterate kernel from it.
+// The kernel variant mask: robot_variant and scene_variant (kernel_table.h) form the robot's and the scenes' bits, plan_iterate
+// (plan.cpp) adds ORC_VAR_WGS4 (IteratePlan::variant, reported by get_plan); with the plan's block size and the precision it names
+// one row of kernel_table.h, which launch_iterate_t in chomp_kernel.hip launches.  (4, 8 and 1024 were the block size's bits.)
 enum : int
 {
    ORC_VAR_TREE      = 1,      // the joint tree branches
    ORC_VAR_GS16      = 2,      // the robot has <= 16 active spheres: 16 lanes per waypoint (DPP-row cost phase)
-   ORC_VAR_T192      = 4,      // workgroups of 192 threads (three wavefronts, four workgroups per CU) instead of 256
-   ORC_VAR_T512      = 8,      // workgroups of 512 threads (eight wavefronts, one workgroup per CU: the latency shape)
    ORC_VAR_KIND      = 16,     // the cost phase's kind is known at compile time (phase_cost KIND): with GS16, without TREE, a fixed-base or
                                // floating chain with its spheres placed on the row; without GS16 the many-sphere path with its J^T form known
    ORC_VAR_ONE_FIELD = 32,     // (with KIND or PAIRS) there is one field and its axes are the world's
    ORC_VAR_FLOATING  = 64,     // (with KIND or PAIRS) the base floats
    ORC_VAR_NO_INACT  = 128,    // (with ONE_FIELD) no inactive sphere is left for the loop over them
    ORC_VAR_WGS4      = 256,    // the kernels built for the register budget of four 256-thread workgroups per CU (fp64)
-   ORC_VAR_PAIRS     = 512,    // 17 .. 32 active spheres: the dense pair list (cost_pairs.h)
-   ORC_VAR_T128      = 1024    // workgroups of 128 threads, eight per CU (the fp64 16-lane family of a fixed-base chain)
+   ORC_VAR_PAIRS     = 512     // 17 .. 32 active spheres: the dense pair list (cost_pairs.h)
 };
 
 // one optimized joint, in topological order.  Non-optimized joints are folded
@@ -118,7 +117,7 @@ struct DevModel
    // A robot that is a chain [0, fk_nanc) which then branches: the branches from joint fk_b_begin on can be walked by
    // another wavefront (which walks the chain as well, without storing): two walks of about half the length
    int fk_split, fk_nanc, fk_b_begin;
-   // The dense self-collision pair list of the 32-lane family (cost_pairs.h; built at create: batch.cpp build_pair_table).
+   // The dense self-collision pair list of the 32-lane family (cost_pairs.h; built at create: fold.cpp build_pair_table).
    // Every pair of lanes that can ever count (spheres on different links, at least one of them active) has ONE entry;
    // round r, lane k of a waypoint's lane group evaluates entry r*GS + k for that waypoint: the net force of the pair
    // on its FIRST sphere (the second receives the opposite).  Entries are in the order of how often the pair is within

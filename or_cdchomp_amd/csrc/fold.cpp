@@ -1,6 +1,7 @@
 // fold.cpp -- the folds of `create` (stages.h): the robot into DevModel, the TSR constraints into DevTsr, the scene table into
 // DevSdf / DevSdfCell rows, the metric into its device tables.  Host arithmetic only; BatchShard::construct uploads the results.
 #include "stages.h"
+#include "kernel_table.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -389,8 +390,13 @@ Lanes choose_lanes(const Robot & robot, const BatchParams & params, const std::v
    // fp32 runs take the family too (256-thread workgroups; the latency shape stays an fp64 chain's)
    const bool pair_chain64 = fp64 && !tree && jt_scan == 1;
    const bool pair_other = GS == 32 && ((tree && jt_scan == 2) || (!tree && jt_scan == 1)) && !sw.pairs_chain64_only;
-   if ((pair_chain64 || pair_other) && GS == 32 && !params.free_start
-       && (asked_block == 0 || asked_block == 256 || asked_block == 512)
+   // (the family is a function of the robot and the run, not of the latency shape asked for -- 512 threads, what the single-run
+   // `create` asks for: where the family has no such kernel, a tree or an fp32 run, the planner drops the request, so that a run alone
+   // has the bits it has inside a batch.  Any other shape asked for is binding: a robot whose pair-list family has no kernel of it
+   // stays on the many-sphere family)
+   const int pair_variant = robot_variant(tree, GS, params.floating_base != 0, jt_scan, false, 0, true, sw.no_kind);
+   const bool pair_shape = asked_block == 0 || asked_block == 512 || kernel_exists(kernel_of(pair_variant, asked_block, fp64 ? 8 : 4));
+   if ((pair_chain64 || pair_other) && GS == 32 && !params.free_start && pair_shape
        && !sw.no_pairs && !sw.no_kind && !sw.block_threads.set)
    {
       const int ns = sw.no_static_lanes ? 0 : std::min((int) inact.size(), GS - Sa);
@@ -676,16 +682,7 @@ FoldedModel<real> fold_robot(const Robot & robot, const BatchParams & params, in
    fold_fk_walk(M, T, sw);
 
    const bool pairs = L.pairs;
-   out.variant = (M.tree ? ORC_VAR_TREE : 0) | ((M.GS == 16) ? ORC_VAR_GS16 : 0);
-   if (M.GS == 16 && !M.tree && M.jt_scan == 1 && M.placed && nj <= 16 && !sw.no_kind)
-      out.variant |= ORC_VAR_KIND | (M.floating ? ORC_VAR_FLOATING : 0);      // the variants that know all this at compile time (chomp_kernel.hip phase_cost KIND)
-   if (M.GS != 16 && !M.floating && M.jt_scan == (M.tree ? 2 : 1) && !sw.no_kind && !pairs)
-      out.variant |= ORC_VAR_KIND;                    // many-sphere path: the J^T form is known
-   if (pairs) out.variant |= ORC_VAR_PAIRS | (M.floating ? ORC_VAR_FLOATING : 0);      // the 32-lane family with the dense pair list
-   // (the family is a function of the robot and the run, not of the shape asked for: the latency shape -- 512 threads, what the
-   // single-run `create` asks for -- exists for the fp64 chain only; a tree or an fp32 run keeps the family at 256 threads, so
-   // that a run alone has the bits it has inside a batch)
-   out.pairs_latency_shape = pairs && sizeof(real) == 8 && !M.tree && M.jt_scan == 1;
+   out.variant = robot_variant(M.tree != 0, M.GS, M.floating != 0, M.jt_scan, M.placed != 0, nj, pairs, sw.no_kind);
    out.pair_entries = pairs ? L.ptab.rounds * M.GS : 0;
 
    ModelScalars & ms = out.scalars;

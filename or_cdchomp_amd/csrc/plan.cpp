@@ -7,14 +7,11 @@
 // The plan is a function of the robot, the run parameters and the module's settings only, never of the batch (a run's bits
 // must not depend on what shares its batch): PlanInput has nothing else in it.
 #include "stages.h"
+#include "kernel_table.h"
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <stdexcept>
-
-// implemented in chomp_kernel.hip
-size_t orc_chomp_lds_bytes(int n_points, int n, int Sa, int S, int nj, int tile_m, int pcr_rows, size_t real_size,
-   int use_momentum, int n_sdfs, int flags, int pair_entries);
 
 namespace orc {
 
@@ -47,14 +44,15 @@ struct Option { int with_pcr, ag_lds, g_lds, t_lds; };
 
 std::vector<Shape> shapes_of(const PlanInput & in, const Switches & sw, int max_wgs, bool budget4, int force_block, bool can128)
 {
+   auto has = [&in](int block) { return kernel_exists(kernel_of(in.variant, block, (int) in.real_bytes)); };
    std::vector<Shape> shapes;
    for (int wgs=max_wgs; wgs>=(budget4 ? 4 : 1); wgs--) shapes.push_back({ 256, wgs });
-   if (max_wgs >= 3 && !(in.variant & ORC_VAR_PAIRS)) shapes.push_back({ 192, 4 });      // (the pair-list family is built for 256-thread workgroups)
+   if (max_wgs >= 3 && has(192)) shapes.push_back({ 192, 4 });      // (the pair-list family is built for 256-thread workgroups)
    // a caller that asked for the 192-thread shape gets it for runs that do not fit four to a CU as well
    if (force_block == 192) for (int wgs=3; wgs>=1; wgs--) shapes.push_back({ 192, wgs });
    // the latency shape: eight wavefronts on one run, one run per CU (a lone wavefront issues a vector
    // instruction every ~9 cycles: two per SIMD halve the time of an iteration; for batches smaller than the chip)
-   if (force_block == 512) shapes.push_back({ 512, 1 });
+   if (force_block == 512 && has(512)) shapes.push_back({ 512, 1 });
    // two wavefronts on a run, up to eight runs per CU (the kernels exist for the fp64 16-lane family of a fixed-base chain at
    // 128 registers): runs with TSR constraints, whose elimination is the work of two wavefronts (csrc/tsr.h), keep all
    // sixteen wavefronts of a CU at it instead of eight
@@ -102,8 +100,8 @@ void try_option(const PlanInput & in, const Switches & sw, const Forced & force,
    int flags = ((in.solve_mode == 2 || in.solve_mode == 3) ? ORC_LDS_SMALL_WORK : 0) | (o.g_lds ? 0 : ORC_LDS_G_GLOBAL) | (o.t_lds ? 0 : ORC_LDS_T_GLOBAL)
              | (want_staged ? ORC_LDS_T_STAGED : 0);
    auto lds_bytes = [&](int t, int fl) {
-      return orc_chomp_lds_bytes(in.m + 2, in.n, in.Sa, in.S, in.nj, t, o.with_pcr ? in.pcr_rows : 0, in.real_bytes,
-                                 in.use_momentum && o.ag_lds, in.n_sdfs, fl, in.pair_entries);
+      return (size_t) lds_layout(in.m + 2, in.n, in.Sa, in.S, in.nj, t, o.with_pcr ? in.pcr_rows : 0, (int) in.real_bytes,
+                                 in.use_momentum && o.ag_lds, in.n_sdfs, (int) in.sdf_bytes, fl, in.pair_entries).total_bytes;
    };
    for (int t=(in.m < 254 ? in.m : 254); t>=1; t--)
    {
@@ -119,7 +117,7 @@ void try_option(const PlanInput & in, const Switches & sw, const Forced & force,
       const double score = score_of(in, sh, o, t, flags);
       if (score > best_score)
       {
-         best_score = score; best.tile_m = t; best.pcr_in_lds = o.with_pcr; best.ag_in_lds = o.ag_lds; best.lds_bytes = need; best.block = sh.block;
+         best_score = score; best.tile_m = t; best.pcr_in_lds = o.with_pcr; best.ag_in_lds = o.ag_lds; best.lds_bytes = need; best.block = sh.block; best.per_cu = sh.wgs;
          best.g_in_lds = o.g_lds; best.lds_flags = flags; best.t_in_lds = o.t_lds;
       }
       break;                                   // largest tile of this plan
@@ -163,14 +161,14 @@ void size_tsr_solve(IteratePlan & P, const PlanInput & in, const Switches & sw)
 IteratePlan plan_iterate(const PlanInput & in, const Switches & sw)
 {
    const int variant = in.variant;
-   const bool fp64 = in.real_bytes == 8;
-   const int max_wgs_budget = (!fp64 && in.GS != 16) ? ORC_WGS_PER_CU_FP32_MANY : ORC_WGS_PER_CU;      // (the kernel variant's register budget)
+   auto has = [&](int var, int block) { return kernel_exists(kernel_of(var, block, (int) in.real_bytes)); };
+   const int max_wgs_budget = waves_per_simd((int) in.real_bytes, in.GS == 16, 256);      // (the family's register budget)
    const int max_wgs_default = sw.wgs.set ? sw.wgs.value : max_wgs_budget;
    // A caller that knows its batches fit the chip in one wave of four workgroups per CU but not of three (769..1024 runs: the
    // 1024 of BASELINE configs[1]) can ask for the 192-thread shape for the whole module: orc_set_workgroup_threads (measured, one
    // launch of 1024 WAM runs: 9.3 M it/s against 8.4 M; from 4096 runs on the order is reversed).
    int force_block_asked = in.module_threads ? in.module_threads : in.params_threads;
-   if ((variant & ORC_VAR_PAIRS) && force_block_asked == 512 && !in.pairs_latency_shape) force_block_asked = 0;
+   if (force_block_asked == 512 && !has(variant, 512)) force_block_asked = 0;      // (the pair list of a tree or an fp32 run has no latency shape)
    // orc_set_workgroups_per_cu(4): the fp64 16-lane kernels of a fixed-base chain also exist at 128 VGPRs, four 256-thread
    // workgroups per CU (three tiles instead of two for the WAM): +3 % when launches overlap, -3 % one launch at a time
    int want_wgs = in.module_per_cu ? in.module_per_cu : in.params_per_cu;
@@ -180,7 +178,7 @@ IteratePlan plan_iterate(const PlanInput & in, const Switches & sw)
    // kernels of a fixed-base chain (+3-5 %) and, for constrained runs, the 128-thread shape (eight runs per CU: +18 %).  One
    // launch of <= 1024 unconstrained runs at a time is 3 % faster with the kernels' own budget, which is the default there.
    // 3 = "the kernels' own budget", said explicitly.
-   const bool can128 = fp64 && (variant & ORC_VAR_KIND) && (variant & ORC_VAR_GS16) && !(variant & (ORC_VAR_TREE | ORC_VAR_FLOATING));
+   const bool can128 = has(variant, 128);
    if (want_wgs == 0 && ((in.n_tsrs > 0 && !(variant & ORC_VAR_FLOATING)) || (variant & ORC_VAR_PAIRS) || (in.overlapping && !(variant & ORC_VAR_FLOATING)))) want_wgs = 4;
    if (want_wgs == 3) want_wgs = 0;
    // (the planner's own 128 is a preference, tried in a pass of its own: a long constrained trajectory that has no 128-thread plan --
@@ -190,7 +188,7 @@ IteratePlan plan_iterate(const PlanInput & in, const Switches & sw)
    // on the 256-thread shapes are ahead again: scripts/diag/short_traj_shapes.py, profiles/r06_regime_sweep.txt)
    const bool short128 = in.m <= 32 && !sw.no_short128;
    const bool planner128 = force_block_asked == 0 && ((in.overlapping && in.n_tsrs > 0) || short128) && can128 && !in.free_start && !sw.block_threads.set;
-   const bool kernels_at_4 = ((variant & ORC_VAR_KIND) && (variant & ORC_VAR_GS16) && (!(variant & ORC_VAR_FLOATING) || (variant & (ORC_VAR_ONE_FIELD | ORC_VAR_NO_INACT)) == (ORC_VAR_ONE_FIELD | ORC_VAR_NO_INACT))) || (variant & ORC_VAR_PAIRS);
+   const bool kernels_at_4 = has(variant | ORC_VAR_WGS4, 256);
 
    IteratePlan P;
    bool budget4 = false;
@@ -205,7 +203,7 @@ IteratePlan plan_iterate(const PlanInput & in, const Switches & sw)
       Forced force;
       force.block = (pass == -1) ? 128 : force_block_asked;
       if (!relax) { force.tile = sw.tile_m.set ? sw.tile_m.value : 0; force.pcr = sw.pcr_lds.set ? sw.pcr_lds.value : -1; force.ag = sw.ag_lds.set ? sw.ag_lds.value : -1; }
-      budget4 = (pass == 0) && (want_wgs == 4) && fp64 && kernels_at_4 && (force.block == 0 || force.block == 256)
+      budget4 = (pass == 0) && (want_wgs == 4) && kernels_at_4 && (force.block == 0 || force.block == 256)
                 && !sw.block_threads.set && !sw.wgs.set && !sw.tile_m.set;      // (the experiments' switches come first)
       if (budget4) { max_wgs = 4; force.block = 256; }
       if (sw.block_threads.set && !relax) force.block = sw.block_threads.value;

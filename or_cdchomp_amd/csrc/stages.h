@@ -167,7 +167,6 @@ struct FoldedModel
    std::vector<int> device_sphere_order;       // XML index of device sphere k
    std::vector<int> slot_xml;                  // XML index of the sphere in lane/slot q of the active block, -1: empty
    int pair_entries = 0;                       // entries of the staged self-collision pair list (rounds x 32; 0: the kernel family does not use one)
-   bool pairs_latency_shape = false;           // the pair-list family's 512-thread kernels exist for this robot and precision (fp64 chains)
    int variant = 0;                            // the robot's part of the kernel variant mask (ORC_VAR_ bits of dev_types.h)
 };
 // `asked_block`: the workgroup shape the caller asked for (the module's setting, else the parameters'; 0: none)
@@ -235,7 +234,6 @@ MetricTables pack_metric(const Metric & metric, const BatchParams & params, int 
 struct PlanInput
 {
    int variant = 0;                            // the variant bits known so far (robot and scenes)
-   bool pairs_latency_shape = false;
    int m = 0, n = 0, nj = 0, Sa = 0, S = 0, GS = 0, n_sdfs = 0, n_tsrs = 0, tsr_kmax = 0, pcr_rows = 0, pair_entries = 0;
    int use_momentum = 0, free_start = 0, derivative = 1, solve_mode = 0;
    size_t real_bytes = 8, sdf_bytes = 0;       // sizeof(real), sizeof(DevSdf<real>)
@@ -247,6 +245,7 @@ struct IteratePlan
 {
    int variant = 0;                            // the final kernel variant mask (with ORC_VAR_WGS4)
    int block = 256;                            // threads per workgroup of the iterate kernel
+   int per_cu = 0;                             // resident workgroups per CU the plan's share of the LDS is sized for (the kernel's registers must hold as many)
    int tile_m = 0, n_tiles = 1, tile_first = 0, tile_rest = 0;   // tiles of an iteration: the first of tile_first moving waypoints, the others of tile_rest
    size_t lds_bytes = 0;
    int lds_flags = 0, pcr_in_lds = 0, ag_in_lds = 1, g_in_lds = 1, t_in_lds = 1;
