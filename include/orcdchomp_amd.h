@@ -289,6 +289,17 @@ int orc_batch_gettraj(orc_module * mod, int batch_id, double * traj_out, size_t 
  * (a pair of spheres: -2 - the XML index of the other sphere), penetration depth in metres. */
 int orc_batch_collision_verdict(orc_module * mod, int batch_id, int * collides_out, double * time_out,
                                 int * sphere_out, int * field_out, double * depth_out);
+/* The same verdict with the retiming and the sample planning done by the kernel that walks the samples: no trajectory
+ * is read back and no sample list is uploaded; what goes to the device is the velocity limits and the tables of the
+ * self-collision leg, which do not depend on the trajectories.  The outputs are those of orc_batch_collision_verdict,
+ * bit for bit (the planning arithmetic is the host's, in double for precision 32 batches too: the specification is
+ * verdict_samples of or_cdchomp_amd/module.py, the host's own planner is orc_host_verdict_samples), with the robot's
+ * self-check setting; n_samples_out [n_runs]: the samples of every run's retimed trajectory, all of them also when the
+ * walk stops at a contact.  Only collides_out is required.  A run of 2^30 samples or more (C-space length / 0.04)
+ * fails the call with "trajectory too long for the batched collision verdict!" before anything of it is walked.  A
+ * batch over several devices: every shard plans and walks its own runs. */
+int orc_batch_collision_verdict_device(orc_module * mod, int batch_id, int * collides_out, double * time_out,
+                                       int * sphere_out, int * field_out, double * depth_out, int * n_samples_out);
 /* optimizer state read-back for tests: which = "G", "AG", "T" ([n_runs][m][n]); "phase" ([n_runs][8] cycle counters with
  * ORC_PHASE_TIMERS=1); "plan" (8 numbers: kernel variant bits -- 512 = the dense pair-list family, 1 = a tree --, threads per
  * workgroup, LDS bytes per workgroup, tile, solve mode (2 closed-form scans, 3 band-inverse generators, 1 dense), workgroups
@@ -326,16 +337,18 @@ int orc_batch_perturb(orc_module * mod, int batch_id, double sigma, const unsign
  * (anything else is rejected), or NULL: n_groups contiguous equal blocks of runs (n_runs % n_groups != 0 is then
  * rejected).  A run is eligible when its status from the last iterate call is 0 or 1, its total cost (costs[run][0] of
  * that call) is finite and, with require_collision_free != 0, the batch's collision verdict for its current trajectory
- * says it does not collide -- the verdict orc_batch_collision_verdict gives, with the robot's self-check setting.  Per
+ * says it does not collide -- the verdict orc_batch_collision_verdict gives, with the robot's self-check setting, taken
+ * by orc_batch_collision_verdict_device's kernel.  Per
  * group the eligible run of lowest total cost wins, a tie goes to the lowest run index: best_run_out [n_groups] (-1 for a
  * group without an eligible run), best_cost_out [n_groups] (+inf there), n_eligible_out [n_groups] the group's eligible
  * runs; any output may be NULL.  A batch that has never been iterated is rejected (orc_batch_iterate with 0 iterations
  * makes the costs valid).  The reduction is a segmented arg-min on the device over the costs and status an iterate call
  * left there: only n_groups triples leave it (a module over several devices: every shard reduces its runs and the host
- * merges n_shards x n_groups candidates by the same rule; groups may span shards).  What stays on the host: the
- * verdict's retiming and sample planning, as in orc_batch_collision_verdict -- with require_collision_free that path
- * still reads the trajectories back; without it no trajectory leaves the device.  The arguments are checked before the
- * verdict is taken: a rejected call costs no read-back. */
+ * merges n_shards x n_groups candidates by the same rule; groups may span shards).  With require_collision_free the
+ * verdict plans its samples on the device and its keys stay there, where the reduction reads them: the velocity limits
+ * and the tables of the self-collision leg go up, no trajectory leaves the device either way.  What stays on the host is
+ * the construction of those tables, which does not depend on the trajectories.  The arguments are checked before the
+ * verdict is taken: a rejected call costs no kernel. */
 int orc_batch_select_best(orc_module * mod, int batch_id, int n_groups, const int * group_of_run, int require_collision_free,
    int * best_run_out, double * best_cost_out, int * n_eligible_out);
 /* The rows runs[0 .. n_sel) of what orc_batch_gettraj returns, gathered on the device and copied as n_sel n_points n
@@ -390,6 +403,12 @@ int orc_host_metric_semisep_rank(int m, int derivative, double dt, int free_star
 /* GSL's default generator restated (src/orcdchomp_mod.cpp:2303-2304,2763,2767): n gaussians with
  * the given sigma from seed, then one uniform; out_gauss[n], out_uniform[1] */
 int orc_host_gsl_stream(unsigned long seed, double sigma, int n, double * out_gauss, double * out_uniform);
+/* the sample plan of the collision verdict for one trajectory [n_points][n], by the functions orc_batch_collision_verdict
+ * runs: retimed at vmax [n - col0] (an entry <= 0 counts as 1) over the columns col0 .. n-1, a sample every 0.04 of
+ * C-space distance; per sample the segment it lies on, the position on the segment and its time.  n_samples_out gets
+ * their number; the arrays (any may be NULL) are filled when cap holds them all, otherwise the return is nonzero */
+int orc_host_verdict_samples(const double * traj, int n_points, int n, int col0, const double * vmax, int cap,
+   int * seg_out, double * u_out, double * time_out, int * n_samples_out);
 
 #ifdef __cplusplus
 }

@@ -80,6 +80,8 @@ SYMBOLS = [
     ("orc_batch_set_convergence", C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_double]),
     ("orc_batch_gettraj", C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_size_t]),
     ("orc_batch_collision_verdict", C.c_int, [C.c_void_p, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p]),
+    ("orc_batch_collision_verdict_device", C.c_int, [C.c_void_p, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p,
+                                                     c_int_p]),
     ("orc_batch_get_state", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, c_double_p, C.c_size_t]),
     ("orc_batch_dims", C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p]),
     ("orc_batch_set_traj", C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_size_t]),
@@ -101,6 +103,8 @@ SYMBOLS = [
                                   c_double_p, C.c_int, c_double_p]),
     ("orc_host_metric_semisep_rank", C.c_int, [C.c_int, C.c_int, C.c_double, C.c_int]),
     ("orc_host_gsl_stream", C.c_int, [C.c_ulong, C.c_double, C.c_int, c_double_p, c_double_p]),
+    ("orc_host_verdict_samples", C.c_int, [c_double_p, C.c_int, C.c_int, C.c_int, c_double_p, C.c_int, c_int_p, c_double_p,
+                                           c_double_p, c_int_p]),
 ]
 
 _LIB = None

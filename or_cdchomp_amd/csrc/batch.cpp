@@ -5,6 +5,7 @@
 #include "module.h"
 #include "kernel_table.h"
 #include "launch.h"
+#include "verdict_device.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -26,7 +27,7 @@ hipError_t orc_launch_perturb_f64(double * traj, int n_runs, int n_points, int n
    const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream);
 hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
    const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream);
-hipError_t orc_launch_select_best(const double * costs, const int * status, const int * collides, const int * group, int n_runs,
+hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs,
    unsigned long long * key, int * count, int * best, hipStream_t stream);
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);
 
@@ -356,6 +357,59 @@ void BatchShard::collision_verdict(const std::vector<int> & offs, const std::vec
    DeviceGuard guard(device);
    if (params.precision == 64) collision_verdict_typed<double>(offs, seg, u, pairs, pair_rsum, inact_pos, key_out, depth_out);
    else collision_verdict_typed<float>(offs, seg, u, pairs, pair_rsum, inact_pos, key_out, depth_out);
+}
+
+// ... with the samples planned by the kernel itself: the trajectories stay where they are
+template <typename real>
+bool BatchShard::collision_verdict_planned_typed(const std::vector<double> & vmax, int col0,
+   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out)
+{
+   hipStream_t st = stream_;
+   hip_check(hipStreamSynchronize(st), "verdict: pending work");
+   if (n_points < 2 || (int) vmax.size() != n - col0) throw std::runtime_error("collision verdict: bad trajectory dimensions!");
+   // samples per pass: 64, or what the LDS of a CU holds of this robot's rows, positions and joint frames next to the plan
+   int chunk = 64;
+   while (chunk > 4 && orc_verdict_planned_lds_bytes(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk) > 160*1024 - 256) chunk -= 4;
+   const size_t lds = orc_verdict_planned_lds_bytes(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk);
+   if (lds > 160*1024 - 256) throw std::runtime_error("trajectory too long for the batched collision verdict!");
+   DevBuf d_xml, d_depth, d_time, d_ns, d_flag, d_pairs, d_vmax, d_rsum, d_inact;
+   d_xml.reset(dev_alloc<int>(slot_xml.size())); d_pairs.reset(dev_alloc<int>(pairs.size()));
+   d_depth.reset(dev_alloc<double>(n_runs)); d_time.reset(dev_alloc<double>(n_runs)); d_ns.reset(dev_alloc<int>(n_runs)); d_flag.reset(dev_alloc<int>(1));
+   if (!d_vkey_) d_vkey_.reset(dev_alloc<unsigned long long>(n_runs));
+   hip_check(hipMemcpyAsync(d_xml.as<void>(), slot_xml.data(), slot_xml.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict xml");
+   hip_check(hipMemcpyAsync(d_pairs.as<void>(), pairs.data(), pairs.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict pairs");
+   hip_check(hipMemsetAsync(d_depth.as<void>(), 0, n_runs*sizeof(double), st), "verdict depth");
+   hip_check(hipMemsetAsync(d_flag.as<void>(), 0, sizeof(int), st), "verdict flag");
+   d_vmax.reset(upload<double>(vmax, st)); d_rsum.reset(upload<real>(pair_rsum, st)); d_inact.reset(upload<real>(inact_pos, st));
+   DevVerdictPlan<real> v;
+   v.model = d_model_.as<const DevModel<real>>(); v.sdfs = d_sdfs_.as<const DevSdf<real>>(); v.n_sdfs = scn_.n_sdfs;
+   v.scene_of_run = d_scene_of_run_.as<int>(); v.scene_nsdf = d_scene_nsdf_.as<int>();
+   v.n_runs = n_runs; v.n_points = n_points; v.n = n; v.col0 = col0; v.chunk = chunk; v.traj = d_traj_.as<const real>();
+   v.vmax = d_vmax.as<const double>(); v.slot_xml = d_xml.as<int>();
+   v.n_pairs = (int) pair_rsum.size(); v.pairs = d_pairs.as<int>(); v.pair_rsum = d_rsum.as<const real>(); v.inact_pos = d_inact.as<const real>();
+   v.key_out = d_vkey_.as<unsigned long long>(); v.depth_out = d_depth.as<double>(); v.time_out = d_time.as<double>();
+   v.n_samples_out = d_ns.as<int>(); v.too_long = d_flag.as<int>();
+   hip_check(orc_launch_verdict_planned(v, lds, st, plan_.variant & ORC_VAR_TREE), "collision_verdict_planned_kernel launch");
+   int too_long = 0;
+   hip_check(hipMemcpyAsync(&too_long, d_flag.as<void>(), sizeof(int), hipMemcpyDeviceToHost, st), "verdict flag");
+   hip_check(hipStreamSynchronize(st), "verdict sync");
+   if (too_long) return false;
+   if (key_out) hip_check(hipMemcpyAsync(key_out, d_vkey_.as<void>(), n_runs*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "verdict keys");
+   if (depth_out) hip_check(hipMemcpyAsync(depth_out, d_depth.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict depth");
+   if (time_out) hip_check(hipMemcpyAsync(time_out, d_time.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict time");
+   if (n_samples_out) hip_check(hipMemcpyAsync(n_samples_out, d_ns.as<void>(), n_runs*sizeof(int), hipMemcpyDeviceToHost, st), "verdict samples");
+   hip_check(hipStreamSynchronize(st), "verdict sync");
+   return true;
+}
+
+bool BatchShard::collision_verdict_planned(const std::vector<double> & vmax, int col0,
+   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out)
+{
+   DeviceGuard guard(device);
+   if (params.precision == 64) return collision_verdict_planned_typed<double>(vmax, col0, pairs, pair_rsum, inact_pos, key_out, depth_out, time_out, n_samples_out);
+   return collision_verdict_planned_typed<float>(vmax, col0, pairs, pair_rsum, inact_pos, key_out, depth_out, time_out, n_samples_out);
 }
 
 // which iterations of this call resample the momentum, and with what noise
@@ -748,31 +802,27 @@ void BatchShard::perturb(double scale, const unsigned int * seeds, const std::ve
    dev_free(d_gen); dev_free(d_seeds);
 }
 
-void BatchShard::select_best(int n_groups, const int * group, const int * collides, unsigned long long * key_out, int * best_out, int * count_out)
+void BatchShard::select_best(int n_groups, const int * group, bool collision_free, unsigned long long * key_out, int * best_out, int * count_out)
 {
    DeviceGuard guard(device);
    hipStream_t st = stream_;
-   int * d_group = nullptr; int * d_col = nullptr; unsigned long long * d_key = nullptr; int * d_best = nullptr; int * d_count = nullptr;
+   if (collision_free && !d_vkey_) throw std::runtime_error("select_best: no collision verdict on the device!");
+   int * d_group = nullptr; unsigned long long * d_key = nullptr; int * d_best = nullptr; int * d_count = nullptr;
    try
    {
       d_group = dev_alloc<int>(n_runs); d_key = dev_alloc<unsigned long long>(n_groups); d_best = dev_alloc<int>(n_groups); d_count = dev_alloc<int>(n_groups);
       hip_check(hipMemcpyAsync(d_group, group, n_runs*sizeof(int), hipMemcpyHostToDevice, st), "select groups");
-      if (collides)
-      {
-         d_col = dev_alloc<int>(n_runs);
-         hip_check(hipMemcpyAsync(d_col, collides, n_runs*sizeof(int), hipMemcpyHostToDevice, st), "select verdict");
-      }
       hip_check(hipMemsetAsync(d_key, 0xff, n_groups*sizeof(unsigned long long), st), "select keys");
       hip_check(hipMemsetAsync(d_best, 0x7f, n_groups*sizeof(int), st), "select runs");      // (0x7f7f7f7f: above every run index)
       hip_check(hipMemsetAsync(d_count, 0, n_groups*sizeof(int), st), "select counts");
-      hip_check(orc_launch_select_best(d_costs_.as<double>(), d_status_.as<int>(), d_col, d_group, n_runs, d_key, d_count, d_best, st), "select_best kernels launch");
+      hip_check(orc_launch_select_best(d_costs_.as<double>(), d_status_.as<int>(), collision_free ? d_vkey_.as<unsigned long long>() : nullptr, d_group, n_runs, d_key, d_count, d_best, st), "select_best kernels launch");
       hip_check(hipMemcpyAsync(key_out, d_key, n_groups*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "select keys");
       hip_check(hipMemcpyAsync(best_out, d_best, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select runs");
       hip_check(hipMemcpyAsync(count_out, d_count, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select counts");
       hip_check(hipStreamSynchronize(st), "select sync");
    }
-   catch (...) { dev_free(d_group); dev_free(d_col); dev_free(d_key); dev_free(d_best); dev_free(d_count); throw; }
-   dev_free(d_group); dev_free(d_col); dev_free(d_key); dev_free(d_best); dev_free(d_count);
+   catch (...) { dev_free(d_group); dev_free(d_key); dev_free(d_best); dev_free(d_count); throw; }
+   dev_free(d_group); dev_free(d_key); dev_free(d_best); dev_free(d_count);
 }
 
 void BatchShard::gettraj_rows(const std::vector<int> & rows, double * out)
@@ -987,13 +1037,13 @@ std::vector<int> Batch::select_groups(int n_groups, const int * group_of_run) co
    return group;
 }
 
-void Batch::select_best(int n_groups, const std::vector<int> & group, const int * collides, int * best_run_out, double * best_cost_out, int * n_eligible_out)
+void Batch::select_best(int n_groups, const std::vector<int> & group, bool collision_free, int * best_run_out, double * best_cost_out, int * n_eligible_out)
 {
    const size_t S = shards.size();
    std::vector<unsigned long long> key(S * n_groups);
    std::vector<int> best(S * n_groups), count(S * n_groups);
    for_shards([&](size_t k) {
-      shards[k]->select_best(n_groups, group.data() + offs[k], collides ? collides + offs[k] : nullptr,
+      shards[k]->select_best(n_groups, group.data() + offs[k], collision_free,
                              key.data() + k * n_groups, best.data() + k * n_groups, count.data() + k * n_groups);
    }, true);
    // the merge of n_shards x n_groups candidates: the lower cost, then the lower run (the shards hold ascending runs)
@@ -1061,6 +1111,19 @@ void Batch::collision_verdict(const std::vector<int> & soffs, const std::vector<
       const std::vector<double> su(u.begin() + soffs[r0], u.begin() + soffs[r1]);
       shards[k]->collision_verdict(so, sg, su, pairs, pair_rsum, inact_pos, key_out + r0, depth_out + r0);
    }, true);
+}
+
+void Batch::collision_verdict_planned(const std::vector<double> & vmax, int col0,
+   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out)
+{
+   std::vector<int> ok(shards.size(), 1);
+   for_shards([&](size_t k) {
+      const int r0 = offs[k];
+      ok[k] = shards[k]->collision_verdict_planned(vmax, col0, pairs, pair_rsum, inact_pos, key_out ? key_out + r0 : nullptr,
+         depth_out ? depth_out + r0 : nullptr, time_out ? time_out + r0 : nullptr, n_samples_out ? n_samples_out + r0 : nullptr) ? 1 : 0;
+   }, true);
+   for (int v : ok) if (!v) throw std::runtime_error("trajectory too long for the batched collision verdict!");
 }
 
 // create's dat_filename (src/orcdchomp_mod.cpp:2306-2310): one file per run; a batch of several

@@ -541,6 +541,15 @@ int orc_batch_collision_verdict(orc_module * mod, int id, int * collides_out, do
    });
 }
 
+int orc_batch_collision_verdict_device(orc_module * mod, int id, int * collides_out, double * time_out, int * sphere_out,
+   int * field_out, double * depth_out, int * n_samples_out)
+{
+   return guarded(mod, [&] {
+      need(collides_out, "collides_out");
+      mod->impl->batch_collision_verdict_device(id, collides_out, time_out, sphere_out, field_out, depth_out, n_samples_out);
+   });
+}
+
 int orc_batch_get_state(orc_module * mod, int id, const char * which, double * out, size_t cap)
 {
    return guarded(mod, [&] {
@@ -597,14 +606,10 @@ int orc_batch_select_best(orc_module * mod, int id, int n_groups, const int * gr
 {
    return guarded(mod, [&] {
       orc::Batch & b = mod->impl->batch(id);
-      const std::vector<int> group = b.select_groups(n_groups, group_of_run);      // (the arguments first: the verdict below reads every trajectory back)
-      std::vector<int> collides;
-      if (require_collision_free)
-      {
-         collides.resize(b.n_runs);
-         mod->impl->batch_collision_verdict(id, collides.data(), nullptr, nullptr, nullptr, nullptr);
-      }
-      b.select_best(n_groups, group, require_collision_free ? collides.data() : nullptr, best_run_out, best_cost_out, n_eligible_out);
+      const std::vector<int> group = b.select_groups(n_groups, group_of_run);      // (the arguments first: the verdict below walks every trajectory)
+      // the verdict's keys stay on the device, where the selection reads them
+      if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      b.select_best(n_groups, group, require_collision_free != 0, best_run_out, best_cost_out, n_eligible_out);
    });
 }
 
@@ -754,6 +759,25 @@ int orc_host_metric_semisep_rank(int m, int derivative, double dt, int free_star
       return M.ss_rank;
    }
    catch (...) { return -1; }
+}
+
+int orc_host_verdict_samples(const double * traj, int n_points, int n, int col0, const double * vmax, int cap,
+   int * seg_out, double * u_out, double * time_out, int * n_samples_out)
+{
+   try
+   {
+      if (!traj || !vmax || n_points < 2 || n < 1 || col0 < 0 || col0 >= n) return 1;
+      std::vector<int> seg; std::vector<double> u, times;
+      orc::host_verdict_samples(traj, n_points, n, col0, std::vector<double>(vmax, vmax + (n - col0)), seg, u, times);
+      if (seg.size() > (size_t) 0x7fffffff) return 1;
+      if (n_samples_out) *n_samples_out = (int) seg.size();
+      if (cap < 0 || seg.size() > (size_t) cap) return 1;
+      if (seg_out) std::copy(seg.begin(), seg.end(), seg_out);
+      if (u_out) std::copy(u.begin(), u.end(), u_out);
+      if (time_out) std::copy(times.begin(), times.end(), time_out);
+      return 0;
+   }
+   catch (...) { return 1; }
 }
 
 int orc_host_gsl_stream(unsigned long seed, double sigma, int n, double * out_gauss, double * out_uniform)

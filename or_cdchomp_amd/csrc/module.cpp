@@ -1379,30 +1379,11 @@ static void plan_collision_samples(const double * traj, int n_points, int n, int
    }
 }
 
-void Module::batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check)
+// the pairs of the verdict's self-collision leg (`|| CheckSelfCollision`, mod.cpp:2998-2999): spheres on links that may
+// collide, in XML order; an end is a slot of the device's position row or an inactive sphere's world position
+static void verdict_self_pairs(const Robot & rob, const Batch & b, bool self_check,
+   std::vector<int> & pairs, std::vector<double> & rsum, std::vector<double> & inact_pos)
 {
-   Batch & b = batch(id);
-   const int col0 = b.params.floating_base ? 7 : 0;
-   Robot rob = robot(b.robot_name);
-   rob.spheres = b.run_spheres;         // the robot's and those of the bodies it held at create (mod.cpp:2992-2996)
-   std::vector<double> vmax;
-   for (int a : b.adofindices) vmax.push_back(a < (int) rob.limit_vel.size() ? rob.limit_vel[a] : 1.0);
-   std::vector<double> traj((size_t) b.n_runs * b.n_points * b.n);
-   b.gettraj(traj.data());
-   std::vector<int> offs(b.n_runs + 1, 0), seg;
-   std::vector<double> u, times;
-   for (int k=0; k<b.n_runs; k++)
-   {
-      const double * tk = &traj[(size_t) k * b.n_points * b.n];
-      const std::vector<double> dtm = retime_linear(tk, b.n_points, b.n, col0, vmax);
-      plan_collision_samples(tk, b.n_points, b.n, col0, dtm, seg, u, times);
-      if (seg.size() >= ((size_t) 1 << 31) - 1) throw std::runtime_error("trajectory too long for the batched collision verdict!");      // (the running total is an int on both sides)
-      offs[k+1] = (int) seg.size();
-      if (offs[k+1] - offs[k] >= (1 << 30)) throw std::runtime_error("trajectory too long for the batched collision verdict!");
-   }
-   // the pairs of the self-collision leg (`|| CheckSelfCollision`, mod.cpp:2998-2999): spheres on links that may
-   // collide, in XML order; an end is a slot of the device's position row or an inactive sphere's world position
-   std::vector<int> pairs; std::vector<double> rsum, inact_pos;
    if ((int) rob.spheres.size() > 128) throw std::runtime_error("too many spheres for the batched collision verdict!");
    if (self_check && rob.self_check)
    {
@@ -1429,6 +1410,39 @@ void Module::batch_collision_verdict(int id, int * collides, double * time, int 
             rsum.push_back(rob.spheres[a].radius + rob.spheres[c].radius);
          }
    }
+}
+
+// the plan of one trajectory as the verdict makes it (orc_host_verdict_samples)
+void host_verdict_samples(const double * traj, int n_points, int n, int col0, const std::vector<double> & vmax,
+   std::vector<int> & seg_out, std::vector<double> & u_out, std::vector<double> & time_out)
+{
+   const std::vector<double> dtm = retime_linear(traj, n_points, n, col0, vmax);
+   plan_collision_samples(traj, n_points, n, col0, dtm, seg_out, u_out, time_out);
+}
+
+void Module::batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check)
+{
+   Batch & b = batch(id);
+   const int col0 = b.params.floating_base ? 7 : 0;
+   Robot rob = robot(b.robot_name);
+   rob.spheres = b.run_spheres;         // the robot's and those of the bodies it held at create (mod.cpp:2992-2996)
+   std::vector<double> vmax;
+   for (int a : b.adofindices) vmax.push_back(a < (int) rob.limit_vel.size() ? rob.limit_vel[a] : 1.0);
+   std::vector<double> traj((size_t) b.n_runs * b.n_points * b.n);
+   b.gettraj(traj.data());
+   std::vector<int> offs(b.n_runs + 1, 0), seg;
+   std::vector<double> u, times;
+   for (int k=0; k<b.n_runs; k++)
+   {
+      const double * tk = &traj[(size_t) k * b.n_points * b.n];
+      const std::vector<double> dtm = retime_linear(tk, b.n_points, b.n, col0, vmax);
+      plan_collision_samples(tk, b.n_points, b.n, col0, dtm, seg, u, times);
+      if (seg.size() >= ((size_t) 1 << 31) - 1) throw std::runtime_error("trajectory too long for the batched collision verdict!");      // (the running total is an int on both sides)
+      offs[k+1] = (int) seg.size();
+      if (offs[k+1] - offs[k] >= (1 << 30)) throw std::runtime_error("trajectory too long for the batched collision verdict!");
+   }
+   std::vector<int> pairs; std::vector<double> rsum, inact_pos;
+   verdict_self_pairs(rob, b, self_check, pairs, rsum, inact_pos);
    std::vector<unsigned long long> key(b.n_runs); std::vector<double> dep(b.n_runs);
    b.collision_verdict(offs, seg, u, pairs, rsum, inact_pos, key.data(), dep.data());
    if (getenv("ORC_DEBUG_VERDICT"))
@@ -1443,6 +1457,32 @@ void Module::batch_collision_verdict(int id, int * collides, double * time, int 
       if (sphere) sphere[k] = hit ? (int)((key[k] >> 16) & 0x7fffull) : -1;
       if (field) field[k] = hit ? (self ? -2 - (int)(key[k] & 0xffffull) : (int)(key[k] & 0xffffull)) : -1;      // a pair: -2 - the other sphere
       if (depth) depth[k] = hit ? dep[k] : 0.0;
+   }
+}
+
+// The verdict above with the planning left to the device (verdict_kernels.hip): what goes up is vmax and the pair tables,
+// what comes back is what the caller asks for.
+void Module::batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples)
+{
+   Batch & b = batch(id);
+   const int col0 = b.params.floating_base ? 7 : 0;
+   Robot rob = robot(b.robot_name);
+   rob.spheres = b.run_spheres;
+   std::vector<double> vmax;
+   for (int a : b.adofindices) vmax.push_back(a < (int) rob.limit_vel.size() ? rob.limit_vel[a] : 1.0);
+   std::vector<int> pairs; std::vector<double> rsum, inact_pos;
+   verdict_self_pairs(rob, b, true, pairs, rsum, inact_pos);
+   const bool want_key = collides || sphere || field;
+   std::vector<unsigned long long> key(want_key ? b.n_runs : 0);
+   b.collision_verdict_planned(vmax, col0, pairs, rsum, inact_pos, want_key ? key.data() : nullptr, depth, time, n_samples);
+   if (!want_key) return;
+   for (int k=0; k<b.n_runs; k++)
+   {
+      const bool hit = key[k] != ORC_VERDICT_NONE;
+      const bool self = hit && ((key[k] >> 31) & 1ull);
+      if (collides) collides[k] = hit ? 1 : 0;
+      if (sphere) sphere[k] = hit ? (int)((key[k] >> 16) & 0x7fffull) : -1;
+      if (field) field[k] = hit ? (self ? -2 - (int)(key[k] & 0xffffull) : (int)(key[k] & 0xffffull)) : -1;
    }
 }
 

@@ -108,8 +108,9 @@ public:
    // gen = the generators of A^-1, U [rank][m] then V [rank][m] (Batch::perturb builds them once for all shards)
    void perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank);
    // per group the lowest cost key among this shard's eligible runs, the lowest LOCAL run that has it, the eligible runs;
-   // group [n_runs] and collides [n_runs] (or NULL: not asked for) are this shard's slices
-   void select_best(int n_groups, const int * group, const int * collides, unsigned long long * key_out, int * best_out, int * count_out);
+   // group [n_runs] is this shard's slice; collision_free: a run whose key of the last collision_verdict_planned (kept on
+   // the device) names a contact is not eligible
+   void select_best(int n_groups, const int * group, bool collision_free, unsigned long long * key_out, int * best_out, int * count_out);
    // rows[k] (local runs) of the trajectory array as doubles: out [rows.size()][n_points][n]
    void gettraj_rows(const std::vector<int> & rows, double * out);
    const Metric & metric() const { return metric_; }
@@ -117,6 +118,12 @@ public:
    void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
                           const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
                           unsigned long long * key_out, double * depth_out);
+   // the same verdict with the retiming and the samples planned on the device (verdict_kernels.hip): nothing but vmax
+   // [n - col0] and the pair tables goes up, and what of key / depth / time / n_samples [n_runs] is not NULL comes back; the
+   // keys stay on the device for select_best.  Returns false when a run has too many samples (nothing is written then)
+   bool collision_verdict_planned(const std::vector<double> & vmax, int col0,
+                                  const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+                                  unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out);
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
    void harvest_events(bool wait);
@@ -139,6 +146,9 @@ private:
    template <typename real> void collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
       const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
       unsigned long long * key_out, double * depth_out);
+   template <typename real> bool collision_verdict_planned_typed(const std::vector<double> & vmax, int col0,
+      const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+      unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out);
    void plan_hmc(int iter_begin, int iter_end);
    int hmc_room(int n_iter, const Switches & now) const;
    void hmc_reserve(int cap, bool pending_work);
@@ -164,6 +174,7 @@ private:
    DevBuf d_costs_, d_trace_; size_t trace_cap_ = 0;
    DevBuf d_conv_prev_, d_conv_streak_;      // [n_runs] the convergence stop's state between the launches of a call
    DevBuf d_status_, d_iters_done_, d_leap_, d_phase_;
+   DevBuf d_vkey_;                           // [n_runs] the keys of the last collision_verdict_planned
    DevBuf d_Aband_, d_beta_s_, d_beta_g_, d_metric64_, d_pcr_, d_Ainv_, d_jl_lo_, d_jl_hi_;
    // TSR hard constraints (csrc/tsr.h): the device copies of the constraints, the per-run workspace
    DevBuf d_tsrs_, d_tsr_ws_, d_tsr_err_;
@@ -208,12 +219,17 @@ public:
    // multi-start: orc_batch_perturb / _select_best / _gettraj_runs (include/orcdchomp_amd.h has the contract)
    void perturb(double sigma, const unsigned int * seeds);
    std::vector<int> select_groups(int n_groups, const int * group_of_run) const;   // the validated group of every run (NULL: contiguous equal blocks); throws
-   void select_best(int n_groups, const std::vector<int> & group, const int * collides, int * best_run_out, double * best_cost_out, int * n_eligible_out);
+   // collision_free: the runs' keys of the collision_verdict_planned made just before (they never left the device)
+   void select_best(int n_groups, const std::vector<int> & group, bool collision_free, int * best_run_out, double * best_cost_out, int * n_eligible_out);
    void gettraj_runs(const int * runs, int n_sel, double * out);
    bool iterated = false;            // an iterate call has been made: the device's costs and status are a call's results
    void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
                           const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
                           unsigned long long * key_out, double * depth_out);
+   // every shard plans and walks its own runs; outputs [n_runs] or NULL; throws when a run has too many samples
+   void collision_verdict_planned(const std::vector<double> & vmax, int col0,
+                                  const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+                                  unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out);
    void get_phase_cycles(long long * out);
    // the convergence stop of every shard's runs for the later iterate calls (validated: throws and changes nothing on a bad spec)
    void set_convergence(const ConvergenceSpec & c);
@@ -292,6 +308,9 @@ public:
    // collision verdict of all runs of a batch (gettraj's re-check, batched on the device): per run
    // collides (0/1), time of the first contact on the retimed trajectory, XML sphere, field, depth
    void batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check = true);
+   // the same verdict planned on the device (no trajectory is read back); every output may be NULL: the keys stay on the
+   // device for Batch::select_best.  n_samples: the samples of every run's retimed trajectory
+   void batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples);
 
    hipStream_t stream = nullptr;     // orc_set_stream: the stream of the first device's work (NULL: its default stream)
    int device;                       // first entry of `devices`
@@ -346,5 +365,8 @@ private:
 
 void hip_check(hipError_t e, const char * what);
 int count_int_conversions(const std::string & pattern);   // integer conversions of a printf pattern, -1: it holds another kind
+// the collision verdict's plan of one trajectory [n_points][n] (retime_linear, then a sample every 0.04 rad): appended to the outputs
+void host_verdict_samples(const double * traj, int n_points, int n, int col0, const std::vector<double> & vmax,
+   std::vector<int> & seg_out, std::vector<double> & u_out, std::vector<double> & time_out);
 
 } // namespace orc

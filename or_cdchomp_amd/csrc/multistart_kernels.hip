@@ -99,28 +99,29 @@ __device__ __forceinline__ unsigned long long cost_key(double c)
    const unsigned long long b = (unsigned long long) __double_as_longlong(c + 0.0);
    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-__device__ __forceinline__ bool run_eligible(const double * costs, const int * status, const int * collides, int r)
+// verdict_key: the runs' keys of the collision verdict (verdict_kernels.hip), or NULL when the verdict is not asked for
+__device__ __forceinline__ bool run_eligible(const double * costs, const int * status, const unsigned long long * verdict_key, int r)
 {
    const int st = status[r];
    const double c = costs[(size_t) r*3];
-   return (st == 0 || st == 1) && isfinite(c) && !(collides && collides[r]);
+   return (st == 0 || st == 1) && isfinite(c) && !(verdict_key && verdict_key[r] != ORC_VERDICT_NONE);
 }
 
 // pass 1: the lowest cost key of every group's eligible runs and their number
-__global__ void select_cost_kernel(const double * costs, const int * status, const int * collides, const int * group, int n_runs,
+__global__ void select_cost_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs,
    unsigned long long * key, int * count)
 {
    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-   if (r >= n_runs || !run_eligible(costs, status, collides, r)) return;
+   if (r >= n_runs || !run_eligible(costs, status, verdict_key, r)) return;
    atomicMin(&key[group[r]], cost_key(costs[(size_t) r*3]));
    atomicAdd(&count[group[r]], 1);
 }
 // pass 2: the lowest index among the runs that have it
-__global__ void select_run_kernel(const double * costs, const int * status, const int * collides, const int * group, int n_runs,
+__global__ void select_run_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs,
    const unsigned long long * key, int * best)
 {
    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-   if (r >= n_runs || !run_eligible(costs, status, collides, r)) return;
+   if (r >= n_runs || !run_eligible(costs, status, verdict_key, r)) return;
    if (cost_key(costs[(size_t) r*3]) == key[group[r]]) atomicMin(&best[group[r]], r);
 }
 
@@ -166,12 +167,12 @@ hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n,
    return launch_perturb<float>(traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, stream);
 }
 // key [n_groups] (all bits set), count [n_groups] (0) and best [n_groups] (INT_MAX) are the caller's to initialise
-hipError_t orc_launch_select_best(const double * costs, const int * status, const int * collides, const int * group, int n_runs,
+hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs,
    unsigned long long * key, int * count, int * best, hipStream_t stream)
 {
    const dim3 grid((n_runs + 255) / 256), block(256);
-   hipLaunchKernelGGL(select_cost_kernel, grid, block, 0, stream, costs, status, collides, group, n_runs, key, count);
-   hipLaunchKernelGGL(select_run_kernel, grid, block, 0, stream, costs, status, collides, group, n_runs, key, best);
+   hipLaunchKernelGGL(select_cost_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, key, count);
+   hipLaunchKernelGGL(select_run_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, key, best);
    return hipGetLastError();
 }
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream)

@@ -7,6 +7,7 @@ errors surface as ``RuntimeError`` carrying the reference's exception message
 Everything is executed by liborcdchomp_amd.so through its C ABI.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -125,6 +126,54 @@ def seed_perturbation(m, n, derivative, dt, sigma, seed, lower, upper, base):
     lo = np.broadcast_to(np.asarray(lower, dtype=np.float64), (n,))
     hi = np.broadcast_to(np.asarray(upper, dtype=np.float64), (n,))
     return np.minimum(np.maximum(base + (float(sigma) * c) * sol, lo), hi)
+
+
+def verdict_samples(traj, vmax, col0=0):
+    """The sample plan of the collision verdict for one trajectory [n_points][n]: the library's retime_linear and
+    plan_collision_samples restated line for line in scalar Python doubles (orc_host_verdict_samples is the host's own;
+    the kernel of orc_batch_collision_verdict_device reproduces the same roundings).  vmax [n - col0]: the velocity limits
+    of the columns col0 .. n-1.  Returns (seg int32 [], u float64 [], time float64 []): per sample the segment it lies on,
+    its position on the segment, its time.  Every sum runs in index order and the clock advances by repeated addition,
+    as the host's do: no numpy reduction, which adds pairwise.  Pure: no library call."""
+    T = np.asarray(traj, dtype=np.float64)
+    if T.ndim != 2 or T.shape[0] < 2:
+        raise ValueError("a trajectory is [n_points][n] with at least two points")
+    n_points, n = T.shape
+    col0 = int(col0)
+    vm = [float(x) for x in np.asarray(vmax, dtype=np.float64).reshape(-1)]
+    if not 0 <= col0 < n or len(vm) != n - col0:
+        raise ValueError("vmax has an entry for every column from col0 on")
+    rows = [[float(x) for x in row] for row in T]
+    # retime_linear: every segment at the largest constant velocity the limits allow
+    dtm = [0.0] * n_points
+    for i in range(1, n_points):
+        for j in range(col0, n):
+            v = vm[j - col0] if vm[j - col0] > 0.0 else 1.0
+            c = abs(rows[i][j] - rows[i - 1][j]) / v
+            dtm[i] = c if dtm[i] < c else dtm[i]          # std::max(dtm[i], c): a NaN candidate is ignored
+    # plan_collision_samples
+    total_dist = 0.0
+    duration = 0.0
+    for i in range(n_points - 1):
+        d2 = 0.0
+        for j in range(col0, n):
+            d = rows[i][j] - rows[i + 1][j]
+            d2 += d * d
+        total_dist += math.sqrt(d2)
+        duration += dtm[i + 1]
+    step_time = duration * 0.04 / total_dist if total_dist > 0.0 else duration + 1.0
+    seg_out, u_out, time_out = [], [], []
+    seg = 0
+    tseg0 = 0.0
+    time = 0.0
+    while time < duration:
+        while seg < n_points - 2 and tseg0 + dtm[seg + 1] < time:
+            tseg0 += dtm[seg + 1]
+            seg += 1
+        u = (time - tseg0) / dtm[seg + 1] if dtm[seg + 1] > 0.0 else 0.0
+        seg_out.append(seg); u_out.append(u); time_out.append(time)
+        time += step_time
+    return np.asarray(seg_out, dtype=np.int32), np.asarray(u_out, dtype=np.float64), np.asarray(time_out, dtype=np.float64)
 
 
 def select_best(costs, status, collides, group_of_run, n_groups):
@@ -488,13 +537,20 @@ class Module:
         self._check(self._lib.orc_batch_gettraj_runs(self._h, bid, _ip(rs), rs.size, _dp(out), out.size))
         return out
 
-    def batch_collision_verdict(self, bid):
+    def batch_collision_verdict(self, bid, on_device=False):
         """gettraj's collision re-check for every run of the batch, on the device: returns a dict of
         arrays per run: collides (0/1), time of the first contact on the retimed trajectory, XML index
-        of the sphere, index of the field, penetration depth [m]"""
+        of the sphere, index of the field, penetration depth [m].  on_device: the samples are planned on the device
+        too (orc_batch_collision_verdict_device; the plan is verdict_samples'): the same results without a read-back of
+        the trajectories, and n_samples, the samples of every run's retimed trajectory"""
         n_runs = self.batch_dims(bid)[0]
         col = np.zeros(n_runs, dtype=np.int32); sph = np.zeros(n_runs, dtype=np.int32); fld = np.zeros(n_runs, dtype=np.int32)
         tim = np.zeros(n_runs); dep = np.zeros(n_runs)
+        if on_device:
+            cnt = np.zeros(n_runs, dtype=np.int32)
+            self._check(self._lib.orc_batch_collision_verdict_device(self._h, bid, _ip(col), _dp(tim), _ip(sph), _ip(fld), _dp(dep),
+                                                                     _ip(cnt)))
+            return dict(collides=col, time=tim, sphere=sph, field=fld, depth=dep, n_samples=cnt)
         self._check(self._lib.orc_batch_collision_verdict(self._h, bid, _ip(col), _dp(tim), _ip(sph), _ip(fld), _dp(dep)))
         return dict(collides=col, time=tim, sphere=sph, field=fld, depth=dep)
 
