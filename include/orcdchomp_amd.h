@@ -196,7 +196,9 @@ int orc_scene_get_sdf(orc_module * mod, const char * kinbody, int sizes[3], doub
 /* ---- kernel-level batch API --------------------------------------------------
  * what the command layer calls; one batch = n_runs independent CHOMP runs that
  * share robot, fields and parameters (struct run, src/orcdchomp_mod.cpp:887-966;
- * cd_chomp, src/libcd/chomp.h:38-101).  A single `create` is a batch of 1. */
+ * cd_chomp, src/libcd/chomp.h:38-101).  A single `create` is a batch of 1.
+ * (The fields may differ per run: orc_batch_create_scenes; so may the seed trajectories: orc_batch_perturb; and
+ * lambda, epsilon, obs_factor and obs_factor_self: orc_batch_set_run_params.) */
 typedef struct orc_batch_params
 {
    int n_points;               /* default 101        (mod.cpp:1840) */
@@ -265,6 +267,30 @@ int orc_batch_iterations_done(orc_module * mod, int batch_id, int * iters_out);
  * HMC runs: the call's momentum resamples are planned for all n_iter iterations, so after a stop the
  * random stream is where a full-length call leaves it (as after a run that left its limits). */
 int orc_batch_set_convergence(orc_module * mod, int batch_id, double rtol, int patience, double obs_max);
+/* Per-run lambda, epsilon, obs_factor and obs_factor_self: a portfolio of parameter sets in one batch.  Each array is
+ * [n_runs], or NULL: every run takes the value the batch was created with.  The call REPLACES the whole table (it does not
+ * merge with an earlier call); all four NULL switches the feature off, the kernels then read no table.  It applies to every
+ * iterate call enqueued after it (orc_batch_iterate, _iterate_async, the iterate / iteratebatch commands, every launch of a
+ * call that launches once per iteration -- max_time, trajs_fileformstr -- and the final cost-only pass); an
+ * orc_batch_iterate_async enqueued before it finishes with the old values (the upload follows it on the shard's stream).  It
+ * may be called between iterate calls: a schedule, such as annealing obs_factor, is a sequence of calls.
+ * The values are converted to the batch's precision once on the host, as create converts orc_batch_params; the kernels pick
+ * the run's record or the batch's own once per phase and share all code after that, so a run with per-run values p is bit
+ * for bit the same run in a batch created with p as its parameters: trajectory, costs, trace, status, iterations done, "AG".
+ * A run's result depends on its own four values only, never on its position, its neighbours or the shard that holds it (a
+ * module over several devices slices the table by shard, as it slices scene_of_run).
+ * Rejected with a nonzero return and a message, the previous table kept and the module usable: an unknown batch; a NaN or
+ * infinite entry in any array; a lambda or epsilon entry <= 0 (the kernels form 1/lambda and 1/epsilon).
+ * Read-back: orc_batch_get_state(..., "run_params", ...) gives [n_runs][4] doubles in the order lambda, epsilon, obs_factor,
+ * obs_factor_self: what the device holds (a precision 32 batch returns them float-rounded; a batch without a table returns
+ * the shared values, rounded alike).
+ * Deliberately NOT per run: epsilon_self feeds the fold (sphere placement on the 16-lane row, the pair list's order and its
+ * always-evaluated rounds), the fold decides the plan, and a plan must not depend on the run; hmc_resample_lambda is planned
+ * by another kernel (or the host) for the whole call; n_points, derivative, use_momentum, use_hmc and precision all shape
+ * the plan. */
+int orc_batch_set_run_params(orc_module * mod, int batch_id,
+   const double * lambda, const double * epsilon,
+   const double * obs_factor, const double * obs_factor_self);
 /* asynchronous form for measurement: enqueue only, results stay on the device */
 int orc_batch_iterate_async(orc_module * mod, int batch_id, int n_iter);
 int orc_batch_sync(orc_module * mod, int batch_id, double * costs_out, int * status_out);
@@ -303,7 +329,8 @@ int orc_batch_collision_verdict_device(orc_module * mod, int batch_id, int * col
 /* optimizer state read-back for tests: which = "G", "AG", "T" ([n_runs][m][n]); "phase" ([n_runs][8] cycle counters with
  * ORC_PHASE_TIMERS=1); "plan" (8 numbers: kernel variant bits -- 512 = the dense pair-list family, 1 = a tree --, threads per
  * workgroup, LDS bytes per workgroup, tile, solve mode (2 closed-form scans, 3 band-inverse generators, 1 dense), workgroups
- * per CU, tiles, lanes per waypoint; a ninth, the moving waypoints of the first tile, when cap_doubles >= 9) */
+ * per CU, tiles, lanes per waypoint; a ninth, the moving waypoints of the first tile, when cap_doubles >= 9);
+ * "run_params" ([n_runs][4]: lambda, epsilon, obs_factor, obs_factor_self as the device holds them, orc_batch_set_run_params) */
 int orc_batch_get_state(orc_module * mod, int batch_id, const char * which, double * out, size_t cap_doubles);
 int orc_batch_dims(orc_module * mod, int batch_id, int * n_runs, int * n_points, int * n);
 /* overwrite the trajectories of a batch (warm start; what `create starttraj` does for one run,
@@ -350,6 +377,16 @@ int orc_batch_perturb(orc_module * mod, int batch_id, double sigma, const unsign
  * the construction of those tables, which does not depend on the trajectories.  The arguments are checked before the
  * verdict is taken: a rejected call costs no kernel. */
 int orc_batch_select_best(orc_module * mod, int batch_id, int n_groups, const int * group_of_run, int require_collision_free,
+   int * best_run_out, double * best_cost_out, int * n_eligible_out);
+/* orc_batch_select_best with the cost that is minimised chosen by the caller: cost_column 0 total, 1 obs, 2 smooth (any other
+ * value is rejected before any device work).  costs[run][0] and [1] contain obs_factor, so the total is not comparable between
+ * runs of different weights (orc_batch_set_run_params); the smoothness cost is.  Eligibility is exactly
+ * orc_batch_select_best's -- status 0 or 1, a finite TOTAL cost, the verdict if asked -- whatever the column; only the key
+ * changes: per group the eligible run with the lowest costs[run][cost_column] wins, a tie goes to the lowest run index, and
+ * best_cost_out is that column's value (+inf for a group without an eligible run).  orc_batch_select_best is the column-0
+ * case; several devices merge by the same rule. */
+int orc_batch_select_best_by(orc_module * mod, int batch_id, int cost_column, int n_groups,
+   const int * group_of_run, int require_collision_free,
    int * best_run_out, double * best_cost_out, int * n_eligible_out);
 /* The rows runs[0 .. n_sel) of what orc_batch_gettraj returns, gathered on the device and copied as n_sel n_points n
  * doubles: traj_out [n_sel][n_points][n].  An entry -1 (what orc_batch_select_best reports for a group without an

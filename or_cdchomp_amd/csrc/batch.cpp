@@ -27,7 +27,7 @@ hipError_t orc_launch_perturb_f64(double * traj, int n_runs, int n_points, int n
    const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream);
 hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
    const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream);
-hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs,
+hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
    unsigned long long * key, int * count, int * best, hipStream_t stream);
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);
 
@@ -603,10 +603,11 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    b.dt = (real) dt;
    b.inv_2dt = (real)(1.0/(2.0*dt));
    b.inv_dt2 = (real)(1.0/(dt*dt));
-   b.lambda = (real) params.lambda;
+   b.shared.lambda = (real) params.lambda;
    b.inv_m = (real)(1.0/m);
-   b.epsilon = (real) params.epsilon; b.epsilon_self = (real) params.epsilon_self;
-   b.obs_factor = (real) params.obs_factor; b.obs_factor_self = (real) params.obs_factor_self;
+   b.shared.epsilon = (real) params.epsilon; b.epsilon_self = (real) params.epsilon_self;
+   b.shared.obs_factor = (real) params.obs_factor; b.shared.obs_factor_self = (real) params.obs_factor_self;
+   b.run_params = run_params_on_ ? d_run_params_.as<const RunParams<real>>() : nullptr;
    b.use_momentum = params.use_momentum; b.use_hmc = params.use_hmc && max_resamples_ > 0;
    b.D = (params.derivative == 1 && params.free_start) ? -1 : params.derivative;
    b.Aband = d_Aband_.as<const real>(); b.beta_s = d_beta_s_.as<const real>(); b.beta_g = d_beta_g_.as<const real>();
@@ -802,7 +803,7 @@ void BatchShard::perturb(double scale, const unsigned int * seeds, const std::ve
    dev_free(d_gen); dev_free(d_seeds);
 }
 
-void BatchShard::select_best(int n_groups, const int * group, bool collision_free, unsigned long long * key_out, int * best_out, int * count_out)
+void BatchShard::select_best(int n_groups, const int * group, bool collision_free, int column, unsigned long long * key_out, int * best_out, int * count_out)
 {
    DeviceGuard guard(device);
    hipStream_t st = stream_;
@@ -815,7 +816,7 @@ void BatchShard::select_best(int n_groups, const int * group, bool collision_fre
       hip_check(hipMemsetAsync(d_key, 0xff, n_groups*sizeof(unsigned long long), st), "select keys");
       hip_check(hipMemsetAsync(d_best, 0x7f, n_groups*sizeof(int), st), "select runs");      // (0x7f7f7f7f: above every run index)
       hip_check(hipMemsetAsync(d_count, 0, n_groups*sizeof(int), st), "select counts");
-      hip_check(orc_launch_select_best(d_costs_.as<double>(), d_status_.as<int>(), collision_free ? d_vkey_.as<unsigned long long>() : nullptr, d_group, n_runs, d_key, d_count, d_best, st), "select_best kernels launch");
+      hip_check(orc_launch_select_best(d_costs_.as<double>(), d_status_.as<int>(), collision_free ? d_vkey_.as<unsigned long long>() : nullptr, d_group, n_runs, column, d_key, d_count, d_best, st), "select_best kernels launch");
       hip_check(hipMemcpyAsync(key_out, d_key, n_groups*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "select keys");
       hip_check(hipMemcpyAsync(best_out, d_best, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select runs");
       hip_check(hipMemcpyAsync(count_out, d_count, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select counts");
@@ -823,6 +824,49 @@ void BatchShard::select_best(int n_groups, const int * group, bool collision_fre
    }
    catch (...) { dev_free(d_group); dev_free(d_key); dev_free(d_best); dev_free(d_count); throw; }
    dev_free(d_group); dev_free(d_key); dev_free(d_best); dev_free(d_count);
+}
+
+// ---- per-run parameters ---------------------------------------------------------------------------------------------
+namespace {
+template <typename real>
+void upload_run_params(const double * table, int n_runs, void * d, hipStream_t st)
+{
+   // the conversion `launch` makes of the shared values: (real) of the caller's double, once
+   std::vector<RunParams<real>> rec(n_runs);
+   for (int k=0; k<n_runs; k++)
+   {
+      rec[k].lambda = (real) table[4*k]; rec[k].epsilon = (real) table[4*k + 1];
+      rec[k].obs_factor = (real) table[4*k + 2]; rec[k].obs_factor_self = (real) table[4*k + 3];
+   }
+   hip_check(hipMemcpyAsync(d, rec.data(), rec.size()*sizeof(RunParams<real>), hipMemcpyHostToDevice, st), "run params");
+   hip_check(hipStreamSynchronize(st), "run params sync");
+}
+}
+
+void BatchShard::set_run_params(const double * table)
+{
+   // the kernarg block of a launch carries the table's address or NULL by value: launches already enqueued are not touched by
+   // the switch, and the copy below follows them on the stream
+   if (!table) { run_params_on_ = false; return; }
+   DeviceGuard guard(device);
+   const size_t rsize = (params.precision == 64) ? sizeof(RunParams<double>) : sizeof(RunParams<float>);
+   if (!d_run_params_) d_run_params_.reset(dev_alloc<char>((size_t) n_runs * rsize));
+   if (params.precision == 64) upload_run_params<double>(table, n_runs, d_run_params_.as<void>(), stream_);
+   else upload_run_params<float>(table, n_runs, d_run_params_.as<void>(), stream_);
+   run_params_on_ = true;
+}
+
+void BatchShard::get_run_params(double * out)
+{
+   if (run_params_on_)
+   {
+      DeviceGuard guard(device);
+      download(d_run_params_.as<void>(), (size_t) n_runs * 4, params.precision, out, stream_);
+      return;
+   }
+   const double shared[4] = { params.lambda, params.epsilon, params.obs_factor, params.obs_factor_self };
+   for (int k=0; k<n_runs; k++)
+      for (int c=0; c<4; c++) out[4*k + c] = (params.precision == 64) ? shared[c] : (double)(float) shared[c];
 }
 
 void BatchShard::gettraj_rows(const std::vector<int> & rows, double * out)
@@ -1037,13 +1081,47 @@ std::vector<int> Batch::select_groups(int n_groups, const int * group_of_run) co
    return group;
 }
 
-void Batch::select_best(int n_groups, const std::vector<int> & group, bool collision_free, int * best_run_out, double * best_cost_out, int * n_eligible_out)
+void Batch::select_column(int column)
+{
+   if (column < 0 || column > 2) throw std::runtime_error("select_best_by: cost_column must be 0 (total), 1 (obs) or 2 (smooth)!");
+}
+
+void Batch::set_run_params(const double * lambda, const double * epsilon, const double * obs_factor, const double * obs_factor_self)
+{
+   const double * arr[4] = { lambda, epsilon, obs_factor, obs_factor_self };
+   static const char * const name[4] = { "lambda", "epsilon", "obs_factor", "obs_factor_self" };
+   if (!lambda && !epsilon && !obs_factor && !obs_factor_self)
+   {
+      for (auto & s : shards) s->set_run_params(nullptr);
+      return;
+   }
+   const double shared[4] = { params.lambda, params.epsilon, params.obs_factor, params.obs_factor_self };
+   std::vector<double> table((size_t) n_runs * 4);
+   for (int c=0; c<4; c++)
+      for (int r=0; r<n_runs; r++)
+      {
+         const double v = arr[c] ? arr[c][r] : shared[c];
+         if (!std::isfinite(v)) throw std::runtime_error(std::string("set_run_params: ") + name[c] + " of run " + std::to_string(r) + " is not a finite number!");
+         // (the kernels form 1/lambda and 1/epsilon)
+         if (c < 2 && !(v > 0.0)) throw std::runtime_error(std::string("set_run_params: ") + name[c] + " of run " + std::to_string(r) + " must be > 0!");
+         table[(size_t) 4*r + c] = v;
+      }
+   // every shard takes its slice, as it took its slice of scene_of_run
+   for_shards([&](size_t k) { shards[k]->set_run_params(table.data() + (size_t) offs[k] * 4); }, true);
+}
+
+void Batch::get_run_params(double * out)
+{
+   for_shards([&](size_t k) { shards[k]->get_run_params(out + (size_t) offs[k] * 4); }, true);
+}
+
+void Batch::select_best(int n_groups, const std::vector<int> & group, bool collision_free, int column, int * best_run_out, double * best_cost_out, int * n_eligible_out)
 {
    const size_t S = shards.size();
    std::vector<unsigned long long> key(S * n_groups);
    std::vector<int> best(S * n_groups), count(S * n_groups);
    for_shards([&](size_t k) {
-      shards[k]->select_best(n_groups, group.data() + offs[k], collision_free,
+      shards[k]->select_best(n_groups, group.data() + offs[k], collision_free, column,
                              key.data() + k * n_groups, best.data() + k * n_groups, count.data() + k * n_groups);
    }, true);
    // the merge of n_shards x n_groups candidates: the lower cost, then the lower run (the shards hold ascending runs)

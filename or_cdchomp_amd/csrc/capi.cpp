@@ -571,6 +571,12 @@ int orc_batch_get_state(orc_module * mod, int id, const char * which, double * o
          std::copy(plan, plan + (cap < 9 ? 8 : 9), out);      // (the first tile's size: appended, read when there is room)
          return;
       }
+      if (std::string(which) == "run_params")
+      {
+         if (cap < (size_t) b.n_runs * 4) throw std::runtime_error("buffer too small!");
+         b.get_run_params(out);
+         return;
+      }
       if (cap < (size_t) b.n_runs * b.m * b.n) throw std::runtime_error("buffer too small!");
       b.get_state(which, out);
    });
@@ -609,8 +615,26 @@ int orc_batch_select_best(orc_module * mod, int id, int n_groups, const int * gr
       const std::vector<int> group = b.select_groups(n_groups, group_of_run);      // (the arguments first: the verdict below walks every trajectory)
       // the verdict's keys stay on the device, where the selection reads them
       if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-      b.select_best(n_groups, group, require_collision_free != 0, best_run_out, best_cost_out, n_eligible_out);
+      b.select_best(n_groups, group, require_collision_free != 0, 0, best_run_out, best_cost_out, n_eligible_out);
    });
+}
+
+int orc_batch_select_best_by(orc_module * mod, int id, int cost_column, int n_groups, const int * group_of_run, int require_collision_free,
+   int * best_run_out, double * best_cost_out, int * n_eligible_out)
+{
+   return guarded(mod, [&] {
+      orc::Batch & b = mod->impl->batch(id);
+      orc::Batch::select_column(cost_column);      // (the arguments first, as in orc_batch_select_best)
+      const std::vector<int> group = b.select_groups(n_groups, group_of_run);
+      if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      b.select_best(n_groups, group, require_collision_free != 0, cost_column, best_run_out, best_cost_out, n_eligible_out);
+   });
+}
+
+int orc_batch_set_run_params(orc_module * mod, int id, const double * lambda, const double * epsilon,
+   const double * obs_factor, const double * obs_factor_self)
+{
+   return guarded(mod, [&] { mod->impl->batch(id).set_run_params(lambda, epsilon, obs_factor, obs_factor_self); });
 }
 
 int orc_batch_gettraj_runs(orc_module * mod, int id, const int * runs, int n_sel, double * out, size_t cap)

@@ -1009,6 +1009,17 @@ __device__ __forceinline__ int run_scene(const BT & b)
    return (b.n_scenes > 1) ? uni(((const __attribute__((address_space(4))) int *) b.scene_of_run)[blockIdx.x]) : 0;
 }
 
+// the record of this workgroup's run's four parameters (wave-uniform; DevBatch::run_params): row blockIdx.x of the table when
+// the batch has one, the batch's own record in the kernarg block otherwise.  This select is the only place where the two differ
+template <typename real, typename BT>
+__device__ __forceinline__ const __attribute__((address_space(4))) RunParams<real> * run_params_of(const BT & b)
+{
+   typedef const __attribute__((address_space(4))) RunParams<real> * P;
+   const unsigned long long v = b.run_params ? (unsigned long long)(b.run_params + blockIdx.x) : (unsigned long long) &b.shared;
+   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned) v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+   return (P)(((unsigned long long) hi << 32) | lo);
+}
+
 // the LDS carve-up and the views derived from it (everything here is wave-uniform)
 template <typename real>
 struct Env
@@ -1083,6 +1094,7 @@ __device__ __forceinline__ Env<real> make_env(const BT & b, unsigned char * smem
    mod.empty_mask = b.ms.placed ? (unsigned int)(~(b.ms.live_mask | b.ms.static_mask) & 0xFFFFull) : 0u;
    mod.static_slot_c = (const __attribute__((address_space(4))) int *) b.model->static_slot;
    mod.static_pos_c = (const __attribute__((address_space(4))) real (*)[3]) b.model->static_pos;
+   mod.rp = run_params_of<real>(b);
    {
       // the run's scene: its index and field count by scalar loads (one scene: scene 0 with all the batch's fields)
       const int scene = run_scene(b);
@@ -1322,7 +1334,7 @@ __device__ __attribute__((noinline)) double phase_cost_start(const void * kp, in
    const bool do_iteration = uni(do_iteration_in) != 0;
    Env<real> E = make_env<real, GS16>(b, orc_smem);
    E.mod.live_mask |= b.ms.static_mask;
-   const real inv_eps = (real)1 / b.epsilon, inv_eps_self = (real)1 / b.epsilon_self;
+   const real inv_eps = (real)1 / E.mod.rp->epsilon, inv_eps_self = (real)1 / b.epsilon_self;
    if constexpr (GS16)
       cost_tile_gs16<real, GS16_U, BLOCK, KArg<real>, true>(b, E.mod, 0, 1, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s, E.r2_s,
                                                           E.slink_s, E.jtype_s, E.jcol_s, inv_eps, inv_eps_self, cost_lane);
@@ -1355,7 +1367,7 @@ __device__ __forceinline__ double phase_cost_body(const void * kp, int ts_in, in
    // the many-sphere path: bit 1 = a fixed base and the J^T ranges of a chain (1) or of a tree in depth-first order (2)
    if constexpr (!GS16 && (KIND & 1) != 0) { E.mod.floating = 0; E.mod.jt_scan = TREE ? 2 : 1; }
    E.mod.live_mask |= b.ms.static_mask;      // the static spheres' lanes take part in the row's pairs
-   const real inv_eps = (real)1 / b.epsilon, inv_eps_self = (real)1 / b.epsilon_self;
+   const real inv_eps = (real)1 / E.mod.rp->epsilon, inv_eps_self = (real)1 / b.epsilon_self;
    __builtin_amdgcn_s_setprio(PRIO_COST);
    if constexpr (GS16)
       cost_tile_gs16<real, GS16_U, BLOCK, KArg<real>, false, (KIND & 2) != 0, (KIND & 1) != 0, (KIND & 8) != 0>(b, E.mod, ts, te, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s, E.r2_s,
@@ -1474,7 +1486,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    // X = A^-1 G   (chomp.c:525-548)
    real * X = LEAN ? toeplitz_scan_solve<real, BLOCK>(b, G_s) : metric_solve<real, BLOCK>(b, pcr_tab, G_s, W_s);
    // T -= AG/lambda   (chomp.c:604-605)
-   const real step = (real)(-1) / b.lambda;
+   const real step = (real)(-1) / E.mod.rp->lambda;
    // the step also notes which columns left their limits (what the first scan of the
    // joint-limit loop would find, chomp.c:615-639): bit c of colmask_s
    unsigned long long viol = 0ull;
@@ -1486,7 +1498,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
          for (int e=tid; e<mn; e+=BLOCK) AG_g[e] = X[e];
       else
       {
-         const real sc = (leapfrog_first ? (real)0.5 : (real)1) / b.lambda;
+         const real sc = (leapfrog_first ? (real)0.5 : (real)1) / E.mod.rp->lambda;
          for (int e=tid; e<mn; e+=BLOCK) AG_s[e] = AG_s[e] + sc * X[e];
       }
       __threadfence_block();
@@ -1520,7 +1532,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    }
    else
    {
-      const real sc = (leapfrog_first ? (real)0.5 : (real)1) / b.lambda;
+      const real sc = (leapfrog_first ? (real)0.5 : (real)1) / E.mod.rp->lambda;
       // (the momentum rows likewise: read four entries ahead where they live in global memory)
       if (batched && !b.ag_in_lds)
       for (int e0=tid; e0<mn; e0+=UPDATE_BATCH*BLOCK)

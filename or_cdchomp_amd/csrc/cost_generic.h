@@ -80,7 +80,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
       const real vnorm = sqrt_rsq(vn2, &inv_vn);
       const real inv_vn2 = inv_vn * inv_vn;                  // only used when vnorm > 1e-6
       const bool moving = vnorm > (real)0.000001;
-      const real wself = vnorm * b.obs_factor_self;
+      const real wself = vnorm * mod.rp->obs_factor_self;
 
       // ---- obstacle term (src/orcdchomp_mod.cpp:1171-1246), in two halves: the cell reads of the fields are issued
       // here and used AFTER the self-collision term, whose range tests (matrix cores) and pair forces do not depend on
@@ -192,7 +192,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
             has = has || better;
             // the gradient only counts within epsilon of the surface (scale == 0 beyond it, below): a field
             // that is the nearest of no sphere of the wavefront inside that range is not rotated back
-            if (__builtin_amdgcn_ballot_w64(better && (val - radius < b.epsilon)) == 0ull) continue;
+            if (__builtin_amdgcn_ballot_w64(better && (val - radius < mod.rp->epsilon)) == 0ull) continue;
 #pragma unroll
             for (int k=0; k<3; k++)
             {
@@ -386,14 +386,14 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
       {
          const bool on = live && has;
          const real dist = best - radius;
-         const real de = dist - b.epsilon;
-         real cs = (dist < (real)0) ? ((real)0.5 * b.epsilon - dist)
-                 : ((dist < b.epsilon) ? ((real)0.5 * inv_eps) * de * de : (real)0);
-         cs *= vnorm * b.obs_factor;
+         const real de = dist - mod.rp->epsilon;
+         real cs = (dist < (real)0) ? ((real)0.5 * mod.rp->epsilon - dist)
+                 : ((dist < mod.rp->epsilon) ? ((real)0.5 * inv_eps) * de * de : (real)0);
+         cs *= vnorm * mod.rp->obs_factor;
          cs = on ? cs : (real)0;
          cost_sphere += (double) cs;
-         const real scale = (dist < (real)0) ? (real)(-1) : ((dist < b.epsilon) ? dist * inv_eps - (real)1 : (real)0);
-         const real sc2 = scale * (vnorm * b.obs_factor);
+         const real scale = (dist < (real)0) ? (real)(-1) : ((dist < mod.rp->epsilon) ? dist * inv_eps - (real)1 : (real)0);
+         const real sc2 = scale * (vnorm * mod.rp->obs_factor);
          real xg[3], xc[3];
 #pragma unroll
          for (int k=0; k<3; k++) { xg[k] = (scale == (real)0) ? (real)0 : bgrad[k] * sc2; xc[k] = acc[k]; }

@@ -318,12 +318,12 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
          vnorm[u] = sqrt_rsq(vn2, &inv_vn);
          inv_vn2[u] = inv_vn * inv_vn;           // only used when vnorm > 1e-6
          moving[u] = vnorm[u] > (real)0.000001;
-         wself[u] = vnorm[u] * b.obs_factor_self;
+         wself[u] = vnorm[u] * mod.rp->obs_factor_self;
          cost_sphere[u] = 0.0;
          // u = v sqrt(w/|v|^2) = v sqrt(obs_factor_self/|v|): (d.u) u = w (d.v) v/|v|^2, the projection
          // term of the self-collision forces (src/orcdchomp_mod.cpp:1299-1303); zero at rest
          real sinv;
-         const real su = sqrt_rsq(moving[u] ? b.obs_factor_self * inv_vn : (real)0, &sinv);
+         const real su = sqrt_rsq(moving[u] ? mod.rp->obs_factor_self * inv_vn : (real)0, &sinv);
 #pragma unroll
          for (int k=0; k<3; k++) uvec[u][k] = vel[u][k] * su;
       }
@@ -378,14 +378,14 @@ __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<rea
       {
          const bool on = live[u] && has[u];
          const real dist = best[u] - radius;
-         const real de = dist - b.epsilon;
-         real cs = (dist < (real)0) ? ((real)0.5 * b.epsilon - dist)
-                 : ((dist < b.epsilon) ? ((real)0.5 * inv_eps) * de * de : (real)0);
-         cs *= vnorm[u] * b.obs_factor;
+         const real de = dist - mod.rp->epsilon;
+         real cs = (dist < (real)0) ? ((real)0.5 * mod.rp->epsilon - dist)
+                 : ((dist < mod.rp->epsilon) ? ((real)0.5 * inv_eps) * de * de : (real)0);
+         cs *= vnorm[u] * mod.rp->obs_factor;
          cs = on ? cs : (real)0;
          cost_sphere[u] += (double) cs;
-         const real scale = (dist < (real)0) ? (real)(-1) : ((dist < b.epsilon) ? dist * inv_eps - (real)1 : (real)0);
-         const real sc2 = scale * (vnorm[u] * b.obs_factor);
+         const real scale = (dist < (real)0) ? (real)(-1) : ((dist < mod.rp->epsilon) ? dist * inv_eps - (real)1 : (real)0);
+         const real sc2 = scale * (vnorm[u] * mod.rp->obs_factor);
          real xg[3], xc[3];
 #pragma unroll
          // (the best field's gradient is finite -- a poisoned value never wins -- and zero without a field, so scale == 0 gives

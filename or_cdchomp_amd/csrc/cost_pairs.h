@@ -114,11 +114,11 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
       const bool moving = vnorm > (real)0.000001;
       // what the pair lanes fetch: w = |v| obs_factor_self and u = v sqrt(w/|v|^2) (zero at rest: a sphere that stands still -- an
       // inactive one on a free lane has the same centre in every row -- adds nothing of its own to a pair)
-      const real wself = vnorm * b.obs_factor_self;
+      const real wself = vnorm * mod.rp->obs_factor_self;
       real uvec[3];
       {
          real sinv;
-         const real su = sqrt_rsq(moving ? b.obs_factor_self * inv_vn : (real)0, &sinv);
+         const real su = sqrt_rsq(moving ? mod.rp->obs_factor_self * inv_vn : (real)0, &sinv);
 #pragma unroll
          for (int k=0; k<3; k++) uvec[k] = vel[k] * su;
       }
@@ -158,14 +158,14 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
 #endif
          const bool on = lane_ok && has;
          const real dist = best - radius;
-         const real de = dist - b.epsilon;
-         real cs = (dist < (real)0) ? ((real)0.5 * b.epsilon - dist)
-                 : ((dist < b.epsilon) ? ((real)0.5 * inv_eps) * de * de : (real)0);
-         cs *= vnorm * b.obs_factor;
+         const real de = dist - mod.rp->epsilon;
+         real cs = (dist < (real)0) ? ((real)0.5 * mod.rp->epsilon - dist)
+                 : ((dist < mod.rp->epsilon) ? ((real)0.5 * inv_eps) * de * de : (real)0);
+         cs *= vnorm * mod.rp->obs_factor;
          cs = on ? cs : (real)0;
          cost_sphere += (double) cs;
-         const real scale = (dist < (real)0) ? (real)(-1) : ((dist < b.epsilon) ? dist * inv_eps - (real)1 : (real)0);
-         const real sc2 = scale * (vnorm * b.obs_factor);
+         const real scale = (dist < (real)0) ? (real)(-1) : ((dist < mod.rp->epsilon) ? dist * inv_eps - (real)1 : (real)0);
+         const real sc2 = scale * (vnorm * mod.rp->obs_factor);
          real xg[3], xc[3];
          // (the best field's gradient is finite -- a poisoned value never wins -- and zero without a field, so scale == 0 gives
          // an exact zero without a select; the guard of the two projections is one select of their common factor)

@@ -209,6 +209,14 @@ struct LdsLayout
    int total_bytes;
 };
 
+// The four step and cost parameters a run may have to itself (orc_batch_set_run_params): one record per run, read with one
+// aligned scalar load (32 bytes in fp64, 16 in fp32).  DevBatch::shared is the batch's own record in the kernarg block.
+template <typename real>
+struct RunParams
+{
+   real lambda, epsilon, obs_factor, obs_factor_self;
+};
+
 template <typename real>
 struct DevBatch
 {
@@ -239,8 +247,13 @@ struct DevBatch
    int * iters_done;       // [n_runs] iterations this launch completed (n_iter unless the run aborted or converged)
    int * leapfrog_first;   // [n_runs]
    // run parameters
-   real dt, inv_2dt, inv_dt2, lambda, inv_m;
-   real epsilon, epsilon_self, obs_factor, obs_factor_self;
+   real dt, inv_2dt, inv_dt2, inv_m;
+   real epsilon_self;      // (not per run: it feeds the fold, and the fold decides the plan)
+   // lambda, epsilon, obs_factor, obs_factor_self: `shared` holds the values the batch was created with; run_params, when set, is
+   // [n_runs] records of this shard's runs (orc_batch_set_run_params).  The phase functions pick the run's record ONCE
+   // (run_params_of in chomp_kernel.hip, next to make_env) and read the four values through it: one code path either way
+   RunParams<real> shared;
+   const RunParams<real> * run_params;
    int use_momentum, use_hmc, D;      // D: the derivative; -1: derivative 1 without a start boundary (tridiagonal, not Toeplitz: none of the kernels' short forms for D == 1 apply)
    // metric: band of A, endpoint couplings of B and trC
    const real * Aband;     // [2D+1][m]
@@ -365,6 +378,7 @@ struct ModelView
    const __attribute__((address_space(4))) DevFkJoint<real> * fkj;     // DevModel::fkj (scalar loads: one record per joint)
    const __attribute__((address_space(4))) int * static_slot_c;         // DevModel::static_slot / static_pos (FK writes them into every row)
    const __attribute__((address_space(4))) real (* static_pos_c)[3];
+   const __attribute__((address_space(4))) RunParams<real> * rp;      // the run's lambda, epsilon, obs_factor, obs_factor_self (make_env; scalar loads)
    // the run's scene (make_env): its field count and its slice of DevBatch::sdfc (scalar loads)
    int n_sdfs;
    const __attribute__((address_space(4))) DevSdfCell<real> * sdfc;

@@ -110,7 +110,13 @@ public:
    // per group the lowest cost key among this shard's eligible runs, the lowest LOCAL run that has it, the eligible runs;
    // group [n_runs] is this shard's slice; collision_free: a run whose key of the last collision_verdict_planned (kept on
    // the device) names a contact is not eligible
-   void select_best(int n_groups, const int * group, bool collision_free, unsigned long long * key_out, int * best_out, int * count_out);
+   // column: which of costs[run][0..2] is minimised (eligibility always asks for a finite TOTAL cost)
+   void select_best(int n_groups, const int * group, bool collision_free, int column, unsigned long long * key_out, int * best_out, int * count_out);
+   // per-run lambda, epsilon, obs_factor, obs_factor_self of this shard's runs (orc_batch_set_run_params): table [n_runs][4] doubles,
+   // validated by Batch::set_run_params, converted to the batch's precision here and uploaded on the shard's stream (so that launches
+   // enqueued before keep the old values); NULL: the later launches read no table
+   void set_run_params(const double * table);
+   void get_run_params(double * out);       // [n_runs][4]: what the device holds, or the shared values when there is no table
    // rows[k] (local runs) of the trajectory array as doubles: out [rows.size()][n_points][n]
    void gettraj_rows(const std::vector<int> & rows, double * out);
    const Metric & metric() const { return metric_; }
@@ -174,6 +180,7 @@ private:
    DevBuf d_costs_, d_trace_; size_t trace_cap_ = 0;
    DevBuf d_conv_prev_, d_conv_streak_;      // [n_runs] the convergence stop's state between the launches of a call
    DevBuf d_status_, d_iters_done_, d_leap_, d_phase_;
+   DevBuf d_run_params_; bool run_params_on_ = false;      // [n_runs] RunParams<real>; kept allocated while off (launches in flight may read it)
    DevBuf d_vkey_;                           // [n_runs] the keys of the last collision_verdict_planned
    DevBuf d_Aband_, d_beta_s_, d_beta_g_, d_metric64_, d_pcr_, d_Ainv_, d_jl_lo_, d_jl_hi_;
    // TSR hard constraints (csrc/tsr.h): the device copies of the constraints, the per-run workspace
@@ -220,7 +227,13 @@ public:
    void perturb(double sigma, const unsigned int * seeds);
    std::vector<int> select_groups(int n_groups, const int * group_of_run) const;   // the validated group of every run (NULL: contiguous equal blocks); throws
    // collision_free: the runs' keys of the collision_verdict_planned made just before (they never left the device)
-   void select_best(int n_groups, const std::vector<int> & group, bool collision_free, int * best_run_out, double * best_cost_out, int * n_eligible_out);
+   // column 0 total, 1 obs, 2 smooth: the cost that is minimised and reported (validate with select_column first)
+   void select_best(int n_groups, const std::vector<int> & group, bool collision_free, int column, int * best_run_out, double * best_cost_out, int * n_eligible_out);
+   static void select_column(int column);   // throws unless 0, 1 or 2
+   // per-run parameters: each array [n_runs] or NULL (the value of `params`); all NULL switches the table off.  Throws and changes
+   // nothing on a NaN or infinite entry or a lambda or epsilon <= 0
+   void set_run_params(const double * lambda, const double * epsilon, const double * obs_factor, const double * obs_factor_self);
+   void get_run_params(double * out);       // [n_runs][4]
    void gettraj_runs(const int * runs, int n_sel, double * out);
    bool iterated = false;            // an iterate call has been made: the device's costs and status are a call's results
    void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,

@@ -107,22 +107,23 @@ __device__ __forceinline__ bool run_eligible(const double * costs, const int * s
    return (st == 0 || st == 1) && isfinite(c) && !(verdict_key && verdict_key[r] != ORC_VERDICT_NONE);
 }
 
+// column: which of a run's costs (0 total, 1 obs, 2 smooth) is the key that is minimised; eligibility does not depend on it
 // pass 1: the lowest cost key of every group's eligible runs and their number
-__global__ void select_cost_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs,
+__global__ void select_cost_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
    unsigned long long * key, int * count)
 {
    const int r = blockIdx.x * blockDim.x + threadIdx.x;
    if (r >= n_runs || !run_eligible(costs, status, verdict_key, r)) return;
-   atomicMin(&key[group[r]], cost_key(costs[(size_t) r*3]));
+   atomicMin(&key[group[r]], cost_key(costs[(size_t) r*3 + column]));
    atomicAdd(&count[group[r]], 1);
 }
 // pass 2: the lowest index among the runs that have it
-__global__ void select_run_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs,
+__global__ void select_run_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
    const unsigned long long * key, int * best)
 {
    const int r = blockIdx.x * blockDim.x + threadIdx.x;
    if (r >= n_runs || !run_eligible(costs, status, verdict_key, r)) return;
-   if (cost_key(costs[(size_t) r*3]) == key[group[r]]) atomicMin(&best[group[r]], r);
+   if (cost_key(costs[(size_t) r*3 + column]) == key[group[r]]) atomicMin(&best[group[r]], r);
 }
 
 // ---- rows of the trajectory array, as doubles -----------------------------------------------------------------------
@@ -167,12 +168,12 @@ hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n,
    return launch_perturb<float>(traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, stream);
 }
 // key [n_groups] (all bits set), count [n_groups] (0) and best [n_groups] (INT_MAX) are the caller's to initialise
-hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs,
+hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
    unsigned long long * key, int * count, int * best, hipStream_t stream)
 {
    const dim3 grid((n_runs + 255) / 256), block(256);
-   hipLaunchKernelGGL(select_cost_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, key, count);
-   hipLaunchKernelGGL(select_run_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, key, best);
+   hipLaunchKernelGGL(select_cost_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, column, key, count);
+   hipLaunchKernelGGL(select_run_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, column, key, best);
    return hipGetLastError();
 }
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream)

@@ -1204,7 +1204,7 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp)
    real * aws = Mws + (size_t) K * K + (size_t) m * n * (n + 1);      // [nj][6][NB]: the joints' world axes and anchors of every block (behind the structured solve's rows)
    const real * AG = b.use_momentum ? E.AG_s : E.AG_g;
    const real * T_s = E.T_s;
-   const real inv_lambda = (real)(-1) / b.lambda;
+   const real inv_lambda = (real)(-1) / E.mod.rp->lambda;
 
 #ifdef ORC_TSR_TIMERS
    long long tmk[6]; tmk[0] = clock64();

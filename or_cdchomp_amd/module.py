@@ -176,15 +176,22 @@ def verdict_samples(traj, vmax, col0=0):
     return np.asarray(seg_out, dtype=np.int32), np.asarray(u_out, dtype=np.float64), np.asarray(time_out, dtype=np.float64)
 
 
-def select_best(costs, status, collides, group_of_run, n_groups):
-    """The rule of orc_batch_select_best.  costs [n_runs] total costs (or [n_runs][3] rows as batch_iterate returns them),
-    status [n_runs], collides [n_runs] (None: the collision verdict is not asked for), group_of_run [n_runs] with entries
-    in [0, n_groups).  A run is eligible when its status is 0 or 1, its cost is finite and it does not collide; per group
-    the eligible run of lowest cost wins, a tie goes to the lowest run index.  Returns (best_run int32 [n_groups], -1 for a
-    group without an eligible run; best_cost [n_groups], +inf there; n_eligible int32 [n_groups]).  Pure numpy."""
+def select_best(costs, status, collides, group_of_run, n_groups, column=0):
+    """The rule of orc_batch_select_best and, with column 1 (obs) or 2 (smooth), of orc_batch_select_best_by.  costs [n_runs]
+    total costs (or [n_runs][3] rows as batch_iterate returns them: needed for a column other than 0), status [n_runs],
+    collides [n_runs] (None: the collision verdict is not asked for), group_of_run [n_runs] with entries in [0, n_groups).
+    A run is eligible when its status is 0 or 1, its TOTAL cost is finite and it does not collide, whatever the column; per
+    group the eligible run of lowest costs[run][column] wins, a tie goes to the lowest run index.  Returns (best_run int32
+    [n_groups], -1 for a group without an eligible run; best_cost [n_groups], that column's value, +inf there; n_eligible
+    int32 [n_groups]).  Pure numpy."""
     costs = np.asarray(costs, dtype=np.float64)
+    if column not in (0, 1, 2):
+        raise ValueError("column is 0 (total), 1 (obs) or 2 (smooth)")
+    total = costs[:, 0] if costs.ndim == 2 else costs
     if costs.ndim == 2:
-        costs = costs[:, 0]
+        costs = costs[:, column]
+    elif column != 0:
+        raise ValueError("a column other than 0 needs the [n_runs][3] cost rows")
     status = np.asarray(status).reshape(-1)
     group = np.asarray(group_of_run).reshape(-1)
     n_runs = costs.shape[0]
@@ -192,7 +199,7 @@ def select_best(costs, status, collides, group_of_run, n_groups):
         raise ValueError("costs, status and group_of_run have one entry per run")
     if n_groups < 1 or (n_runs and (group.min() < 0 or group.max() >= n_groups)):
         raise ValueError("group_of_run entries must lie in [0, n_groups)")
-    ok = ((status == 0) | (status == 1)) & np.isfinite(costs)
+    ok = ((status == 0) | (status == 1)) & np.isfinite(total)
     if collides is not None:
         ok &= np.asarray(collides).reshape(-1) == 0
     best_run = np.full(n_groups, -1, dtype=np.int32)
@@ -207,6 +214,45 @@ def select_best(costs, status, collides, group_of_run, n_groups):
             best_run[g] = r
             best_cost[g] = costs[r]
     return best_run, best_cost, n_eligible
+
+
+RUN_PARAMS = ("lambda", "epsilon", "obs_factor", "obs_factor_self")      # the columns of the "run_params" read-back
+
+
+def run_params_table(shared, n_runs, precision, lambda_=None, epsilon=None, obs_factor=None, obs_factor_self=None):
+    """What orc_batch_get_state "run_params" returns after orc_batch_set_run_params with these arguments: [n_runs][4]
+    doubles in the order of RUN_PARAMS.  shared: the batch's own four values (a dict with RUN_PARAMS' keys -- "lambda_" is
+    accepted for "lambda" -- or a sequence in that order); each argument a scalar (every run), an array [n_runs], or None
+    (the shared value); precision 32 rounds every entry to float, as the device holds it.  Raises ValueError where the call
+    is rejected: a NaN or infinite entry, a lambda or epsilon <= 0 (the shared values are checked too when they are used:
+    the call validates the table it would install), an array of another length.  Pure numpy."""
+    if isinstance(shared, dict):
+        shared = [shared["lambda_"] if (k == "lambda" and "lambda_" in shared) else shared[k] for k in RUN_PARAMS]
+    shared = [float(x) for x in shared]
+    if len(shared) != 4:
+        raise ValueError("shared holds lambda, epsilon, obs_factor, obs_factor_self")
+    if precision not in (32, 64):
+        raise ValueError("precision is 32 or 64")
+    n_runs = int(n_runs)
+    out = np.zeros((n_runs, 4))
+    for c, v in enumerate((lambda_, epsilon, obs_factor, obs_factor_self)):
+        if v is None:
+            col = np.full(n_runs, shared[c])
+        else:
+            col = np.asarray(v, dtype=np.float64)
+            if col.ndim == 0:
+                col = np.full(n_runs, float(col))
+            col = col.reshape(-1)
+            if col.size != n_runs:
+                raise ValueError("%s has %d entries for %d runs" % (RUN_PARAMS[c], col.size, n_runs))
+        if not np.isfinite(col).all():
+            raise ValueError("%s has an entry that is not a finite number" % RUN_PARAMS[c])
+        if c < 2 and not (col > 0.0).all():
+            raise ValueError("%s entries must be > 0" % RUN_PARAMS[c])
+        out[:, c] = col
+    if precision == 32:
+        out = out.astype(np.float32).astype(np.float64)
+    return out
 
 
 def contiguous_groups(n_runs, n_groups):
@@ -506,11 +552,32 @@ class Module:
             raise ValueError("seeds has %d entries for %d runs" % (sd.size, n_runs))
         self._check(self._lib.orc_batch_perturb(self._h, bid, float(sigma), sd.ctypes.data_as(_capi.c_uint_p)))
 
-    def batch_select_best(self, bid, groups=None, n_groups=None, collision_free=True):
+    def batch_set_run_params(self, bid, lambda_=None, epsilon=None, obs_factor=None, obs_factor_self=None):
+        """lambda, epsilon, obs_factor and obs_factor_self per run for the batch's later iterate calls
+        (orc_batch_set_run_params; the table is run_params_table's).  Each argument: an array [n_runs], a scalar (every
+        run), or None (the value the batch was created with).  The call replaces the whole table; all four None switches
+        it off."""
+        n_runs = self.batch_dims(bid)[0]
+        arrs = []
+        for name, v in zip(RUN_PARAMS, (lambda_, epsilon, obs_factor, obs_factor_self)):
+            if v is None:
+                arrs.append(None)
+                continue
+            a = np.asarray(v, dtype=np.float64)
+            a = np.full(n_runs, float(a)) if a.ndim == 0 else np.ascontiguousarray(a.reshape(-1))
+            if a.size != n_runs:
+                raise ValueError("%s has %d entries for %d runs" % (name, a.size, n_runs))
+            arrs.append(a)
+        self._check(self._lib.orc_batch_set_run_params(self._h, bid, *[None if a is None else _dp(a) for a in arrs]))
+
+    def batch_select_best(self, bid, groups=None, n_groups=None, collision_free=True, by="total"):
         """The best run of every group after an iterate call, reduced on the device (orc_batch_select_best; the rule is
-        select_best's).  groups: group_of_run [n_runs] (n_groups defaults to its maximum + 1), or None for n_groups
+        select_best's).  by: the cost that is minimised and returned, "total" (the default), "obs" or "smooth"
+        (orc_batch_select_best_by: the one that compares across runs of different obs_factor is "smooth").  groups: group_of_run [n_runs] (n_groups defaults to its maximum + 1), or None for n_groups
         contiguous equal blocks (one group when n_groups is None too).  Returns (best_run int32 [n_groups], -1 for a
         group without an eligible run; best_cost [n_groups], +inf there; n_eligible int32 [n_groups])."""
+        if by not in ("total", "obs", "smooth"):
+            raise ValueError('by is "total", "obs" or "smooth"')
         n_runs = self.batch_dims(bid)[0]
         gp = None
         if groups is not None:
@@ -524,8 +591,13 @@ class Module:
         n_groups = int(n_groups)
         size = max(n_groups, 1)
         best = np.zeros(size, dtype=np.int32); cost = np.zeros(size); cnt = np.zeros(size, dtype=np.int32)
-        self._check(self._lib.orc_batch_select_best(self._h, bid, n_groups, None if gp is None else _ip(gp),
-                                                    1 if collision_free else 0, _ip(best), _dp(cost), _ip(cnt)))
+        if by == "total":
+            self._check(self._lib.orc_batch_select_best(self._h, bid, n_groups, None if gp is None else _ip(gp),
+                                                        1 if collision_free else 0, _ip(best), _dp(cost), _ip(cnt)))
+        else:
+            self._check(self._lib.orc_batch_select_best_by(self._h, bid, ("total", "obs", "smooth").index(by), n_groups,
+                                                           None if gp is None else _ip(gp), 1 if collision_free else 0,
+                                                           _ip(best), _dp(cost), _ip(cnt)))
         return best[:n_groups], cost[:n_groups], cnt[:n_groups]
 
     def batch_gettraj_runs(self, bid, runs):
@@ -563,8 +635,10 @@ class Module:
         return {k: int(v) for k, v in zip(keys, out)}
 
     def batch_state(self, bid, which):
+        """"G", "AG", "T": [n_runs][m][n]; "run_params": [n_runs][4] lambda, epsilon, obs_factor, obs_factor_self as the
+        device holds them (run_params_table)"""
         n_runs, n_points, n = self.batch_dims(bid)
-        out = np.zeros((n_runs, n_points - 2, n))
+        out = np.zeros((n_runs, 4)) if which == "run_params" else np.zeros((n_runs, n_points - 2, n))
         self._check(self._lib.orc_batch_get_state(self._h, bid, which.encode(), _dp(out), out.size))
         return out
 
