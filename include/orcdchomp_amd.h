@@ -327,7 +327,11 @@ int orc_batch_collision_verdict(orc_module * mod, int batch_id, int * collides_o
 int orc_batch_collision_verdict_device(orc_module * mod, int batch_id, int * collides_out, double * time_out,
                                        int * sphere_out, int * field_out, double * depth_out, int * n_samples_out);
 /* optimizer state read-back for tests: which = "G", "AG", "T" ([n_runs][m][n]); "phase" ([n_runs][8] cycle counters with
- * ORC_PHASE_TIMERS=1); "plan" (8 numbers: kernel variant bits -- 512 = the dense pair-list family, 1 = a tree --, threads per
+ * ORC_PHASE_TIMERS=1); "waves" ([n_runs][8][2], with ORC_PHASE_TIMERS=1: the hardware-ID register and the XCC-ID register of
+ * every wavefront of the run's workgroup as read at the start of the last launch, 4294967295 for a wavefront the workgroup does
+ * not have; HW_ID holds the wave slot in bits 0-3, the SIMD in 4-5, the CU in 8-11, the shader array in 12, the shader engine
+ * in 13-15; the second number holds the XCC in bits 0-3 and, in bits 8.., the logical wavefront the hardware wavefront is in
+ * the launch's last iteration, ORC_WAVE_ROTATE); "plan" (8 numbers: kernel variant bits -- 512 = the dense pair-list family, 1 = a tree --, threads per
  * workgroup, LDS bytes per workgroup, tile, solve mode (2 closed-form scans, 3 band-inverse generators, 1 dense), workgroups
  * per CU, tiles, lanes per waypoint; a ninth, the moving waypoints of the first tile, when cap_doubles >= 9);
  * "run_params" ([n_runs][4]: lambda, epsilon, obs_factor, obs_factor_self as the device holds them, orc_batch_set_run_params) */

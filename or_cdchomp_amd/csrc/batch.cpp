@@ -77,6 +77,7 @@ void BatchShard::construct(const Robot & robot, const double * starts, const dou
    const unsigned int * seeds)
 {
    sw_ = Switches::read();
+   if (sw_.wave_rotate < 0 || sw_.wave_rotate > orc::WAVE_ROTATE_MAX) throw std::runtime_error("ORC_WAVE_ROTATE must be 0, 1 or 2!");
    const BatchParams & p = params;
    if (p.precision != 64 && p.precision != 32) throw std::runtime_error("precision must be 32 or 64!");
    const int n_adof = (int) robot.active_dofs.size();
@@ -151,7 +152,12 @@ void BatchShard::seed_runs(const Robot & robot, const double * starts, const dou
    std::vector<int> ones(n_runs, 1);                              // leapfrog_first = 1, chomp.c:80
    hip_check(hipMemcpyAsync(d_leap_.as<void>(), ones.data(), n_runs*sizeof(int), hipMemcpyHostToDevice, st), "leap");
    hip_check(hipStreamSynchronize(st), "sync");
-   if (sw_.phase_timers) d_phase_.reset(dev_alloc<long long>((size_t) n_runs * 8));
+   if (sw_.phase_timers)
+   {
+      d_phase_.reset(dev_alloc<long long>((size_t) n_runs * 8));
+      d_hwid_.reset(dev_alloc<unsigned int>((size_t) n_runs * 16));
+      hip_check(hipMemset(d_hwid_.as<void>(), 0xff, (size_t) n_runs * 16 * sizeof(unsigned int)), "memset");      // (all ones: a wavefront the workgroup does not have)
+   }
 }
 
 // hmc state (mod.cpp:2303-2304, 2634-2635)
@@ -603,10 +609,9 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    b.dt = (real) dt;
    b.inv_2dt = (real)(1.0/(2.0*dt));
    b.inv_dt2 = (real)(1.0/(dt*dt));
-   b.shared.lambda = (real) params.lambda;
    b.inv_m = (real)(1.0/m);
-   b.shared.epsilon = (real) params.epsilon; b.epsilon_self = (real) params.epsilon_self;
-   b.shared.obs_factor = (real) params.obs_factor; b.shared.obs_factor_self = (real) params.obs_factor_self;
+   b.shared = run_params_record<real>(params.lambda, params.epsilon, params.obs_factor, params.obs_factor_self);
+   b.epsilon_self = (real) params.epsilon_self; b.inv_epsilon_self = (real)1 / b.epsilon_self;
    b.run_params = run_params_on_ ? d_run_params_.as<const RunParams<real>>() : nullptr;
    b.use_momentum = params.use_momentum; b.use_hmc = params.use_hmc && max_resamples_ > 0;
    b.D = (params.derivative == 1 && params.free_start) ? -1 : params.derivative;
@@ -619,13 +624,15 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    b.ss_rank = (met_.solve_mode == 3) ? metric_.ss_rank : 0;
    b.jl_lo = d_jl_lo_.as<const real>(); b.jl_hi = d_jl_hi_.as<const real>();
    b.hmc_iters = d_hmc_iters_; b.noise = (const real *) d_noise_; b.max_resamples = max_resamples_;
+   if (m >= (1 << ORC_IT_SHIFT) || max_resamples_ >= (1 << ORC_IT_SHIFT)) throw std::runtime_error("too many waypoints or resamples for the phase arguments!");
    b.n_iter = n_iter; b.final_eval = final_eval ? 1 : 0; b.carry_status = carry ? 1 : 0;
    b.conv_patience = conv.patience > 0 ? conv.patience : 0;
    b.conv_rtol = conv.rtol; b.conv_obs_max = conv.obs_max;
    b.conv_prev = d_conv_prev_.as<double>(); b.conv_streak = d_conv_streak_.as<int>();      // (a launch that starts a call does not read them)
-   b.phase_cycles = d_phase_.as<long long>();
+   b.phase_cycles = d_phase_.as<long long>(); b.wave_hwid = d_hwid_.as<unsigned int>();
    b.pcr_in_lds = P.pcr_in_lds; b.pcr_sym = met_.pcr_sym; b.pcr_rows = met_.pcr_rows; b.ag_in_lds = P.ag_in_lds;
    b.stagger_mode = sw_.stagger_mode; b.stagger_sleeps = sw_.stagger_sleeps; b.lim_generic = sw_.lim_generic;
+   b.wave_rotate = sw_.wave_rotate;
    b.band_toeplitz = met_.band_toeplitz;
    for (int k=0; k<=ORC_SS_MAX_RANK; k++) { b.band_c64[k] = met_.band_c64[k]; b.band_c[k] = (real) met_.band_c64[k]; }
    if (params.derivative == 1 && m >= 2)
@@ -761,6 +768,13 @@ void BatchShard::get_phase_cycles(long long * out)
    hip_check(hipMemcpy(out, d_phase_.as<void>(), (size_t) n_runs*8*sizeof(long long), hipMemcpyDeviceToHost), "phase");
 }
 
+void BatchShard::get_wave_hwid(unsigned int * out)
+{
+   DeviceGuard guard(device);
+   if (!d_hwid_) throw std::runtime_error("wave placement is recorded with the phase timers (set ORC_PHASE_TIMERS=1 before create)");
+   hip_check(hipMemcpy(out, d_hwid_.as<void>(), (size_t) n_runs*16*sizeof(unsigned int), hipMemcpyDeviceToHost), "waves");
+}
+
 void BatchShard::set_traj(const double * traj)
 {
    DeviceGuard guard(device);
@@ -833,11 +847,7 @@ void upload_run_params(const double * table, int n_runs, void * d, hipStream_t s
 {
    // the conversion `launch` makes of the shared values: (real) of the caller's double, once
    std::vector<RunParams<real>> rec(n_runs);
-   for (int k=0; k<n_runs; k++)
-   {
-      rec[k].lambda = (real) table[4*k]; rec[k].epsilon = (real) table[4*k + 1];
-      rec[k].obs_factor = (real) table[4*k + 2]; rec[k].obs_factor_self = (real) table[4*k + 3];
-   }
+   for (int k=0; k<n_runs; k++) rec[k] = run_params_record<real>(table[4*k], table[4*k + 1], table[4*k + 2], table[4*k + 3]);
    hip_check(hipMemcpyAsync(d, rec.data(), rec.size()*sizeof(RunParams<real>), hipMemcpyHostToDevice, st), "run params");
    hip_check(hipStreamSynchronize(st), "run params sync");
 }
@@ -861,7 +871,12 @@ void BatchShard::get_run_params(double * out)
    if (run_params_on_)
    {
       DeviceGuard guard(device);
-      download(d_run_params_.as<void>(), (size_t) n_runs * 4, params.precision, out, stream_);
+      // (a record is eight reals: the four parameters, 1/epsilon, padding)
+      constexpr size_t W = sizeof(RunParams<double>) / sizeof(double);
+      static_assert(W == sizeof(RunParams<float>) / sizeof(float), "RunParams");
+      std::vector<double> rec((size_t) n_runs * W);
+      download(d_run_params_.as<void>(), rec.size(), params.precision, rec.data(), stream_);
+      for (int k=0; k<n_runs; k++) std::copy(rec.begin() + k*W, rec.begin() + k*W + 4, out + (size_t) 4*k);
       return;
    }
    const double shared[4] = { params.lambda, params.epsilon, params.obs_factor, params.obs_factor_self };
@@ -1175,6 +1190,11 @@ void Batch::gettraj_runs(const int * runs, int n_sel, double * out)
 void Batch::get_phase_cycles(long long * out)
 {
    for (size_t k=0; k<shards.size(); k++) shards[k]->get_phase_cycles(out + (size_t) offs[k] * 8);
+}
+
+void Batch::get_wave_hwid(unsigned int * out)
+{
+   for (size_t k=0; k<shards.size(); k++) shards[k]->get_wave_hwid(out + (size_t) offs[k] * 16);
 }
 
 void Batch::collision_verdict(const std::vector<int> & soffs, const std::vector<int> & seg, const std::vector<double> & u,

@@ -563,6 +563,14 @@ int orc_batch_get_state(orc_module * mod, int id, const char * which, double * o
          for (size_t i=0; i<tmp.size(); i++) out[i] = (double) tmp[i];
          return;
       }
+      if (std::string(which) == "waves")
+      {
+         if (cap < (size_t) b.n_runs * 16) throw std::runtime_error("buffer too small!");
+         std::vector<unsigned int> tmp((size_t) b.n_runs * 16);
+         b.get_wave_hwid(tmp.data());
+         for (size_t i=0; i<tmp.size(); i++) out[i] = (double) tmp[i];
+         return;
+      }
       if (std::string(which) == "plan")
       {
          if (cap < 8) throw std::runtime_error("buffer too small!");

@@ -30,6 +30,7 @@
 #include "dev_types.h"
 #include "kernel_table.h"
 #include "launch.h"
+#include "wave_roles.h"
 
 // the device arithmetic may fuse a*b+c (the host files are built with -ffp-contract=off so that
 // the SDF build stays bit-identical to the reference; the kernels are held to a tolerance)
@@ -188,11 +189,11 @@ __device__ __forceinline__ double sum_partials(const double * r)
 }
 // sum over the whole workgroup; every thread receives the result.
 template <int BLOCK>
-__device__ __forceinline__ double block_sum(double v, double * red)
+__device__ __forceinline__ double block_sum(double v, double * red, int tid)
 {
    v = wave_sum(v);
    __syncthreads();
-   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+   if ((tid & 63) == 0) red[tid >> 6] = v;
    __syncthreads();
    return sum_partials<BLOCK>(red);
 }
@@ -207,7 +208,7 @@ __device__ __forceinline__ int div_n(int e, float rn) { return (int)(((float) e 
 // buffer (src or tmp).  Coefficients: pcr[l][0][i] (towards i-s), pcr[l][1][i]
 // (towards i+s), then the inverse of the reduced diagonal.
 template <typename real, int BLOCK, typename BT>
-__device__ __forceinline__ real * pcr_solve(const BT & b, const real * tab, real * src, real * tmp)
+__device__ __forceinline__ real * pcr_solve(const BT & b, const real * tab, real * src, real * tmp, int tid)
 {
    const int m = b.m, n = b.n, mn = m*n;
    const float rn = 1.0f / (float) n;
@@ -218,7 +219,7 @@ __device__ __forceinline__ real * pcr_solve(const BT & b, const real * tab, real
    {
       const real * ka = tab + (size_t)(b.pcr_sym ? l : 2*l) * m;
       const real * kc = ka + m;
-      for (int e=threadIdx.x; e<mn; e+=BLOCK)
+      for (int e=tid; e<mn; e+=BLOCK)
       {
          const int i = div_n(e, rn);
          real d = cur[e];
@@ -231,7 +232,7 @@ __device__ __forceinline__ real * pcr_solve(const BT & b, const real * tab, real
       stride <<= 1;
    }
    const real * invb = tab + (size_t)(b.pcr_rows - 1) * m;
-   for (int e=threadIdx.x; e<mn; e+=BLOCK)
+   for (int e=tid; e<mn; e+=BLOCK)
       cur[e] *= invb[div_n(e, rn)];
    __syncthreads();
    return cur;
@@ -239,10 +240,10 @@ __device__ __forceinline__ real * pcr_solve(const BT & b, const real * tab, real
 
 // dense fallback (derivative D >= 2): x = Ainv d
 template <typename real, int BLOCK, typename BT>
-__device__ __forceinline__ real * dense_solve(const BT & b, real * src, real * tmp)
+__device__ __forceinline__ real * dense_solve(const BT & b, real * src, real * tmp, int tid)
 {
    const int m = b.m, n = b.n, mn = m*n;
-   for (int e=threadIdx.x; e<mn; e+=BLOCK)
+   for (int e=tid; e<mn; e+=BLOCK)
    {
       const int i = e / n, c = e - i*n;
       real s = (real)0;
@@ -324,10 +325,10 @@ __device__ __forceinline__ void toeplitz_scan_column_long(PT buf, int m, int n, 
 // where cyclic reduction costs one per level.  (The reference multiplies by the dense inverse,
 // src/libcd/chomp.c:525-548: the same products, summed in another order.)
 template <typename real, int BLOCK, typename BT>
-__device__ __forceinline__ real * toeplitz_scan_solve(const BT & b, real * buf)
+__device__ __forceinline__ real * toeplitz_scan_solve(const BT & b, real * buf, int tid)
 {
    const int m = b.m, n = b.n;
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+   const int lane = tid & 63, wave = tid >> 6;
    const int rpl = (m + 63) >> 6;
    const real kinv = (real)(-1) / ((real)(m + 1) * b.a_off);      // 1/((m+1) ca), ca = -a_off
    if (rpl > ORC_SCAN_RPL)      // (more than 256 moving waypoints: the rows are read twice instead of held in registers, below)
@@ -524,13 +525,13 @@ __device__ __forceinline__ void semisep_scan_column_any(PT buf, int m, int n, in
 // all n columns of buf [m][n] in place, a wavefront per column at a time: ONE barrier, like the scan solve of derivative 1.
 // A column that is zero throughout (the joint-limit rounds solve for a Gjlimit with a few non-zero columns) is left alone.
 template <typename real, int BLOCK>
-__device__ __attribute__((noinline)) real * semisep_solve_call(real * buf_in, const real * tab_in, int m_in, int n_in, int rank_in)
+__device__ __attribute__((noinline)) real * semisep_solve_call(real * buf_in, const real * tab_in, int m_in, int n_in, int rank_in, int tid)
 {
    // (a function of its own: six instantiations of the column solve, of no interest to a `derivative 1` run's instruction cache)
    const int m = __builtin_amdgcn_readfirstlane(m_in), n = __builtin_amdgcn_readfirstlane(n_in), rank = __builtin_amdgcn_readfirstlane(rank_in);
    real * buf = (real *) uni64((unsigned long long) buf_in);
    const real * tab = (const real *) uni64((unsigned long long) tab_in);
-   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+   const int lane = tid & 63, wave = tid >> 6;
    const int rpl = (m + 63) >> 6;
    const double * U = (const double *) tab, * V = U + rank*m;      // (the metric's tables: DevBatch::ss_rank)
    for (int c=wave; c<n; c+=BLOCK/64)
@@ -785,11 +786,11 @@ __device__ __attribute__((noinline)) LimResult limit_rounds_call_global_small(re
 }
 
 template <typename real, int BLOCK, typename BT>
-__device__ __forceinline__ real * metric_solve(const BT & b, const real * tab, real * src, real * tmp)
+__device__ __forceinline__ real * metric_solve(const BT & b, const real * tab, real * src, real * tmp, int tid)
 {
-   if (b.solve_mode == 2) return toeplitz_scan_solve<real, BLOCK>(b, src);
-   if (b.solve_mode == 3) return semisep_solve_call<real, BLOCK>(src, tab, b.m, b.n, b.ss_rank);
-   return b.solve_mode == 0 ? pcr_solve<real, BLOCK>(b, tab, src, tmp) : dense_solve<real, BLOCK>(b, src, tmp);
+   if (b.solve_mode == 2) return toeplitz_scan_solve<real, BLOCK>(b, src, tid);
+   if (b.solve_mode == 3) return semisep_solve_call<real, BLOCK>(src, tab, b.m, b.n, b.ss_rank, tid);
+   return b.solve_mode == 0 ? pcr_solve<real, BLOCK>(b, tab, src, tmp, tid) : dense_solve<real, BLOCK>(b, src, tmp, tid);
 }
 
 // Row i, column c of A T + B for a higher derivative (|D| >= 2, or derivative 1 without a start boundary), in the
@@ -918,7 +919,7 @@ __device__ __forceinline__ real smooth_grad(const BT & b, const real * T_s, int 
 // their own -- inlined, band_row tripled the lean update phase of every `derivative 1` kernel (2.1 k -> 5.4 k instructions) and cost
 // BASELINE configs[1] 1 % through the instruction cache alone (profiles/r06_ab_experiments.txt).
 template <typename real, int BLOCK>
-__device__ __attribute__((noinline)) void band_gradient_pass(const void * kp, const real * tab_in, const real * T_in, const real * Gc_in, real * G_in)
+__device__ __attribute__((noinline)) void band_gradient_pass(const void * kp, const real * tab_in, const real * T_in, const real * Gc_in, real * G_in, int tid)
 {
    // (the kernarg block's address, wave-uniform again; through uni64: readfirstlane returns an int, and OR-ing the low half in as
    // one sign-extends it -- a launch whose kernarg address has bit 31 set then reads from a wild pointer: the first version did)
@@ -928,7 +929,7 @@ __device__ __attribute__((noinline)) void band_gradient_pass(const void * kp, co
    real * G_s = (real *) uni64((unsigned long long) G_in);
    const int n = b.n, mn = b.m*n;
    const float rn_f = 1.0f / (float) n;
-   for (int e=threadIdx.x; e<mn; e+=BLOCK)
+   for (int e=tid; e<mn; e+=BLOCK)
    {
       const int i = div_n(e, rn_f), c = e - i*n;
       real g = Gc[e];
@@ -939,7 +940,7 @@ __device__ __attribute__((noinline)) void band_gradient_pass(const void * kp, co
    }
 }
 template <typename real, int BLOCK>
-__device__ __attribute__((noinline)) double band_cost_pass(const void * kp, const real * tab_in, const real * T_in)
+__device__ __attribute__((noinline)) double band_cost_pass(const void * kp, const real * tab_in, const real * T_in, int tid)
 {
    // (the kernarg block's address, wave-uniform again; through uni64: readfirstlane returns an int, and OR-ing the low half in as
    // one sign-extends it -- a launch whose kernarg address has bit 31 set then reads from a wild pointer: the first version did)
@@ -948,7 +949,7 @@ __device__ __attribute__((noinline)) double band_cost_pass(const void * kp, cons
    const int n = b.n, mn = b.m*n;
    const float rn_f = 1.0f / (float) n;
    double acc = 0.0;
-   for (int e=threadIdx.x; e<mn; e+=BLOCK)
+   for (int e=tid; e<mn; e+=BLOCK)
    {
       const int i = div_n(e, rn_f), c = e - i*n;
       if (sizeof(real) == 4 && b.metric64)
@@ -1019,6 +1020,27 @@ __device__ __forceinline__ const __attribute__((address_space(4))) RunParams<rea
    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned) v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
    return (P)(((unsigned long long) hi << 32) | lo);
 }
+
+// The LOGICAL thread index every phase hands its work out by (wave_roles.h): the hardware index rotated by `rot` whole
+// wavefronts, the lane unchanged.  `rot` is wave-uniform -- the switch from the kernarg block, the workgroup index, and the low bits
+// of the iteration number, which the kernel's loop packs into an argument the phase takes anyway (pack_it: the loop carries no
+// scalar more across the calls) -- so it costs a phase call a handful of scalar instructions and two vector ones.
+// The compiler is told the range: the cost passes address with 24-bit multiplies that depend on it.
+template <int BLOCK, typename BT>
+__device__ __forceinline__ int orc_tid(const BT & b, int it_bits)
+{
+   const int rot = orc::wave_rot(b.wave_rotate, (int) blockIdx.x, it_bits, BLOCK);
+   const int t = orc::logical_tid((int) threadIdx.x, rot, BLOCK);
+   __builtin_assume(t >= 0 && t < BLOCK);
+   return t;
+}
+constexpr int IT_SHIFT = ORC_IT_SHIFT;      // (the payloads stay below 2^24: checked where a launch is prepared, batch.cpp)
+__device__ __forceinline__ int pack_it(int v, int it) { return v | ((it & 7) << IT_SHIFT); }
+__device__ __forceinline__ int packed_it(int v) { return (v >> IT_SHIFT) & 7; }
+__device__ __forceinline__ int packed_arg(int v) { return v & ((1 << IT_SHIFT) - 1); }
+// the thread that keeps the phase timers: the first of the last logical wavefront, which takes part in every phase (the first
+// wavefronts only meet the barrier of an FK phase that has fewer groups than the workgroup has wavefronts)
+template <int BLOCK> __device__ __forceinline__ bool marks(int tid) { return tid == BLOCK - 64; }
 
 // the LDS carve-up and the views derived from it (everything here is wave-uniform)
 template <typename real>
@@ -1138,7 +1160,7 @@ __device__ __forceinline__ void conv_begin(KArg<real> & b, int run)
 // phase_costs, after a complete iteration with costs (obs, smooth) (workgroup-uniform): the rule of convergence_stop
 // (or_cdchomp_amd/module.py); raises the stop flag when the streak reaches the patience
 template <typename real>
-__device__ __forceinline__ void conv_step(KArg<real> & b, double obs_in, double smooth_in)
+__device__ __forceinline__ void conv_step(KArg<real> & b, double obs_in, double smooth_in, int tid)
 {
    ConvState * cs = conv_state();
    const double obs = unir(obs_in), smooth = unir(smooth_in);
@@ -1147,7 +1169,7 @@ __device__ __forceinline__ void conv_step(KArg<real> & b, double obs_in, double 
    const bool settled = ::fabs(prev - tot) <= b.conv_rtol * ::fabs(prev) && obs <= b.conv_obs_max;
    const int streak = settled ? uni(cs->streak) + 1 : 0;
    __syncthreads();                                  // (every wavefront has read the state)
-   if (threadIdx.x == 0) { cs->prev = tot; cs->streak = streak; cs->stop = (streak >= b.conv_patience) ? 1 : 0; }
+   if (tid == 0) { cs->prev = tot; cs->streak = streak; cs->stop = (streak >= b.conv_patience) ? 1 : 0; }
    __syncthreads();
 }
 
@@ -1155,9 +1177,9 @@ __device__ __forceinline__ void conv_step(KArg<real> & b, double obs_in, double 
 
 // per-phase cycle counters (diagnostics: b.phase_cycles == null in production), kept in the LDS header
 template <typename real, typename BT>
-__device__ __forceinline__ void phase_mark(const BT & b, const Env<real> & E, int slot)
+__device__ __forceinline__ void phase_mark(const BT & b, const Env<real> & E, int slot, bool marker)
 {
-   if (b.phase_cycles && threadIdx.x == 0)
+   if (b.phase_cycles && marker)
    {
       long long * tm = (long long *)((unsigned char *) E.red + 168);
       const long long now = clock64();
@@ -1173,9 +1195,18 @@ __device__ __attribute__((noinline)) void phase_setup(const void * kp)
    KArg<real> & b = *uniform_kernarg<real>(kp);
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
    const DevModel<real> & gmod = *b.model;      // global copy: read once
-   const int tid = threadIdx.x;
+   const int tid = orc_tid<BLOCK>(b, 0);
    const int n = b.n, m = b.m, np = b.n_points, mn = m*n;
    const int nj = E.mod.nj, Sa = E.mod.Sa, S = E.mod.S;
+   // where this wavefront sits (diagnostics: b.wave_hwid == null in production): its hardware-ID register, read once per launch
+   // (scripts/wave_placement.py; one record per hardware wavefront of the run's workgroup) and, in bits 8.. of the second word, the
+   // logical wavefront it is in the launch's last iteration (what ORC_WAVE_ROTATE made of it)
+   if (b.wave_hwid && (threadIdx.x & 63) == 0)
+   {
+      unsigned int * rec = b.wave_hwid + ((size_t) blockIdx.x * 8 + (threadIdx.x >> 6)) * 2;
+      rec[0] = __builtin_amdgcn_s_getreg(ORC_GETREG_HW_ID);
+      rec[1] = __builtin_amdgcn_s_getreg(ORC_GETREG_XCC_ID) | ((unsigned int)(orc_tid<BLOCK>(b, (b.n_iter - 1) & 7) >> 6) << 8);
+   }
    if (b.t_in_lds)
    {
       // start_tsr: the start point is the first moving row.  The row in front of it is not a trajectory
@@ -1253,7 +1284,7 @@ __device__ __attribute__((noinline)) void phase_setup(const void * kp)
 #undef ORC_R2
    }
    __syncthreads();
-   phase_mark<real>(b, E, -1);
+   phase_mark<real>(b, E, -1, marks<BLOCK>(tid));
 }
 
 // ---- hmc momentum resample (src/orcdchomp_mod.cpp:2755-2768): AG <- the call's noise slot ----
@@ -1261,20 +1292,19 @@ template <typename real, bool GS16, int BLOCK, int WGS = 0>
 __device__ __attribute__((noinline)) void phase_hmc(const void * kp, int slot_in)
 {
    KArg<real> & b = *uniform_kernarg<real>(kp);
-   const int slot = uni(slot_in);
+   const int slot = packed_arg(uni(slot_in)), tid = orc_tid<BLOCK>(b, packed_it(uni(slot_in)));
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
    const int mn = b.m * b.n;
    const real * nz = b.noise + ((size_t) blockIdx.x * b.max_resamples + slot) * mn;
-   for (int e=threadIdx.x; e<mn; e+=BLOCK) E.AG_s[e] = nz[e];
+   for (int e=tid; e<mn; e+=BLOCK) E.AG_s[e] = nz[e];
    __syncthreads();
 }
 
 // copy `count` reals between global memory and LDS with eight loads in flight per thread (a plain loop waits for every
 // load before it issues the next: a round trip through L2 or the Infinity Cache per 2 KB)
 template <typename real, int BLOCK>
-__device__ __forceinline__ void copy_batched(real * dst, const real * src, int count)
+__device__ __forceinline__ void copy_batched(real * dst, const real * src, int count, int tid)
 {
-   const int tid = threadIdx.x;
    int e = tid;
    for (; e + 7*BLOCK < count; e += 8*BLOCK)
    {
@@ -1292,9 +1322,9 @@ template <typename real, bool TREE, bool GS16, int BLOCK, int WGS = 0>
 __device__ __forceinline__ void phase_fk_body(const void * kp, int ts_in, int te_in)
 {
    KArg<real> & b = *uniform_kernarg<real>(kp);
-   const int ts = uni(ts_in), te = uni(te_in);
+   const int ts = uni(ts_in), te = packed_arg(uni(te_in));
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
-   const int tid = threadIdx.x, n = b.n;
+   const int tid = orc_tid<BLOCK>(b, packed_it(uni(te_in))), n = b.n;
    const int nfk = te - ts + 2;          // waypoints ts .. te+1 (global index)
    __builtin_amdgcn_s_setprio(PRIO_FK);          // latency-bound phases go first when they have something to issue
    // a wavefront walks 20 waypoints: five triads of lanes (x, y, z rows) in each of its four rows of 16.  A robot whose
@@ -1302,7 +1332,8 @@ __device__ __forceinline__ void phase_fk_body(const void * kp, int ts_in, int te
    // joints up to fk_b_begin, the other the chain (without storing) and the joints from fk_b_begin on
    const int lane16 = tid & 15, triad = (lane16 * 11) >> 5, wave = uni(tid >> 6);      // (the compiler must know the walk's joint indices as uniform: scalar loads)
    const int nseg = (b.ms.fk_split && (BLOCK/64) % 2 == 0) ? 2 : 1;
-   const int seg = (nseg == 2) ? (wave & 1) : 0, group = (nseg == 2) ? (wave >> 1) : wave, groups = (BLOCK/64) / nseg;
+   // (the groups go to the LAST wavefronts: the first ones have the partial cost rounds and the joint-limit rounds, wave_roles.h)
+   const int seg = orc::fk_seg_of_wave(wave, nseg), group = orc::fk_group_of_wave(wave, BLOCK, nseg), groups = orc::fk_groups(BLOCK, nseg);
    const int nj = E.mod.nj;
    const int n_anc = seg ? b.ms.fk_nanc : 0, j_begin = seg ? b.ms.fk_b_begin : 0, j_end = (nseg == 2 && !seg) ? b.ms.fk_b_begin : nj;
    const int wv = group * 20 + ((tid >> 4) & 3) * 5 + triad;
@@ -1316,7 +1347,7 @@ __device__ __forceinline__ void phase_fk_body(const void * kp, int ts_in, int te
                                     E.pos_s + wr*E.pstr, E.ax_s + wr*E.astr, !b.t_in_lds);
    }
    __syncthreads();
-   phase_mark<real>(b, E, 0);
+   phase_mark<real>(b, E, 0, marks<BLOCK>(tid));
 }
 template <typename real, bool TREE, bool GS16, int BLOCK, int WGS = 0>
 __device__ __attribute__((noinline)) void phase_fk(const void * kp, int ts_in, int te_in)
@@ -1331,16 +1362,17 @@ template <typename real, bool TREE, bool GS16, int BLOCK, int WGS = 0>
 __device__ __attribute__((noinline)) double phase_cost_start(const void * kp, int do_iteration_in, double cost_lane)
 {
    KArg<real> & b = *uniform_kernarg<real>(kp);
-   const bool do_iteration = uni(do_iteration_in) != 0;
+   const bool do_iteration = packed_arg(uni(do_iteration_in)) != 0;
+   const int tid = orc_tid<BLOCK>(b, packed_it(uni(do_iteration_in)));
    Env<real> E = make_env<real, GS16>(b, orc_smem);
    E.mod.live_mask |= b.ms.static_mask;
-   const real inv_eps = (real)1 / E.mod.rp->epsilon, inv_eps_self = (real)1 / b.epsilon_self;
+   const real inv_eps = E.mod.rp->inv_epsilon, inv_eps_self = b.inv_epsilon_self;
    if constexpr (GS16)
       cost_tile_gs16<real, GS16_U, BLOCK, KArg<real>, true>(b, E.mod, 0, 1, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s, E.r2_s,
-                                                          E.slink_s, E.jtype_s, E.jcol_s, inv_eps, inv_eps_self, cost_lane);
+                                                          E.slink_s, E.jtype_s, E.jcol_s, inv_eps, inv_eps_self, cost_lane, tid);
    else
       cost_tile_generic<real, BLOCK, KArg<real>, true>(b, E.mod, E.sdfs_s, 0, 1, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s,
-                                                      E.slink_s, E.jtype_s, E.jcol_s, E.pstr, E.astr, inv_eps, inv_eps_self, cost_lane, nullptr);
+                                                      E.slink_s, E.jtype_s, E.jcol_s, E.pstr, E.astr, inv_eps, inv_eps_self, cost_lane, nullptr, tid);
    __syncthreads();
    return cost_lane;
 }
@@ -1360,25 +1392,26 @@ template <typename real, bool TREE, bool GS16, int BLOCK, int KIND = 0, bool ITE
 __device__ __forceinline__ double phase_cost_body(const void * kp, int ts_in, int te_in, double cost_lane)
 {
    KArg<real> & b = *uniform_kernarg<real>(kp);
-   const int ts = uni(ts_in), te = uni(te_in);
+   const int ts = uni(ts_in), te = packed_arg(uni(te_in));
+   const int tid = orc_tid<BLOCK>(b, packed_it(uni(te_in)));
    const bool do_iteration = ITER;
    Env<real> E = make_env<real, GS16>(b, orc_smem);
    if constexpr (GS16 && (KIND & 1) != 0) { E.mod.floating = (KIND & 4) ? 1 : 0; E.mod.jt_scan = 1; E.mod.placed = 1; }
    // the many-sphere path: bit 1 = a fixed base and the J^T ranges of a chain (1) or of a tree in depth-first order (2)
    if constexpr (!GS16 && (KIND & 1) != 0) { E.mod.floating = 0; E.mod.jt_scan = TREE ? 2 : 1; }
    E.mod.live_mask |= b.ms.static_mask;      // the static spheres' lanes take part in the row's pairs
-   const real inv_eps = (real)1 / E.mod.rp->epsilon, inv_eps_self = (real)1 / b.epsilon_self;
+   const real inv_eps = E.mod.rp->inv_epsilon, inv_eps_self = b.inv_epsilon_self;      // (formed once, on the host: RunParams)
    __builtin_amdgcn_s_setprio(PRIO_COST);
    if constexpr (GS16)
       cost_tile_gs16<real, GS16_U, BLOCK, KArg<real>, false, (KIND & 2) != 0, (KIND & 1) != 0, (KIND & 8) != 0>(b, E.mod, ts, te, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s, E.r2_s,
-                                         E.slink_s, E.jtype_s, E.jcol_s, inv_eps, inv_eps_self, cost_lane);
+                                         E.slink_s, E.jtype_s, E.jcol_s, inv_eps, inv_eps_self, cost_lane, tid);
    else if constexpr ((KIND & 16) != 0)
    {
       // 17 .. 32 active spheres on a chain: the dense pair list (KIND 16; 16 | 2 | 8: one field with the world's axes, a fixed
       // base, no inactive sphere left for the loop over them)
       if constexpr ((KIND & 2) != 0) E.mod.floating = 0;
       cost_tile_pairs<real, BLOCK, KArg<real>, (KIND & 2) != 0, (KIND & 8) != 0>(b, E.mod, ts, te, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s,
-                                         E.slink_s, E.pent_s, E.pgat_s, inv_eps, inv_eps_self, cost_lane);
+                                         E.slink_s, E.pent_s, E.pgat_s, inv_eps, inv_eps_self, cost_lane, tid);
    }
    else
    {
@@ -1388,7 +1421,7 @@ __device__ __forceinline__ double phase_cost_body(const void * kp, int ts_in, in
       long long * gdbg = nullptr;
 #endif
       cost_tile_generic<real, BLOCK>(b, E.mod, E.sdfs_s, ts, te, do_iteration, E.T_s, E.Gc, E.pos_s, E.ax_s, E.srad_s, E.sinact_s,
-                                     E.slink_s, E.jtype_s, E.jcol_s, E.pstr, E.astr, inv_eps, inv_eps_self, cost_lane, gdbg);
+                                     E.slink_s, E.jtype_s, E.jcol_s, E.pstr, E.astr, inv_eps, inv_eps_self, cost_lane, gdbg, tid);
    }
    __syncthreads();
 #ifdef ORC_COST_TIMERS
@@ -1402,7 +1435,7 @@ __device__ __forceinline__ double phase_cost_body(const void * kp, int ts_in, in
       printf("cost sections (cycles of wavefront 0, whole launch): setup %lld obstacle %lld self %lld jt %lld between %lld\n",
              orc_cost_dbg[0], orc_cost_dbg[1], orc_cost_dbg[2], orc_cost_dbg[3], orc_cost_dbg[4]);
 #endif
-   phase_mark<real>(b, E, 1);
+   phase_mark<real>(b, E, 1, marks<BLOCK>(tid));
    return cost_lane;
 }
 template <typename real, bool TREE, bool GS16, int BLOCK, int KIND = 0, bool ITER = true, int WGS = 0>
@@ -1422,7 +1455,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    KArg<real> & b = *uniform_kernarg<real>(kp);
    const int it = uni(it_in), leapfrog_first = uni(leapfrog_first_in);
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
-   const int run = blockIdx.x, tid = threadIdx.x;
+   const int run = blockIdx.x, tid = orc_tid<BLOCK>(b, it & 7);
    const int n = b.n, m = b.m, mn = m*n;
    const float rn_f = 1.0f / (float) n;        // for div_n
    double * red = E.red; int * redi = E.redi; unsigned int * colmask_s = E.colmask_s;
@@ -1434,7 +1467,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
       // the trajectory lives in global memory (FK reads it there, larger tiles in exchange); this phase works on a copy in the
       // tile buffers, which are dead by now: one coalesced read here and one write at the end instead of stencils and
       // column scans through L2 (the preceding cost pass ended with a barrier)
-      copy_batched<real, BLOCK>(T_s, E.traj_g, b.n_points*n);
+      copy_batched<real, BLOCK>(T_s, E.traj_g, b.n_points*n, tid);
       __syncthreads();
    }
 
@@ -1442,7 +1475,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    if (tid < 2) colmask_s[tid] = 0u;       // read last after the previous step's barrier, set again after the next one
    // G = G/m + A T + B   (chomp.c:492, 515-522)
    const bool band = !LEAN && b.D != 1;      // (a metric that is not the tridiagonal Toeplitz one: its pass is a function of its own)
-   if (band) band_gradient_pass<real, BLOCK>(kp, pcr_tab, T_s, Gc, G_s);
+   if (band) band_gradient_pass<real, BLOCK>(kp, pcr_tab, T_s, Gc, G_s, tid);
    // (four entries of a thread per trip, their gradient rows read first: where the plan keeps the rows in global memory a plain
    // loop made one round trip through L2 per entry, eleven in a row for a 200-waypoint run of 14 dofs: BASELINE configs[3] +2 %;
    // for the three entries per thread of a 7 x 100 run it costs 0.7 %: those take the plain loop)
@@ -1484,7 +1517,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    if (!LEAN && b.Gdbg)
       for (int e=tid; e<mn; e+=BLOCK) b.Gdbg[(size_t) run*mn + e] = G_s[e];
    // X = A^-1 G   (chomp.c:525-548)
-   real * X = LEAN ? toeplitz_scan_solve<real, BLOCK>(b, G_s) : metric_solve<real, BLOCK>(b, pcr_tab, G_s, W_s);
+   real * X = LEAN ? toeplitz_scan_solve<real, BLOCK>(b, G_s, tid) : metric_solve<real, BLOCK>(b, pcr_tab, G_s, W_s, tid);
    // T -= AG/lambda   (chomp.c:604-605)
    const real step = (real)(-1) / E.mod.rp->lambda;
    // the step also notes which columns left their limits (what the first scan of the
@@ -1503,9 +1536,9 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
       }
       __threadfence_block();
       __syncthreads();
-      phase_mark<real>(b, E, 3);
-      phase_tsr<real, GS16, BLOCK, WGS>(kp);
-      phase_mark<real>(b, E, 2);      // (slot 2: the constraint step)
+      phase_mark<real>(b, E, 3, marks<BLOCK>(tid));
+      phase_tsr<real, GS16, BLOCK, WGS>(kp, tid);
+      phase_mark<real>(b, E, 2, marks<BLOCK>(tid));      // (slot 2: the constraint step)
       const real * AGc = b.use_momentum ? AG_s : AG_g;
       for (int e=tid; e<mn; e+=BLOCK)
       {
@@ -1571,7 +1604,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
       if ((unsigned int)(viol >> 32)) atomicOr(&colmask_s[1], (unsigned int)(viol >> 32));
    }
    __syncthreads();
-   phase_mark<real>(b, E, 3);
+   phase_mark<real>(b, E, 3, marks<BLOCK>(tid));
 
    // joint-limit projection (chomp.c:608-655)
    int num_limadjs = 0;
@@ -1728,7 +1761,7 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
       if (!sparse_done)
       {
          __syncthreads();
-         real * GA = metric_solve<real, BLOCK>(b, pcr_tab, G_s, W_s);
+         real * GA = metric_solve<real, BLOCK>(b, pcr_tab, G_s, W_s, tid);
          const real sc = (real)1.01 * gl / GA[ge];
          __syncthreads();
          for (int e=tid; e<mn; e+=BLOCK) T_s[n + e] += sc * GA[e];
@@ -1738,10 +1771,10 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    if (staged)
    {
       // the moving rows back to global memory (the end points do not move); every path above ended with a barrier
-      copy_batched<real, BLOCK>(E.traj_g + n, T_s + n, mn);
+      copy_batched<real, BLOCK>(E.traj_g + n, T_s + n, mn, tid);
       __syncthreads();
    }
-   phase_mark<real>(b, E, 4);
+   phase_mark<real>(b, E, 4, marks<BLOCK>(tid));
    if (b.phase_cycles && tid == 0) E.phc_s[6] += num_limadjs;   // rounds (phc[7]: kinds of rounds, see LimResult)
    return num_limadjs;
 }
@@ -1756,9 +1789,9 @@ template <typename real, bool GS16, int BLOCK, int WGS = 0>
 __device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int do_iteration_in, double cost_lane)
 {
    KArg<real> & b = *uniform_kernarg<real>(kp);
-   const bool do_iteration = uni(do_iteration_in) != 0;
+   const bool do_iteration = packed_arg(uni(do_iteration_in)) != 0;
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
-   const int tid = threadIdx.x;
+   const int tid = orc_tid<BLOCK>(b, packed_it(uni(do_iteration_in)));
    const int n = b.n, m = b.m, np = b.n_points, mn = m*n;
    const float rn_f = 1.0f / (float) n;
    const real * T_s = E.T_u;
@@ -1766,14 +1799,14 @@ __device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int 
    if (staged && !do_iteration)
    {
       // the cost-only pass that ends a call: no update phase has staged the trajectory
-      copy_batched<real, BLOCK>(E.T_u, E.traj_g, np*n);
+      copy_batched<real, BLOCK>(E.T_u, E.traj_g, np*n, tid);
       __syncthreads();
    }
    PassCosts pc;
    __builtin_amdgcn_s_setprio(PRIO_UPDATE);
    {
       double acc = 0.0;
-      if (b.D != 1) acc = band_cost_pass<real, BLOCK>(kp, E.pcr_tab, T_s);
+      if (b.D != 1) acc = band_cost_pass<real, BLOCK>(kp, E.pcr_tab, T_s, tid);
       else
       for (int e=tid; e<mn; e+=BLOCK)
       {
@@ -1798,7 +1831,7 @@ __device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int 
       pc.smooth = sum_partials<BLOCK>(E.red + 8);
       pc.obs /= (double) m;
    }
-   phase_mark<real>(b, E, 5);
+   phase_mark<real>(b, E, 5, marks<BLOCK>(tid));
 
    // start_tsr: the row in front of the start point follows the point after it (see phase_setup)
    if (do_iteration && b.free_start)
@@ -1821,7 +1854,7 @@ __device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int 
       }
       __syncthreads();
    }
-   if (b.conv_patience && do_iteration) conv_step<real>(b, pc.obs, pc.smooth);
+   if (b.conv_patience && do_iteration) conv_step<real>(b, pc.obs, pc.smooth, tid);
    return pc;
 }
 
@@ -1834,7 +1867,7 @@ __device__ __attribute__((noinline)) void phase_finish(const void * kp, int stat
    int status = uni(status_in);
    const int iters_done = uni(iters_done_in), leapfrog_first = uni(leapfrog_first_in), have_costs = uni(have_costs_in);
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
-   const int run = blockIdx.x, tid = threadIdx.x;
+   const int run = blockIdx.x, tid = orc_tid<BLOCK>(b, 0);      // (after the last iteration's barrier: any rotation serves)
    const int n = b.n, m = b.m, np = b.n_points, mn = m*n;
    __syncthreads();
    // a run the convergence stop ended (in this launch, or in an earlier one of the call) reports status 1
@@ -1880,7 +1913,6 @@ void chomp_iterate_kernel(const DevBatch<real> b)
 {
    const void * kp = (const void *) __builtin_amdgcn_kernarg_segment_ptr();      // DevBatch b is the kernel's only argument
    const int run = blockIdx.x;
-   const int tid = threadIdx.x;
 
    // a launch that continues an iterate call: the run left its joint limits in an earlier launch of the call, the
    // reference has thrown out of the call by now (workgroup-uniform).  A run that converged in an earlier launch of the
@@ -1922,7 +1954,7 @@ void chomp_iterate_kernel(const DevBatch<real> b)
       if (do_iteration && b.use_hmc && b.use_momentum && next_resample < b.max_resamples
           && b.hmc_iters[(size_t) run * b.max_resamples + next_resample] == it)
       {
-         phase_hmc<real, GS16, BLOCK, WGS>(kp, next_resample);
+         phase_hmc<real, GS16, BLOCK, WGS>(kp, pack_it(next_resample, it));
          leapfrog_first = 1;
          next_resample++;
       }
@@ -1932,6 +1964,11 @@ void chomp_iterate_kernel(const DevBatch<real> b)
       {
          const int ts = (tk == 0) ? 0 : b.tile_first + (tk - 1) * b.tile_rest;
          const int te = (tk == b.n_tiles - 1) ? b.m : b.tile_first + tk * b.tile_rest;
+         // (the tile's end as the phases take it, with the iteration's bits for their rotation: formed here, behind an empty asm,
+         // so that no part of it is a loop invariant the compiler would carry across the calls)
+         int itv = it;
+         __asm__ volatile("" : "+s"(itv));
+         const int tep = pack_it(te, itv);
          // ORC_STAGGER_MODE=9 (a timing experiment, wrong results): only the first tile is walked and a pause stands in for a
          // barrier across workgroups -- what an iteration of ONE run would take with its tiles on as many CUs
          // (scripts/single_run_latency.py, profiles/r04_single_run_ceiling.txt)
@@ -1939,10 +1976,13 @@ void chomp_iterate_kernel(const DevBatch<real> b)
 #ifndef ORC_ABLATE_FK
          // a wavefront without a waypoint in the tile (20 per wavefront: the second of a 128-thread workgroup in each of its tiles of 14)
          // only joins the phase's barrier: it saves the call's ~120 scalar registers moved through the vector pipe
-         if (!b.ms.fk_split && uni(tid >> 6) * 20 >= te - ts + 2) __syncthreads();
-         else phase_fk<real, TREE, GS16, BLOCK, WGS>(kp, ts, te);      // (skipping the call for the wavefronts without a waypoint in the tile -- their share of the callee-saved registers -- measured nothing: profiles/r04_ab_experiments.txt)
+         // (the FK groups go to the last logical wavefronts, wave_roles.h: it is the first ones that have nothing to walk.  Without a
+         // rotation the logical wavefront is the hardware's; under ORC_WAVE_ROTATE every wavefront makes the call and the idle ones
+         // find nothing to walk inside it: forming the rotation here cost the kernel function a spilled register)
+         if (!b.ms.fk_split && !b.wave_rotate && orc::fk_wave_idle(uni((int)(threadIdx.x >> 6)), BLOCK, 1, te - ts + 2)) __syncthreads();
+         else phase_fk<real, TREE, GS16, BLOCK, WGS>(kp, ts, tep);      // (skipping the call for the wavefronts without a waypoint in the tile -- their share of the callee-saved registers -- measured nothing: profiles/r04_ab_experiments.txt)
 #ifdef ORC_ABLATE_FKTWICE      // timing experiments: the FK phase twice (what a 2x slower FK would cost)
-         phase_fk<real, TREE, GS16, BLOCK, WGS>(kp, ts, te);
+         phase_fk<real, TREE, GS16, BLOCK, WGS>(kp, ts, tep);
 #endif
 #endif
 #ifndef ORC_ABLATE_COST
@@ -1951,11 +1991,11 @@ void chomp_iterate_kernel(const DevBatch<real> b)
          // of scratch traffic per launch of BASELINE configs[4], most of what the HBM counters saw)
          // The 16-lane pass and the FK phase stay calls: inside the kernel function they measured slower (the FK phase's hoisted loop
          // invariants spill to scratch; profiles/r04_ab_experiments.txt, profiles/r05_ab_experiments.txt)
-         if (do_iteration && !GS16) cost_lane = phase_cost_body<real, TREE, GS16, BLOCK, KIND, true>(kp, ts, te, cost_lane);
+         if (do_iteration && !GS16) cost_lane = phase_cost_body<real, TREE, GS16, BLOCK, KIND, true>(kp, ts, tep, cost_lane);
          else
-         cost_lane = do_iteration ? phase_cost<real, TREE, GS16, BLOCK, KIND, true, WGS>(kp, ts, te, cost_lane)
-                                  : phase_cost<real, TREE, GS16, BLOCK, KIND, false, WGS>(kp, ts, te, cost_lane);
-         if (tk == 0 && b.free_start) cost_lane = phase_cost_start<real, TREE, GS16, BLOCK, WGS>(kp, do_iteration ? 1 : 0, cost_lane);
+         cost_lane = do_iteration ? phase_cost<real, TREE, GS16, BLOCK, KIND, true, WGS>(kp, ts, tep, cost_lane)
+                                  : phase_cost<real, TREE, GS16, BLOCK, KIND, false, WGS>(kp, ts, tep, cost_lane);
+         if (tk == 0 && b.free_start) cost_lane = phase_cost_start<real, TREE, GS16, BLOCK, WGS>(kp, pack_it(do_iteration ? 1 : 0, it), cost_lane);
 #endif
       } // tiles
 
@@ -1973,10 +2013,10 @@ void chomp_iterate_kernel(const DevBatch<real> b)
       // the log line; the trajectory keeps what the limit rounds made of it (workgroup-uniform)
       if (status != 0) break;
 
-      PassCosts pc = phase_costs<real, GS16, BLOCK, WGS>(kp, do_iteration ? 1 : 0, cost_lane);
+      PassCosts pc = phase_costs<real, GS16, BLOCK, WGS>(kp, pack_it(do_iteration ? 1 : 0, it), cost_lane);
       pc.obs = unir(pc.obs); pc.smooth = unir(pc.smooth);
 
-      if (tid == 0 && b.trace && do_iteration)
+      if (threadIdx.x == 0 && b.trace && do_iteration)      // (wave-uniform values: any one thread)
       {
          double * tr = b.trace + ((size_t) run * b.n_iter + it) * 3;
          tr[0] = pc.obs + pc.smooth; tr[1] = pc.obs; tr[2] = pc.smooth;

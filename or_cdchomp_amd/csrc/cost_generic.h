@@ -24,12 +24,11 @@ template <typename real, int BLOCK, typename BT, bool START = false>
 __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<real> & mod,
    const DevSdf<real> * sdfs, int ts, int te, bool do_iteration, const real * T_s, real * Gc, const real * pos_s, const real * ax_s,
    const real * srad_s, const real * sinact_s, const int * slink_s, const int * jtype_s, const int * jcol_s,
-   int pstr, int astr, real inv_eps, real inv_eps_self, double & cost_lane, long long * dbg)
+   int pstr, int astr, real inv_eps, real inv_eps_self, double & cost_lane, long long * dbg, const int tid)
 {
    long long tm = 0;
 #define ORC_GMARK(slot) do { if (dbg) { const long long now_ = clock64(); dbg[slot] += now_ - tm; tm = now_; } } while (0)
 
-   const int tid = threadIdx.x;
    const int Sa = mod.Sa, S = mod.S, nj = mod.nj, n = b.n, GS = mod.GS;
    const real inf = M<real>::inf();
    const int items = (te - ts) * GS;

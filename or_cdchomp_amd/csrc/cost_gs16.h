@@ -251,9 +251,8 @@ template <typename real, int U, int BLOCK, typename BT, bool START = false, bool
 __device__ __forceinline__ void cost_tile_gs16(const BT & b, const ModelView<real> & mod,
    int ts, int te, bool do_iteration, const real * T_s, real * G_s, const real * pos_s, const real * ax_s,
    const real * srad_s, const real * sinact_s, const real * r2_s, const int * slink_s, const int * jtype_s, const int * jcol_s,
-   real inv_eps, real inv_eps_self, double & cost_lane)
+   real inv_eps, real inv_eps_self, double & cost_lane, const int tid)
 {
-   const int tid = threadIdx.x;
    const int Sa = mod.Sa, S = mod.S, nj = mod.nj, n = b.n;
    const int pstr = (Sa*3) | 1, astr = (nj*6) | 1;   // padded waypoint strides (LdsLayout::pstr/astr)
    const int nw = te - ts;                      // moving waypoints of this tile

@@ -52,11 +52,10 @@ __device__ __forceinline__ PairEnt<float> pair_entry(const __attribute__((addres
 template <typename real, int BLOCK, typename BT, bool ONEF = false, bool NOINACT = false>
 __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<real> & mod, int ts, int te, bool do_iteration,
    const real * T_s, real * G_s, const real * pos_s, const real * ax_s, const real * srad_s, const real * sinact_s, const int * slink_s,
-   const real * pent_gen, const int * pgat_gen, real inv_eps, real inv_eps_self, double & cost_lane)
+   const real * pent_gen, const int * pgat_gen, real inv_eps, real inv_eps_self, double & cost_lane, const int tid)
 {
    typedef const __attribute__((address_space(3))) real * lds_real_p;
    typedef const __attribute__((address_space(3))) int * lds_int_p;
-   const int tid = threadIdx.x;
    const int Sa = mod.Sa, S = mod.S, nj = mod.nj, n = b.n;
    const int pstr = (Sa*3) | 1, astr = (nj*6) | 1;   // padded waypoint strides (LdsLayout::pstr/astr)
    const int nw = te - ts;                      // moving waypoints of this tile

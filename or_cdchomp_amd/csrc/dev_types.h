@@ -23,6 +23,10 @@
 #define ORC_SCAN_RPL      4       // rows per lane of the scan solve: m <= 64*ORC_SCAN_RPL
 #define ORC_VERDICT_NONE  0x7fffffffffffffffull      // key of a run without a contact (collision_verdict_kernel)
 #define ORC_LDS_HEADER    256     // bytes in front of the LDS carve-up: reduction scratch [16] doubles, [8] ints, column masks, timer mark, phase counters [8]
+// s_getreg operands (id | offset << 6 | (size - 1) << 11) of the two registers that say where a wavefront sits (gfx9 / gfx940 numbering):
+// HW_ID: wave slot [3:0], SIMD [5:4], pipe [7:6], CU [11:8], shader array [12], shader engine [15:13], ...; XCC_ID: the die [3:0]
+#define ORC_GETREG_HW_ID  ((31 << 11) | 4)
+#define ORC_GETREG_XCC_ID ((3 << 11) | 20)
 #define ORC_LIM_LIST      64      // violated entries the sparse joint-limit rounds handle
 #define ORC_LIM_SCRATCH  (256 + ORC_LIM_LIST*16)   // bytes: 4 wave records + header, entry list
 #define ORC_PAIR_ROUNDS   16      // rounds of the dense self-collision pair list at most (cost_pairs.h): 16 x 32 lanes hold every pair of 32 spheres
@@ -209,13 +213,28 @@ struct LdsLayout
    int total_bytes;
 };
 
-// The four step and cost parameters a run may have to itself (orc_batch_set_run_params): one record per run, read with one
-// aligned scalar load (32 bytes in fp64, 16 in fp32).  DevBatch::shared is the batch's own record in the kernarg block.
+// The four step and cost parameters a run may have to itself (orc_batch_set_run_params): one record per run, read with aligned
+// scalar loads (64 bytes in fp64, 32 in fp32).  DevBatch::shared is the batch's own record in the kernarg block.
+// inv_epsilon = 1/epsilon rides along, formed where the record is written (run_params_record: on the host, once per record): the
+// cost phases formed it -- and 1/epsilon_self, now DevBatch::inv_epsilon_self -- as full divisions on the vector pipe at the top
+// of every call, eight wave-calls per run-iteration of the headline.  Both are the correctly rounded quotient of the same two
+// numbers in the run's precision, so the bits are the ones the kernels computed.
 template <typename real>
 struct RunParams
 {
    real lambda, epsilon, obs_factor, obs_factor_self;
+   real inv_epsilon;
+   real pad_[3];
 };
+template <typename real>
+inline RunParams<real> run_params_record(double lambda, double epsilon, double obs_factor, double obs_factor_self)
+{
+   RunParams<real> r;
+   r.lambda = (real) lambda; r.epsilon = (real) epsilon; r.obs_factor = (real) obs_factor; r.obs_factor_self = (real) obs_factor_self;
+   r.inv_epsilon = (real)1 / r.epsilon;
+   r.pad_[0] = r.pad_[1] = r.pad_[2] = (real)0;
+   return r;
+}
 
 template <typename real>
 struct DevBatch
@@ -249,6 +268,7 @@ struct DevBatch
    // run parameters
    real dt, inv_2dt, inv_dt2, inv_m;
    real epsilon_self;      // (not per run: it feeds the fold, and the fold decides the plan)
+   real inv_epsilon_self;  // (real)1 / epsilon_self (see RunParams::inv_epsilon)
    // lambda, epsilon, obs_factor, obs_factor_self: `shared` holds the values the batch was created with; run_params, when set, is
    // [n_runs] records of this shard's runs (orc_batch_set_run_params).  The phase functions pick the run's record ONCE
    // (run_params_of in chomp_kernel.hip, next to make_env) and read the four values through it: one code path either way
@@ -290,6 +310,8 @@ struct DevBatch
    int lim_generic;        // diagnostics: joint-limit rounds by the general (workgroup, any metric) loop
    int stagger_mode;       // 0 none; 1 odd workgroups, 2 every other group of 256: start half an iteration late
    int stagger_sleeps;     // length of that delay in s_sleep(127) units (~8k cycles each)
+   int wave_rotate;        // ORC_WAVE_ROTATE: the rotation of the logical thread index by whole wavefronts (wave_roles.h): 0 none, 1 by workgroup, 2 and by iteration
+   unsigned int * wave_hwid;  // [n_runs][8][2] or null: diagnostics (ORC_PHASE_TIMERS), HW_ID and XCC_ID of every wavefront of a run's workgroup at kernel start
    // TSR hard constraints (tsr.h): n_tsrs == 0 when there are none
    const DevTsr<real> * tsrs;
    int n_tsrs, cons_k;        // constraints; rows of the system over all moving points

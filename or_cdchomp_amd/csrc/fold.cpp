@@ -28,6 +28,7 @@ Switches Switches::read()
    const Int staged = num("ORC_T_STAGED");
    s.t_staged_off = staged.set && staged.value == 0;
    s.lim_generic = num_or("ORC_LIM_GENERIC", 0); s.stagger_mode = num_or("ORC_STAGGER_MODE", 0); s.stagger_sleeps = num_or("ORC_STAGGER_SLEEPS", 10);
+   s.wave_rotate = num_or("ORC_WAVE_ROTATE", 0);
    s.scan_max_m = num_or("ORC_SCAN_MAX_M", 1 << 30); s.wgs128 = num_or("ORC_WGS128", 8);
    s.block_threads = num("ORC_BLOCK_THREADS"); s.tile_m = num("ORC_TILE_M"); s.pcr_lds = num("ORC_PCR_LDS"); s.ag_lds = num("ORC_AG_LDS");
    s.wgs = num("ORC_WGS"); s.g_lds = num("ORC_G_LDS"); s.t_lds = num("ORC_T_LDS"); s.hmc_room = num("ORC_HMC_ROOM");

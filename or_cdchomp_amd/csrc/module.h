@@ -131,6 +131,7 @@ public:
                                   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
                                   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out);
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
+   void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
    void harvest_events(bool wait);
 
@@ -179,7 +180,7 @@ private:
    DevBuf d_traj_, d_AG_, d_G_, d_Gcost_;
    DevBuf d_costs_, d_trace_; size_t trace_cap_ = 0;
    DevBuf d_conv_prev_, d_conv_streak_;      // [n_runs] the convergence stop's state between the launches of a call
-   DevBuf d_status_, d_iters_done_, d_leap_, d_phase_;
+   DevBuf d_status_, d_iters_done_, d_leap_, d_phase_, d_hwid_;
    DevBuf d_run_params_; bool run_params_on_ = false;      // [n_runs] RunParams<real>; kept allocated while off (launches in flight may read it)
    DevBuf d_vkey_;                           // [n_runs] the keys of the last collision_verdict_planned
    DevBuf d_Aband_, d_beta_s_, d_beta_g_, d_metric64_, d_pcr_, d_Ainv_, d_jl_lo_, d_jl_hi_;
@@ -244,6 +245,7 @@ public:
                                   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
                                   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out);
    void get_phase_cycles(long long * out);
+   void get_wave_hwid(unsigned int * out);
    // the convergence stop of every shard's runs for the later iterate calls (validated: throws and changes nothing on a bad spec)
    void set_convergence(const ConvergenceSpec & c);
    const ConvergenceSpec & convergence() const { return shards[0]->conv; }

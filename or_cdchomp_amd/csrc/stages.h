@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "dev_types.h"
+#include "wave_roles.h"
 #include "host_math.h"
 
 namespace orc {
@@ -123,6 +124,7 @@ struct Switches
    bool no_band_toeplitz = false, tsr_dense = false;
    bool t_staged_off = false;                             // ORC_T_STAGED=0
    int lim_generic = 0, stagger_mode = 0, stagger_sleeps = 10, scan_max_m = 1 << 30, wgs128 = 8;
+   int wave_rotate = 0;      // ORC_WAVE_ROTATE (wave_roles.h): rotation of the logical thread index; values outside 0 .. WAVE_ROTATE_MAX are refused at create
    Int block_threads, tile_m, pcr_lds, ag_lds, wgs, g_lds, t_lds, hmc_room;
    static Switches read();
 };

@@ -1069,11 +1069,11 @@ __device__ void tsr_substitute(const BT & b_, const Env<real> & E, const real * 
 // for blocks the structured solve has no shape for, and after a zero pivot there.  A function of its own: inside phase_tsr its state
 // cost the structured path its scalar registers.
 template <typename real, bool GS16, int BLOCK, int WGS = 0>
-__device__ __attribute__((noinline)) void tsr_dense_step(const void * kp)
+__device__ __attribute__((noinline)) void tsr_dense_step(const void * kp, const int tid)
 {
    KArg<real> & b = *uniform_kernarg<real>(kp);
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
-   const int tid = threadIdx.x, run = blockIdx.x;
+   const int run = blockIdx.x;      // (tid: the caller's logical thread index, wave_roles.h)
    const int n = b.n, m = b.m, K = b.cons_k, NB = b.tsr_blocks;
    real * ws = b.tsr_ws + (size_t) run * b.tsr_ws_stride;
    real * hws = ws;
@@ -1188,12 +1188,12 @@ __device__ __attribute__((noinline)) void tsr_dense_step(const void * kp)
 }
 
 template <typename real, bool GS16, int BLOCK, int WGS = 0>
-__device__ __attribute__((noinline)) void phase_tsr(const void * kp)
+__device__ __attribute__((noinline)) void phase_tsr(const void * kp, const int tid)
 {
    KArg<real> & b = *uniform_kernarg<real>(kp);
    const Env<real> E = make_env<real, GS16>(b, orc_smem);
    const DevModel<real> & gm = *b.model;
-   const int tid = threadIdx.x, run = blockIdx.x;
+   const int run = blockIdx.x;      // (tid: the caller's logical thread index, wave_roles.h)
    const int n = b.n, m = b.m, K = b.cons_k, NB = b.tsr_blocks;
    real * ws = b.tsr_ws + (size_t) run * b.tsr_ws_stride;
    real * hws = ws;                          // [K]  h, then the solution
@@ -1319,5 +1319,5 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp)
       // a singular block: the dense path below treats the case the way the reference does
    }
 #endif
-   tsr_dense_step<real, GS16, BLOCK, WGS>(kp);
+   tsr_dense_step<real, GS16, BLOCK, WGS>(kp, tid);
 }
