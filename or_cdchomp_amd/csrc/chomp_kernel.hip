@@ -1003,6 +1003,15 @@ __device__ __forceinline__ KArg<real> * uniform_kernarg(const void * p)
    return (KArg<real> *)(((unsigned long long) hi << 32) | lo);
 }
 __device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+// the kernarg block again, as an address the compiler knows nothing about: what is read through it is read where it is used, by a
+// scalar load, and is not kept in a register from an earlier read (the kernel's loop, between its phase calls)
+template <typename real>
+__device__ __forceinline__ KArg<real> * fresh_kernarg(const void * p)
+{
+   unsigned long long v = (unsigned long long) p;
+   __asm__ volatile("" : "+s"(v));
+   return (KArg<real> *) v;
+}
 // the scene of this workgroup's run (wave-uniform; DevBatch::scene_of_run)
 template <typename BT>
 __device__ __forceinline__ int run_scene(const BT & b)
@@ -1449,13 +1458,12 @@ __device__ __attribute__((noinline)) double phase_cost(const void * kp, int ts_i
 // Runs of the common kind (tridiagonal Toeplitz metric by the scan solve, at most 64 dofs, no debug read-back) take a copy of the update
 // phase compiled without the other paths: fewer live scalars, fewer registers saved and restored per call.
 // LEAN 1 / 2: the caller has checked solve_mode == 2, n <= 64, no lim_generic, no Gdbg, and no TSR constraint (1) or some (2) (the kernel's loop)
+// The body is shared by phase_update and phase_update_costs (below): they form the kernarg reference, the LDS views and the
+// logical thread index once and hand them in.
 template <typename real, bool TREE, bool GS16, int BLOCK, int WGS = 0, int LEAN = 0>
-__device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in, int leapfrog_first_in)
+__device__ __forceinline__ int phase_update_body(const void * kp, KArg<real> & b, const Env<real> & E, int tid, int it, int leapfrog_first)
 {
-   KArg<real> & b = *uniform_kernarg<real>(kp);
-   const int it = uni(it_in), leapfrog_first = uni(leapfrog_first_in);
-   const Env<real> E = make_env<real, GS16>(b, orc_smem);
-   const int run = blockIdx.x, tid = orc_tid<BLOCK>(b, it & 7);
+   const int run = blockIdx.x;
    const int n = b.n, m = b.m, mn = m*n;
    const float rn_f = 1.0f / (float) n;        // for div_n
    double * red = E.red; int * redi = E.redi; unsigned int * colmask_s = E.colmask_s;
@@ -1778,6 +1786,15 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
    if (b.phase_cycles && tid == 0) E.phc_s[6] += num_limadjs;   // rounds (phc[7]: kinds of rounds, see LimResult)
    return num_limadjs;
 }
+template <typename real, bool TREE, bool GS16, int BLOCK, int WGS = 0, int LEAN = 0>
+__device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in, int leapfrog_first_in)
+{
+   KArg<real> & b = *uniform_kernarg<real>(kp);
+   const int it = uni(it_in), leapfrog_first = uni(leapfrog_first_in);
+   const Env<real> E = make_env<real, GS16>(b, orc_smem);
+   const int tid = orc_tid<BLOCK>(b, it & 7);
+   return phase_update_body<real, TREE, GS16, BLOCK, WGS, LEAN>(kp, b, E, tid, it, leapfrog_first);
+}
 
 // ---- the two costs of a pass: obstacle cost of the trajectory the gradient was taken at
 // (chomp.c:484-491: the sum the cost phase left in the lanes, over m) and smoothness cost of the
@@ -1785,13 +1802,9 @@ __device__ __attribute__((noinline)) int phase_update(const void * kp, int it_in
 // quaternion renormalisation of the same iteration, as in the reference (cd_chomp_iterate returns
 // before mod.cpp:2806-2808 runs); then that renormalisation.
 struct PassCosts { double obs, smooth; };
-template <typename real, bool GS16, int BLOCK, int WGS = 0>
-__device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int do_iteration_in, double cost_lane)
+template <typename real, bool GS16, int BLOCK>
+__device__ __forceinline__ PassCosts phase_costs_body(const void * kp, KArg<real> & b, const Env<real> & E, int tid, bool do_iteration, double cost_lane)
 {
-   KArg<real> & b = *uniform_kernarg<real>(kp);
-   const bool do_iteration = packed_arg(uni(do_iteration_in)) != 0;
-   const Env<real> E = make_env<real, GS16>(b, orc_smem);
-   const int tid = orc_tid<BLOCK>(b, packed_it(uni(do_iteration_in)));
    const int n = b.n, m = b.m, np = b.n_points, mn = m*n;
    const float rn_f = 1.0f / (float) n;
    const real * T_s = E.T_u;
@@ -1856,6 +1869,39 @@ __device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int 
    }
    if (b.conv_patience && do_iteration) conv_step<real>(b, pc.obs, pc.smooth, tid);
    return pc;
+}
+// the cost-only pass that ends a call (do_iteration == false: no update in front of it, it stages the trajectory itself), and the
+// second of the two calls of the general update mode, which is not fused
+template <typename real, bool GS16, int BLOCK, int WGS = 0>
+__device__ __attribute__((noinline)) PassCosts phase_costs(const void * kp, int do_iteration_in, double cost_lane)
+{
+   KArg<real> & b = *uniform_kernarg<real>(kp);
+   const bool do_iteration = packed_arg(uni(do_iteration_in)) != 0;
+   const Env<real> E = make_env<real, GS16>(b, orc_smem);
+   const int tid = orc_tid<BLOCK>(b, packed_it(uni(do_iteration_in)));
+   return phase_costs_body<real, GS16, BLOCK>(kp, b, E, tid, do_iteration, cost_lane);
+}
+
+// ---- update and costs of an iteration in one call: both run on every wavefront, one straight after the other, on the same (staged)
+// trajectory, so the second call's register saves, kernarg reference, LDS views and thread index are saved.  The costs part is
+// not made when the limit rounds gave up (chomp.c:651-655: the caller sets status -1 and leaves the loop) ----
+struct UpdateCosts { double obs, smooth; int num_limadjs; };
+template <typename real, bool TREE, bool GS16, int BLOCK, int WGS = 0, int LEAN = 0>
+__device__ __attribute__((noinline)) UpdateCosts phase_update_costs(const void * kp, int it_in, int leapfrog_first_in, double cost_lane)
+{
+   KArg<real> & b = *uniform_kernarg<real>(kp);
+   const int it = uni(it_in), leapfrog_first = uni(leapfrog_first_in);
+   const Env<real> E = make_env<real, GS16>(b, orc_smem);
+   const int tid = orc_tid<BLOCK>(b, it & 7);
+   UpdateCosts uc;
+   uc.obs = 0.0; uc.smooth = 0.0;
+   uc.num_limadjs = uni(phase_update_body<real, TREE, GS16, BLOCK, WGS, LEAN>(kp, b, E, tid, it, leapfrog_first));
+   if (uc.num_limadjs < 1000)
+   {
+      const PassCosts pc = phase_costs_body<real, GS16, BLOCK>(kp, b, E, tid, true, cost_lane);
+      uc.obs = pc.obs; uc.smooth = pc.smooth;
+   }
+   return uc;
 }
 
 // ---- write back: trajectory, momentum, costs, status ----
@@ -1939,11 +1985,17 @@ void chomp_iterate_kernel(const DevBatch<real> b)
    double done_obs = 0.0, done_smooth = 0.0;
    int have_costs = 0;
    int iters_done = 0;
-   const int total_passes = b.n_iter + (b.final_eval ? 1 : 0);
 
-   for (int it=0; it<total_passes; it++)
+   // The loop carries across the phase calls only what crosses iterations (kp, it, tk, status, leapfrog_first, next_resample,
+   // iters_done, have_costs, done_obs, done_smooth, cost_lane).  Every field of the kernarg block it tests is read where it is
+   // tested, through a reference formed anew after each call (fresh_kernarg: the compiler cannot tell it from a new address, so it
+   // keeps no field alive across a call -- a scalar load from the scalar cache instead of a register carried through VGPR lanes
+   // around every call; this target has no scalar spill to memory)
+   KArg<real> * bp = fresh_kernarg<real>(kp);
+   for (int it=0; it<bp->n_iter + (bp->final_eval ? 1 : 0); it++)
    {
-      const bool do_iteration = (it < b.n_iter);
+      bp = fresh_kernarg<real>(kp);
+      const bool do_iteration = (it < bp->n_iter);
       // the convergence stop (orc_batch_set_convergence): phase_costs raised the flag after the run's last complete
       // iteration; its remaining iterations are passed over, on to the final cost-only pass, so that the run ends exactly
       // where a call of that many iterations leaves it.  (Passing over rather than leaving the loop: a loop exit or a jump
@@ -1951,8 +2003,8 @@ void chomp_iterate_kernel(const DevBatch<real> b)
       if (do_iteration && uni(conv_state()->stop)) continue;
 
       // ---- hmc momentum resample (src/orcdchomp_mod.cpp:2755-2768) ----------
-      if (do_iteration && b.use_hmc && b.use_momentum && next_resample < b.max_resamples
-          && b.hmc_iters[(size_t) run * b.max_resamples + next_resample] == it)
+      if (do_iteration && bp->use_hmc && bp->use_momentum && next_resample < bp->max_resamples
+          && bp->hmc_iters[(size_t) run * bp->max_resamples + next_resample] == it)
       {
          phase_hmc<real, GS16, BLOCK, WGS>(kp, pack_it(next_resample, it));
          leapfrog_first = 1;
@@ -1960,10 +2012,12 @@ void chomp_iterate_kernel(const DevBatch<real> b)
       }
 
       double cost_lane = 0.0;
-      for (int tk=0; tk<b.n_tiles; tk++)
+      for (int tk=0; ; tk++)
       {
-         const int ts = (tk == 0) ? 0 : b.tile_first + (tk - 1) * b.tile_rest;
-         const int te = (tk == b.n_tiles - 1) ? b.m : b.tile_first + tk * b.tile_rest;
+         bp = fresh_kernarg<real>(kp);
+         if (!(tk < bp->n_tiles)) break;
+         const int ts = (tk == 0) ? 0 : bp->tile_first + (tk - 1) * bp->tile_rest;
+         const int te = (tk == bp->n_tiles - 1) ? bp->m : bp->tile_first + tk * bp->tile_rest;
          // (the tile's end as the phases take it, with the iteration's bits for their rotation: formed here, behind an empty asm,
          // so that no part of it is a loop invariant the compiler would carry across the calls)
          int itv = it;
@@ -1972,14 +2026,14 @@ void chomp_iterate_kernel(const DevBatch<real> b)
          // ORC_STAGGER_MODE=9 (a timing experiment, wrong results): only the first tile is walked and a pause stands in for a
          // barrier across workgroups -- what an iteration of ONE run would take with its tiles on as many CUs
          // (scripts/single_run_latency.py, profiles/r04_single_run_ceiling.txt)
-         if (b.stagger_mode == 9 && tk > 0) { if (tk == 1) for (int k=0; k<b.stagger_sleeps; k++) __builtin_amdgcn_s_sleep(10); continue; }
+         if (bp->stagger_mode == 9 && tk > 0) { if (tk == 1) for (int k=0; k<bp->stagger_sleeps; k++) __builtin_amdgcn_s_sleep(10); continue; }
 #ifndef ORC_ABLATE_FK
          // a wavefront without a waypoint in the tile (20 per wavefront: the second of a 128-thread workgroup in each of its tiles of 14)
          // only joins the phase's barrier: it saves the call's ~120 scalar registers moved through the vector pipe
          // (the FK groups go to the last logical wavefronts, wave_roles.h: it is the first ones that have nothing to walk.  Without a
          // rotation the logical wavefront is the hardware's; under ORC_WAVE_ROTATE every wavefront makes the call and the idle ones
          // find nothing to walk inside it: forming the rotation here cost the kernel function a spilled register)
-         if (!b.ms.fk_split && !b.wave_rotate && orc::fk_wave_idle(uni((int)(threadIdx.x >> 6)), BLOCK, 1, te - ts + 2)) __syncthreads();
+         if (!bp->ms.fk_split && !bp->wave_rotate && orc::fk_wave_idle(uni((int)(threadIdx.x >> 6)), BLOCK, 1, te - ts + 2)) __syncthreads();
          else phase_fk<real, TREE, GS16, BLOCK, WGS>(kp, ts, tep);      // (skipping the call for the wavefronts without a waypoint in the tile -- their share of the callee-saved registers -- measured nothing: profiles/r04_ab_experiments.txt)
 #ifdef ORC_ABLATE_FKTWICE      // timing experiments: the FK phase twice (what a 2x slower FK would cost)
          phase_fk<real, TREE, GS16, BLOCK, WGS>(kp, ts, tep);
@@ -1995,30 +2049,45 @@ void chomp_iterate_kernel(const DevBatch<real> b)
          else
          cost_lane = do_iteration ? phase_cost<real, TREE, GS16, BLOCK, KIND, true, WGS>(kp, ts, tep, cost_lane)
                                   : phase_cost<real, TREE, GS16, BLOCK, KIND, false, WGS>(kp, ts, tep, cost_lane);
-         if (tk == 0 && b.free_start) cost_lane = phase_cost_start<real, TREE, GS16, BLOCK, WGS>(kp, pack_it(do_iteration ? 1 : 0, it), cost_lane);
+         bp = fresh_kernarg<real>(kp);
+         if (tk == 0 && bp->free_start) cost_lane = phase_cost_start<real, TREE, GS16, BLOCK, WGS>(kp, pack_it(do_iteration ? 1 : 0, it), cost_lane);
 #endif
       } // tiles
 
+      // update and costs of an iteration in one call (phase_update_costs) for the two lean update modes.  The general mode keeps
+      // its two calls: fused, its frame is larger than the update's alone (NOTES/call-overhead.md), and that frame lies on the
+      // deepest call chain of the kernel.  The cost-only pass that ends a call has no update in front of it
+      PassCosts pc;
+      bp = fresh_kernarg<real>(kp);
+      const bool lean = bp->solve_mode == 2 && bp->n <= 64 && !bp->lim_generic && bp->Gdbg == nullptr;      // (workgroup-uniform)
       if (do_iteration)
       {
-         const bool lean = b.solve_mode == 2 && b.n <= 64 && !b.lim_generic && b.Gdbg == nullptr;      // (workgroup-uniform)
-         const int num_limadjs = !lean ? uni(phase_update<real, TREE, GS16, BLOCK, WGS, 0>(kp, it, leapfrog_first))
-                               : (b.n_tsrs == 0 ? uni(phase_update<real, TREE, GS16, BLOCK, WGS, 1>(kp, it, leapfrog_first))
-                                                : uni(phase_update<real, TREE, GS16, BLOCK, WGS, 2>(kp, it, leapfrog_first)));
-         if (b.use_momentum) leapfrog_first = 0;
-         if (!(num_limadjs < 1000)) status = -1;
+         int num_limadjs;
+         if (!lean) num_limadjs = uni(phase_update<real, TREE, GS16, BLOCK, WGS, 0>(kp, it, leapfrog_first));
+         else
+         {
+            const UpdateCosts uc = (bp->n_tsrs == 0) ? phase_update_costs<real, TREE, GS16, BLOCK, WGS, 1>(kp, it, leapfrog_first, cost_lane)
+                                                     : phase_update_costs<real, TREE, GS16, BLOCK, WGS, 2>(kp, it, leapfrog_first, cost_lane);
+            num_limadjs = uni(uc.num_limadjs);
+            pc.obs = uc.obs; pc.smooth = uc.smooth;
+         }
+         bp = fresh_kernarg<real>(kp);
+         if (bp->use_momentum) leapfrog_first = 0;
+         // "ran too many joint limit fixes! aborting ..." (chomp.c:651-655): cd_chomp_iterate returns
+         // before the smoothness cost, mod::iterate throws before the quaternion renormalisation and
+         // the log line; the trajectory keeps what the limit rounds made of it (workgroup-uniform)
+         if (!(num_limadjs < 1000)) { status = -1; break; }
       }
-      // "ran too many joint limit fixes! aborting ..." (chomp.c:651-655): cd_chomp_iterate returns
-      // before the smoothness cost, mod::iterate throws before the quaternion renormalisation and
-      // the log line; the trajectory keeps what the limit rounds made of it (workgroup-uniform)
-      if (status != 0) break;
-
-      PassCosts pc = phase_costs<real, GS16, BLOCK, WGS>(kp, pack_it(do_iteration ? 1 : 0, it), cost_lane);
+      if (!do_iteration || !lean)
+      {
+         pc = phase_costs<real, GS16, BLOCK, WGS>(kp, pack_it(do_iteration ? 1 : 0, it), cost_lane);
+         bp = fresh_kernarg<real>(kp);
+      }
       pc.obs = unir(pc.obs); pc.smooth = unir(pc.smooth);
 
-      if (threadIdx.x == 0 && b.trace && do_iteration)      // (wave-uniform values: any one thread)
+      if (threadIdx.x == 0 && bp->trace && do_iteration)      // (wave-uniform values: any one thread)
       {
-         double * tr = b.trace + ((size_t) run * b.n_iter + it) * 3;
+         double * tr = bp->trace + ((size_t) run * bp->n_iter + it) * 3;
          tr[0] = pc.obs + pc.smooth; tr[1] = pc.obs; tr[2] = pc.smooth;
       }
       done_obs = pc.obs; done_smooth = pc.smooth; have_costs = 1;
