@@ -392,6 +392,48 @@ int orc_batch_select_best(orc_module * mod, int batch_id, int n_groups, const in
 int orc_batch_select_best_by(orc_module * mod, int batch_id, int cost_column, int n_groups,
    const int * group_of_run, int require_collision_free,
    int * best_run_out, double * best_cost_out, int * n_eligible_out);
+/* Successive halving between two iterate calls: every group keeps its best `keep` runs, and every other run of the group
+ * becomes a freshly perturbed copy of one of them; a group with nothing worth keeping restarts from the straight line.
+ * cost_column, n_groups and group_of_run (NULL: contiguous equal blocks) mean what they mean in orc_batch_select_best_by.
+ * collision_mode 0 ignores the collision verdict, 1 requires a collision-free run, 2 prefers one.  The rule is respawn_plan
+ * of or_cdchomp_amd/module.py:
+ *   Candidates: a run whose status of the last iterate call is 0 or 1 and whose TOTAL cost is finite; with mode 1 a run that
+ *     collides is not a candidate (orc_batch_select_best's eligibility); with mode 2 it stays one but ranks behind every
+ *     collision-free candidate.  Modes 1 and 2 take the verdict of the current trajectories as orc_batch_select_best does
+ *     (orc_batch_collision_verdict_device's kernel; the keys stay on the device).
+ *   Order: a group's candidates ascending by (collides -- mode 2 only --, costs[run][cost_column] with -0 equal to +0, run
+ *     index).  The first min(keep, candidates) are the group's survivors: n_survivors_out [n_groups].
+ *   Sources: source_of_run_out [n_runs].  A survivor's source is its own index.  The other runs of the group, candidates or
+ *     not, in ascending run index: the j-th of them (from 0) gets the survivor of rank j mod n_survivors, so the best
+ *     survivor receives the most copies.  In a group without a survivor every run's source is -1, the straight line.
+ *   A survivor: no bit of it changes (trajectory, "AG", leapfrog_first).
+ *   Source s != r: the moving rows [1, n_points-1) of run r become those of run s; BOTH END ROWS OF r STAY, so the call is
+ *     meant for groups whose runs share start and goal.  "AG" and leapfrog_first of r become those of s.
+ *   Source -1: moving row i becomes s + (g - s) * i / (n_points - 1) column by column, s and g the run's own stored first
+ *     and last rows widened to double, evaluated in double in that order and rounded once to the batch's precision (the
+ *     statement create seeds with); "AG" = 0 and leapfrog_first = 1, as create leaves them.
+ *   Perturbation: with sigma > 0 every run that is not a survivor then receives exactly the displacement
+ *     orc_batch_perturb(sigma, seeds) would add to it on its new trajectory (seeds[r], the same scale, the clamp to the
+ *     joint limits); survivors receive none.  sigma == 0 clones only; seeds may then be NULL.
+ * Nothing else of a run changes: its scene, its orc_batch_set_run_params record (a clone continues under its OWN parameter
+ * set), its hmc stream, costs, status, trace and iterations done stay.  The costs on the device now describe trajectories
+ * that no longer exist, so the batch counts as not iterated: orc_batch_select_best[_by] and a second orc_batch_respawn are
+ * refused until the next iterate call (orc_batch_iterate with 0 iterations is enough).
+ * On the device: the host sorts the runs by group (a counting sort of n_runs ints) and uploads that table and the seeds; one
+ * workgroup per group ranks its members by counting, without atomics; one kernel copies, one perturbs.  The three run on
+ * the shard's stream behind one another with one synchronisation at the end (the verdict of modes 1 and 2 is
+ * orc_batch_collision_verdict_device's call in front of them); n_runs + n_groups ints come back and no trajectory crosses
+ * the link.  A module over several devices: every shard works on the groups it holds.  Outputs may be NULL.
+ * Rejected with a nonzero return and a message, before any device work, the batch unchanged bit for bit and the module
+ * usable: an unknown batch; a batch that has not been iterated since create or the last respawn; cost_column outside 0..2;
+ * collision_mode outside 0..2; keep < 1; n_groups < 1, a group_of_run entry outside [0, n_groups), or a NULL group_of_run
+ * with n_runs % n_groups != 0; a NaN, negative or infinite sigma; seeds == NULL with sigma > 0; every batch
+ * orc_batch_perturb rejects (floating base, start_tsr, a metric with the dense inverse only, m n > 20 136), whatever sigma
+ * is; a group whose runs lie on more than one shard of a module over several devices (no copy crosses devices); a group of
+ * more than 4 096 runs (the ranking kernel stages a group's keys in the LDS of one workgroup). */
+int orc_batch_respawn(orc_module * mod, int batch_id, int cost_column, int n_groups, const int * group_of_run,
+   int collision_mode, int keep, double sigma, const unsigned int * seeds,
+   int * source_of_run_out, int * n_survivors_out);
 /* The rows runs[0 .. n_sel) of what orc_batch_gettraj returns, gathered on the device and copied as n_sel n_points n
  * doubles: traj_out [n_sel][n_points][n].  An entry -1 (what orc_batch_select_best reports for a group without an
  * eligible run) gives a row of NaN; duplicates are allowed; runs that live on different shards work.  Any other entry

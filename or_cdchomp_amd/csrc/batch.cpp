@@ -24,9 +24,15 @@ hipError_t orc_launch_hmc_plan_f32(uint32_t * state, int * next, int n_runs, int
 // multistart_kernels.hip
 size_t orc_perturb_lds_bytes(int m, int n);
 hipError_t orc_launch_perturb_f64(double * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
-   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream);
+   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
+   const int * source_of_run, hipStream_t stream);
 hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
-   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream);
+   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
+   const int * source_of_run, hipStream_t stream);
+hipError_t orc_launch_respawn_rank(const double * costs, const int * status, const unsigned long long * verdict_key, int mode, int column, int keep,
+   int n_groups, const int * group_offs, const int * members, int max_group, int * source_of_run, int * n_survivors, hipStream_t stream);
+hipError_t orc_launch_respawn_copy(void * traj, void * AG, int precision, int * leapfrog_first, const int * source_of_run,
+   int n_runs, int n_points, int n, int m, hipStream_t stream);
 hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
    unsigned long long * key, int * count, int * best, hipStream_t stream);
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);
@@ -808,13 +814,58 @@ void BatchShard::perturb(double scale, const unsigned int * seeds, const std::ve
       hip_check(hipMemcpyAsync(d_seeds, seeds, n_runs*sizeof(unsigned int), hipMemcpyHostToDevice, st), "perturb seeds");
       const double * U = d_gen, * V = d_gen + (size_t) rank * m, * lo = d_gen + (size_t) 2 * rank * m, * hi = lo + n;
       hipError_t e;
-      if (params.precision == 64) e = orc_launch_perturb_f64(d_traj_.as<double>(), n_runs, n_points, n, m, d_seeds, rank, U, V, scale, lo, hi, lds, st);
-      else e = orc_launch_perturb_f32(d_traj_.as<float>(), n_runs, n_points, n, m, d_seeds, rank, U, V, scale, lo, hi, lds, st);
+      if (params.precision == 64) e = orc_launch_perturb_f64(d_traj_.as<double>(), n_runs, n_points, n, m, d_seeds, rank, U, V, scale, lo, hi, lds, nullptr, st);
+      else e = orc_launch_perturb_f32(d_traj_.as<float>(), n_runs, n_points, n, m, d_seeds, rank, U, V, scale, lo, hi, lds, nullptr, st);
       hip_check(e, "perturb_kernel launch");
       hip_check(hipStreamSynchronize(st), "perturb sync");
    }
    catch (...) { dev_free(d_gen); dev_free(d_seeds); throw; }
    dev_free(d_gen); dev_free(d_seeds);
+}
+
+void BatchShard::respawn(int n_groups, const std::vector<int> & group_offs, const std::vector<int> & members, int column, int mode, int keep,
+   double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank, int * source_out, int * n_survivors_out)
+{
+   DeviceGuard guard(device);
+   hipStream_t st = stream_;
+   if (mode != 0 && !d_vkey_) throw std::runtime_error("respawn: no collision verdict on the device!");
+   int max_group = 0;
+   for (int g=0; g<n_groups; g++) max_group = std::max(max_group, group_offs[g+1] - group_offs[g]);
+   // one upload of ints (the group table, then the members), one of doubles (the generators, then the limits of the columns)
+   std::vector<int> table(group_offs);
+   table.insert(table.end(), members.begin(), members.end());
+   std::vector<double> host(gen);
+   host.insert(host.end(), jl_lo_.begin(), jl_lo_.end());
+   host.insert(host.end(), jl_hi_.begin(), jl_hi_.end());
+   const bool move = scale > 0.0;
+   DevBuf d_table, d_out, d_gen, d_seeds;
+   d_table.reset(dev_alloc<int>(table.size()));
+   d_out.reset(dev_alloc<int>((size_t) n_runs + n_groups));      // source_of_run, then n_survivors
+   hip_check(hipMemcpyAsync(d_table.as<void>(), table.data(), table.size()*sizeof(int), hipMemcpyHostToDevice, st), "respawn groups");
+   int * d_source = d_out.as<int>(), * d_nsurv = d_source + n_runs;
+   const int * d_offs = d_table.as<int>(), * d_members = d_offs + group_offs.size();
+   hip_check(orc_launch_respawn_rank(d_costs_.as<double>(), d_status_.as<int>(), mode ? d_vkey_.as<unsigned long long>() : nullptr, mode, column, keep,
+      n_groups, d_offs, d_members, max_group, d_source, d_nsurv, st), "respawn_rank_kernel launch");
+   hip_check(orc_launch_respawn_copy(d_traj_.as<void>(), d_AG_.as<void>(), params.precision, d_leap_.as<int>(), d_source, n_runs, n_points, n, m, st),
+      "respawn_copy_kernel launch");
+   if (move)
+   {
+      d_gen.reset(dev_alloc<double>(host.size()));
+      d_seeds.reset(dev_alloc<unsigned int>(n_runs));
+      hip_check(hipMemcpyAsync(d_gen.as<void>(), host.data(), host.size()*sizeof(double), hipMemcpyHostToDevice, st), "respawn generators");
+      hip_check(hipMemcpyAsync(d_seeds.as<void>(), seeds, n_runs*sizeof(unsigned int), hipMemcpyHostToDevice, st), "respawn seeds");
+      const double * U = d_gen.as<double>(), * V = U + (size_t) rank * m, * lo = U + (size_t) 2 * rank * m, * hi = lo + n;
+      const size_t lds = orc_perturb_lds_bytes(m, n);
+      hipError_t e;
+      if (params.precision == 64) e = orc_launch_perturb_f64(d_traj_.as<double>(), n_runs, n_points, n, m, d_seeds.as<unsigned int>(), rank, U, V, scale, lo, hi, lds, d_source, st);
+      else e = orc_launch_perturb_f32(d_traj_.as<float>(), n_runs, n_points, n, m, d_seeds.as<unsigned int>(), rank, U, V, scale, lo, hi, lds, d_source, st);
+      hip_check(e, "perturb_kernel launch");
+   }
+   std::vector<int> back((size_t) n_runs + n_groups);
+   hip_check(hipMemcpyAsync(back.data(), d_out.as<void>(), back.size()*sizeof(int), hipMemcpyDeviceToHost, st), "respawn plan");
+   hip_check(hipStreamSynchronize(st), "respawn sync");
+   std::copy(back.begin(), back.begin() + n_runs, source_out);
+   std::copy(back.begin() + n_runs, back.end(), n_survivors_out);
 }
 
 void BatchShard::select_best(int n_groups, const int * group, bool collision_free, int column, unsigned long long * key_out, int * best_out, int * count_out)
@@ -1030,10 +1081,9 @@ void Batch::set_traj(const double * traj)
 }
 
 // ---- multi-start ----------------------------------------------------------------------------------------------------
-void Batch::perturb(double sigma, const unsigned int * seeds)
+Batch::PerturbPlan Batch::perturb_plan(double sigma) const
 {
    if (!(sigma >= 0.0) || !std::isfinite(sigma)) throw std::runtime_error("perturb: sigma must be a finite number >= 0!");
-   if (!seeds) throw std::runtime_error("null argument: seeds");
    if (params.floating_base) throw std::runtime_error("perturb: floating-base batches (quaternion columns) are not supported!");
    if (params.free_start) throw std::runtime_error("perturb: batches with a free start point (start_tsr) are not supported!");
    const Metric & M = shards[0]->metric();
@@ -1042,9 +1092,12 @@ void Batch::perturb(double sigma, const unsigned int * seeds)
       throw std::runtime_error("perturb: the device has only the dense inverse of this batch's metric (derivative > 4, or too few waypoints for it)!");
    if ((size_t) m * n > BatchShard::ORC_PERTURB_MAX_MN)
       throw std::runtime_error("perturb: the run's m x n Gaussians do not fit the LDS of one CU (m n <= " + std::to_string(BatchShard::ORC_PERTURB_MAX_MN) + ")!");
-   if (sigma == 0.0) return;
+   PerturbPlan plan;
+   plan.D = D;
+   if (sigma == 0.0) return plan;
    // the generators of A^-1: U [D][m], then V [D][m]
-   std::vector<double> gen((size_t) 2 * D * m);
+   std::vector<double> & gen = plan.gen;
+   gen.assign((size_t) 2 * D * m, 0.0);
    if (D == 1)
    {
       // A = a tridiag(-1, 2, -1) (both ends fixed): Ainv[i][j] = (i+1) (m-j) / ((m+1) a) for i <= j
@@ -1071,8 +1124,17 @@ void Batch::perturb(double sigma, const unsigned int * seeds)
    for (int i=0; i<m; i++) s2 += row[i] * row[i];
    if (!(s2 > 0.0) || !std::isfinite(s2)) throw std::runtime_error("perturb: the metric's inverse has no middle row!");
    const double c = 1.0 / std::sqrt(s2);
-   const double scale = sigma * c;
-   for_shards([&](size_t k) { shards[k]->perturb(scale, seeds + offs[k], gen, D); }, true);
+   plan.scale = sigma * c;
+   return plan;
+}
+
+void Batch::perturb(double sigma, const unsigned int * seeds)
+{
+   if (!(sigma >= 0.0) || !std::isfinite(sigma)) throw std::runtime_error("perturb: sigma must be a finite number >= 0!");
+   if (!seeds) throw std::runtime_error("null argument: seeds");
+   const PerturbPlan plan = perturb_plan(sigma);
+   if (sigma == 0.0) return;
+   for_shards([&](size_t k) { shards[k]->perturb(plan.scale, seeds + offs[k], plan.gen, plan.D); }, true);
 }
 
 std::vector<int> Batch::select_groups(int n_groups, const int * group_of_run) const
@@ -1099,6 +1161,64 @@ std::vector<int> Batch::select_groups(int n_groups, const int * group_of_run) co
 void Batch::select_column(int column)
 {
    if (column < 0 || column > 2) throw std::runtime_error("select_best_by: cost_column must be 0 (total), 1 (obs) or 2 (smooth)!");
+}
+
+Batch::RespawnPlan Batch::respawn_plan(int cost_column, int n_groups, const int * group_of_run, int collision_mode, int keep, double sigma,
+   const unsigned int * seeds) const
+{
+   if (!iterated) throw std::runtime_error("respawn: the batch has not been iterated since it was created or respawned (orc_batch_iterate with 0 iterations makes its costs valid)!");
+   select_column(cost_column);
+   if (collision_mode < 0 || collision_mode > 2) throw std::runtime_error("respawn: collision_mode must be 0 (ignore), 1 (require) or 2 (prefer)!");
+   if (keep < 1) throw std::runtime_error("respawn: keep must be >=1!");
+   const std::vector<int> group = select_groups(n_groups, group_of_run);
+   RespawnPlan plan;
+   plan.perturb = perturb_plan(sigma);
+   if (sigma > 0.0 && !seeds) throw std::runtime_error("null argument: seeds (respawn with sigma > 0)");
+   plan.column = cost_column; plan.mode = collision_mode; plan.keep = keep; plan.n_groups = n_groups;
+   // a counting sort of the runs by group: the members of a group ascending
+   std::vector<int> first(n_groups + 1, 0);
+   for (int r=0; r<n_runs; r++) first[group[r] + 1]++;
+   for (int g=0; g<n_groups; g++)
+   {
+      if (first[g+1] > BatchShard::ORC_RESPAWN_MAX_GROUP)
+         throw std::runtime_error("respawn: group " + std::to_string(g) + " has " + std::to_string(first[g+1]) + " runs, more than the ranking kernel takes (" + std::to_string(BatchShard::ORC_RESPAWN_MAX_GROUP) + ")!");
+      first[g+1] += first[g];
+   }
+   std::vector<int> sorted(n_runs), fill(first.begin(), first.end() - 1);
+   for (int r=0; r<n_runs; r++) sorted[fill[group[r]]++] = r;
+   // every group to the shard that holds its runs
+   plan.shards.resize(shards.size());
+   for (auto & sh : plan.shards) sh.group_offs.assign(1, 0);
+   for (int g=0; g<n_groups; g++)
+   {
+      if (first[g+1] == first[g]) continue;      // (a group without runs: no survivor, nothing to do)
+      size_t k = 0;
+      while (sorted[first[g]] >= offs[k+1]) k++;
+      if (sorted[first[g+1] - 1] >= offs[k+1])
+         throw std::runtime_error("respawn: the runs of group " + std::to_string(g) + " lie on more than one shard of the module's devices (a copy does not cross devices)!");
+      RespawnPlan::Shard & sh = plan.shards[k];
+      sh.groups.push_back(g);
+      for (int q=first[g]; q<first[g+1]; q++) sh.members.push_back(sorted[q] - offs[k]);
+      sh.group_offs.push_back((int) sh.members.size());
+   }
+   return plan;
+}
+
+void Batch::respawn(const RespawnPlan & plan, const unsigned int * seeds, int * source_of_run_out, int * n_survivors_out)
+{
+   std::vector<int> source(n_runs, -1), nsurv(plan.n_groups, 0);
+   iterated = false;      // whatever happens from here on: the device's costs no longer describe its trajectories
+   for_shards([&](size_t k) {
+      const RespawnPlan::Shard & sh = plan.shards[k];
+      if (sh.groups.empty()) return;
+      std::vector<int> ns(sh.groups.size());
+      shards[k]->respawn((int) sh.groups.size(), sh.group_offs, sh.members, plan.column, plan.mode, plan.keep, plan.perturb.scale,
+         seeds ? seeds + offs[k] : nullptr, plan.perturb.gen, plan.perturb.D, source.data() + offs[k], ns.data());
+      for (int r=offs[k]; r<offs[k+1]; r++) if (source[r] >= 0) source[r] += offs[k];
+      for (size_t q=0; q<sh.groups.size(); q++) nsurv[sh.groups[q]] = ns[q];
+   }, true);
+   if (source_of_run_out) std::copy(source.begin(), source.end(), source_of_run_out);
+   if (n_survivors_out) std::copy(nsurv.begin(), nsurv.end(), n_survivors_out);
 }
 
 void Batch::set_run_params(const double * lambda, const double * epsilon, const double * obs_factor, const double * obs_factor_self)

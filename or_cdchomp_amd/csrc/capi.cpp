@@ -639,6 +639,19 @@ int orc_batch_select_best_by(orc_module * mod, int id, int cost_column, int n_gr
    });
 }
 
+int orc_batch_respawn(orc_module * mod, int id, int cost_column, int n_groups, const int * group_of_run, int collision_mode, int keep,
+   double sigma, const unsigned int * seeds, int * source_of_run_out, int * n_survivors_out)
+{
+   return guarded(mod, [&] {
+      orc::Batch & b = mod->impl->batch(id);
+      // every argument first, on the host: a rejected call costs no kernel and changes no bit
+      const orc::Batch::RespawnPlan plan = b.respawn_plan(cost_column, n_groups, group_of_run, collision_mode, keep, sigma, seeds);
+      // the verdict of the current trajectories; its keys stay on the device, where the ranking reads them
+      if (collision_mode != 0) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      b.respawn(plan, seeds, source_of_run_out, n_survivors_out);
+   });
+}
+
 int orc_batch_set_run_params(orc_module * mod, int id, const double * lambda, const double * epsilon,
    const double * obs_factor, const double * obs_factor_self)
 {

@@ -112,6 +112,15 @@ public:
    // the device) names a contact is not eligible
    // column: which of costs[run][0..2] is minimised (eligibility always asks for a finite TOTAL cost)
    void select_best(int n_groups, const int * group, bool collision_free, int column, unsigned long long * key_out, int * best_out, int * count_out);
+   // respawn (orc_batch_respawn): the largest group the ranking kernel takes (14 bytes of LDS per member: 56 KB)
+   static constexpr int ORC_RESPAWN_MAX_GROUP = 4096;
+   // This shard's groups as a CSR over its LOCAL runs (group_offs [n_groups + 1], members ascending per group, every run in one
+   // group): ranks every group, makes every run that does not survive a copy of its source or the straight line, perturbs those
+   // runs when scale > 0 (seeds, gen, rank: as in perturb).  mode 1, 2: the keys of the collision_verdict_planned made just
+   // before.  One synchronisation, at the end; source_out [n_runs] (local runs, -1: the line) and n_survivors_out [n_groups]
+   // are what comes back
+   void respawn(int n_groups, const std::vector<int> & group_offs, const std::vector<int> & members, int column, int mode, int keep,
+      double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank, int * source_out, int * n_survivors_out);
    // per-run lambda, epsilon, obs_factor, obs_factor_self of this shard's runs (orc_batch_set_run_params): table [n_runs][4] doubles,
    // validated by Batch::set_run_params, converted to the batch's precision here and uploaded on the shard's stream (so that launches
    // enqueued before keep the old values); NULL: the later launches read no table
@@ -226,6 +235,22 @@ public:
    void set_traj(const double * traj);
    // multi-start: orc_batch_perturb / _select_best / _gettraj_runs (include/orcdchomp_amd.h has the contract)
    void perturb(double sigma, const unsigned int * seeds);
+   // what a perturbation of this batch needs: the generators of A^-1 (U [D][m], then V [D][m]) and sigma c; throws for a bad
+   // sigma and for the batches orc_batch_perturb rejects, whatever sigma is; sigma == 0: scale 0 and no generators
+   struct PerturbPlan { std::vector<double> gen; int D = 0; double scale = 0.0; };
+   PerturbPlan perturb_plan(double sigma) const;
+   // respawn (orc_batch_respawn): respawn_plan checks every argument and builds the shards' group tables without any device
+   // work (throws); respawn then runs on every shard that has a group.  The verdict, for mode 1 and 2, is taken between the two
+   struct RespawnPlan
+   {
+      int column = 0, mode = 0, keep = 1, n_groups = 0;
+      PerturbPlan perturb;
+      struct Shard { std::vector<int> groups, group_offs, members; };      // the shard's groups (the caller's numbers), their CSR over local runs
+      std::vector<Shard> shards;
+   };
+   RespawnPlan respawn_plan(int cost_column, int n_groups, const int * group_of_run, int collision_mode, int keep, double sigma,
+      const unsigned int * seeds) const;
+   void respawn(const RespawnPlan & plan, const unsigned int * seeds, int * source_of_run_out, int * n_survivors_out);
    std::vector<int> select_groups(int n_groups, const int * group_of_run) const;   // the validated group of every run (NULL: contiguous equal blocks); throws
    // collision_free: the runs' keys of the collision_verdict_planned made just before (they never left the device)
    // column 0 total, 1 obs, 2 smooth: the cost that is minimised and reported (validate with select_column first)

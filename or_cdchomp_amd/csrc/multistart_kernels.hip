@@ -1,5 +1,6 @@
 // multistart_kernels.hip -- multi-start batches: perturbed seed trajectories, the best run per problem, the rows of the
-// winners, all on the device (orc_batch_perturb, orc_batch_select_best, orc_batch_gettraj_runs).
+// winners, the losing runs respawned from the winners, all on the device (orc_batch_perturb, orc_batch_select_best,
+// orc_batch_gettraj_runs, orc_batch_respawn).
 //
 // The reference has no multi-start; K runs of one planning problem start from one straight line (seed_traj_kernel) and are
 // K identical runs unless something diversifies them.  perturb_kernel adds to the moving waypoints of every run a smooth
@@ -35,13 +36,16 @@ __device__ __forceinline__ double wave_suffix_excl(double v)      // sum over th
 // lane l owns the rows [l R, (l+1) R), R = ceil(m / 64), of every column: its partial sums go through one prefix and one suffix wave scan per generator, then it walks its rows.
 // A run's result depends on its seed, the scale and the batch's parameters only: nothing here reads the run's index
 // but the addresses.
+// source_of_run: NULL (orc_batch_perturb: every run), or the plan of a respawn: a run that is its own source is a survivor
+// and its workgroup leaves it alone.
 template <typename real>
 __global__ __launch_bounds__(64)
 void perturb_kernel(real * traj, int n_points, int n, int m, const unsigned int * seeds, int D,
-   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi)
+   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, const int * source_of_run)
 {
    extern __shared__ double smem[];
    const int run = blockIdx.x, lane = threadIdx.x & 63;
+   if (source_of_run && source_of_run[run] == run) return;      // (the whole workgroup: nobody waits at a barrier)
    const size_t mn = (size_t) m * n;
    double * x = smem;
    MtWave g; g.mt = (uint32_t *)(smem + mn);
@@ -135,10 +139,121 @@ __global__ void gather_rows_kernel(const real * traj, const int * rows, int n_se
    for (int q=blockIdx.y; q<n_sel; q+=gridDim.y) out[(size_t) q * row_len + e] = (double) traj[(size_t) rows[q] * row_len + e];
 }
 
+// ---- respawn: every group's survivors, and the losing runs made copies of them (orc_batch_respawn) -------------------
+// One workgroup of four wavefronts per group; the group's runs are members[group_offs[g] .. group_offs[g+1]), ascending.
+// A member's order key is (class, cost_key of its cost column, its position in the list): class 0 a candidate, 1 a candidate
+// that collides (mode 2: behind every free one), 2 not a candidate (behind everything; never ranked).  The keys are staged
+// in LDS; a wavefront takes one member at a time and its lanes 64 others, and the member's rank is the number of set bits
+// of the ballots "this one comes before it": a count, no atomics, the same whatever the schedule.  Then the first
+// wavefront walks the list once, 64 positions a step, numbers the runs that do not survive by a prefix count of the
+// survivors' ballot and deals them the survivors in rank order, round and round.
+// LDS per member: the key (8 bytes), the survivor of its rank (4), its class (1), whether it survives (1).
+__global__ __launch_bounds__(256)
+void respawn_rank_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, int mode, int column, int keep,
+   const int * group_offs, const int * members, int * source_of_run, int * n_survivors)
+{
+   extern __shared__ double smem[];
+   const int g = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+   const int G = group_offs[g+1] - group_offs[g];
+   const int * mem = members + group_offs[g];
+   if (G <= 0) { if (tid == 0) n_survivors[g] = 0; return; }
+   unsigned long long * key = (unsigned long long *) smem;
+   int * surv = (int *)(key + G);
+   unsigned char * cls = (unsigned char *)(surv + G);
+   unsigned char * stays = cls + G;
+   for (int i=tid; i<G; i+=256)
+   {
+      const int r = mem[i], st = status[r];
+      const bool hit = mode != 0 && verdict_key[r] != ORC_VERDICT_NONE;
+      const bool cand = (st == 0 || st == 1) && isfinite(costs[(size_t) r*3]) && !(mode == 1 && hit);
+      cls[i] = cand ? ((mode == 2 && hit) ? 1 : 0) : 2;
+      key[i] = cost_key(costs[(size_t) r*3 + column]);
+   }
+   __syncthreads();
+   int n_cand = 0;      // (every wavefront counts for itself)
+   for (int j0=0; j0<G; j0+=64)
+   {
+      const int j = j0 + lane;
+      n_cand += __popcll(__builtin_amdgcn_ballot_w64(j < G && cls[j] < 2));
+   }
+   const int n_surv = keep < n_cand ? keep : n_cand;
+   for (int i=wave; i<G; i+=4)
+   {
+      const int ci = cls[i];
+      const unsigned long long ki = key[i];
+      if (ci == 2) { if (lane == 0) stays[i] = 0; continue; }      // (the same for the whole wavefront)
+      int rank = 0;
+      for (int j0=0; j0<G; j0+=64)
+      {
+         const int j = j0 + lane;
+         bool before = false;
+         if (j < G)
+         {
+            const int cj = cls[j];
+            const unsigned long long kj = key[j];
+            before = cj < ci || (cj == ci && (kj < ki || (kj == ki && j < i)));
+         }
+         rank += __popcll(__builtin_amdgcn_ballot_w64(before));
+      }
+      if (lane == 0)
+      {
+         stays[i] = rank < n_surv;
+         if (rank < n_surv) surv[rank] = mem[i];
+      }
+   }
+   __syncthreads();
+   if (wave != 0) return;
+   int below = 0;      // survivors in front of this step's positions
+   for (int j0=0; j0<G; j0+=64)
+   {
+      const int j = j0 + lane;
+      const bool s = j < G && stays[j];
+      const unsigned long long mask = __builtin_amdgcn_ballot_w64(s);
+      if (j < G)
+      {
+         const int loser = j - (below + __popcll(mask & ((1ull << lane) - 1ull)));      // its number among the group's other runs
+         const int r = mem[j];
+         source_of_run[r] = s ? r : (n_surv ? surv[loser % n_surv] : -1);
+      }
+      below += __popcll(mask);
+   }
+   if (lane == 0) n_survivors[g] = n_surv;
+}
+
+// One workgroup per run; a survivor (its own source) is not touched, so a source is never written: safe in place.  The
+// line is seed_traj_kernel's statement on the run's own stored ends.
+template <typename real>
+__global__ __launch_bounds__(256)
+void respawn_copy_kernel(real * traj, real * AG, int * leapfrog_first, const int * source_of_run, int n_points, int n, int m)
+{
+   const int r = blockIdx.x, s = source_of_run[r];
+   if (s == r) return;
+   const size_t mn = (size_t) m * n;
+   real * T = traj + ((size_t) r * n_points + 1) * n;      // (the moving rows: both ends are fixed)
+   real * A = AG + (size_t) r * mn;
+   if (s >= 0)
+   {
+      const real * Ts = traj + ((size_t) s * n_points + 1) * n;
+      const real * As = AG + (size_t) s * mn;
+      for (size_t e=threadIdx.x; e<mn; e+=blockDim.x) { T[e] = Ts[e]; A[e] = As[e]; }
+      if (threadIdx.x == 0) leapfrog_first[r] = leapfrog_first[s];
+      return;
+   }
+   const real * first = traj + (size_t) r * n_points * n, * last = first + (size_t)(n_points - 1) * n;
+   for (size_t e=threadIdx.x; e<mn; e+=blockDim.x)
+   {
+      const int i = (int)(e / n) + 1, c = (int)(e % n);
+      const double sv = (double) first[c], gv = (double) last[c];
+      T[e] = (real)(sv + (gv - sv) * i / (n_points - 1));
+      A[e] = (real) 0;
+   }
+   if (threadIdx.x == 0) leapfrog_first[r] = 1;
+}
+
 template <typename real>
 hipError_t launch_perturb(real * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
    const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
-   hipStream_t stream)
+   const int * source_of_run, hipStream_t stream)
 {
    if (lds > 64 * 1024)
    {
@@ -146,7 +261,7 @@ hipError_t launch_perturb(real * traj, int n_runs, int n_points, int n, int m, c
       if (e != hipSuccess) return e;
    }
    hipLaunchKernelGGL(perturb_kernel<real>, dim3(n_runs), dim3(64), lds, stream, traj, n_points, n, m, seeds, D, genU, genV, scale,
-      lim_lo, lim_hi);
+      lim_lo, lim_hi, source_of_run);
    return hipGetLastError();
 }
 
@@ -157,15 +272,41 @@ size_t orc_perturb_lds_bytes(int m, int n)
 {
    return (size_t) m * n * sizeof(double) + 624 * sizeof(uint32_t);
 }
+// source_of_run: NULL, or the plan of a respawn (its survivors are skipped)
 hipError_t orc_launch_perturb_f64(double * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
-   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream)
+   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
+   const int * source_of_run, hipStream_t stream)
 {
-   return launch_perturb<double>(traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, stream);
+   return launch_perturb<double>(traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, source_of_run, stream);
 }
 hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
-   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds, hipStream_t stream)
+   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
+   const int * source_of_run, hipStream_t stream)
 {
-   return launch_perturb<float>(traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, stream);
+   return launch_perturb<float>(traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, source_of_run, stream);
+}
+// LDS of a group's workgroup: 14 bytes per member of the largest group (the caller refuses groups over
+// BatchShard::ORC_RESPAWN_MAX_GROUP, module.h: 56 KB, inside what a kernel has without asking)
+size_t orc_respawn_rank_lds_bytes(int max_group)
+{
+   return ((size_t) max_group * 14 + 15) & ~(size_t) 15;
+}
+// verdict_key may be NULL with mode 0; source_of_run [n_runs of the shard] and n_survivors [n_groups] are written in full
+// when every run is a member of one group
+hipError_t orc_launch_respawn_rank(const double * costs, const int * status, const unsigned long long * verdict_key, int mode, int column, int keep,
+   int n_groups, const int * group_offs, const int * members, int max_group, int * source_of_run, int * n_survivors, hipStream_t stream)
+{
+   if (n_groups < 1) return hipSuccess;
+   hipLaunchKernelGGL(respawn_rank_kernel, dim3(n_groups), dim3(256), orc_respawn_rank_lds_bytes(max_group), stream, costs, status, verdict_key,
+      mode, column, keep, group_offs, members, source_of_run, n_survivors);
+   return hipGetLastError();
+}
+hipError_t orc_launch_respawn_copy(void * traj, void * AG, int precision, int * leapfrog_first, const int * source_of_run,
+   int n_runs, int n_points, int n, int m, hipStream_t stream)
+{
+   if (precision == 64) hipLaunchKernelGGL(respawn_copy_kernel<double>, dim3(n_runs), dim3(256), 0, stream, (double *) traj, (double *) AG, leapfrog_first, source_of_run, n_points, n, m);
+   else hipLaunchKernelGGL(respawn_copy_kernel<float>, dim3(n_runs), dim3(256), 0, stream, (float *) traj, (float *) AG, leapfrog_first, source_of_run, n_points, n, m);
+   return hipGetLastError();
 }
 // key [n_groups] (all bits set), count [n_groups] (0) and best [n_groups] (INT_MAX) are the caller's to initialise
 hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,

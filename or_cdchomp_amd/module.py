@@ -216,6 +216,77 @@ def select_best(costs, status, collides, group_of_run, n_groups, column=0):
     return best_run, best_cost, n_eligible
 
 
+def cost_key(c):
+    """A cost as the unsigned key of the same order that the device compares (cost_key of csrc/multistart_kernels.hip): the
+    bits of c + 0.0, so that -0 is +0, inverted for a negative number and with the sign bit set otherwise.  Python int."""
+    b = int((np.float64(c) + np.float64(0.0)).view(np.uint64))
+    return (~b) & 0xFFFFFFFFFFFFFFFF if b >> 63 else b | 0x8000000000000000
+
+
+def respawn_plan(costs, status, collides, group_of_run, n_groups, keep, mode=2, column=0):
+    """The rule of orc_batch_respawn: which runs of every group survive and what every other run becomes a copy of.  costs
+    [n_runs][3] rows as batch_iterate returns them (or [n_runs] total costs with column 0), status [n_runs], collides
+    [n_runs] (may be None with mode 0), group_of_run [n_runs] with entries in [0, n_groups).
+    A run is a candidate when its status is 0 or 1 and its TOTAL cost is finite; mode 0 ignores the verdict, mode 1 drops a
+    colliding run from the candidates (select_best's eligibility), mode 2 keeps it but ranks it behind every collision-free
+    candidate.  A group's candidates are ordered by (collides -- mode 2 only --, cost_key(costs[run][column]), run index),
+    ascending; the first min(keep, candidates) are its survivors.  A survivor's source is itself; the group's other runs,
+    candidates or not, in ascending run index: the j-th gets the survivor of rank j mod n_survivors; in a group without a
+    survivor every run's source is -1, the straight line.  Returns (source_of_run int32 [n_runs], n_survivors int32
+    [n_groups]).  Pure numpy."""
+    costs = np.asarray(costs, dtype=np.float64)
+    if column not in (0, 1, 2):
+        raise ValueError("column is 0 (total), 1 (obs) or 2 (smooth)")
+    if mode not in (0, 1, 2):
+        raise ValueError("mode is 0 (ignore), 1 (require) or 2 (prefer)")
+    if keep < 1:
+        raise ValueError("keep must be >= 1")
+    total = costs[:, 0] if costs.ndim == 2 else costs
+    if costs.ndim == 2:
+        costs = costs[:, column]
+    elif column != 0:
+        raise ValueError("a column other than 0 needs the [n_runs][3] cost rows")
+    status = np.asarray(status).reshape(-1)
+    group = np.asarray(group_of_run).reshape(-1)
+    n_runs = costs.shape[0]
+    if status.shape[0] != n_runs or group.shape[0] != n_runs:
+        raise ValueError("costs, status and group_of_run have one entry per run")
+    if n_groups < 1 or (n_runs and (group.min() < 0 or group.max() >= n_groups)):
+        raise ValueError("group_of_run entries must lie in [0, n_groups)")
+    if mode == 0:
+        hit = np.zeros(n_runs, dtype=bool)
+    else:
+        if collides is None:
+            raise ValueError("modes 1 and 2 need the collision verdict")
+        hit = np.asarray(collides).reshape(-1) != 0
+        if hit.shape[0] != n_runs:
+            raise ValueError("collides has one entry per run")
+    candidate = ((status == 0) | (status == 1)) & np.isfinite(total)
+    if mode == 1:
+        candidate &= ~hit
+    source = np.full(n_runs, -1, dtype=np.int32)
+    n_survivors = np.zeros(n_groups, dtype=np.int32)
+    members = [[] for _ in range(n_groups)]
+    for r in range(n_runs):
+        members[int(group[r])].append(r)
+    for g in range(n_groups):
+        order = sorted((r for r in members[g] if candidate[r]),
+                       key=lambda r: (int(hit[r]) if mode == 2 else 0, cost_key(costs[r]), r))
+        survivors = order[:min(int(keep), len(order))]
+        n_survivors[g] = len(survivors)
+        if not survivors:
+            continue
+        kept = set(survivors)
+        j = 0
+        for r in members[g]:
+            if r in kept:
+                source[r] = r
+            else:
+                source[r] = survivors[j % len(survivors)]
+                j += 1
+    return source, n_survivors
+
+
 RUN_PARAMS = ("lambda", "epsilon", "obs_factor", "obs_factor_self")      # the columns of the "run_params" read-back
 
 
@@ -599,6 +670,44 @@ class Module:
                                                            None if gp is None else _ip(gp), 1 if collision_free else 0,
                                                            _ip(best), _dp(cost), _ip(cnt)))
         return best[:n_groups], cost[:n_groups], cnt[:n_groups]
+
+    def batch_respawn(self, bid, keep, sigma, seeds, groups=None, n_groups=None, collision="prefer", by="total"):
+        """Successive halving between two iterate calls, on the device (orc_batch_respawn; the rule is respawn_plan's):
+        every group keeps its best `keep` runs untouched, and every other run of the group becomes a copy of one of them
+        (moving waypoints, momentum), perturbed like batch_perturb(sigma, seeds) would perturb it; a group without a
+        candidate restarts from the straight line.  The runs of a group are meant to share start and goal: a copy keeps
+        its own end rows.  collision: "ignore", "require" (a colliding run is no candidate) or "prefer" (it ranks behind
+        every collision-free one); by: "total", "obs" or "smooth", the cost that orders the candidates; groups and
+        n_groups as in batch_select_best.  sigma 0 clones only, and seeds may then be None.  Afterwards the batch counts as
+        not iterated: batch_select_best and another batch_respawn need an iterate call first (0 iterations are enough).
+        Returns (source_of_run int32 [n_runs]: the run itself for a survivor, -1 for the straight line; n_survivors int32
+        [n_groups])."""
+        if by not in ("total", "obs", "smooth"):
+            raise ValueError('by is "total", "obs" or "smooth"')
+        if collision not in ("ignore", "require", "prefer"):
+            raise ValueError('collision is "ignore", "require" or "prefer"')
+        n_runs = self.batch_dims(bid)[0]
+        gp = None
+        if groups is not None:
+            gp = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+            if gp.size != n_runs:
+                raise ValueError("groups has %d entries for %d runs" % (gp.size, n_runs))
+            if n_groups is None:
+                n_groups = int(gp.max()) + 1
+        elif n_groups is None:
+            n_groups = 1
+        n_groups = int(n_groups)
+        sd = None
+        if seeds is not None:
+            sd = np.ascontiguousarray(seeds, dtype=np.uint32).reshape(-1)
+            if sd.size != n_runs:
+                raise ValueError("seeds has %d entries for %d runs" % (sd.size, n_runs))
+        source = np.zeros(n_runs, dtype=np.int32); kept = np.zeros(max(n_groups, 1), dtype=np.int32)
+        self._check(self._lib.orc_batch_respawn(self._h, bid, ("total", "obs", "smooth").index(by), n_groups,
+                                                None if gp is None else _ip(gp), ("ignore", "require", "prefer").index(collision),
+                                                int(keep), float(sigma), None if sd is None else sd.ctypes.data_as(_capi.c_uint_p),
+                                                _ip(source), _ip(kept)))
+        return source, kept[:n_groups]
 
     def batch_gettraj_runs(self, bid, runs):
         """The rows `runs` of batch_gettraj, gathered on the device (orc_batch_gettraj_runs): [len(runs)][n_points][n];
