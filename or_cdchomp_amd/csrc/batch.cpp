@@ -326,6 +326,29 @@ void BatchShard::build_device(const Robot & robot)
    plan_ = plan_iterate(in, sw_);
 }
 
+// What the two verdicts share: the tables that the walk reads (verdict_walk.h) go up, the depths are zeroed and `w` is
+// filled, but for key_out.  The chunk: 64 samples per pass, or what the LDS of a CU holds of this robot's rows, positions and
+// joint frames behind what the kernel itself keeps there (lds_bytes(chunk): the kernel's dynamic LDS).
+template <typename real>
+void BatchShard::verdict_walk_args(const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+   const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w)
+{
+   hipStream_t st = stream_;
+   t.xml.reset(dev_alloc<int>(slot_xml.size())); t.pairs.reset(dev_alloc<int>(pairs.size())); t.depth.reset(dev_alloc<double>(n_runs));
+   hip_check(hipMemcpyAsync(t.xml.as<void>(), slot_xml.data(), slot_xml.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict xml");
+   hip_check(hipMemcpyAsync(t.pairs.as<void>(), pairs.data(), pairs.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict pairs");
+   hip_check(hipMemsetAsync(t.depth.as<void>(), 0, n_runs*sizeof(double), st), "verdict depth");
+   t.rsum.reset(upload<real>(pair_rsum, st)); t.inact.reset(upload<real>(inact_pos, st));
+   int chunk = 64;
+   while (chunk > 4 && lds_bytes(chunk) > 160*1024 - 256) chunk -= 4;
+   w.model = d_model_.as<const DevModel<real>>(); w.sdfs = d_sdfs_.as<const DevSdf<real>>(); w.n_sdfs = scn_.n_sdfs;
+   w.scene_of_run = d_scene_of_run_.as<int>(); w.scene_nsdf = d_scene_nsdf_.as<int>();
+   w.n_runs = n_runs; w.n_points = n_points; w.n = n; w.chunk = chunk; w.traj = d_traj_.as<const real>();
+   w.slot_xml = t.xml.as<int>();
+   w.n_pairs = (int) pair_rsum.size(); w.pairs = t.pairs.as<int>(); w.pair_rsum = t.rsum.as<const real>(); w.inact_pos = t.inact.as<const real>();
+   w.depth_out = t.depth.as<double>();
+}
+
 // first contact of every run's trajectory with a field, in the run's precision
 template <typename real>
 void BatchShard::collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
@@ -335,30 +358,19 @@ void BatchShard::collision_verdict_typed(const std::vector<int> & offs, const st
    hipStream_t st = stream_;
    hip_check(hipStreamSynchronize(st), "verdict: pending work");
    const size_t ns = seg.size();
-   DevBuf d_offs, d_seg, d_xml, d_key, d_depth, d_pairs, d_u, d_rsum, d_inact;
-   d_offs.reset(dev_alloc<int>(offs.size())); d_seg.reset(dev_alloc<int>(ns)); d_xml.reset(dev_alloc<int>(slot_xml.size()));
-   d_key.reset(dev_alloc<unsigned long long>(n_runs)); d_depth.reset(dev_alloc<double>(n_runs));
+   const auto lds_bytes = [this](int chunk) { return orc_verdict_lds_bytes(n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
+   VerdictTables t;
+   DevVerdict<real> v;
+   verdict_walk_args<real>(pairs, pair_rsum, inact_pos, lds_bytes, t, v);
+   DevBuf d_offs, d_seg, d_key, d_u;
+   d_offs.reset(dev_alloc<int>(offs.size())); d_seg.reset(dev_alloc<int>(ns)); d_key.reset(dev_alloc<unsigned long long>(n_runs));
    hip_check(hipMemcpyAsync(d_offs.as<void>(), offs.data(), offs.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict offs");
    hip_check(hipMemcpyAsync(d_seg.as<void>(), seg.data(), ns*sizeof(int), hipMemcpyHostToDevice, st), "verdict seg");
-   hip_check(hipMemcpyAsync(d_xml.as<void>(), slot_xml.data(), slot_xml.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict xml");
-   hip_check(hipMemsetAsync(d_depth.as<void>(), 0, n_runs*sizeof(double), st), "verdict depth");
-   d_pairs.reset(dev_alloc<int>(pairs.size()));
-   hip_check(hipMemcpyAsync(d_pairs.as<void>(), pairs.data(), pairs.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict pairs");
-   // samples per pass: 64, or what the LDS of a CU holds of this robot's rows, positions and joint frames
-   int chunk = 64;
-   while (chunk > 4 && orc_verdict_lds_bytes(n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk) > 160*1024 - 256) chunk -= 4;
-   d_u.reset(upload<real>(u, st)); d_rsum.reset(upload<real>(pair_rsum, st)); d_inact.reset(upload<real>(inact_pos, st));
-   DevVerdict<real> v;
-   v.model = d_model_.as<const DevModel<real>>(); v.sdfs = d_sdfs_.as<const DevSdf<real>>(); v.n_sdfs = scn_.n_sdfs;
-   v.scene_of_run = d_scene_of_run_.as<int>(); v.scene_nsdf = d_scene_nsdf_.as<int>();
-   v.n_runs = n_runs; v.n_points = n_points; v.n = n; v.chunk = chunk; v.traj = d_traj_.as<const real>();
-   v.offs = d_offs.as<int>(); v.seg = d_seg.as<int>(); v.u = d_u.as<const real>(); v.slot_xml = d_xml.as<int>();
-   v.key_out = d_key.as<unsigned long long>(); v.depth_out = d_depth.as<double>();
-   v.n_pairs = (int) pair_rsum.size(); v.pairs = d_pairs.as<int>(); v.pair_rsum = d_rsum.as<const real>(); v.inact_pos = d_inact.as<const real>();
-   hip_check(orc_launch_verdict(v, orc_verdict_lds_bytes(n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk), st, plan_.variant & ORC_VAR_TREE),
-             "collision_verdict_kernel launch");
+   d_u.reset(upload<real>(u, st));
+   v.offs = d_offs.as<int>(); v.seg = d_seg.as<int>(); v.u = d_u.as<const real>(); v.key_out = d_key.as<unsigned long long>();
+   hip_check(orc_launch_verdict(v, lds_bytes(v.chunk), st, plan_.variant & ORC_VAR_TREE), "collision_verdict_kernel launch");
    hip_check(hipMemcpyAsync(key_out, d_key.as<void>(), n_runs*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "verdict keys");
-   hip_check(hipMemcpyAsync(depth_out, d_depth.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict depth");
+   hip_check(hipMemcpyAsync(depth_out, t.depth.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict depth");
    hip_check(hipStreamSynchronize(st), "verdict sync");
 }
 
@@ -380,27 +392,20 @@ bool BatchShard::collision_verdict_planned_typed(const std::vector<double> & vma
    hipStream_t st = stream_;
    hip_check(hipStreamSynchronize(st), "verdict: pending work");
    if (n_points < 2 || (int) vmax.size() != n - col0) throw std::runtime_error("collision verdict: bad trajectory dimensions!");
-   // samples per pass: 64, or what the LDS of a CU holds of this robot's rows, positions and joint frames next to the plan
-   int chunk = 64;
-   while (chunk > 4 && orc_verdict_planned_lds_bytes(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk) > 160*1024 - 256) chunk -= 4;
-   const size_t lds = orc_verdict_planned_lds_bytes(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk);
-   if (lds > 160*1024 - 256) throw std::runtime_error("trajectory too long for the batched collision verdict!");
-   DevBuf d_xml, d_depth, d_time, d_ns, d_flag, d_pairs, d_vmax, d_rsum, d_inact;
-   d_xml.reset(dev_alloc<int>(slot_xml.size())); d_pairs.reset(dev_alloc<int>(pairs.size()));
-   d_depth.reset(dev_alloc<double>(n_runs)); d_time.reset(dev_alloc<double>(n_runs)); d_ns.reset(dev_alloc<int>(n_runs)); d_flag.reset(dev_alloc<int>(1));
-   if (!d_vkey_) d_vkey_.reset(dev_alloc<unsigned long long>(n_runs));
-   hip_check(hipMemcpyAsync(d_xml.as<void>(), slot_xml.data(), slot_xml.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict xml");
-   hip_check(hipMemcpyAsync(d_pairs.as<void>(), pairs.data(), pairs.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict pairs");
-   hip_check(hipMemsetAsync(d_depth.as<void>(), 0, n_runs*sizeof(double), st), "verdict depth");
-   hip_check(hipMemsetAsync(d_flag.as<void>(), 0, sizeof(int), st), "verdict flag");
-   d_vmax.reset(upload<double>(vmax, st)); d_rsum.reset(upload<real>(pair_rsum, st)); d_inact.reset(upload<real>(inact_pos, st));
+   // (the plan's arrays sit in the LDS too)
+   const auto lds_bytes = [this](int chunk) { return orc_verdict_planned_lds_bytes(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
+   VerdictTables t;
    DevVerdictPlan<real> v;
-   v.model = d_model_.as<const DevModel<real>>(); v.sdfs = d_sdfs_.as<const DevSdf<real>>(); v.n_sdfs = scn_.n_sdfs;
-   v.scene_of_run = d_scene_of_run_.as<int>(); v.scene_nsdf = d_scene_nsdf_.as<int>();
-   v.n_runs = n_runs; v.n_points = n_points; v.n = n; v.col0 = col0; v.chunk = chunk; v.traj = d_traj_.as<const real>();
-   v.vmax = d_vmax.as<const double>(); v.slot_xml = d_xml.as<int>();
-   v.n_pairs = (int) pair_rsum.size(); v.pairs = d_pairs.as<int>(); v.pair_rsum = d_rsum.as<const real>(); v.inact_pos = d_inact.as<const real>();
-   v.key_out = d_vkey_.as<unsigned long long>(); v.depth_out = d_depth.as<double>(); v.time_out = d_time.as<double>();
+   verdict_walk_args<real>(pairs, pair_rsum, inact_pos, lds_bytes, t, v);
+   const size_t lds = lds_bytes(v.chunk);
+   if (lds > 160*1024 - 256) throw std::runtime_error("trajectory too long for the batched collision verdict!");
+   DevBuf d_time, d_ns, d_flag, d_vmax;
+   d_time.reset(dev_alloc<double>(n_runs)); d_ns.reset(dev_alloc<int>(n_runs)); d_flag.reset(dev_alloc<int>(1));
+   if (!d_vkey_) d_vkey_.reset(dev_alloc<unsigned long long>(n_runs));
+   hip_check(hipMemsetAsync(d_flag.as<void>(), 0, sizeof(int), st), "verdict flag");
+   d_vmax.reset(upload<double>(vmax, st));
+   v.col0 = col0; v.vmax = d_vmax.as<const double>();
+   v.key_out = d_vkey_.as<unsigned long long>(); v.time_out = d_time.as<double>();
    v.n_samples_out = d_ns.as<int>(); v.too_long = d_flag.as<int>();
    hip_check(orc_launch_verdict_planned(v, lds, st, plan_.variant & ORC_VAR_TREE), "collision_verdict_planned_kernel launch");
    int too_long = 0;
@@ -408,7 +413,7 @@ bool BatchShard::collision_verdict_planned_typed(const std::vector<double> & vma
    hip_check(hipStreamSynchronize(st), "verdict sync");
    if (too_long) return false;
    if (key_out) hip_check(hipMemcpyAsync(key_out, d_vkey_.as<void>(), n_runs*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "verdict keys");
-   if (depth_out) hip_check(hipMemcpyAsync(depth_out, d_depth.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict depth");
+   if (depth_out) hip_check(hipMemcpyAsync(depth_out, t.depth.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict depth");
    if (time_out) hip_check(hipMemcpyAsync(time_out, d_time.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict time");
    if (n_samples_out) hip_check(hipMemcpyAsync(n_samples_out, d_ns.as<void>(), n_runs*sizeof(int), hipMemcpyDeviceToHost, st), "verdict samples");
    hip_check(hipStreamSynchronize(st), "verdict sync");

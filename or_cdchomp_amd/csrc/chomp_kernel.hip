@@ -2128,137 +2128,6 @@ __global__ void seed_traj_kernel(real * traj, const double * starts, const doubl
    }
 }
 
-// ---------------------------------------------------------------------------
-// Collision verdict of every run's trajectory: one workgroup per run walks the run's samples (planned
-// on the host: every 0.04 rad of C-space distance along the retimed trajectory, as the reference's
-// re-check in gettraj, src/orcdchomp_mod.cpp:2958-3006) up to 64 at a time (DevVerdict::chunk): rows interpolated on their
-// segments -> FK (fk.h, four lanes per sample) -> every active sphere against every field.  The
-// first contact in (sample, XML sphere, field) order is reported, which is where the reference's
-// loop stops.
-template <typename real, bool TREE>
-__global__ __launch_bounds__(ORC_BLOCK)
-void collision_verdict_kernel(DevVerdict<real> v)
-{
-   extern __shared__ __align__(16) unsigned char smem_raw[];
-   const DevModel<real> & gmod = *v.model;
-   const int run = blockIdx.x, tid = threadIdx.x;
-   const int n = v.n, np = v.n_points, nj = gmod.nj, Sa = gmod.Sa;
-   const int pstr = (Sa*3) | 1, astr = (nj*6) | 1, chunk = v.chunk;
-   // the run's scene: its slice of the descriptors and its field count
-   const int scene = v.scene_of_run ? v.scene_of_run[run] : 0;
-   const int n_fields = v.scene_nsdf ? v.scene_nsdf[scene] : v.n_sdfs;
-   const DevSdf<real> * sdfs = v.sdfs + (size_t) scene * v.n_sdfs;
-   unsigned long long * key_s = (unsigned long long *) smem_raw;     // [2]: the first contact's key (sample << 32 | pair bit << 31 | sphere << 16 | field or partner)
-   real * lds = (real *)(smem_raw + 16);
-   real * rows_s = lds;                                              // [chunk][n]
-   real * pos_s = rows_s + ((chunk*n + 3) & ~3);                        // [chunk][pstr]
-   real * ax_s = pos_s + ((chunk*pstr + 3) & ~3);                       // [chunk][astr]
-   real * base_s = ax_s + ((chunk*astr + 3) & ~3);                      // [12]
-   real * srad_s = base_s + 12;                                      // [Sa]
-   int * slot_s = (int *)(srad_s + ((Sa + 3) & ~3));                 // [Sa_real]
-   int * xml_s = slot_s + ((gmod.Sa_real + 3) & ~3);                 // [Sa]
-   int * jctl_s = xml_s + ((Sa + 3) & ~3);                            // [nj][2]
-   for (int e=tid; e<12; e+=ORC_BLOCK) base_s[e] = (e < 9) ? gmod.base_R[e] : gmod.base_t[e-9];
-   for (int e=tid; e<Sa; e+=ORC_BLOCK) { srad_s[e] = gmod.sph_radius[e]; xml_s[e] = v.slot_xml[e]; }
-   for (int e=tid; e<gmod.Sa_real; e+=ORC_BLOCK) slot_s[e] = gmod.slot_of[e];
-   for (int e=tid; e<nj; e+=ORC_BLOCK) { jctl_s[2*e] = gmod.joints[e].packed; jctl_s[2*e+1] = 0; }
-   if (tid == 0) key_s[0] = ORC_VERDICT_NONE;
-   ModelView<real> mod;
-   mod.nj = nj; mod.n = n; mod.floating = gmod.floating; mod.tree = gmod.tree; mod.Sa = Sa; mod.S = gmod.S; mod.GS = gmod.GS;
-   mod.base_sph_begin = gmod.base_sph_begin; mod.base_sph_end = gmod.base_sph_end; mod.jt_scan = 0;
-   mod.Sa_real = gmod.Sa_real; mod.placed = gmod.placed; mod.live_mask = gmod.live_mask; mod.slot_of = slot_s;
-   mod.base_R = base_s; mod.base_t = base_s + 9;
-   mod.jctl = jctl_s; mod.sph_affects = nullptr; mod.n_static = 0; mod.empty_mask = 0u;
-   mod.jpk = (const __attribute__((address_space(4))) int *) gmod.jpacked;
-   mod.jpk2 = (const __attribute__((address_space(4))) int *) gmod.jpacked2;
-   mod.sph_pos_c = (const __attribute__((address_space(4))) real (*)[3]) gmod.sph_pos;
-   mod.joints_c = (const __attribute__((address_space(4))) DevJoint<real> *) gmod.joints;
-   mod.slot_c = (const __attribute__((address_space(4))) int *) gmod.slot_of;
-   mod.fkj = (const __attribute__((address_space(4))) DevFkJoint<real> *) gmod.fkj;
-   __syncthreads();
-
-   const real * traj = v.traj + (size_t) run * np * n;
-   const int s0 = v.offs[run], s1 = v.offs[run+1];
-   double my_depth = 0.0; unsigned long long my_key = ORC_VERDICT_NONE;
-   for (int base=s0; base<s1; base+=chunk)
-   {
-      const int count = (s1 - base < chunk) ? s1 - base : chunk;
-      // rows of the samples: a0 + (a1 - a0) u on their segments
-      for (int e=tid; e<count*n; e+=ORC_BLOCK)
-      {
-         const int s = e / n, c = e - s*n;
-         const int sg = v.seg[base + s];
-         const real uu = v.u[base + s];
-         const real a0 = traj[sg*n + c], a1 = traj[(sg+1)*n + c];
-         rows_s[s*n + c] = a0 + (a1 - a0) * uu;
-      }
-      __syncthreads();
-      if (mod.floating && tid < count)
-      {
-         real * row = rows_s + tid*n;
-         const real len = M<real>::sqrt_(row[3]*row[3] + row[4]*row[4] + row[5]*row[5] + row[6]*row[6]);
-         const real inv = (real)1 / len;
-         row[3] *= inv; row[4] *= inv; row[5] *= inv; row[6] *= inv;
-      }
-      __syncthreads();
-      {
-         // 20 samples per wavefront (fk.h: triads of lanes)
-         const int lane16 = tid & 15, triad = (lane16 * 11) >> 5;
-         const int s = (tid >> 6) * 20 + ((tid >> 4) & 3) * 5 + triad;
-         const bool valid = (lane16 < 15) && (s < count);
-         const int sr = valid ? s : 0;
-         fk_waypoint_triad<real, TREE>(mod, rows_s + sr*n, 0, 0, nj, true, (lane16 < 15) ? lane16 - 3*triad : 0, valid, pos_s + sr*pstr, ax_s + sr*astr);
-      }
-      __syncthreads();
-      for (int item=tid; item<count*Sa; item+=ORC_BLOCK)
-      {
-         const int s = item / Sa, slot = item - s*Sa;
-         if (!((mod.live_mask >> slot) & 1ull)) continue;
-         const real * p = pos_s + s*pstr + slot*3;
-         const real radius = srad_s[slot];
-         for (int i=0; i<n_fields; i++)
-         {
-            const DevSdf<real> & F = sdfs[i];
-            real gp[3], gg[3], val;
-#pragma unroll
-            for (int k=0; k<3; k++)
-               gp[k] = F.Rgw[k*3+0]*p[0] + F.Rgw[k*3+1]*p[1] + F.Rgw[k*3+2]*p[2] + F.tgw[k];
-            if (sdf_lookup(F, gp, val, gg)) continue;                 // outside this field
-            if (val - radius < (real)0)
-            {
-               const unsigned long long key = ((unsigned long long)(base - s0 + s) << 32) | ((unsigned long long) xml_s[slot] << 16) | (unsigned long long) i;
-               if (key < my_key) { my_key = key; my_depth = (double)(radius - val); }
-               atomicMin(&key_s[0], key);
-            }
-         }
-      }
-      // self collision: a pair of spheres on links that may collide overlaps
-      for (int item=tid; item<count*v.n_pairs; item+=ORC_BLOCK)
-      {
-         const int s = item / v.n_pairs, pi = item - s*v.n_pairs;
-         const int ea = v.pairs[pi*4+0], eb = v.pairs[pi*4+1];
-         const real * pa = (ea >= 0) ? pos_s + s*pstr + ea*3 : v.inact_pos + (-1 - ea)*3;
-         const real * pb = (eb >= 0) ? pos_s + s*pstr + eb*3 : v.inact_pos + (-1 - eb)*3;
-         const real dx = pa[0]-pb[0], dy = pa[1]-pb[1], dz = pa[2]-pb[2];
-         const real dist = M<real>::sqrt_(dx*dx + dy*dy + dz*dz);
-         const real rs = v.pair_rsum[pi];
-         if (dist - rs < (real)0)
-         {
-            const unsigned long long key = ((unsigned long long)(base - s0 + s) << 32) | (1ull << 31) | ((unsigned long long) v.pairs[pi*4+2] << 16) | (unsigned long long) v.pairs[pi*4+3];
-            if (key < my_key) { my_key = key; my_depth = (double)(rs - dist); }
-            atomicMin(&key_s[0], key);
-         }
-      }
-      __syncthreads();
-      if (key_s[0] != ORC_VERDICT_NONE) break;          // a contact in this chunk: later samples cannot come first
-      __syncthreads();
-   }
-   __syncthreads();
-   const unsigned long long first = key_s[0];
-   if (tid == 0) v.key_out[run] = first;
-   if (first != ORC_VERDICT_NONE && my_key == first) v.depth_out[run] = my_depth;
-}
-
 } // namespace
 
 // ---------------------------------------------------------------------------
@@ -2310,34 +2179,3 @@ hipError_t orc_launch_seed(real * traj, const double * starts, const double * go
 }
 template hipError_t orc_launch_seed<double>(double *, const double *, const double *, int, int, int, int, hipStream_t);
 template hipError_t orc_launch_seed<float>(float *, const double *, const double *, int, int, int, int, hipStream_t);
-
-template <typename real>
-static hipError_t launch_verdict_t(const DevVerdict<real> & v, size_t lds, hipStream_t stream, int tree)
-{
-   static std::atomic<unsigned long long> attr_set{0ull};
-   int dev = 0;
-   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-   if (!((attr_set.load() >> dev) & 1ull))
-   {
-      hipError_t e = hipFuncSetAttribute((const void *) collision_verdict_kernel<real, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void *) collision_verdict_kernel<real, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
-      if (e != hipSuccess) return e;
-      attr_set.fetch_or(1ull << dev);
-   }
-   if (lds > 160*1024 - 256) return hipErrorInvalidValue;
-   if (tree) hipLaunchKernelGGL((collision_verdict_kernel<real, true>), dim3(v.n_runs), dim3(ORC_BLOCK), lds, stream, v);
-   else hipLaunchKernelGGL((collision_verdict_kernel<real, false>), dim3(v.n_runs), dim3(ORC_BLOCK), lds, stream, v);
-   return hipGetLastError();
-}
-hipError_t orc_launch_verdict(const DevVerdict<double> & v, size_t lds, hipStream_t stream, int tree) { return launch_verdict_t<double>(v, lds, stream, tree); }
-hipError_t orc_launch_verdict(const DevVerdict<float> & v, size_t lds, hipStream_t stream, int tree) { return launch_verdict_t<float>(v, lds, stream, tree); }
-
-// dynamic LDS of collision_verdict_kernel (the carve-up at its top)
-size_t orc_verdict_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk)
-{
-   const int pstr = (Sa*3) | 1, astr = (nj*6) | 1;
-   auto r4 = [](int x) { return (x + 3) & ~3; };
-   size_t reals = (size_t) r4(chunk*n) + r4(chunk*pstr) + r4(chunk*astr) + 12 + r4(Sa);
-   size_t ints = (size_t) r4(Sa_real) + r4(Sa);
-   return 16 + reals * real_size + ints * 4 + (size_t) nj * 8 + 64;
-}

@@ -345,35 +345,6 @@ struct DevBatch
    int * conv_streak;         // [n_runs] settled iterations in a row (carry_status launches continue it)
 };
 
-// Collision verdict of the trajectories of a batch (the step after the path: gettraj's re-check,
-// src/orcdchomp_mod.cpp:2958-3006, with the optimizer's own sphere / field model).
-template <typename real>
-struct DevVerdict
-{
-   const DevModel<real> * model;
-   const DevSdf<real> * sdfs;  // [n_scenes][n_sdfs]
-   int n_sdfs;                 // fields of the largest scene
-   const int * scene_of_run;   // [n_runs] (DevBatch::scene_of_run)
-   const int * scene_nsdf;     // [n_scenes]
-   int n_runs, n_points, n;
-   int chunk;                  // samples walked at a time (<= 64: as many as the CU's LDS holds of this robot)
-   const real * traj;          // [n_runs][n_points][n]
-   const int * offs;           // [n_runs+1] first sample of every run
-   const int * seg;            // [samples] segment of the trajectory the sample lies on
-   const real * u;             // [samples] position on the segment, 0..1
-   const int * slot_xml;       // [Sa lanes] XML index of the sphere in a slot, -1: empty
-   // self collision (src/orcdchomp_mod.cpp:2998-2999: `|| CheckSelfCollision`): the pairs of spheres on links that may
-   // collide, XML order (a < b); an end of a pair is a slot of the position row, or -1 - k: inactive sphere k of inact_pos
-   int n_pairs;
-   const int * pairs;          // [n_pairs][4]: end a, end b, XML index of a, XML index of b
-   const real * pair_rsum;     // [n_pairs] r_a + r_b
-   const real * inact_pos;     // [inactive spheres][3] world positions
-   // first contact of a run, or INT_MAX: (sample << 16) | (self << 15) | (XML sphere (a) << 8) | (field, or XML sphere b):
-   // within a sample the fields come first (sphere, field order), then the pairs
-   unsigned long long * key_out;   // [n_runs]: ORC_VERDICT_NONE, or sample << 32 | pair bit << 31 | XML sphere << 16 | field or partner sphere
-   double * depth_out;         // [n_runs] penetration depth of that contact
-};
-
 // LDS carve-up of one workgroup (struct LdsLayout above), computed on the host (lds_layout below)
 // and handed to the kernels in the kernarg block.
 // Offsets are in units of `real` after a header of ORC_LDS_HEADER bytes (reduction scratch).

@@ -6,10 +6,6 @@
 // the row of kernel_table.h that (variant, block, precision) names; hipErrorInvalidValue when the library holds no such kernel
 hipError_t orc_launch_iterate(const DevBatch<double> & b, size_t lds, hipStream_t stream, int variant, int block);
 hipError_t orc_launch_iterate(const DevBatch<float> & b, size_t lds, hipStream_t stream, int variant, int block);
-hipError_t orc_launch_verdict(const DevVerdict<double> & v, size_t lds, hipStream_t stream, int tree);
-hipError_t orc_launch_verdict(const DevVerdict<float> & v, size_t lds, hipStream_t stream, int tree);
-// dynamic LDS of collision_verdict_kernel
-size_t orc_verdict_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);
 // straight-line seed trajectories (instantiated for double and float)
 template <typename real>
 hipError_t orc_launch_seed(real * traj, const double * starts, const double * goals, int n_runs, int n_points, int n, int floating, hipStream_t stream);

@@ -1420,14 +1420,41 @@ void host_verdict_samples(const double * traj, int n_points, int n, int col0, co
    plan_collision_samples(traj, n_points, n, col0, dtm, seg_out, u_out, time_out);
 }
 
+// what both verdicts take from a batch: the robot with the spheres of the runs, the velocity limits of the batch's columns and
+// the pairs of the self-collision leg
+struct VerdictInputs
+{
+   int col0;
+   std::vector<double> vmax;
+   std::vector<int> pairs;
+   std::vector<double> rsum, inact_pos;
+};
+static VerdictInputs verdict_inputs(const Robot & robot, const Batch & b, bool self_check)
+{
+   VerdictInputs in;
+   in.col0 = b.params.floating_base ? 7 : 0;
+   Robot rob = robot;
+   rob.spheres = b.run_spheres;         // the robot's and those of the bodies it held at create (mod.cpp:2992-2996)
+   for (int a : b.adofindices) in.vmax.push_back(a < (int) rob.limit_vel.size() ? rob.limit_vel[a] : 1.0);
+   verdict_self_pairs(rob, b, self_check, in.pairs, in.rsum, in.inact_pos);
+   return in;
+}
+
+// key: sample << 32 | pair bit << 31 | XML sphere << 16 | field (or, for a pair, the other sphere), into run k's entries of
+// the outputs that are not NULL
+static void verdict_decode(unsigned long long key, int k, int * collides, int * sphere, int * field)
+{
+   const bool hit = key != ORC_VERDICT_NONE;
+   const bool self = hit && ((key >> 31) & 1ull);
+   if (collides) collides[k] = hit ? 1 : 0;
+   if (sphere) sphere[k] = hit ? (int)((key >> 16) & 0x7fffull) : -1;
+   if (field) field[k] = hit ? (self ? -2 - (int)(key & 0xffffull) : (int)(key & 0xffffull)) : -1;      // a pair: -2 - the other sphere
+}
+
 void Module::batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check)
 {
    Batch & b = batch(id);
-   const int col0 = b.params.floating_base ? 7 : 0;
-   Robot rob = robot(b.robot_name);
-   rob.spheres = b.run_spheres;         // the robot's and those of the bodies it held at create (mod.cpp:2992-2996)
-   std::vector<double> vmax;
-   for (int a : b.adofindices) vmax.push_back(a < (int) rob.limit_vel.size() ? rob.limit_vel[a] : 1.0);
+   const VerdictInputs in = verdict_inputs(robot(b.robot_name), b, self_check);
    std::vector<double> traj((size_t) b.n_runs * b.n_points * b.n);
    b.gettraj(traj.data());
    std::vector<int> offs(b.n_runs + 1, 0), seg;
@@ -1435,27 +1462,21 @@ void Module::batch_collision_verdict(int id, int * collides, double * time, int 
    for (int k=0; k<b.n_runs; k++)
    {
       const double * tk = &traj[(size_t) k * b.n_points * b.n];
-      const std::vector<double> dtm = retime_linear(tk, b.n_points, b.n, col0, vmax);
-      plan_collision_samples(tk, b.n_points, b.n, col0, dtm, seg, u, times);
+      const std::vector<double> dtm = retime_linear(tk, b.n_points, b.n, in.col0, in.vmax);
+      plan_collision_samples(tk, b.n_points, b.n, in.col0, dtm, seg, u, times);
       if (seg.size() >= ((size_t) 1 << 31) - 1) throw std::runtime_error("trajectory too long for the batched collision verdict!");      // (the running total is an int on both sides)
       offs[k+1] = (int) seg.size();
       if (offs[k+1] - offs[k] >= (1 << 30)) throw std::runtime_error("trajectory too long for the batched collision verdict!");
    }
-   std::vector<int> pairs; std::vector<double> rsum, inact_pos;
-   verdict_self_pairs(rob, b, self_check, pairs, rsum, inact_pos);
    std::vector<unsigned long long> key(b.n_runs); std::vector<double> dep(b.n_runs);
-   b.collision_verdict(offs, seg, u, pairs, rsum, inact_pos, key.data(), dep.data());
+   b.collision_verdict(offs, seg, u, in.pairs, in.rsum, in.inact_pos, key.data(), dep.data());
    if (getenv("ORC_DEBUG_VERDICT"))
       for (int k=0; k<b.n_runs; k++) fprintf(stderr, "verdict run %d key %016llx samples %d\n", k, key[k], offs[k+1] - offs[k]);
    for (int k=0; k<b.n_runs; k++)
    {
-      // key: sample << 32 | pair bit << 31 | XML sphere << 16 | field (or, for a pair, the other sphere)
       const bool hit = key[k] != ORC_VERDICT_NONE;
-      const bool self = hit && ((key[k] >> 31) & 1ull);
-      if (collides) collides[k] = hit ? 1 : 0;
+      verdict_decode(key[k], k, collides, sphere, field);
       if (time) time[k] = hit ? times[(size_t) offs[k] + (size_t)(key[k] >> 32)] : -1.0;
-      if (sphere) sphere[k] = hit ? (int)((key[k] >> 16) & 0x7fffull) : -1;
-      if (field) field[k] = hit ? (self ? -2 - (int)(key[k] & 0xffffull) : (int)(key[k] & 0xffffull)) : -1;      // a pair: -2 - the other sphere
       if (depth) depth[k] = hit ? dep[k] : 0.0;
    }
 }
@@ -1465,25 +1486,11 @@ void Module::batch_collision_verdict(int id, int * collides, double * time, int 
 void Module::batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples)
 {
    Batch & b = batch(id);
-   const int col0 = b.params.floating_base ? 7 : 0;
-   Robot rob = robot(b.robot_name);
-   rob.spheres = b.run_spheres;
-   std::vector<double> vmax;
-   for (int a : b.adofindices) vmax.push_back(a < (int) rob.limit_vel.size() ? rob.limit_vel[a] : 1.0);
-   std::vector<int> pairs; std::vector<double> rsum, inact_pos;
-   verdict_self_pairs(rob, b, true, pairs, rsum, inact_pos);
+   const VerdictInputs in = verdict_inputs(robot(b.robot_name), b, true);
    const bool want_key = collides || sphere || field;
    std::vector<unsigned long long> key(want_key ? b.n_runs : 0);
-   b.collision_verdict_planned(vmax, col0, pairs, rsum, inact_pos, want_key ? key.data() : nullptr, depth, time, n_samples);
-   if (!want_key) return;
-   for (int k=0; k<b.n_runs; k++)
-   {
-      const bool hit = key[k] != ORC_VERDICT_NONE;
-      const bool self = hit && ((key[k] >> 31) & 1ull);
-      if (collides) collides[k] = hit ? 1 : 0;
-      if (sphere) sphere[k] = hit ? (int)((key[k] >> 16) & 0x7fffull) : -1;
-      if (field) field[k] = hit ? (self ? -2 - (int)(key[k] & 0xffffull) : (int)(key[k] & 0xffffull)) : -1;
-   }
+   b.collision_verdict_planned(in.vmax, in.col0, in.pairs, in.rsum, in.inact_pos, want_key ? key.data() : nullptr, depth, time, n_samples);
+   for (int k=0; k<(int) key.size(); k++) verdict_decode(key[k], k, collides, sphere, field);
 }
 
 // src/orcdchomp_mod.cpp:2854-3011

@@ -17,6 +17,8 @@
 #include <vector>
 #include "stages.h"      // Robot, Sdf, SceneTable, TsrSpec, BatchParams; the stages of `create`
 
+template <typename real> struct DevVerdictWalk;      // verdict_device.h
+
 namespace orc {
 
 struct KinBody                    // a kinbody of oriented boxes (InitFromBoxes style) and / or triangles (a mesh: KinBody::InitFromTrimesh, the .iv files of the reference's scene)
@@ -159,6 +161,10 @@ private:
    template <typename real> void seed_runs(const Robot & robot, const double * starts, const double * goals, const double * basegoals);
    void start_hmc(const unsigned int * seeds);
    template <typename real> void launch(int n_iter, bool final_eval, bool carry);
+   // what both verdicts put on the device (batch.cpp): the tables of DevVerdictWalk, which the handles keep until the kernel has run
+   struct VerdictTables { DevBuf xml, pairs, rsum, inact, depth; };
+   template <typename real> void verdict_walk_args(const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
+      const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w);
    template <typename real> void collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
       const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
       unsigned long long * key_out, double * depth_out);

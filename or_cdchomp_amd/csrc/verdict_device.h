@@ -1,12 +1,13 @@
-// verdict_device.h -- the collision verdict that plans its own samples (verdict_kernels.hip), as batch.cpp launches it.
+// verdict_device.h -- the two collision verdicts of a batch (verdict_kernels.hip), as batch.cpp launches them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dev_types.h"
 
-// Collision verdict of the trajectories of a batch with the retiming and the sample planning on the device: what
-// DevVerdict (dev_types.h) takes as offs / seg / u, the kernel derives from the trajectory and vmax.
+// Collision verdict of the trajectories of a batch (the step after the path: gettraj's re-check,
+// src/orcdchomp_mod.cpp:2958-3006, with the optimizer's own sphere / field model): what the walk over a run's samples
+// reads and writes (verdict_walk.h), whoever planned the samples.
 template <typename real>
-struct DevVerdictPlan
+struct DevVerdictWalk
 {
    const DevModel<real> * model;
    const DevSdf<real> * sdfs;  // [n_scenes][n_sdfs]
@@ -14,24 +15,46 @@ struct DevVerdictPlan
    const int * scene_of_run;   // [n_runs] (DevBatch::scene_of_run)
    const int * scene_nsdf;     // [n_scenes]
    int n_runs, n_points, n;
-   int col0;                   // first column the retiming reads (7 with a floating base)
-   int chunk;                  // samples walked at a time (<= 64, a multiple of 4)
+   int chunk;                  // samples walked at a time (<= 64, a multiple of 4: as many as the CU's LDS holds of this robot)
    const real * traj;          // [n_runs][n_points][n]
-   const double * vmax;        // [n - col0] velocity limits of the retimed columns
    const int * slot_xml;       // [Sa lanes] XML index of the sphere in a slot, -1: empty
-   // the self-collision leg, as in DevVerdict
+   // self collision (src/orcdchomp_mod.cpp:2998-2999: `|| CheckSelfCollision`): the pairs of spheres on links that may
+   // collide, XML order (a < b); an end of a pair is a slot of the position row, or -1 - k: inactive sphere k of inact_pos
    int n_pairs;
-   const int * pairs;          // [n_pairs][4]
-   const real * pair_rsum;     // [n_pairs]
-   const real * inact_pos;     // [inactive spheres][3]
-   unsigned long long * key_out;   // [n_runs] as DevVerdict::key_out
-   double * depth_out;         // [n_runs] penetration depth of the first contact (the caller zeroes it)
-   double * time_out;          // [n_runs] its time on the retimed trajectory, -1 without a contact
+   const int * pairs;          // [n_pairs][4]: end a, end b, XML index of a, XML index of b
+   const real * pair_rsum;     // [n_pairs] r_a + r_b
+   const real * inact_pos;     // [inactive spheres][3] world positions
+   // first contact of a run: ORC_VERDICT_NONE, or sample << 32 | pair bit << 31 | XML sphere (a) << 16 | field, or XML
+   // sphere b of a pair.  Within a sample the fields come first (sphere, field order), then the pairs
+   unsigned long long * key_out;   // [n_runs]
+   double * depth_out;         // [n_runs] penetration depth of that contact (the caller zeroes it)
+};
+
+// ... of samples the host planned (Module::batch_collision_verdict)
+template <typename real>
+struct DevVerdict : DevVerdictWalk<real>
+{
+   const int * offs;           // [n_runs+1] first sample of every run
+   const int * seg;            // [samples] segment of the trajectory the sample lies on
+   const real * u;             // [samples] position on the segment, 0..1
+};
+
+// ... with the retiming and the sample planning on the device: what DevVerdict takes as offs / seg / u, the kernel derives
+// from the trajectory and vmax
+template <typename real>
+struct DevVerdictPlan : DevVerdictWalk<real>
+{
+   int col0;                   // first column the retiming reads (7 with a floating base)
+   const double * vmax;        // [n - col0] velocity limits of the retimed columns
+   double * time_out;          // [n_runs] the first contact's time on the retimed trajectory, -1 without a contact
    int * n_samples_out;        // [n_runs] samples the run's trajectory has (all of them, also when the walk stops at a contact)
    int * too_long;             // [1] set when a run has 2^30 samples or more: nothing of that run is walked (the caller zeroes it)
 };
 
+hipError_t orc_launch_verdict(const DevVerdict<double> & v, size_t lds, hipStream_t stream, int tree);
+hipError_t orc_launch_verdict(const DevVerdict<float> & v, size_t lds, hipStream_t stream, int tree);
 hipError_t orc_launch_verdict_planned(const DevVerdictPlan<double> & v, size_t lds, hipStream_t stream, int tree);
 hipError_t orc_launch_verdict_planned(const DevVerdictPlan<float> & v, size_t lds, hipStream_t stream, int tree);
-// dynamic LDS of collision_verdict_planned_kernel
+// dynamic LDS of collision_verdict_kernel and of collision_verdict_planned_kernel
+size_t orc_verdict_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);
 size_t orc_verdict_planned_lds_bytes(int n_points, int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);

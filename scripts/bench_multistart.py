@@ -35,7 +35,6 @@ import or_cdchomp_amd  # noqa: E402
 from or_cdchomp_amd import _capi  # noqa: E402
 
 NEW = ("orc_batch_perturb", "orc_batch_select_best", "orc_batch_gettraj_runs")
-DEVICE_PLAN = ("orc_batch_collision_verdict_device", "orc_host_verdict_samples")      # what the build before the device-planned verdict lacks
 KW = dict(common.CONFIG2_KW)
 N_BLOCK, N_PROBLEMS, N_STARTS = 8192, 64, 128
 SIGMA = 0.3
@@ -166,15 +165,10 @@ def device_link_bytes(mod, bid, select):
 
 def verdict_child(args):
     """one build's leg of a round: wall times of the three calls on the iterated block"""
-    have_device = os.environ.get("ORC_LIB") is None
-    if not have_device:
-        _capi.SYMBOLS = [s for s in _capi.SYMBOLS if s[0] not in DEVICE_PLAN]
     mod = or_cdchomp_amd.Module(0)
     model = common.setup_product_wam(mod)
     bid = iterated_block(mod, model)
-    rec = dict(lib=os.path.basename(_capi.LIB_PATH), select_cf_s=[], verdict_host_s=[])
-    if have_device:
-        rec["verdict_device_s"] = []
+    rec = dict(lib=os.path.basename(_capi.LIB_PATH), select_cf_s=[], verdict_host_s=[], verdict_device_s=[])
     for rnd in range(2):                                     # (a warm-up, then the timed call)
         t0 = time.perf_counter()
         best = mod.batch_select_best(bid, n_groups=N_PROBLEMS, collision_free=True)
@@ -182,19 +176,17 @@ def verdict_child(args):
         t0 = time.perf_counter()
         host = mod.batch_collision_verdict(bid)
         rec["verdict_host_s"].append(time.perf_counter() - t0)
-        if have_device:
-            t0 = time.perf_counter()
-            dev = mod.batch_collision_verdict(bid, on_device=True)
-            rec["verdict_device_s"].append(time.perf_counter() - t0)
-            assert all(np.array_equal(dev[k], host[k]) for k in host)
+        t0 = time.perf_counter()
+        dev = mod.batch_collision_verdict(bid, on_device=True)
+        rec["verdict_device_s"].append(time.perf_counter() - t0)
+        assert all(np.array_equal(dev[k], host[k]) for k in host)
     rec = {k: (v[-1] if isinstance(v, list) else v) for k, v in rec.items()}
     rec.update(winners=[int(x) for x in best[0]], colliding=int(host["collides"].sum()))
     n_runs, n_points, n = mod.batch_dims(bid)
-    if have_device:
-        rec["select_cf_bytes"], rec["samples"] = device_link_bytes(mod, bid, True)
-        rec["verdict_device_bytes"] = device_link_bytes(mod, bid, False)[0]
-        # the host-planned route: the trajectories down, 4 (n_runs + 1) + (4 + 8) samples up, keys and depths down
-        rec["verdict_host_bytes"] = n_runs * n_points * n * 8 + 4 * (n_runs + 1) + 12 * rec["samples"] + n_runs * 16
+    rec["select_cf_bytes"], rec["samples"] = device_link_bytes(mod, bid, True)
+    rec["verdict_device_bytes"] = device_link_bytes(mod, bid, False)[0]
+    # the host-planned route: the trajectories down, 4 (n_runs + 1) + (4 + 8) samples up, keys and depths down
+    rec["verdict_host_bytes"] = n_runs * n_points * n * 8 + 4 * (n_runs + 1) + 12 * rec["samples"] + n_runs * 16
     mod.batch_destroy(bid)
     mod.close()
     print("VERDICT_CHILD " + json.dumps(rec))
@@ -231,9 +223,8 @@ def verdict_rounds(args):
     out = dict(runs=N_BLOCK, rounds=args.reps)
     for name, recs in legs.items():
         for key in ("select_cf_s", "verdict_host_s", "verdict_device_s"):
-            if key in recs[0]:
-                out["%s_%s" % (name, key)] = med([r[key] for r in recs])
-                out["%s_%s_all" % (name, key)] = [r[key] for r in recs]
+            out["%s_%s" % (name, key)] = med([r[key] for r in recs])
+            out["%s_%s_all" % (name, key)] = [r[key] for r in recs]
     last = legs["this"][-1]
     out.update(samples=last["samples"], colliding=last["colliding"], select_cf_bytes=last["select_cf_bytes"],
                verdict_device_bytes=last["verdict_device_bytes"], verdict_host_bytes=last["verdict_host_bytes"],
