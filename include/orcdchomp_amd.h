@@ -326,6 +326,35 @@ int orc_batch_collision_verdict(orc_module * mod, int batch_id, int * collides_o
  * batch over several devices: every shard plans and walks its own runs. */
 int orc_batch_collision_verdict_device(orc_module * mod, int batch_id, int * collides_out, double * time_out,
                                        int * sphere_out, int * field_out, double * depth_out, int * n_samples_out);
+/* orc_batch_collision_verdict_device asked about some of the runs only: the workgroup of a run that is not examined returns
+ * before it stages or walks anything, so the call costs what the examined runs cost.  It replaces "the verdict of every run,
+ * then look at the ones that matter": after an iterate call the runs that left their joint limits (status -1) end far outside
+ * them, their retimed trajectories are by far the longest of the batch, and no selection rule can pick them.
+ *   which 0: examine [n_runs] bytes, nonzero: examine the run.  NULL is rejected.
+ *   which 1: the candidates -- the runs whose status of the last iterate call is 0 or 1 and whose total cost is finite, the
+ *     eligibility of orc_batch_select_best without its verdict (`candidates` of or_cdchomp_amd/module.py), decided on the
+ *     device from what that call left there.  examine must be NULL; a batch that has not been iterated is rejected as
+ *     orc_batch_select_best rejects it.
+ * An examined run: the outputs of orc_batch_collision_verdict_device, bit for bit.  A run that is not examined: collides -1
+ * and n_samples -1, and time -1, sphere -1, field -1, depth 0 as a run without a contact reports them.  An examined run of
+ * 2^30 samples or more: collides -2 and n_samples -2, otherwise like a run that is not examined, AND THE CALL SUCCEEDS: one
+ * hopeless run no longer takes the verdict of the others with it (`verdict_subset` of module.py is the specification of
+ * all three).  n_samples_out == NULL: the samples behind a first contact are not counted -- one lane steps through them by
+ * repeated addition, up to 2^30 times -- and "too long" is then what is decided before anything is walked (C-space length
+ * / 0.04 >= 2^30); the other outputs do not change.  Only collides_out is required.  Several devices: every shard takes its
+ * slice of examine, a shard without a run to examine does nothing.
+ * Rejected with a nonzero return and a message before any device work, the module usable: any other `which`; a NULL examine
+ * with which 0 or an examine with which 1; collides_out == NULL; an unknown batch; which 1 on a batch never iterated. */
+int orc_batch_collision_verdict_subset(orc_module * mod, int batch_id, int which, const unsigned char * examine,
+                                       int * collides_out, double * time_out, int * sphere_out, int * field_out,
+                                       double * depth_out, int * n_samples_out);
+/* Which runs the verdict inside orc_batch_select_best[_by] (require_collision_free) and orc_batch_respawn (collision_mode 1
+ * and 2) examines.  scope 0, the default: every run, orc_batch_collision_verdict_device's call in every respect.  scope 1:
+ * the candidates (which 1 above), the samples behind a contact not counted, and the call fails with "trajectory too long
+ * for the batched collision verdict!" only when a CANDIDATE is too long.  The documented results of those calls do not
+ * depend on the scope: a run that is no candidate was never eligible and never a survivor, whatever its verdict.  Any other
+ * scope is rejected and the setting kept; it persists until it is set again, like orc_batch_set_convergence. */
+int orc_batch_set_verdict_scope(orc_module * mod, int batch_id, int scope);
 /* optimizer state read-back for tests: which = "G", "AG", "T" ([n_runs][m][n]); "phase" ([n_runs][8] cycle counters with
  * ORC_PHASE_TIMERS=1); "waves" ([n_runs][8][2], with ORC_PHASE_TIMERS=1: the hardware-ID register and the XCC-ID register of
  * every wavefront of the run's workgroup as read at the start of the last launch, 4294967295 for a wavefront the workgroup does

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("ORC_LIB") or os.path.join(_HERE, "liborcdchomp_amd.so
 c_double_p = C.POINTER(C.c_double)
 c_int_p = C.POINTER(C.c_int)
 c_uint_p = C.POINTER(C.c_uint)
+c_ubyte_p = C.POINTER(C.c_ubyte)
 
 
 class RobotDesc(C.Structure):
@@ -82,6 +83,9 @@ SYMBOLS = [
     ("orc_batch_collision_verdict", C.c_int, [C.c_void_p, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p]),
     ("orc_batch_collision_verdict_device", C.c_int, [C.c_void_p, C.c_int, c_int_p, c_double_p, c_int_p, c_int_p, c_double_p,
                                                      c_int_p]),
+    ("orc_batch_collision_verdict_subset", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_ubyte_p, c_int_p, c_double_p, c_int_p,
+                                                     c_int_p, c_double_p, c_int_p]),
+    ("orc_batch_set_verdict_scope", C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     ("orc_batch_get_state", C.c_int, [C.c_void_p, C.c_int, C.c_char_p, c_double_p, C.c_size_t]),
     ("orc_batch_dims", C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p]),
     ("orc_batch_set_traj", C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_size_t]),

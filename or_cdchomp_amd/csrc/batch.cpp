@@ -387,7 +387,7 @@ void BatchShard::collision_verdict(const std::vector<int> & offs, const std::vec
 template <typename real>
 bool BatchShard::collision_verdict_planned_typed(const std::vector<double> & vmax, int col0,
    const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out)
+   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out, const VerdictScope & scope)
 {
    hipStream_t st = stream_;
    hip_check(hipStreamSynchronize(st), "verdict: pending work");
@@ -399,7 +399,7 @@ bool BatchShard::collision_verdict_planned_typed(const std::vector<double> & vma
    verdict_walk_args<real>(pairs, pair_rsum, inact_pos, lds_bytes, t, v);
    const size_t lds = lds_bytes(v.chunk);
    if (lds > 160*1024 - 256) throw std::runtime_error("trajectory too long for the batched collision verdict!");
-   DevBuf d_time, d_ns, d_flag, d_vmax;
+   DevBuf d_time, d_ns, d_flag, d_vmax, d_examine;
    d_time.reset(dev_alloc<double>(n_runs)); d_ns.reset(dev_alloc<int>(n_runs)); d_flag.reset(dev_alloc<int>(1));
    if (!d_vkey_) d_vkey_.reset(dev_alloc<unsigned long long>(n_runs));
    hip_check(hipMemsetAsync(d_flag.as<void>(), 0, sizeof(int), st), "verdict flag");
@@ -407,6 +407,15 @@ bool BatchShard::collision_verdict_planned_typed(const std::vector<double> & vma
    v.col0 = col0; v.vmax = d_vmax.as<const double>();
    v.key_out = d_vkey_.as<unsigned long long>(); v.time_out = d_time.as<double>();
    v.n_samples_out = d_ns.as<int>(); v.too_long = d_flag.as<int>();
+   v.examine = nullptr; v.cand_status = nullptr; v.cand_costs = nullptr;
+   if (scope.which == 0)
+   {
+      d_examine.reset(dev_alloc<unsigned char>(n_runs));
+      hip_check(hipMemcpyAsync(d_examine.as<void>(), scope.examine, n_runs, hipMemcpyHostToDevice, st), "verdict runs");
+      v.examine = d_examine.as<unsigned char>();
+   }
+   else if (scope.which == 1) { v.cand_status = d_status_.as<int>(); v.cand_costs = d_costs_.as<double>(); }      // (what the last iterate call left)
+   v.count_rest = scope.count_rest ? 1 : 0; v.long_marks_run = scope.long_marks_run ? 1 : 0;
    hip_check(orc_launch_verdict_planned(v, lds, st, plan_.variant & ORC_VAR_TREE), "collision_verdict_planned_kernel launch");
    int too_long = 0;
    hip_check(hipMemcpyAsync(&too_long, d_flag.as<void>(), sizeof(int), hipMemcpyDeviceToHost, st), "verdict flag");
@@ -422,11 +431,11 @@ bool BatchShard::collision_verdict_planned_typed(const std::vector<double> & vma
 
 bool BatchShard::collision_verdict_planned(const std::vector<double> & vmax, int col0,
    const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out)
+   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out, const VerdictScope & scope)
 {
    DeviceGuard guard(device);
-   if (params.precision == 64) return collision_verdict_planned_typed<double>(vmax, col0, pairs, pair_rsum, inact_pos, key_out, depth_out, time_out, n_samples_out);
-   return collision_verdict_planned_typed<float>(vmax, col0, pairs, pair_rsum, inact_pos, key_out, depth_out, time_out, n_samples_out);
+   if (params.precision == 64) return collision_verdict_planned_typed<double>(vmax, col0, pairs, pair_rsum, inact_pos, key_out, depth_out, time_out, n_samples_out, scope);
+   return collision_verdict_planned_typed<float>(vmax, col0, pairs, pair_rsum, inact_pos, key_out, depth_out, time_out, n_samples_out, scope);
 }
 
 // which iterations of this call resample the momentum, and with what noise
@@ -1048,6 +1057,22 @@ void Batch::set_convergence(const ConvergenceSpec & c)
    for (auto & s : shards) s->conv = v;
 }
 
+void Batch::set_verdict_scope(int scope)
+{
+   if (scope != 0 && scope != 1) throw std::runtime_error("set_verdict_scope: scope is 0 (all runs) or 1 (the candidates)!");
+   verdict_scope = scope;
+}
+
+// With scope 1 the selection's verdict asks about the candidates only -- a run that is none was never eligible -- and, as
+// nobody reads n_samples there, does not count the samples behind a contact; a candidate that is too long fails the call as
+// before.
+VerdictScope Batch::selection_scope() const
+{
+   VerdictScope s;
+   if (verdict_scope == 1) { s.which = 1; s.count_rest = false; }
+   return s;
+}
+
 void Batch::sync(double * costs_out, int * status_out, int * iters_out)
 {
    // the host-side gather: every shard copies its block straight into the caller's arrays
@@ -1338,13 +1363,19 @@ void Batch::collision_verdict(const std::vector<int> & soffs, const std::vector<
 
 void Batch::collision_verdict_planned(const std::vector<double> & vmax, int col0,
    const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out)
+   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out, const VerdictScope & scope)
 {
+   // (scope.which is -1, 0 or 1: the callers' own values, Module::batch_collision_verdict_subset checks the C caller's)
+   if (scope.which == 0 && !scope.examine) throw std::runtime_error("collision verdict: which 0 needs examine [n_runs]!");
+   if (scope.which == 1 && scope.examine) throw std::runtime_error("collision verdict: which 1 (the candidates) takes no examine!");
+   if (scope.which == 1 && !iterated) throw std::runtime_error("select_best: the batch has not been iterated (orc_batch_iterate with 0 iterations makes its costs valid)!");
    std::vector<int> ok(shards.size(), 1);
    for_shards([&](size_t k) {
       const int r0 = offs[k];
+      VerdictScope mine = scope;      // (every shard takes its slice of the caller's bytes)
+      if (mine.examine) mine.examine += r0;
       ok[k] = shards[k]->collision_verdict_planned(vmax, col0, pairs, pair_rsum, inact_pos, key_out ? key_out + r0 : nullptr,
-         depth_out ? depth_out + r0 : nullptr, time_out ? time_out + r0 : nullptr, n_samples_out ? n_samples_out + r0 : nullptr) ? 1 : 0;
+         depth_out ? depth_out + r0 : nullptr, time_out ? time_out + r0 : nullptr, n_samples_out ? n_samples_out + r0 : nullptr, mine) ? 1 : 0;
    }, true);
    for (int v : ok) if (!v) throw std::runtime_error("trajectory too long for the batched collision verdict!");
 }

@@ -550,6 +550,20 @@ int orc_batch_collision_verdict_device(orc_module * mod, int id, int * collides_
    });
 }
 
+int orc_batch_collision_verdict_subset(orc_module * mod, int id, int which, const unsigned char * examine, int * collides_out,
+   double * time_out, int * sphere_out, int * field_out, double * depth_out, int * n_samples_out)
+{
+   return guarded(mod, [&] {
+      need(collides_out, "collides_out");
+      mod->impl->batch_collision_verdict_subset(id, which, examine, collides_out, time_out, sphere_out, field_out, depth_out, n_samples_out);
+   });
+}
+
+int orc_batch_set_verdict_scope(orc_module * mod, int id, int scope)
+{
+   return guarded(mod, [&] { mod->impl->batch(id).set_verdict_scope(scope); });
+}
+
 int orc_batch_get_state(orc_module * mod, int id, const char * which, double * out, size_t cap)
 {
    return guarded(mod, [&] {
@@ -622,7 +636,7 @@ int orc_batch_select_best(orc_module * mod, int id, int n_groups, const int * gr
       orc::Batch & b = mod->impl->batch(id);
       const std::vector<int> group = b.select_groups(n_groups, group_of_run);      // (the arguments first: the verdict below walks every trajectory)
       // the verdict's keys stay on the device, where the selection reads them
-      if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b.selection_scope());
       b.select_best(n_groups, group, require_collision_free != 0, 0, best_run_out, best_cost_out, n_eligible_out);
    });
 }
@@ -634,7 +648,7 @@ int orc_batch_select_best_by(orc_module * mod, int id, int cost_column, int n_gr
       orc::Batch & b = mod->impl->batch(id);
       orc::Batch::select_column(cost_column);      // (the arguments first, as in orc_batch_select_best)
       const std::vector<int> group = b.select_groups(n_groups, group_of_run);
-      if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b.selection_scope());
       b.select_best(n_groups, group, require_collision_free != 0, cost_column, best_run_out, best_cost_out, n_eligible_out);
    });
 }
@@ -647,7 +661,7 @@ int orc_batch_respawn(orc_module * mod, int id, int cost_column, int n_groups, c
       // every argument first, on the host: a rejected call costs no kernel and changes no bit
       const orc::Batch::RespawnPlan plan = b.respawn_plan(cost_column, n_groups, group_of_run, collision_mode, keep, sigma, seeds);
       // the verdict of the current trajectories; its keys stay on the device, where the ranking reads them
-      if (collision_mode != 0) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+      if (collision_mode != 0) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b.selection_scope());
       b.respawn(plan, seeds, source_of_run_out, n_survivors_out);
    });
 }

@@ -1483,14 +1483,36 @@ void Module::batch_collision_verdict(int id, int * collides, double * time, int 
 
 // The verdict above with the planning left to the device (verdict_kernels.hip): what goes up is vmax and the pair tables,
 // what comes back is what the caller asks for.
-void Module::batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples)
+void Module::batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples,
+   const VerdictScope & scope)
 {
    Batch & b = batch(id);
    const VerdictInputs in = verdict_inputs(robot(b.robot_name), b, true);
    const bool want_key = collides || sphere || field;
    std::vector<unsigned long long> key(want_key ? b.n_runs : 0);
-   b.collision_verdict_planned(in.vmax, in.col0, in.pairs, in.rsum, in.inact_pos, want_key ? key.data() : nullptr, depth, time, n_samples);
+   b.collision_verdict_planned(in.vmax, in.col0, in.pairs, in.rsum, in.inact_pos, want_key ? key.data() : nullptr, depth, time, n_samples, scope);
    for (int k=0; k<(int) key.size(); k++) verdict_decode(key[k], k, collides, sphere, field);
+}
+
+// ... of the runs the caller names.  The kernel tells a run it did not examine (ORC_VERDICT_SKIPPED) and one it found too long
+// (ORC_VERDICT_TOO_LONG) in n_samples, whether or not the caller takes that array; both have the key of a run without a
+// contact, so time, sphere, field and depth are already what such a run reports.
+void Module::batch_collision_verdict_subset(int id, int which, const unsigned char * examine, int * collides, double * time, int * sphere,
+   int * field, double * depth, int * n_samples)
+{
+   Batch & b = batch(id);
+   if (which != 0 && which != 1) throw std::runtime_error("collision verdict: which is 0 (the runs of examine) or 1 (the candidates)!");
+   VerdictScope scope;
+   scope.which = which; scope.examine = examine;
+   scope.count_rest = n_samples != nullptr;
+   scope.long_marks_run = true;
+   std::vector<int> ns(b.n_runs);
+   batch_collision_verdict_device(id, collides, time, sphere, field, depth, ns.data(), scope);
+   for (int k=0; k<b.n_runs; k++)
+   {
+      if (ns[k] < 0 && collides) collides[k] = ns[k];
+      if (n_samples) n_samples[k] = ns[k];
+   }
 }
 
 // src/orcdchomp_mod.cpp:2854-3011

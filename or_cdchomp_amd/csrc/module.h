@@ -69,6 +69,17 @@ private:
    int device_ = -1;
 };
 
+// Which runs a device-planned collision verdict examines, and what it does about the samples nobody walks (the fields of the
+// same names in DevVerdictPlan, verdict_device.h).  The default is orc_batch_collision_verdict_device's: every run, the
+// samples behind a contact counted, a run that is too long fails the call.
+struct VerdictScope
+{
+   int which = -1;                            // -1 every run; 0 the runs of `examine`; 1 the candidates (run_candidate.h)
+   const unsigned char * examine = nullptr;   // which 0: a byte per run of the BATCH, nonzero: examine it (a shard takes its slice)
+   bool count_rest = true;                    // false: n_samples of an examined run is not exact and nobody counts to 2^30
+   bool long_marks_run = false;               // true: a run that is too long reports n_samples ORC_VERDICT_TOO_LONG and the call succeeds
+};
+
 // the convergence stop of a batch's runs (orc_batch_set_convergence; dev_types.h DevBatch::conv_*): patience 0 is off
 struct ConvergenceSpec
 {
@@ -137,10 +148,12 @@ public:
                           unsigned long long * key_out, double * depth_out);
    // the same verdict with the retiming and the samples planned on the device (verdict_kernels.hip): nothing but vmax
    // [n - col0] and the pair tables goes up, and what of key / depth / time / n_samples [n_runs] is not NULL comes back; the
-   // keys stay on the device for select_best.  Returns false when a run has too many samples (nothing is written then)
+   // keys stay on the device for select_best.  Returns false when a run has too many samples (nothing is written then).
+   // scope: the runs that are examined (its `examine` is this shard's slice); a run that is not has the key ORC_VERDICT_NONE
    bool collision_verdict_planned(const std::vector<double> & vmax, int col0,
                                   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-                                  unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out);
+                                  unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out,
+                                  const VerdictScope & scope = VerdictScope());
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
@@ -170,7 +183,7 @@ private:
       unsigned long long * key_out, double * depth_out);
    template <typename real> bool collision_verdict_planned_typed(const std::vector<double> & vmax, int col0,
       const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-      unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out);
+      unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out, const VerdictScope & scope);
    void plan_hmc(int iter_begin, int iter_end);
    int hmc_room(int n_iter, const Switches & now) const;
    void hmc_reserve(int cap, bool pending_work);
@@ -271,10 +284,17 @@ public:
    void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
                           const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
                           unsigned long long * key_out, double * depth_out);
-   // every shard plans and walks its own runs; outputs [n_runs] or NULL; throws when a run has too many samples
+   // every shard plans and walks its own runs; outputs [n_runs] or NULL; throws when a run has too many samples (unless
+   // scope.long_marks_run).  scope.which 1 on a batch that has not been iterated throws select_best's message
    void collision_verdict_planned(const std::vector<double> & vmax, int col0,
                                   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-                                  unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out);
+                                  unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out,
+                                  const VerdictScope & scope = VerdictScope());
+   // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
+   // kept until it is set again
+   int verdict_scope = 0;
+   void set_verdict_scope(int scope);        // throws unless 0 or 1
+   VerdictScope selection_scope() const;     // what that verdict is taken with
    void get_phase_cycles(long long * out);
    void get_wave_hwid(unsigned int * out);
    // the convergence stop of every shard's runs for the later iterate calls (validated: throws and changes nothing on a bad spec)
@@ -356,7 +376,13 @@ public:
    void batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check = true);
    // the same verdict planned on the device (no trajectory is read back); every output may be NULL: the keys stay on the
    // device for Batch::select_best.  n_samples: the samples of every run's retimed trajectory
-   void batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples);
+   void batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples,
+      const VerdictScope & scope = VerdictScope());
+   // ... of a subset of the runs (orc_batch_collision_verdict_subset): which 0 the runs with a nonzero byte in examine [n_runs],
+   // which 1 the candidates; a run that is not examined reports collides -1, one that is too long -2; n_samples NULL: the
+   // samples behind a contact are not counted
+   void batch_collision_verdict_subset(int id, int which, const unsigned char * examine, int * collides, double * time, int * sphere,
+      int * field, double * depth, int * n_samples);
 
    hipStream_t stream = nullptr;     // orc_set_stream: the stream of the first device's work (NULL: its default stream)
    int device;                       // first entry of `devices`

@@ -14,6 +14,7 @@
 #include <cstdint>
 #include "dev_types.h"
 #include "mt_wave.h"
+#include "run_candidate.h"
 
 namespace {
 
@@ -106,9 +107,7 @@ __device__ __forceinline__ unsigned long long cost_key(double c)
 // verdict_key: the runs' keys of the collision verdict (verdict_kernels.hip), or NULL when the verdict is not asked for
 __device__ __forceinline__ bool run_eligible(const double * costs, const int * status, const unsigned long long * verdict_key, int r)
 {
-   const int st = status[r];
-   const double c = costs[(size_t) r*3];
-   return (st == 0 || st == 1) && isfinite(c) && !(verdict_key && verdict_key[r] != ORC_VERDICT_NONE);
+   return orc_run_candidate(status[r], costs[(size_t) r*3]) && !(verdict_key && verdict_key[r] != ORC_VERDICT_NONE);
 }
 
 // column: which of a run's costs (0 total, 1 obs, 2 smooth) is the key that is minimised; eligibility does not depend on it
@@ -163,9 +162,9 @@ void respawn_rank_kernel(const double * costs, const int * status, const unsigne
    unsigned char * stays = cls + G;
    for (int i=tid; i<G; i+=256)
    {
-      const int r = mem[i], st = status[r];
+      const int r = mem[i];
       const bool hit = mode != 0 && verdict_key[r] != ORC_VERDICT_NONE;
-      const bool cand = (st == 0 || st == 1) && isfinite(costs[(size_t) r*3]) && !(mode == 1 && hit);
+      const bool cand = orc_run_candidate(status[r], costs[(size_t) r*3]) && !(mode == 1 && hit);
       cls[i] = cand ? ((mode == 2 && hit) ? 1 : 0) : 2;
       key[i] = cost_key(costs[(size_t) r*3 + column]);
    }

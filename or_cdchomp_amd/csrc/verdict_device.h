@@ -49,7 +49,19 @@ struct DevVerdictPlan : DevVerdictWalk<real>
    double * time_out;          // [n_runs] the first contact's time on the retimed trajectory, -1 without a contact
    int * n_samples_out;        // [n_runs] samples the run's trajectory has (all of them, also when the walk stops at a contact)
    int * too_long;             // [1] set when a run has 2^30 samples or more: nothing of that run is walked (the caller zeroes it)
+   // Which runs are examined (orc_batch_collision_verdict_subset, orc_batch_set_verdict_scope); all NULL / 1 / 0: every run,
+   // as orc_batch_collision_verdict_device.  A run that is not examined stages and walks nothing: key ORC_VERDICT_NONE, time
+   // -1, n_samples ORC_VERDICT_SKIPPED, its depth left as the caller zeroed it.
+   const unsigned char * examine;   // [n_runs] nonzero: examine the run; NULL: every run, or the candidates below
+   const int * cand_status;    // [n_runs] with examine NULL: the runs orc_run_candidate (run_candidate.h) passes on the status ...
+   const double * cand_costs;  // [n_runs][3] ... and the costs an iterate call left; both NULL: every run
+   int count_rest;             // 1: the samples behind a contact are counted (n_samples_out is exact); 0: n_samples_out is what was
+                               // planned when the walk stopped, and "too long" is only what is decided before anything is walked
+   int long_marks_run;         // 0: a run that is too long sets *too_long; 1: it reports like a run that is not examined, with
+                               // n_samples ORC_VERDICT_TOO_LONG, and *too_long stays
 };
+#define ORC_VERDICT_SKIPPED  (-1)
+#define ORC_VERDICT_TOO_LONG (-2)
 
 hipError_t orc_launch_verdict(const DevVerdict<double> & v, size_t lds, hipStream_t stream, int tree);
 hipError_t orc_launch_verdict(const DevVerdict<float> & v, size_t lds, hipStream_t stream, int tree);

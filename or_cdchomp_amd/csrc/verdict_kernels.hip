@@ -8,7 +8,9 @@
 // (plan_collision_samples) and uploads the list.  In collision_verdict_planned_kernel (orc_batch_collision_verdict_device,
 // orc_batch_select_best with require_collision_free, orc_batch_respawn) the run's workgroup does that itself: a fifth
 // wavefront, the planner, retimes the run and steps the sample times a chunk ahead of the four wavefronts that walk them,
-// so no trajectory leaves the device and no sample list exists.
+// so no trajectory leaves the device and no sample list exists.  It can be asked about a subset of the runs
+// (orc_batch_collision_verdict_subset, orc_batch_set_verdict_scope): a caller's byte per run, or the candidates of
+// run_candidate.h; the workgroup of any other run returns before it stages anything.
 //
 // The planning arithmetic is the host's, rounding for rounding (module.py verdict_samples is its specification): doubles
 // for either precision, no fused multiply-add, the sums in index order, time advanced by repeated addition.  What is
@@ -20,6 +22,7 @@
 #include <atomic>
 #include "dev_types.h"
 #include "verdict_device.h"
+#include "run_candidate.h"
 
 #define ORC_VD_WORKERS ORC_BLOCK            // threads that walk the samples (verdict_walk.h)
 #define ORC_VD_BLOCK   (ORC_BLOCK + 64)     // ... and the planner's wavefront
@@ -153,6 +156,18 @@ void collision_verdict_planned_kernel(DevVerdictPlan<real> v)
    const DevModel<real> & gmod = *v.model;
    const int run = blockIdx.x, tid = threadIdx.x;
    const bool planner = tid >= ORC_VD_WORKERS;
+   // ---- is the run examined at all?  One answer for the workgroup (the run is the block's index and the tables are read at
+   // that index, a uniform address; readfirstlane makes the branch a scalar one whatever loads the compiler picks), taken
+   // before anything is staged and before the first barrier
+   if (v.examine || v.cand_status)
+   {
+      const int walk = v.examine ? (v.examine[run] != 0) : (orc_run_candidate(v.cand_status[run], v.cand_costs[(size_t) run*3]) ? 1 : 0);
+      if (!__builtin_amdgcn_readfirstlane(walk))
+      {
+         if (tid == 0) { v.key_out[run] = ORC_VERDICT_NONE; v.time_out[run] = -1.0; v.n_samples_out[run] = ORC_VERDICT_SKIPPED; }
+         return;
+      }
+   }
    const int n = v.n, np = v.n_points, chunk = v.chunk;
    const DevSdf<real> * sdfs; int n_fields;
    verdict_scene<real>(v, run, sdfs, n_fields);
@@ -189,7 +204,12 @@ void collision_verdict_planned_kernel(DevVerdictPlan<real> v)
    __syncthreads();
    if (long_s[0])      // (workgroup-uniform)
    {
-      if (tid == 0) { v.key_out[run] = ORC_VERDICT_NONE; v.time_out[run] = -1.0; v.n_samples_out[run] = 0; *v.too_long = 1; }
+      if (tid == 0)
+      {
+         v.key_out[run] = ORC_VERDICT_NONE; v.time_out[run] = -1.0;
+         if (v.long_marks_run) v.n_samples_out[run] = ORC_VERDICT_TOO_LONG;
+         else { v.n_samples_out[run] = 0; *v.too_long = 1; }
+      }
       return;
    }
    if (planner && tid - ORC_VD_WORKERS < cnt_s[0])
@@ -230,6 +250,22 @@ void collision_verdict_planned_kernel(DevVerdictPlan<real> v)
       __syncthreads();
       if (done) break;
    }
+   // the samples behind a contact are counted all the same, when the caller wants their number; a run that is too long only
+   // by that count and must not fail the call reports nothing of its walk (kernel arguments: the same for every workgroup)
+   if (v.count_rest && v.long_marks_run)
+   {
+      if (tid == ORC_VD_WORKERS)
+      {
+         planned = plan_count_rest(time, step_time, duration, planned);
+         long_s[0] = planned >= ORC_VD_MAX_SAMPLES ? 1 : 0;
+      }
+      __syncthreads();
+      if (long_s[0])
+      {
+         if (tid == 0) { v.key_out[run] = ORC_VERDICT_NONE; v.time_out[run] = -1.0; v.n_samples_out[run] = ORC_VERDICT_TOO_LONG; }
+         return;
+      }
+   }
    const unsigned long long first = key_s[0];
    if (tid == 0)
    {
@@ -238,12 +274,14 @@ void collision_verdict_planned_kernel(DevVerdictPlan<real> v)
       v.time_out[run] = (first != ORC_VERDICT_NONE) ? times_s[(ci & 1) * chunk + ((int)(first >> 32) - ci * chunk)] : -1.0;
    }
    if (first != ORC_VERDICT_NONE && my_key == first) v.depth_out[run] = my_depth;
-   // the samples behind a contact are counted all the same
    if (tid == ORC_VD_WORKERS)
    {
-      planned = plan_count_rest(time, step_time, duration, planned);
+      if (v.count_rest && !v.long_marks_run)
+      {
+         planned = plan_count_rest(time, step_time, duration, planned);
+         if (planned >= ORC_VD_MAX_SAMPLES) *v.too_long = 1;
+      }
       v.n_samples_out[run] = planned;
-      if (planned >= ORC_VD_MAX_SAMPLES) *v.too_long = 1;
    }
 }
 

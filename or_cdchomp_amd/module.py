@@ -176,6 +176,45 @@ def verdict_samples(traj, vmax, col0=0):
     return np.asarray(seg_out, dtype=np.int32), np.asarray(u_out, dtype=np.float64), np.asarray(time_out, dtype=np.float64)
 
 
+def candidates(costs, status):
+    """The runs an iterate call left worth asking about: status 0 or 1 and a finite TOTAL cost -- the eligibility of
+    select_best without the collision verdict, the candidates of respawn_plan before theirs, and the runs
+    orc_batch_collision_verdict_subset examines with which 1 (orc_run_candidate of csrc/run_candidate.h).  costs [n_runs]
+    total costs or [n_runs][3] rows as batch_iterate returns them, status [n_runs].  Returns a bool array [n_runs].  Pure
+    numpy."""
+    costs = np.asarray(costs, dtype=np.float64)
+    total = costs[:, 0] if costs.ndim == 2 else costs.reshape(-1)
+    status = np.asarray(status).reshape(-1)
+    if status.shape[0] != total.shape[0]:
+        raise ValueError("costs and status have one entry per run")
+    return ((status == 0) | (status == 1)) & np.isfinite(total)
+
+
+VERDICT_SKIPPED = -1       # collides and n_samples of a run the subset verdict did not examine
+VERDICT_TOO_LONG = -2      # ... of an examined run of 2^30 samples or more
+
+
+def verdict_subset(full, examine):
+    """What orc_batch_collision_verdict_subset must return for the runs `examine` [n_runs] (nonzero: examined), given `full`,
+    the dict batch_collision_verdict(on_device=True) returns for every run of the same batch: an examined run keeps every
+    entry of `full` bit for bit; any other run reports collides -1 and n_samples -1, and time -1, sphere -1, field -1,
+    depth +0 as a run without a contact does.  (A run of 2^30 samples or more has no entry in any `full` -- that call fails
+    -- and reports collides -2, n_samples -2 and the rest alike.)  Returns a new dict with the keys of `full`.  Pure numpy."""
+    ex = np.asarray(examine).reshape(-1) != 0
+    skipped = dict(collides=VERDICT_SKIPPED, time=-1.0, sphere=-1, field=-1, depth=0.0, n_samples=VERDICT_SKIPPED)
+    out = {}
+    for key, val in full.items():
+        val = np.asarray(val)
+        if val.shape != ex.shape:
+            raise ValueError("%s has %s entries for %d runs" % (key, val.shape, ex.size))
+        if key not in skipped:
+            raise ValueError("%s is no output of the collision verdict" % key)
+        res = np.full(val.shape, skipped[key], dtype=val.dtype)
+        res[ex] = val[ex]
+        out[key] = res
+    return out
+
+
 def select_best(costs, status, collides, group_of_run, n_groups, column=0):
     """The rule of orc_batch_select_best and, with column 1 (obs) or 2 (smooth), of orc_batch_select_best_by.  costs [n_runs]
     total costs (or [n_runs][3] rows as batch_iterate returns them: needed for a column other than 0), status [n_runs],
@@ -199,7 +238,7 @@ def select_best(costs, status, collides, group_of_run, n_groups, column=0):
         raise ValueError("costs, status and group_of_run have one entry per run")
     if n_groups < 1 or (n_runs and (group.min() < 0 or group.max() >= n_groups)):
         raise ValueError("group_of_run entries must lie in [0, n_groups)")
-    ok = ((status == 0) | (status == 1)) & np.isfinite(total)
+    ok = candidates(total, status)
     if collides is not None:
         ok &= np.asarray(collides).reshape(-1) == 0
     best_run = np.full(n_groups, -1, dtype=np.int32)
@@ -261,7 +300,7 @@ def respawn_plan(costs, status, collides, group_of_run, n_groups, keep, mode=2, 
         hit = np.asarray(collides).reshape(-1) != 0
         if hit.shape[0] != n_runs:
             raise ValueError("collides has one entry per run")
-    candidate = ((status == 0) | (status == 1)) & np.isfinite(total)
+    candidate = candidates(total, status)
     if mode == 1:
         candidate &= ~hit
     source = np.full(n_runs, -1, dtype=np.int32)
@@ -718,15 +757,51 @@ class Module:
         self._check(self._lib.orc_batch_gettraj_runs(self._h, bid, _ip(rs), rs.size, _dp(out), out.size))
         return out
 
-    def batch_collision_verdict(self, bid, on_device=False):
+    def batch_set_verdict_scope(self, bid, scope):
+        """Which runs the verdict inside batch_select_best(collision_free=True) and batch_respawn("require" / "prefer")
+        examines (orc_batch_set_verdict_scope): "all", the default, or "candidates" (candidates(costs, status): the only runs
+        those calls can pick).  The results of those calls do not depend on it; what changes is what the verdict walks, and
+        that a run which is no candidate can no longer fail them by being too long.  Kept until it is set again."""
+        if scope not in ("all", "candidates"):
+            raise ValueError('scope is "all" or "candidates"')
+        self._check(self._lib.orc_batch_set_verdict_scope(self._h, bid, ("all", "candidates").index(scope)))
+
+    def batch_collision_verdict(self, bid, on_device=False, runs=None, count=True):
         """gettraj's collision re-check for every run of the batch, on the device: returns a dict of
         arrays per run: collides (0/1), time of the first contact on the retimed trajectory, XML index
         of the sphere, index of the field, penetration depth [m].  on_device: the samples are planned on the device
         too (orc_batch_collision_verdict_device; the plan is verdict_samples'): the same results without a read-back of
-        the trajectories, and n_samples, the samples of every run's retimed trajectory"""
+        the trajectories, and n_samples, the samples of every run's retimed trajectory.  runs (with on_device): a boolean /
+        0-1 array [n_runs] of the runs to examine, or "candidates" (candidates(costs, status) of the last iterate call,
+        decided on the device): orc_batch_collision_verdict_subset, whose result is verdict_subset's -- a run that is not
+        examined costs nothing and reports collides -1, an examined run of 2^30 samples or more reports -2 instead of
+        failing the call.  count=False (with runs): n_samples_out == NULL, the samples behind a first contact are not
+        counted and the dict has no n_samples; the other entries are the same"""
         n_runs = self.batch_dims(bid)[0]
         col = np.zeros(n_runs, dtype=np.int32); sph = np.zeros(n_runs, dtype=np.int32); fld = np.zeros(n_runs, dtype=np.int32)
         tim = np.zeros(n_runs); dep = np.zeros(n_runs)
+        if runs is not None:
+            if not on_device:
+                raise ValueError("runs needs on_device=True: the host-planned verdict reads every trajectory back")
+            cnt = np.zeros(n_runs, dtype=np.int32) if count else None
+            if isinstance(runs, str):
+                if runs != "candidates":
+                    raise ValueError('runs is an array [n_runs] or "candidates"')
+                which, ex = 1, None
+            else:
+                ex = np.ascontiguousarray(np.asarray(runs).reshape(-1) != 0, dtype=np.uint8)
+                if ex.size != n_runs:
+                    raise ValueError("runs has %d entries for %d runs" % (ex.size, n_runs))
+                which = 0
+            self._check(self._lib.orc_batch_collision_verdict_subset(
+                self._h, bid, which, None if ex is None else ex.ctypes.data_as(_capi.c_ubyte_p), _ip(col), _dp(tim), _ip(sph),
+                _ip(fld), _dp(dep), None if cnt is None else _ip(cnt)))
+            out = dict(collides=col, time=tim, sphere=sph, field=fld, depth=dep)
+            if cnt is not None:
+                out["n_samples"] = cnt
+            return out
+        if not count:
+            raise ValueError("count=False needs runs: the all-runs verdict always counts")
         if on_device:
             cnt = np.zeros(n_runs, dtype=np.int32)
             self._check(self._lib.orc_batch_collision_verdict_device(self._h, bid, _ip(col), _dp(tim), _ip(sph), _ip(fld), _dp(dep),

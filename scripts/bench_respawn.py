@@ -10,8 +10,15 @@
          three respawns; keep 4, collision "require" and "prefer", sigma 0.1, 0.3 and 0.6 (of the first perturbation and of
          every respawn).  Per leg the share of problems with a collision-free winner, the median smoothness cost of the
          winners, and the problems gained and lost against the straight leg.
+  verdict-subset (--verdict-subset: these legs alone, written to profiles/verdict_subset_<build>.json)
+         the same block after its 100 iterations: the device-planned verdict of every run on this build and on the parent's
+         library (--parent-lib), the verdict of the candidates only (batch_collision_verdict(runs="candidates")),
+         batch_respawn("prefer") under batch_set_verdict_scope "all" and "candidates", and from the all-runs call n_samples by
+         the runs' status (runs, maximum, sum): where the verdict's time goes.  Each leg of a round is a child process
+         (--verdict-child parent | this | candidates: the candidates' legs do not follow the all-runs verdict in one process)
+         that first takes the verdict of a small batch as its own warm-up.
 A warm-up and REPS (default 5) alternated rounds, medians.  Writes profiles/respawn_<build>.json and prints one line.
-   python scripts/bench_respawn.py [--reps N] [--parent-lib FILE] [--headline FILE] [--gain-from FILE]
+   python scripts/bench_respawn.py [--reps N] [--parent-lib FILE] [--headline FILE] [--gain-from FILE] [--verdict-subset]
 --gain-from takes the gain table of an earlier record of this script over instead of measuring it again; --headline embeds a JSON file of bench.py headline values of this build and its parent, taken next to it."""
 import argparse
 import json
@@ -88,7 +95,7 @@ def iterated_block(mod, model):
 def cost_child(which):
     """one leg of a round: the block, a warm-up call on a block of its own, the timed call"""
     if os.environ.get("ORC_LIB"):
-        _capi.SYMBOLS = [s for s in _capi.SYMBOLS if s[0] != "orc_batch_respawn"]
+        _capi.SYMBOLS = [s for s in _capi.SYMBOLS if s[0] not in NEW_SYMBOLS]
     mod = or_cdchomp_amd.Module(0)
     model = common.setup_product_wam(mod)
     group = np.repeat(np.arange(N_PROBLEMS, dtype=np.int32), N_STARTS)
@@ -150,6 +157,103 @@ def cost_rounds(args):
     return out
 
 
+NEW_SYMBOLS = ("orc_batch_respawn", "orc_batch_collision_verdict_subset", "orc_batch_set_verdict_scope")      # what a parent's library may lack
+
+
+def verdict_child(which):
+    """One leg of a verdict-subset round, a process of its own so that no leg finds the block's pages or the allocator warm
+    from another: `parent` (the library of ORC_LIB) and `this` take the all-runs verdict, then (`this`) one respawn under scope
+    "all" on a fresh block; `candidates` takes the candidates' verdict with the count (n_samples returned), then without it (count=False: that
+    second call follows the first on the same block), then one respawn under scope "candidates" on a fresh block."""
+    if os.environ.get("ORC_LIB"):
+        _capi.SYMBOLS = [s for s in _capi.SYMBOLS if s[0] not in NEW_SYMBOLS[1:]]
+    mod = or_cdchomp_amd.Module(0)
+    model = common.setup_product_wam(mod)
+    seeds = np.arange(N_BLOCK, dtype=np.uint32) + 70001
+    rec = dict(lib=os.path.basename(_capi.LIB_PATH), which=which)
+    small = mod.batch_create(model.name, common.wam_goals(8, seed=3), **KW)      # (the kernel's first launch of the process)
+    mod.batch_collision_verdict(small, on_device=True)
+    mod.batch_destroy(small)
+    bid = iterated_block(mod, model)
+    costs, status = mod.batch_sync(bid)
+    rec["status_counts"] = {str(st): int((status == st).sum()) for st in sorted(set(status.tolist()))}
+    if which in ("parent", "this"):
+        t0 = time.perf_counter()
+        full = mod.batch_collision_verdict(bid, on_device=True)
+        rec["all_s"] = time.perf_counter() - t0
+        ns = full["n_samples"].astype(np.int64)
+        rec["by_status"] = {str(st): dict(runs=int((status == st).sum()), max=int(ns[status == st].max()), sum=int(ns[status == st].sum()),
+                                          median=float(np.median(ns[status == st])), colliding=int(full["collides"][status == st].sum()))
+                            for st in sorted(set(status.tolist()))}
+        rec["colliding"] = int(full["collides"].sum())
+        rec["collides_sum_of_run_index"] = int(np.flatnonzero(full["collides"]).sum())
+        scope = "all"
+        if which == "this":      # (the respawn of either scope on a block of its own)
+            mod.batch_destroy(bid)
+            bid = iterated_block(mod, model)
+    else:
+        from or_cdchomp_amd.module import candidates
+        cand = candidates(costs, status)
+        t0 = time.perf_counter()
+        part = mod.batch_collision_verdict(bid, on_device=True, runs="candidates")
+        rec["candidates_s"] = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        plain = mod.batch_collision_verdict(bid, on_device=True, runs="candidates", count=False)
+        rec["candidates_nocount_s"] = time.perf_counter() - t0
+        assert np.array_equal(part["collides"] == -1, ~cand) and np.array_equal(plain["collides"], part["collides"])
+        rec["candidates"] = int(cand.sum())
+        rec["colliding_candidates"] = int((part["collides"] == 1).sum())
+        rec["collides_sum_of_run_index"] = int(np.flatnonzero(part["collides"] == 1).sum())
+        mod.batch_destroy(bid)
+        bid = iterated_block(mod, model)
+        scope = "candidates"
+    if which != "parent":
+        mod.batch_set_verdict_scope(bid, scope)
+        t0 = time.perf_counter()
+        source, n_surv = mod.batch_respawn(bid, KEEP, SIGMA, seeds, n_groups=N_PROBLEMS, collision="prefer")
+        rec["respawn_s"] = time.perf_counter() - t0
+        rec["source_sum"] = int(source.astype(np.int64).sum()); rec["survivors"] = int(n_surv.sum())
+    mod.batch_destroy(bid)
+    mod.close()
+    print("VERDICT_CHILD " + json.dumps(rec))
+
+
+def verdict_rounds(args):
+    legs = dict(this=[], parent=[], candidates=[])
+    for rnd in range(args.reps + 1):
+        for which in ("parent", "this", "candidates"):
+            if which == "parent" and not args.parent_lib:
+                continue
+            env = dict(os.environ)
+            env.pop("ORC_LIB", None)
+            if which == "parent":
+                env["ORC_LIB"] = os.path.abspath(args.parent_lib)
+            out = subprocess.run([sys.executable, os.path.abspath(__file__), "--verdict-child", which], env=env, check=True,
+                                 stdout=subprocess.PIPE, timeout=600).stdout.decode()
+            rec = json.loads([ln for ln in out.splitlines() if ln.startswith("VERDICT_CHILD ")][-1][len("VERDICT_CHILD "):])
+            print("round %d %s: %s" % (rnd, which, {k: round(v, 4) for k, v in rec.items() if k.endswith("_s")}), file=sys.stderr, flush=True)
+            if rnd:
+                legs[which].append(rec)
+    t, p, c = legs["this"], legs["parent"], legs["candidates"]
+    assert all(r["status_counts"] == t[0]["status_counts"] for r in t + p + c), "every leg must see the same block"
+    assert all(r["by_status"] == t[0]["by_status"] and r["colliding"] == t[0]["colliding"] for r in t + p), "every all-runs leg must give the same verdict"
+    assert all(r["source_sum"] == t[0]["source_sum"] and r["survivors"] == t[0]["survivors"] for r in t + c), "the scope must not change the plan"
+    out = dict(runs=N_BLOCK, problems=N_PROBLEMS, starts=N_STARTS, keep=KEEP, sigma=SIGMA, rounds=args.reps,
+               candidates=c[0]["candidates"], colliding_candidates=c[0]["colliding_candidates"], survivors=t[0]["survivors"],
+               colliding=t[0]["colliding"], n_samples_by_status=t[0]["by_status"])
+
+    def leg(name, recs, key):
+        out[name + "_s"] = med([r[key] for r in recs]); out[name + "_rounds"] = [r[key] for r in recs]
+    leg("all", t, "all_s"); leg("respawn_all", t, "respawn_s")
+    leg("candidates", c, "candidates_s"); leg("candidates_nocount", c, "candidates_nocount_s"); leg("respawn_candidates", c, "respawn_s")
+    if p:
+        out["parent_lib"] = p[0]["lib"]
+        leg("parent_all", p, "all_s")
+    out["candidates_over_all"] = out["candidates_s"] / out["all_s"]
+    out["respawn_candidates_over_all"] = out["respawn_candidates_s"] / out["respawn_all_s"]
+    return out
+
+
 def gain(mod, model, K=16, keep=4, sigmas=(0.1, 0.3, 0.6)):
     goals = np.repeat(common.wam_goals(1024, seed=20250101), K, axis=0)
     P, n_runs = 1024, 1024 * K
@@ -194,9 +298,25 @@ def main():
     ap.add_argument("--headline", default="")
     ap.add_argument("--cost-child", default="")
     ap.add_argument("--gain-from", default="", help="a record of this script whose gain table is taken over instead of measured again")
+    ap.add_argument("--verdict-child", default="")
+    ap.add_argument("--verdict-subset", action="store_true", help="the verdict-subset legs alone, to profiles/verdict_subset_<build>.json")
     args = ap.parse_args()
     if args.cost_child:
         return cost_child(args.cost_child)
+    if args.verdict_child:
+        return verdict_child(args.verdict_child)
+    if args.verdict_subset:
+        rec = dict(build=_capi.csrc_hash(), reps=args.reps, verdict_subset=verdict_rounds(args))
+        if args.headline:
+            with open(args.headline) as f:
+                rec["headline"] = json.load(f)
+        os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
+        with open(os.path.join(ROOT, "profiles", "verdict_subset_%s.json" % rec["build"]), "w") as f:
+            json.dump(rec, f, indent=1)
+        v = rec["verdict_subset"]
+        print(json.dumps(dict(build=rec["build"], verdict_subset={k: (round(x, 5) if isinstance(x, float) else x) for k, x in v.items()
+                                                                  if not k.endswith("_rounds")})))
+        return
     rec = dict(build=_capi.csrc_hash(), reps=args.reps, cost=cost_rounds(args))
     if args.gain_from:
         with open(args.gain_from) as f:
