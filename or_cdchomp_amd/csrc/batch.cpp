@@ -1,11 +1,10 @@
-// batch.cpp -- a batch of independent CHOMP runs on one GPU.
+// batch.cpp -- a batch of independent CHOMP runs on one GPU (its collision verdicts: verdict.cpp).
 // Host side of struct run / cd_chomp (src/orcdchomp_mod.cpp:887-966, 2104-2674;
 // src/libcd/chomp.h:38-101): uploads what the stages of `create` fold and plan (stages.h), keeps
 // the per-run state in HBM (run-major), plans the hmc resamples, launches the fused kernel.
 #include "module.h"
 #include "kernel_table.h"
 #include "launch.h"
-#include "verdict_device.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -46,29 +45,7 @@ void DevBuf::reset(void * p)
    if (p) hip_check(hipGetDevice(&device_), "hipGetDevice");
 }
 
-namespace {
-
-template <typename T>
-T * dev_alloc(size_t count)
-{
-   T * p = nullptr;
-   hip_check(hipMalloc((void **) &p, (count ? count : 1) * sizeof(T)), "hipMalloc");
-   return p;
-}
-
-template <typename real>
-real * upload(const std::vector<double> & v, hipStream_t s)
-{
-   std::vector<real> tmp(v.begin(), v.end());
-   real * d = dev_alloc<real>(tmp.size());
-   hip_check(hipMemcpyAsync(d, tmp.data(), tmp.size() * sizeof(real), hipMemcpyHostToDevice, s), "upload");
-   hip_check(hipStreamSynchronize(s), "upload sync");
-   return d;
-}
-
-void dev_free(void * p) { if (p) (void) hipFree(p); }
-
-} // namespace
+static void dev_free(void * p) { if (p) (void) hipFree(p); }
 
 BatchShard::BatchShard(Module * mod, int dev, hipStream_t stream, const Robot & robot, const BatchParams & p, int nruns,
    const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
@@ -324,118 +301,6 @@ void BatchShard::build_device(const Robot & robot)
    in.module_threads = mod_->workgroup_threads; in.module_per_cu = mod_->workgroups_per_cu;
    in.params_threads = params.workgroup_threads; in.params_per_cu = params.workgroups_per_cu;
    plan_ = plan_iterate(in, sw_);
-}
-
-// What the two verdicts share: the tables that the walk reads (verdict_walk.h) go up, the depths are zeroed and `w` is
-// filled, but for key_out.  The chunk: 64 samples per pass, or what the LDS of a CU holds of this robot's rows, positions and
-// joint frames behind what the kernel itself keeps there (lds_bytes(chunk): the kernel's dynamic LDS).
-template <typename real>
-void BatchShard::verdict_walk_args(const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w)
-{
-   hipStream_t st = stream_;
-   t.xml.reset(dev_alloc<int>(slot_xml.size())); t.pairs.reset(dev_alloc<int>(pairs.size())); t.depth.reset(dev_alloc<double>(n_runs));
-   hip_check(hipMemcpyAsync(t.xml.as<void>(), slot_xml.data(), slot_xml.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict xml");
-   hip_check(hipMemcpyAsync(t.pairs.as<void>(), pairs.data(), pairs.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict pairs");
-   hip_check(hipMemsetAsync(t.depth.as<void>(), 0, n_runs*sizeof(double), st), "verdict depth");
-   t.rsum.reset(upload<real>(pair_rsum, st)); t.inact.reset(upload<real>(inact_pos, st));
-   int chunk = 64;
-   while (chunk > 4 && lds_bytes(chunk) > 160*1024 - 256) chunk -= 4;
-   w.model = d_model_.as<const DevModel<real>>(); w.sdfs = d_sdfs_.as<const DevSdf<real>>(); w.n_sdfs = scn_.n_sdfs;
-   w.scene_of_run = d_scene_of_run_.as<int>(); w.scene_nsdf = d_scene_nsdf_.as<int>();
-   w.n_runs = n_runs; w.n_points = n_points; w.n = n; w.chunk = chunk; w.traj = d_traj_.as<const real>();
-   w.slot_xml = t.xml.as<int>();
-   w.n_pairs = (int) pair_rsum.size(); w.pairs = t.pairs.as<int>(); w.pair_rsum = t.rsum.as<const real>(); w.inact_pos = t.inact.as<const real>();
-   w.depth_out = t.depth.as<double>();
-}
-
-// first contact of every run's trajectory with a field, in the run's precision
-template <typename real>
-void BatchShard::collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
-   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out)
-{
-   hipStream_t st = stream_;
-   hip_check(hipStreamSynchronize(st), "verdict: pending work");
-   const size_t ns = seg.size();
-   const auto lds_bytes = [this](int chunk) { return orc_verdict_lds_bytes(n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
-   VerdictTables t;
-   DevVerdict<real> v;
-   verdict_walk_args<real>(pairs, pair_rsum, inact_pos, lds_bytes, t, v);
-   DevBuf d_offs, d_seg, d_key, d_u;
-   d_offs.reset(dev_alloc<int>(offs.size())); d_seg.reset(dev_alloc<int>(ns)); d_key.reset(dev_alloc<unsigned long long>(n_runs));
-   hip_check(hipMemcpyAsync(d_offs.as<void>(), offs.data(), offs.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict offs");
-   hip_check(hipMemcpyAsync(d_seg.as<void>(), seg.data(), ns*sizeof(int), hipMemcpyHostToDevice, st), "verdict seg");
-   d_u.reset(upload<real>(u, st));
-   v.offs = d_offs.as<int>(); v.seg = d_seg.as<int>(); v.u = d_u.as<const real>(); v.key_out = d_key.as<unsigned long long>();
-   hip_check(orc_launch_verdict(v, lds_bytes(v.chunk), st, plan_.variant & ORC_VAR_TREE), "collision_verdict_kernel launch");
-   hip_check(hipMemcpyAsync(key_out, d_key.as<void>(), n_runs*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "verdict keys");
-   hip_check(hipMemcpyAsync(depth_out, t.depth.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict depth");
-   hip_check(hipStreamSynchronize(st), "verdict sync");
-}
-
-void BatchShard::collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
-   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out)
-{
-   DeviceGuard guard(device);
-   if (params.precision == 64) collision_verdict_typed<double>(offs, seg, u, pairs, pair_rsum, inact_pos, key_out, depth_out);
-   else collision_verdict_typed<float>(offs, seg, u, pairs, pair_rsum, inact_pos, key_out, depth_out);
-}
-
-// ... with the samples planned by the kernel itself: the trajectories stay where they are
-template <typename real>
-bool BatchShard::collision_verdict_planned_typed(const std::vector<double> & vmax, int col0,
-   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out, const VerdictScope & scope)
-{
-   hipStream_t st = stream_;
-   hip_check(hipStreamSynchronize(st), "verdict: pending work");
-   if (n_points < 2 || (int) vmax.size() != n - col0) throw std::runtime_error("collision verdict: bad trajectory dimensions!");
-   // (the plan's arrays sit in the LDS too)
-   const auto lds_bytes = [this](int chunk) { return orc_verdict_planned_lds_bytes(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
-   VerdictTables t;
-   DevVerdictPlan<real> v;
-   verdict_walk_args<real>(pairs, pair_rsum, inact_pos, lds_bytes, t, v);
-   const size_t lds = lds_bytes(v.chunk);
-   if (lds > 160*1024 - 256) throw std::runtime_error("trajectory too long for the batched collision verdict!");
-   DevBuf d_time, d_ns, d_flag, d_vmax, d_examine;
-   d_time.reset(dev_alloc<double>(n_runs)); d_ns.reset(dev_alloc<int>(n_runs)); d_flag.reset(dev_alloc<int>(1));
-   if (!d_vkey_) d_vkey_.reset(dev_alloc<unsigned long long>(n_runs));
-   hip_check(hipMemsetAsync(d_flag.as<void>(), 0, sizeof(int), st), "verdict flag");
-   d_vmax.reset(upload<double>(vmax, st));
-   v.col0 = col0; v.vmax = d_vmax.as<const double>();
-   v.key_out = d_vkey_.as<unsigned long long>(); v.time_out = d_time.as<double>();
-   v.n_samples_out = d_ns.as<int>(); v.too_long = d_flag.as<int>();
-   v.examine = nullptr; v.cand_status = nullptr; v.cand_costs = nullptr;
-   if (scope.which == 0)
-   {
-      d_examine.reset(dev_alloc<unsigned char>(n_runs));
-      hip_check(hipMemcpyAsync(d_examine.as<void>(), scope.examine, n_runs, hipMemcpyHostToDevice, st), "verdict runs");
-      v.examine = d_examine.as<unsigned char>();
-   }
-   else if (scope.which == 1) { v.cand_status = d_status_.as<int>(); v.cand_costs = d_costs_.as<double>(); }      // (what the last iterate call left)
-   v.count_rest = scope.count_rest ? 1 : 0; v.long_marks_run = scope.long_marks_run ? 1 : 0;
-   hip_check(orc_launch_verdict_planned(v, lds, st, plan_.variant & ORC_VAR_TREE), "collision_verdict_planned_kernel launch");
-   int too_long = 0;
-   hip_check(hipMemcpyAsync(&too_long, d_flag.as<void>(), sizeof(int), hipMemcpyDeviceToHost, st), "verdict flag");
-   hip_check(hipStreamSynchronize(st), "verdict sync");
-   if (too_long) return false;
-   if (key_out) hip_check(hipMemcpyAsync(key_out, d_vkey_.as<void>(), n_runs*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "verdict keys");
-   if (depth_out) hip_check(hipMemcpyAsync(depth_out, t.depth.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict depth");
-   if (time_out) hip_check(hipMemcpyAsync(time_out, d_time.as<void>(), n_runs*sizeof(double), hipMemcpyDeviceToHost, st), "verdict time");
-   if (n_samples_out) hip_check(hipMemcpyAsync(n_samples_out, d_ns.as<void>(), n_runs*sizeof(int), hipMemcpyDeviceToHost, st), "verdict samples");
-   hip_check(hipStreamSynchronize(st), "verdict sync");
-   return true;
-}
-
-bool BatchShard::collision_verdict_planned(const std::vector<double> & vmax, int col0,
-   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out, const VerdictScope & scope)
-{
-   DeviceGuard guard(device);
-   if (params.precision == 64) return collision_verdict_planned_typed<double>(vmax, col0, pairs, pair_rsum, inact_pos, key_out, depth_out, time_out, n_samples_out, scope);
-   return collision_verdict_planned_typed<float>(vmax, col0, pairs, pair_rsum, inact_pos, key_out, depth_out, time_out, n_samples_out, scope);
 }
 
 // which iterations of this call resample the momentum, and with what noise
@@ -1345,39 +1210,6 @@ void Batch::get_phase_cycles(long long * out)
 void Batch::get_wave_hwid(unsigned int * out)
 {
    for (size_t k=0; k<shards.size(); k++) shards[k]->get_wave_hwid(out + (size_t) offs[k] * 16);
-}
-
-void Batch::collision_verdict(const std::vector<int> & soffs, const std::vector<int> & seg, const std::vector<double> & u,
-   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out)
-{
-   for_shards([&](size_t k) {
-      const int r0 = offs[k], r1 = offs[k+1];
-      std::vector<int> so(r1 - r0 + 1);
-      for (int r=r0; r<=r1; r++) so[r - r0] = soffs[r] - soffs[r0];
-      const std::vector<int> sg(seg.begin() + soffs[r0], seg.begin() + soffs[r1]);
-      const std::vector<double> su(u.begin() + soffs[r0], u.begin() + soffs[r1]);
-      shards[k]->collision_verdict(so, sg, su, pairs, pair_rsum, inact_pos, key_out + r0, depth_out + r0);
-   }, true);
-}
-
-void Batch::collision_verdict_planned(const std::vector<double> & vmax, int col0,
-   const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-   unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out, const VerdictScope & scope)
-{
-   // (scope.which is -1, 0 or 1: the callers' own values, Module::batch_collision_verdict_subset checks the C caller's)
-   if (scope.which == 0 && !scope.examine) throw std::runtime_error("collision verdict: which 0 needs examine [n_runs]!");
-   if (scope.which == 1 && scope.examine) throw std::runtime_error("collision verdict: which 1 (the candidates) takes no examine!");
-   if (scope.which == 1 && !iterated) throw std::runtime_error("select_best: the batch has not been iterated (orc_batch_iterate with 0 iterations makes its costs valid)!");
-   std::vector<int> ok(shards.size(), 1);
-   for_shards([&](size_t k) {
-      const int r0 = offs[k];
-      VerdictScope mine = scope;      // (every shard takes its slice of the caller's bytes)
-      if (mine.examine) mine.examine += r0;
-      ok[k] = shards[k]->collision_verdict_planned(vmax, col0, pairs, pair_rsum, inact_pos, key_out ? key_out + r0 : nullptr,
-         depth_out ? depth_out + r0 : nullptr, time_out ? time_out + r0 : nullptr, n_samples_out ? n_samples_out + r0 : nullptr, mine) ? 1 : 0;
-   }, true);
-   for (int v : ok) if (!v) throw std::runtime_error("trajectory too long for the batched collision verdict!");
 }
 
 // create's dat_filename (src/orcdchomp_mod.cpp:2306-2310): one file per run; a batch of several

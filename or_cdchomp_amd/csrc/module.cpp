@@ -1,4 +1,4 @@
-// module.cpp -- environment stand-ins, SDF commands, command grammar.
+// module.cpp -- environment stand-ins, SDF commands, command grammar (the collision verdict behind gettraj: verdict.cpp).
 // Reference: src/orcdchomp_mod.cpp (commands), src/orcwrap.cpp (argv adaptor).
 #include "module.h"
 #include <algorithm>
@@ -618,21 +618,6 @@ std::string serialize_traj(const std::string & robot, const std::vector<int> & a
    }
    o << "\n</data>\n</trajectory>\n";
    return o.str();
-}
-
-// LinearTrajectoryRetimer stand-in (reference: RetimeActiveDOFTrajectory(..., "LinearTrajectoryRetimer"),
-// src/orcdchomp_mod.cpp:2905-2911): each segment is traversed at the largest constant velocity
-// the dof velocity limits allow.
-std::vector<double> retime_linear(const double * traj, int n_points, int n, int col0, const std::vector<double> & vmax)
-{
-   std::vector<double> dtm(n_points, 0.0);
-   for (int i=1; i<n_points; i++)
-      for (int j=col0; j<n; j++)
-      {
-         const double v = vmax[j-col0] > 0.0 ? vmax[j-col0] : 1.0;
-         dtm[i] = std::max(dtm[i], std::fabs(traj[(size_t) i*n+j] - traj[(size_t)(i-1)*n+j]) / v);
-      }
-   return dtm;
 }
 
 // reads a trajectory document: the rows of its <data> block and where its groups sit in a row.  A document without
@@ -1355,166 +1340,6 @@ std::string Module::cmd_iterate(const std::vector<std::string> & argv, bool batc
    return o.str();
 }
 
-// Samples of a retimed trajectory every 0.04 rad of C-space distance, the grid of the reference's
-// re-check (src/orcdchomp_mod.cpp:2958-3006): for every sample the segment it lies on, the position
-// on the segment and its time.
-static void plan_collision_samples(const double * traj, int n_points, int n, int col0, const std::vector<double> & dtm,
-   std::vector<int> & seg_out, std::vector<double> & u_out, std::vector<double> & time_out)
-{
-   double total_dist = 0.0, duration = 0.0;
-   for (int i=0; i+1<n_points; i++)
-   {
-      double d2 = 0.0;
-      for (int j=col0; j<n; j++) { const double d = traj[(size_t) i*n+j] - traj[(size_t)(i+1)*n+j]; d2 += d*d; }
-      total_dist += std::sqrt(d2);
-      duration += dtm[i+1];
-   }
-   const double step_time = total_dist > 0.0 ? duration * 0.04 / total_dist : duration + 1.0;
-   int seg = 0; double tseg0 = 0.0;
-   for (double time=0.0; time<duration; time+=step_time)
-   {
-      while (seg < n_points-2 && tseg0 + dtm[seg+1] < time) { tseg0 += dtm[seg+1]; seg++; }
-      const double u = dtm[seg+1] > 0.0 ? (time - tseg0) / dtm[seg+1] : 0.0;
-      seg_out.push_back(seg); u_out.push_back(u); time_out.push_back(time);
-   }
-}
-
-// the pairs of the verdict's self-collision leg (`|| CheckSelfCollision`, mod.cpp:2998-2999): spheres on links that may
-// collide, in XML order; an end is a slot of the device's position row or an inactive sphere's world position
-static void verdict_self_pairs(const Robot & rob, const Batch & b, bool self_check,
-   std::vector<int> & pairs, std::vector<double> & rsum, std::vector<double> & inact_pos)
-{
-   if ((int) rob.spheres.size() > 128) throw std::runtime_error("too many spheres for the batched collision verdict!");
-   if (self_check && rob.self_check)
-   {
-      const std::vector<unsigned char> & excl = b.run_self_excl;      // sphere by sphere, taken at create (held bodies: Robot::run_self_pairs_excluded)
-      const int ns = (int) rob.spheres.size();
-      std::vector<int> end_of(ns, 0);
-      std::vector<Xform> frames;
-      rob.fk(rob.transform, rob.dof_values, frames);
-      for (int si=0; si<ns; si++)
-      {
-         int slot = -1;
-         for (size_t q=0; q<b.slot_xml.size(); q++) if (b.slot_xml[q] == si) slot = (int) q;
-         if (slot >= 0) { end_of[si] = slot; continue; }
-         end_of[si] = -1 - (int)(inact_pos.size() / 3);
-         double r[3];
-         mat3_vec(frames[rob.spheres[si].link].R, rob.spheres[si].pos, r);
-         for (int q=0; q<3; q++) inact_pos.push_back(r[q] + frames[rob.spheres[si].link].t[q]);
-      }
-      for (int a=0; a<ns; a++)
-         for (int c=a+1; c<ns; c++)
-         {
-            if (excl[(size_t) a * ns + c]) continue;
-            pairs.push_back(end_of[a]); pairs.push_back(end_of[c]); pairs.push_back(a); pairs.push_back(c);
-            rsum.push_back(rob.spheres[a].radius + rob.spheres[c].radius);
-         }
-   }
-}
-
-// the plan of one trajectory as the verdict makes it (orc_host_verdict_samples)
-void host_verdict_samples(const double * traj, int n_points, int n, int col0, const std::vector<double> & vmax,
-   std::vector<int> & seg_out, std::vector<double> & u_out, std::vector<double> & time_out)
-{
-   const std::vector<double> dtm = retime_linear(traj, n_points, n, col0, vmax);
-   plan_collision_samples(traj, n_points, n, col0, dtm, seg_out, u_out, time_out);
-}
-
-// what both verdicts take from a batch: the robot with the spheres of the runs, the velocity limits of the batch's columns and
-// the pairs of the self-collision leg
-struct VerdictInputs
-{
-   int col0;
-   std::vector<double> vmax;
-   std::vector<int> pairs;
-   std::vector<double> rsum, inact_pos;
-};
-static VerdictInputs verdict_inputs(const Robot & robot, const Batch & b, bool self_check)
-{
-   VerdictInputs in;
-   in.col0 = b.params.floating_base ? 7 : 0;
-   Robot rob = robot;
-   rob.spheres = b.run_spheres;         // the robot's and those of the bodies it held at create (mod.cpp:2992-2996)
-   for (int a : b.adofindices) in.vmax.push_back(a < (int) rob.limit_vel.size() ? rob.limit_vel[a] : 1.0);
-   verdict_self_pairs(rob, b, self_check, in.pairs, in.rsum, in.inact_pos);
-   return in;
-}
-
-// key: sample << 32 | pair bit << 31 | XML sphere << 16 | field (or, for a pair, the other sphere), into run k's entries of
-// the outputs that are not NULL
-static void verdict_decode(unsigned long long key, int k, int * collides, int * sphere, int * field)
-{
-   const bool hit = key != ORC_VERDICT_NONE;
-   const bool self = hit && ((key >> 31) & 1ull);
-   if (collides) collides[k] = hit ? 1 : 0;
-   if (sphere) sphere[k] = hit ? (int)((key >> 16) & 0x7fffull) : -1;
-   if (field) field[k] = hit ? (self ? -2 - (int)(key & 0xffffull) : (int)(key & 0xffffull)) : -1;      // a pair: -2 - the other sphere
-}
-
-void Module::batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check)
-{
-   Batch & b = batch(id);
-   const VerdictInputs in = verdict_inputs(robot(b.robot_name), b, self_check);
-   std::vector<double> traj((size_t) b.n_runs * b.n_points * b.n);
-   b.gettraj(traj.data());
-   std::vector<int> offs(b.n_runs + 1, 0), seg;
-   std::vector<double> u, times;
-   for (int k=0; k<b.n_runs; k++)
-   {
-      const double * tk = &traj[(size_t) k * b.n_points * b.n];
-      const std::vector<double> dtm = retime_linear(tk, b.n_points, b.n, in.col0, in.vmax);
-      plan_collision_samples(tk, b.n_points, b.n, in.col0, dtm, seg, u, times);
-      if (seg.size() >= ((size_t) 1 << 31) - 1) throw std::runtime_error("trajectory too long for the batched collision verdict!");      // (the running total is an int on both sides)
-      offs[k+1] = (int) seg.size();
-      if (offs[k+1] - offs[k] >= (1 << 30)) throw std::runtime_error("trajectory too long for the batched collision verdict!");
-   }
-   std::vector<unsigned long long> key(b.n_runs); std::vector<double> dep(b.n_runs);
-   b.collision_verdict(offs, seg, u, in.pairs, in.rsum, in.inact_pos, key.data(), dep.data());
-   if (getenv("ORC_DEBUG_VERDICT"))
-      for (int k=0; k<b.n_runs; k++) fprintf(stderr, "verdict run %d key %016llx samples %d\n", k, key[k], offs[k+1] - offs[k]);
-   for (int k=0; k<b.n_runs; k++)
-   {
-      const bool hit = key[k] != ORC_VERDICT_NONE;
-      verdict_decode(key[k], k, collides, sphere, field);
-      if (time) time[k] = hit ? times[(size_t) offs[k] + (size_t)(key[k] >> 32)] : -1.0;
-      if (depth) depth[k] = hit ? dep[k] : 0.0;
-   }
-}
-
-// The verdict above with the planning left to the device (verdict_kernels.hip): what goes up is vmax and the pair tables,
-// what comes back is what the caller asks for.
-void Module::batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples,
-   const VerdictScope & scope)
-{
-   Batch & b = batch(id);
-   const VerdictInputs in = verdict_inputs(robot(b.robot_name), b, true);
-   const bool want_key = collides || sphere || field;
-   std::vector<unsigned long long> key(want_key ? b.n_runs : 0);
-   b.collision_verdict_planned(in.vmax, in.col0, in.pairs, in.rsum, in.inact_pos, want_key ? key.data() : nullptr, depth, time, n_samples, scope);
-   for (int k=0; k<(int) key.size(); k++) verdict_decode(key[k], k, collides, sphere, field);
-}
-
-// ... of the runs the caller names.  The kernel tells a run it did not examine (ORC_VERDICT_SKIPPED) and one it found too long
-// (ORC_VERDICT_TOO_LONG) in n_samples, whether or not the caller takes that array; both have the key of a run without a
-// contact, so time, sphere, field and depth are already what such a run reports.
-void Module::batch_collision_verdict_subset(int id, int which, const unsigned char * examine, int * collides, double * time, int * sphere,
-   int * field, double * depth, int * n_samples)
-{
-   Batch & b = batch(id);
-   if (which != 0 && which != 1) throw std::runtime_error("collision verdict: which is 0 (the runs of examine) or 1 (the candidates)!");
-   VerdictScope scope;
-   scope.which = which; scope.examine = examine;
-   scope.count_rest = n_samples != nullptr;
-   scope.long_marks_run = true;
-   std::vector<int> ns(b.n_runs);
-   batch_collision_verdict_device(id, collides, time, sphere, field, depth, ns.data(), scope);
-   for (int k=0; k<b.n_runs; k++)
-   {
-      if (ns[k] < 0 && collides) collides[k] = ns[k];
-      if (n_samples) n_samples[k] = ns[k];
-   }
-}
-
 // src/orcdchomp_mod.cpp:2854-3011
 std::string Module::cmd_gettraj(const std::vector<std::string> & argv, bool batchmode)
 {
@@ -1547,104 +1372,18 @@ std::string Module::cmd_gettraj(const std::vector<std::string> & argv, bool batc
       if (verdict_ptr) batch_collision_verdict(run, verdict_ptr, nullptr, nullptr, nullptr, nullptr, !no_self_check);
       return "";
    }
-   const int col0 = b.params.floating_base ? 7 : 0;
-   Robot rob = robot(b.robot_name);
-   rob.spheres = b.run_spheres;
-   std::vector<double> vmax;
-   for (int a : b.adofindices) vmax.push_back(a < (int) rob.limit_vel.size() ? rob.limit_vel[a] : 1.0);
+   const VerdictInputs in = verdict_inputs(robot(b.robot_name), b, false, false);      // col0 and vmax: the kernels' pair tables are not built
    // timing (mod.cpp:2905-2911)
-   const std::vector<double> dtm = retime_linear(traj.data(), b.n_points, b.n, col0, vmax);
+   const std::vector<double> dtm = retime_linear(traj.data(), b.n_points, b.n, in.col0, in.vmax);
    if (!no_collision_check)
    {
-      // The reference samples the timed trajectory every 0.04 rad of C-space distance and asks
-      // OpenRAVE for environment/self collisions (mod.cpp:2958-3006).  Here the verdict comes from
-      // the model the optimizer itself uses: a configuration collides when an active sphere
-      // penetrates a signed distance field (interpolated field value below the sphere radius).
-      double total_dist = 0.0, duration = 0.0;
-      for (int i=0; i+1<b.n_points; i++)
-      {
-         double d2 = 0.0;
-         for (int j=col0; j<b.n; j++) { const double d = traj[(size_t) i*b.n+j] - traj[(size_t)(i+1)*b.n+j]; d2 += d*d; }
-         total_dist += std::sqrt(d2);
-         duration += dtm[i+1];
-      }
-      const double step_time = total_dist > 0.0 ? duration * 0.04 / total_dist : duration + 1.0;
-      std::vector<Xform> frames;
-      std::vector<double> q = rob.dof_values;
-      const std::vector<unsigned char> & self_excl = b.run_self_excl;
-      const size_t n_run_spheres = rob.spheres.size();
-      bool collides = false;
-      std::ostringstream details;
-      int seg = 0; double tseg0 = 0.0;
-      for (double time=0.0; time<duration && !(collides && !no_collision_exception); time+=step_time)
-      {
-         while (seg < b.n_points-2 && tseg0 + dtm[seg+1] < time) { tseg0 += dtm[seg+1]; seg++; }
-         const double u = dtm[seg+1] > 0.0 ? (time - tseg0) / dtm[seg+1] : 0.0;
-         Pose base = rob.transform;
-         if (col0)
-         {
-            for (int j=0; j<7; j++) base.v[j] = traj[(size_t) seg*b.n+j] + (traj[(size_t)(seg+1)*b.n+j] - traj[(size_t) seg*b.n+j]) * u;
-            pose_normalize(base);
-         }
-         for (size_t a=0; a<b.adofindices.size(); a++)
-         {
-            const double a0 = traj[(size_t) seg*b.n+col0+a], a1 = traj[(size_t)(seg+1)*b.n+col0+a];
-            q[b.adofindices[a]] = a0 + (a1 - a0) * u;
-         }
-         rob.fk(base, q, frames);
-         for (size_t si=0; si<rob.spheres.size() && !collides; si++)
-         {
-            const Robot::Sphere & sp = rob.spheres[si];
-            bool active = col0 != 0;
-            for (size_t a=0; a<b.adofindices.size() && !active; a++) active = rob.does_affect(b.adofindices[a], sp.link);
-            if (!active) continue;
-            double pw[3];
-            mat3_vec(frames[sp.link].R, sp.pos, pw);
-            for (int k=0; k<3; k++) pw[k] += frames[sp.link].t[k];
-            // the module's fields where their kinbodies stand now; a batch with per-run scenes: the placements of run 0's scene
-            const size_t n_fields = b.per_run_scenes ? b.scenes->scenes[b.scenes->scene_of_run[0]].size() : sdfs.size();
-            for (size_t fi=0; fi<n_fields; fi++)
-            {
-               const ScenePlacement * pl = b.per_run_scenes ? &b.scenes->scenes[b.scenes->scene_of_run[0]][fi] : nullptr;
-               const Sdf & f = pl ? *pl->sdf : *sdfs[fi];
-               const Pose pose_world_gsdf = pose_compose(pl ? pl->pose_world_kinbody : body_transform(f.kinbody_name), f.pose);
-               double pg[3], val;
-               pose_apply(pose_invert(pose_world_gsdf), pw, pg);
-               if (grid_interp(f.grid, pg, &val)) continue;
-               if (val - sp.radius < 0.0)
-               {
-                  collides = true;
-                  details << "Collision at t=" << time << ": sphere " << si << " of " << b.robot_name
-                          << " is " << (sp.radius - val) << " m inside the field of " << f.kinbody_name << "\n";
-                  break;
-               }
-            }
-         }
-         // ... || CheckSelfCollision (mod.cpp:2998-2999): two spheres on links that may collide overlap
-         for (size_t a=0; a<rob.spheres.size() && !collides && !no_self_check && rob.self_check; a++)
-            for (size_t c=a+1; c<rob.spheres.size(); c++)
-            {
-               const Robot::Sphere & sa = rob.spheres[a], & sc = rob.spheres[c];
-               if (self_excl[a * n_run_spheres + c]) continue;
-               double pa[3], pc[3], d2 = 0.0;
-               mat3_vec(frames[sa.link].R, sa.pos, pa);
-               mat3_vec(frames[sc.link].R, sc.pos, pc);
-               for (int k=0; k<3; k++) { const double d = (pa[k] + frames[sa.link].t[k]) - (pc[k] + frames[sc.link].t[k]); d2 += d*d; }
-               const double dist = std::sqrt(d2), rs = sa.radius + sc.radius;
-               if (dist - rs < 0.0)
-               {
-                  collides = true;
-                  details << "Collision at t=" << time << ": spheres " << a << " and " << c << " of " << b.robot_name
-                          << " overlap by " << (rs - dist) << " m\n";
-                  break;
-               }
-            }
-      }
-      last_collision_details = no_collision_details ? std::string() : details.str();
+      std::string details;
+      const bool collides = host_recheck(*this, b, traj.data(), dtm, !no_self_check, details);
+      last_collision_details = no_collision_details ? std::string() : details;
       if (collides && !no_collision_exception) throw std::runtime_error("Resulting trajectory is in collision!");
    }
    // active dof columns only (mod.cpp:2899-2903)
-   return serialize_traj(b.robot_name, b.adofindices, traj.data(), b.n_points, b.n, col0, dtm);
+   return serialize_traj(b.robot_name, b.adofindices, traj.data(), b.n_points, b.n, in.col0, dtm);
 }
 
 // src/orcdchomp_mod.cpp:3013-3037

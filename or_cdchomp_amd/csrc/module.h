@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 #include "stages.h"      // Robot, Sdf, SceneTable, TsrSpec, BatchParams; the stages of `create`
+#include "verdict.h"     // VerdictInputs, the sample clock, the free functions of the collision verdict
 
 template <typename real> struct DevVerdictWalk;      // verdict_device.h
 
@@ -49,6 +50,7 @@ private:
    bool changed_ = false;
 };
 
+void hip_check(hipError_t e, const char * what);
 // device memory released on the device it was allocated on
 std::shared_ptr<void> device_buffer(int device, size_t bytes);
 
@@ -68,6 +70,22 @@ private:
    void * p_ = nullptr;
    int device_ = -1;
 };
+// what a DevBuf is reset with: an array of `count` elements (at least one); below, a host vector uploaded as `real`s (waits for the copy)
+template <typename T> T * dev_alloc(size_t count)
+{
+   T * p = nullptr;
+   hip_check(hipMalloc((void **) &p, (count ? count : 1) * sizeof(T)), "hipMalloc");
+   return p;
+}
+
+template <typename real> real * upload(const std::vector<double> & v, hipStream_t s)
+{
+   std::vector<real> tmp(v.begin(), v.end());
+   real * d = dev_alloc<real>(tmp.size());
+   hip_check(hipMemcpyAsync(d, tmp.data(), tmp.size() * sizeof(real), hipMemcpyHostToDevice, s), "upload");
+   hip_check(hipStreamSynchronize(s), "upload sync");
+   return d;
+}
 
 // Which runs a device-planned collision verdict examines, and what it does about the samples nobody walks (the fields of the
 // same names in DevVerdictPlan, verdict_device.h).  The default is orc_batch_collision_verdict_device's: every run, the
@@ -142,18 +160,15 @@ public:
    // rows[k] (local runs) of the trajectory array as doubles: out [rows.size()][n_points][n]
    void gettraj_rows(const std::vector<int> & rows, double * out);
    const Metric & metric() const { return metric_; }
-   // first contact of every run's trajectory with a field, on the device (Module::batch_collision_verdict plans the samples)
+   // (verdict.cpp) first contact of every run's trajectory with a field, on the device (Module::batch_collision_verdict plans the samples)
    void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
-                          const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-                          unsigned long long * key_out, double * depth_out);
+                          const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
    // the same verdict with the retiming and the samples planned on the device (verdict_kernels.hip): nothing but vmax
    // [n - col0] and the pair tables goes up, and what of key / depth / time / n_samples [n_runs] is not NULL comes back; the
    // keys stay on the device for select_best.  Returns false when a run has too many samples (nothing is written then).
    // scope: the runs that are examined (its `examine` is this shard's slice); a run that is not has the key ORC_VERDICT_NONE
-   bool collision_verdict_planned(const std::vector<double> & vmax, int col0,
-                                  const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-                                  unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out,
-                                  const VerdictScope & scope = VerdictScope());
+   bool collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
+                                  int * n_samples_out, const VerdictScope & scope = VerdictScope());
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
@@ -174,16 +189,13 @@ private:
    template <typename real> void seed_runs(const Robot & robot, const double * starts, const double * goals, const double * basegoals);
    void start_hmc(const unsigned int * seeds);
    template <typename real> void launch(int n_iter, bool final_eval, bool carry);
-   // what both verdicts put on the device (batch.cpp): the tables of DevVerdictWalk, which the handles keep until the kernel has run
+   // what both verdicts put on the device (verdict.cpp): the tables of DevVerdictWalk, which the handles keep until the kernel has run
    struct VerdictTables { DevBuf xml, pairs, rsum, inact, depth; };
-   template <typename real> void verdict_walk_args(const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-      const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w);
+   template <typename real> void verdict_walk_args(const VerdictInputs & in, const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w);
    template <typename real> void collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
-      const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-      unsigned long long * key_out, double * depth_out);
-   template <typename real> bool collision_verdict_planned_typed(const std::vector<double> & vmax, int col0,
-      const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-      unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out, const VerdictScope & scope);
+      const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
+   template <typename real> bool collision_verdict_planned_typed(const VerdictInputs & in, unsigned long long * key_out, double * depth_out,
+      double * time_out, int * n_samples_out, const VerdictScope & scope);
    void plan_hmc(int iter_begin, int iter_end);
    int hmc_room(int n_iter, const Switches & now) const;
    void hmc_reserve(int cap, bool pending_work);
@@ -282,14 +294,11 @@ public:
    void gettraj_runs(const int * runs, int n_sel, double * out);
    bool iterated = false;            // an iterate call has been made: the device's costs and status are a call's results
    void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
-                          const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-                          unsigned long long * key_out, double * depth_out);
+                          const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
    // every shard plans and walks its own runs; outputs [n_runs] or NULL; throws when a run has too many samples (unless
    // scope.long_marks_run).  scope.which 1 on a batch that has not been iterated throws select_best's message
-   void collision_verdict_planned(const std::vector<double> & vmax, int col0,
-                                  const std::vector<int> & pairs, const std::vector<double> & pair_rsum, const std::vector<double> & inact_pos,
-                                  unsigned long long * key_out, double * depth_out, double * time_out, int * n_samples_out,
-                                  const VerdictScope & scope = VerdictScope());
+   void collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
+                                  int * n_samples_out, const VerdictScope & scope = VerdictScope());
    // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
    // kept until it is set again
    int verdict_scope = 0;
@@ -371,7 +380,7 @@ public:
       const std::vector<int> * devices_override = nullptr, std::shared_ptr<const SceneTable> scenes = nullptr);
    Batch & batch(int id);
    void destroy_batch(int id);
-   // collision verdict of all runs of a batch (gettraj's re-check, batched on the device): per run
+   // collision verdict of all runs of a batch (gettraj's re-check, batched on the device; verdict.cpp): per run
    // collides (0/1), time of the first contact on the retimed trajectory, XML sphere, field, depth
    void batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check = true);
    // the same verdict planned on the device (no trajectory is read back); every output may be NULL: the keys stay on the
@@ -435,10 +444,6 @@ private:
    std::mutex timing_mutex_;
 };
 
-void hip_check(hipError_t e, const char * what);
 int count_int_conversions(const std::string & pattern);   // integer conversions of a printf pattern, -1: it holds another kind
-// the collision verdict's plan of one trajectory [n_points][n] (retime_linear, then a sample every 0.04 rad): appended to the outputs
-void host_verdict_samples(const double * traj, int n_points, int n, int col0, const std::vector<double> & vmax,
-   std::vector<int> & seg_out, std::vector<double> & u_out, std::vector<double> & time_out);
 
 } // namespace orc

@@ -1,4 +1,4 @@
-// verdict_device.h -- the two collision verdicts of a batch (verdict_kernels.hip), as batch.cpp launches them.
+// verdict_device.h -- the two collision verdicts of a batch (verdict_kernels.hip), as verdict.cpp launches them.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "dev_types.h"
