@@ -1,7 +1,7 @@
 // batch.cpp -- a batch of independent CHOMP runs on one GPU (its collision verdicts: verdict.cpp).
 // Host side of struct run / cd_chomp (src/orcdchomp_mod.cpp:887-966, 2104-2674;
 // src/libcd/chomp.h:38-101): uploads what the stages of `create` fold and plan (stages.h), keeps
-// the per-run state in HBM (run-major), plans the hmc resamples, launches the fused kernel.
+// the per-run state in HBM (run-major), launches the fused kernel (the hmc resamples of a call: hmc.cpp).
 #include "module.h"
 #include "kernel_table.h"
 #include "launch.h"
@@ -12,29 +12,6 @@
 #include <stdexcept>
 #include <thread>
 #include <exception>
-#include <cstdlib>
-
-// launch wrappers implemented in hmc_kernels.hip
-hipError_t orc_launch_hmc_seed(uint32_t * state, int * next, const unsigned int * seeds, int n_runs, hipStream_t stream);
-hipError_t orc_launch_hmc_plan_f64(uint32_t * state, int * next, int n_runs, int iter_begin, int iter_end, int cap, size_t mn, double lambda,
-   double * noise, int * iters, int * overflow, hipStream_t stream);
-hipError_t orc_launch_hmc_plan_f32(uint32_t * state, int * next, int n_runs, int iter_begin, int iter_end, int cap, size_t mn, double lambda,
-   float * noise, int * iters, int * overflow, hipStream_t stream);
-// multistart_kernels.hip
-size_t orc_perturb_lds_bytes(int m, int n);
-hipError_t orc_launch_perturb_f64(double * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
-   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
-   const int * source_of_run, hipStream_t stream);
-hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
-   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
-   const int * source_of_run, hipStream_t stream);
-hipError_t orc_launch_respawn_rank(const double * costs, const int * status, const unsigned long long * verdict_key, int mode, int column, int keep,
-   int n_groups, const int * group_offs, const int * members, int max_group, int * source_of_run, int * n_survivors, hipStream_t stream);
-hipError_t orc_launch_respawn_copy(void * traj, void * AG, int precision, int * leapfrog_first, const int * source_of_run,
-   int n_runs, int n_points, int n, int m, hipStream_t stream);
-hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
-   unsigned long long * key, int * count, int * best, hipStream_t stream);
-hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);
 
 namespace orc {
 
@@ -44,8 +21,6 @@ void DevBuf::reset(void * p)
    p_ = p; device_ = -1;
    if (p) hip_check(hipGetDevice(&device_), "hipGetDevice");
 }
-
-static void dev_free(void * p) { if (p) (void) hipFree(p); }
 
 BatchShard::BatchShard(Module * mod, int dev, hipStream_t stream, const Robot & robot, const BatchParams & p, int nruns,
    const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
@@ -86,7 +61,7 @@ void BatchShard::construct(const Robot & robot, const double * starts, const dou
 
    if (p.precision == 64) { build_device<double>(robot); seed_runs<double>(robot, starts, goals, basegoals); }
    else { build_device<float>(robot); seed_runs<float>(robot, starts, goals, basegoals); }
-   start_hmc(seeds);
+   hmc_.reset(new HmcPlanner(mod_, device, stream_, n_runs, (size_t) m * n, p.precision, p.hmc_resample_lambda, p.use_hmc != 0, sw_, seeds));
 }
 
 // endpoints of every run, the straight-line seed on the device (mod.cpp:2417-2464) and the runs' state
@@ -143,48 +118,13 @@ void BatchShard::seed_runs(const Robot & robot, const double * starts, const dou
    }
 }
 
-// hmc state (mod.cpp:2303-2304, 2634-2635)
-// the streams live on the device for large batches (one thread per run draws the plan of a call),
-// in host GslRng objects otherwise (and whenever the caller supplies the noise: set_noise)
-void BatchShard::start_hmc(const unsigned int * seeds)
-{
-   const BatchParams & p = params;
-   hipStream_t st = stream_;
-   hmc_on_device_ = p.use_hmc && (n_runs >= 256 || sw_.hmc_device) && !sw_.hmc_host;
-   if (hmc_on_device_)
-   {
-      d_mt_.reset(dev_alloc<uint32_t>((size_t) 625 * n_runs)); d_mt_bak_.reset(dev_alloc<uint32_t>((size_t) 625 * n_runs));
-      d_hmc_next_.reset(dev_alloc<int>(n_runs)); d_hmc_next_bak_.reset(dev_alloc<int>(n_runs)); d_overflow_.reset(dev_alloc<int>(1));
-      DevBuf d_seeds;
-      if (seeds)
-      {
-         d_seeds.reset(dev_alloc<unsigned int>(n_runs));
-         hip_check(hipMemcpyAsync(d_seeds.as<void>(), seeds, n_runs*sizeof(unsigned int), hipMemcpyHostToDevice, st), "seeds");
-      }
-      hip_check(orc_launch_hmc_seed(d_mt_.as<uint32_t>(), d_hmc_next_.as<int>(), d_seeds.as<unsigned int>(), n_runs, st), "hmc seed");
-      hip_check(hipStreamSynchronize(st), "hmc seed sync");
-      hip_check(hipMemsetAsync(d_overflow_.as<void>(), 0, sizeof(int), st), "hmc overflow");
-      hip_check(hipStreamSynchronize(st), "hmc overflow");
-      // (the plan's buffers -- [n_runs][cap][m n] of noise: 1.8 GB for BASELINE config 4 -- are the first iterate call's to
-      // allocate: a caller that creates many batches ahead of time holds none of them until a batch runs)
-   }
-   else
-   {
-      rng_.resize(p.use_hmc ? n_runs : 0);
-      for (int k=0; k<(int) rng_.size(); k++) rng_[k].set(seeds ? seeds[k] : 0);
-   }
-   hmc_resample_iter_.assign(n_runs, 0);
-   ext_noise_used_.assign(n_runs, 0);
-}
-
 BatchShard::~BatchShard()
 {
    DeviceGuard guard(device);
    (void) hipStreamSynchronize(stream_);
    try { harvest_events(true); } catch (...) {}
-   for (int k=0; k<2; k++) if (ev_plan_[k]) (void) hipEventDestroy(ev_plan_[k]);
    for (auto & ev : pending_events_) { mod_->release_event(device, ev.first); mod_->release_event(device, ev.second); }
-   // (the device buffers and the shard's share of the fields' copies go with their handles)
+   // (the device buffers, the hmc plan and the shard's share of the fields' copies go with their handles)
 }
 
 // kernel timing: a launch is bracketed by two events on the shard's stream
@@ -303,171 +243,8 @@ void BatchShard::build_device(const Robot & robot)
    plan_ = plan_iterate(in, sw_);
 }
 
-// which iterations of this call resample the momentum, and with what noise
-// (src/orcdchomp_mod.cpp:2755-2768; r->iter restarts at 0 on every call, 2752)
-// runs [0, count) split over the host cores (the per-run noise streams are independent)
-static void parallel_for_runs(int count, const std::function<void(int, int)> & body)
-{
-   unsigned hw = std::thread::hardware_concurrency();
-   int nt = (int) std::min<unsigned>(hw ? hw : 1u, 16u);      // containers often grant far fewer cores than they list
-   if (count < 64 || nt < 2) { body(0, count); return; }
-   nt = std::min(nt, count / 16);
-   std::vector<std::thread> pool;
-   for (int t=0; t<nt; t++)
-   {
-      const int lo = (int)((long long) count * t / nt), hi = (int)((long long) count * (t+1) / nt);
-      pool.emplace_back([&body, lo, hi]() { body(lo, hi); });
-   }
-   for (std::thread & th : pool) th.join();
-}
-
-// Resamples of the iterations [iter_begin, iter_end) of an iterate call; the kernel gets their
-// positions relative to iter_begin, the noise scale uses the call's own counter (mod.cpp:2757).
-// room for the momentum resamples of one iterate call of n_iter iterations: Poisson(n_iter lambda) + 8 standard
-// deviations + 6 (a run draws more than that in a call with probability ~1e-12)
-int BatchShard::hmc_room(int n_iter, const Switches & now) const
-{
-   if (now.hmc_room.set) return now.hmc_room.value;      // tests: too little room on purpose
-   const double mean = n_iter * params.hmc_resample_lambda;
-   return (int) std::ceil(mean + 8.0 * std::sqrt(mean) + 6.0);
-}
-
-// the plan's buffers (resample iterations [n_runs][cap], noise [n_runs][cap][m n]) for `cap` resamples per run
-void BatchShard::hmc_reserve(int cap, bool pending_work)
-{
-   const size_t rsize = (params.precision == 64) ? 8 : 4;
-   const size_t icount = (size_t) n_runs * cap, ncount = icount * m * n;
-   // the buffers of this shard's stream, shared by every batch that runs on it (Module::plan_buffers)
-   Module::PlanBuffers & pb = mod_->plan_buffers(device, stream_);
-   if (icount > pb.iters_count || ncount * rsize > pb.noise_bytes)
-   {
-      if (pending_work) hip_check(hipStreamSynchronize(stream_), "hmc buffers: pending work");      // (an earlier launch may still read them)
-      if (icount > pb.iters_count) { dev_free(pb.iters); pb.iters = nullptr; pb.iters_count = 0; pb.iters = dev_alloc<int>(icount); pb.iters_count = icount; }
-      if (ncount * rsize > pb.noise_bytes) { dev_free(pb.noise); pb.noise = nullptr; pb.noise_bytes = 0; hip_check(hipMalloc(&pb.noise, ncount * rsize), "noise"); pb.noise_bytes = ncount * rsize; }
-   }
-   plan_shared_ = true;
-   d_hmc_iters_ = pb.iters; hmc_cap_iters_ = pb.iters_count;
-   d_noise_ = pb.noise; noise_cap_ = pb.noise_bytes;
-}
-
-void BatchShard::plan_hmc(int iter_begin, int iter_end)
-{
-   const size_t mn = (size_t) m * n;
-   const int n_iter = iter_end - iter_begin;
-   if (hmc_on_device_)
-   {
-      const size_t rsize = (params.precision == 64) ? 8 : 4;
-      // (the two switches of the plan are a call's, not a create's: the overflow test sets ORC_HMC_ROOM between the two)
-      const Switches now = Switches::read();
-      if (!now.hmc_plan_sync)
-      {
-         // The plan of the call runs on the device's high-priority plan stream, ordered between the shard's earlier
-         // work and the iterate launch by events: the host does not wait for it (queued on the shard's own stream it
-         // sat behind the other stream's iterate launch for ~14 ms of a config-4 step, and the host with it).
-         // Room for the resamples of a call: hmc_room(); a run that still needs more raises the overflow flag, which the
-         // call's sync reports as an error.  The buffers of a 100-iteration call exist since `create`.
-         const int cap = hmc_room(n_iter, now);
-         hmc_reserve(cap, true);
-         hipStream_t ps = mod_->plan_stream(device);
-         for (int k=0; k<2; k++) if (!ev_plan_[k]) hip_check(hipEventCreateWithFlags(&ev_plan_[k], hipEventDisableTiming), "hipEventCreate");
-         overflow_armed_ = true;
-         hip_check(hipEventRecord(ev_plan_[0], stream_), "hipEventRecord");
-         hip_check(hipStreamWaitEvent(ps, ev_plan_[0], 0), "hipStreamWaitEvent");
-         // (the flag is cleared where it is read, sync_begin: calls queued without a sync in between add to it)
-         hipError_t e = (params.precision == 64)
-            ? orc_launch_hmc_plan_f64(d_mt_.as<uint32_t>(), d_hmc_next_.as<int>(), n_runs, iter_begin, iter_end, cap, mn, params.hmc_resample_lambda, (double *) d_noise_, d_hmc_iters_, d_overflow_.as<int>(), ps)
-            : orc_launch_hmc_plan_f32(d_mt_.as<uint32_t>(), d_hmc_next_.as<int>(), n_runs, iter_begin, iter_end, cap, mn, params.hmc_resample_lambda, (float *) d_noise_, d_hmc_iters_, d_overflow_.as<int>(), ps);
-         hip_check(e, "hmc plan");
-         hip_check(hipEventRecord(ev_plan_[1], ps), "hipEventRecord");
-         hip_check(hipStreamWaitEvent(stream_, ev_plan_[1], 0), "hipStreamWaitEvent");
-         max_resamples_ = cap;
-         return;
-      }
-      int cap = 6 + (int) std::ceil(n_iter * params.hmc_resample_lambda * 3.0);
-      // (this path keeps buffers of its own: an earlier call without the switch may have left the stream's shared ones here)
-      if (plan_shared_) { d_hmc_iters_ = nullptr; d_noise_ = nullptr; hmc_cap_iters_ = 0; noise_cap_ = 0; plan_shared_ = false; }
-      for (;;)
-      {
-         const size_t icount = (size_t) n_runs * cap, ncount = icount * mn;
-         if (icount > hmc_cap_iters_) { own_hmc_iters_.reset(); own_hmc_iters_.reset(dev_alloc<int>(icount)); d_hmc_iters_ = own_hmc_iters_.as<int>(); hmc_cap_iters_ = icount; }
-         if (ncount * rsize > noise_cap_) { own_noise_.reset(); own_noise_.reset(dev_alloc<char>(ncount * rsize)); d_noise_ = own_noise_.as<void>(); noise_cap_ = ncount * rsize; }
-         // a run with more resamples than `cap` makes the call start over with twice the room
-         hip_check(hipMemcpyAsync(d_mt_bak_.as<void>(), d_mt_.as<void>(), (size_t) 625 * n_runs * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream_), "hmc backup");
-         hip_check(hipMemcpyAsync(d_hmc_next_bak_.as<void>(), d_hmc_next_.as<void>(), n_runs * sizeof(int), hipMemcpyDeviceToDevice, stream_), "hmc backup");
-         hip_check(hipMemsetAsync(d_overflow_.as<void>(), 0, sizeof(int), stream_), "hmc overflow");
-         hipError_t e = (params.precision == 64)
-            ? orc_launch_hmc_plan_f64(d_mt_.as<uint32_t>(), d_hmc_next_.as<int>(), n_runs, iter_begin, iter_end, cap, mn, params.hmc_resample_lambda, (double *) d_noise_, d_hmc_iters_, d_overflow_.as<int>(), stream_)
-            : orc_launch_hmc_plan_f32(d_mt_.as<uint32_t>(), d_hmc_next_.as<int>(), n_runs, iter_begin, iter_end, cap, mn, params.hmc_resample_lambda, (float *) d_noise_, d_hmc_iters_, d_overflow_.as<int>(), stream_);
-         hip_check(e, "hmc plan");
-         int over = 0;
-         hip_check(hipMemcpyAsync(&over, d_overflow_.as<void>(), sizeof(int), hipMemcpyDeviceToHost, stream_), "hmc overflow");
-         hip_check(hipStreamSynchronize(stream_), "hmc plan sync");
-         if (!over) { max_resamples_ = cap; return; }
-         hip_check(hipMemcpyAsync(d_mt_.as<void>(), d_mt_bak_.as<void>(), (size_t) 625 * n_runs * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream_), "hmc restore");
-         hip_check(hipMemcpyAsync(d_hmc_next_.as<void>(), d_hmc_next_bak_.as<void>(), n_runs * sizeof(int), hipMemcpyDeviceToDevice, stream_), "hmc restore");
-         cap *= 2;
-      }
-   }
-   std::vector<std::vector<int>> iters(n_runs);
-   std::vector<std::vector<double>> noise(n_runs);
-   int maxr = 0;
-   parallel_for_runs(n_runs, [&](int k_lo, int k_hi) {
-   for (int k=k_lo; k<k_hi; k++)
-   {
-      int & used_ext = ext_noise_used_[k];
-      for (int it=iter_begin; it<iter_end; it++)
-      {
-         if (it != hmc_resample_iter_[k]) continue;
-         const double alpha = 100.0 * std::exp(0.02 * it);
-         const double sigma = 1.0 / std::sqrt(alpha);
-         const size_t off = noise[k].size();
-         noise[k].resize(off + mn);
-         for (size_t e=0; e<mn; e++) noise[k][off+e] = rng_[k].gaussian(sigma);
-         if (ext_noise_blocks_ > 0 && used_ext < ext_noise_blocks_)
-            std::memcpy(&noise[k][off], &ext_noise_[((size_t) k * ext_noise_blocks_ + used_ext) * mn], mn*sizeof(double));
-         used_ext++;
-         iters[k].push_back(it - iter_begin);
-         hmc_resample_iter_[k] += 1 + (int)(-std::log(rng_[k].uniform()) / params.hmc_resample_lambda);
-      }
-   }
-   });
-   for (int k=0; k<n_runs; k++) maxr = std::max(maxr, (int) iters[k].size());
-   max_resamples_ = maxr;
-   if (maxr == 0) return;
-   std::vector<int> flat((size_t) n_runs * maxr, -1);
-   for (int k=0; k<n_runs; k++) for (size_t r=0; r<iters[k].size(); r++) flat[(size_t) k*maxr + r] = iters[k][r];
-   if (flat.size() > hmc_cap_iters_)
-   {
-      own_hmc_iters_.reset(); own_hmc_iters_.reset(dev_alloc<int>(flat.size())); d_hmc_iters_ = own_hmc_iters_.as<int>(); hmc_cap_iters_ = flat.size();
-   }
-   hip_check(hipMemcpyAsync(d_hmc_iters_, flat.data(), flat.size()*sizeof(int), hipMemcpyHostToDevice, stream_), "hmc iters");
-   const size_t ncount = (size_t) n_runs * maxr * mn;
-   const size_t rsize = (params.precision == 64) ? 8 : 4;
-   if (ncount * rsize > noise_cap_)
-   {
-      own_noise_.reset(); own_noise_.reset(dev_alloc<char>(ncount * rsize)); d_noise_ = own_noise_.as<void>(); noise_cap_ = ncount * rsize;
-   }
-   if (params.precision == 64)
-   {
-      std::vector<double> buf(ncount, 0.0);
-      parallel_for_runs(n_runs, [&](int k_lo, int k_hi) {
-         for (int k=k_lo; k<k_hi; k++) std::copy(noise[k].begin(), noise[k].end(), buf.begin() + (size_t) k*maxr*mn);
-      });
-      hip_check(hipMemcpyAsync(d_noise_, buf.data(), ncount*8, hipMemcpyHostToDevice, stream_), "noise");
-      hip_check(hipStreamSynchronize(stream_), "noise sync");
-   }
-   else
-   {
-      std::vector<float> buf(ncount, 0.f);
-      for (int k=0; k<n_runs; k++)
-         for (size_t e=0; e<noise[k].size(); e++) buf[(size_t) k*maxr*mn + e] = (float) noise[k][e];
-      hip_check(hipMemcpyAsync(d_noise_, buf.data(), ncount*4, hipMemcpyHostToDevice, stream_), "noise");
-      hip_check(hipStreamSynchronize(stream_), "noise sync");
-   }
-}
-
 template <typename real>
-void BatchShard::launch(int n_iter, bool final_eval, bool carry)
+void BatchShard::launch(int n_iter, bool final_eval, bool carry, const HmcPlan & hmc)
 {
    const IteratePlan & P = plan_;
    DevBatch<real> b;
@@ -498,7 +275,7 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    b.shared = run_params_record<real>(params.lambda, params.epsilon, params.obs_factor, params.obs_factor_self);
    b.epsilon_self = (real) params.epsilon_self; b.inv_epsilon_self = (real)1 / b.epsilon_self;
    b.run_params = run_params_on_ ? d_run_params_.as<const RunParams<real>>() : nullptr;
-   b.use_momentum = params.use_momentum; b.use_hmc = params.use_hmc && max_resamples_ > 0;
+   b.use_momentum = params.use_momentum; b.use_hmc = params.use_hmc && hmc.max_resamples > 0;
    b.D = (params.derivative == 1 && params.free_start) ? -1 : params.derivative;
    b.Aband = d_Aband_.as<const real>(); b.beta_s = d_beta_s_.as<const real>(); b.beta_g = d_beta_g_.as<const real>();
    b.metric64 = d_metric64_.as<const double>();
@@ -508,8 +285,8 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
    b.pcr = d_pcr_.as<const real>(); b.Ainv = d_Ainv_.as<const real>();
    b.ss_rank = (met_.solve_mode == 3) ? metric_.ss_rank : 0;
    b.jl_lo = d_jl_lo_.as<const real>(); b.jl_hi = d_jl_hi_.as<const real>();
-   b.hmc_iters = d_hmc_iters_; b.noise = (const real *) d_noise_; b.max_resamples = max_resamples_;
-   if (m >= (1 << ORC_IT_SHIFT) || max_resamples_ >= (1 << ORC_IT_SHIFT)) throw std::runtime_error("too many waypoints or resamples for the phase arguments!");
+   b.hmc_iters = hmc.iters; b.noise = (const real *) hmc.noise; b.max_resamples = hmc.max_resamples;
+   if (m >= (1 << ORC_IT_SHIFT) || hmc.max_resamples >= (1 << ORC_IT_SHIFT)) throw std::runtime_error("too many waypoints or resamples for the phase arguments!");
    b.n_iter = n_iter; b.final_eval = final_eval ? 1 : 0; b.carry_status = carry ? 1 : 0;
    b.conv_patience = conv.patience > 0 ? conv.patience : 0;
    b.conv_rtol = conv.rtol; b.conv_obs_max = conv.obs_max;
@@ -544,7 +321,7 @@ void BatchShard::launch(int n_iter, bool final_eval, bool carry)
 void BatchShard::iterate_async(int n_iter, int iter_begin, bool final_eval, bool carry)
 {
    if (n_iter < 0) throw std::runtime_error("n_iter must be >=0!");
-   if (unusable_) throw std::runtime_error("hmc: an earlier iterate call of this batch ran out of room for its momentum resamples; destroy the batch and create it again!");
+   hmc_->check_usable();
    DeviceGuard guard(device);
    last_n_iter = n_iter;
    const size_t tneed = (size_t) n_runs * (n_iter ? n_iter : 1) * 3;
@@ -553,14 +330,10 @@ void BatchShard::iterate_async(int n_iter, int iter_begin, bool final_eval, bool
       hip_check(hipStreamSynchronize(stream_), "sync");
       d_trace_.reset(); d_trace_.reset(dev_alloc<double>(tneed)); trace_cap_ = tneed;
    }
-   max_resamples_ = 0;
-   if (iter_begin == 0) std::fill(ext_noise_used_.begin(), ext_noise_used_.end(), 0);
-   // The plan's buffers belong to the stream (Module::plan_buffers): the plan and the launch that reads it go into the stream
-   // as one piece -- another shard on the same stream, launched from another host thread, must not get its plan in between.
+   // (the lock of the stream's plan buffers, where the plan takes it, is held through the launch that reads them)
    std::unique_lock<std::mutex> plan_lock;
-   if (params.use_hmc && n_iter > 0 && hmc_on_device_) plan_lock = std::unique_lock<std::mutex>(mod_->plan_buffers(device, stream_).enqueue);
-   if (params.use_hmc && n_iter > 0) plan_hmc(iter_begin, iter_begin + n_iter);
-   if (params.precision == 64) launch<double>(n_iter, final_eval, carry); else launch<float>(n_iter, final_eval, carry);
+   const HmcPlan hmc = hmc_->plan(iter_begin, n_iter, plan_lock);
+   if (params.precision == 64) launch<double>(n_iter, final_eval, carry, hmc); else launch<float>(n_iter, final_eval, carry, hmc);
 }
 
 void BatchShard::sync_begin(double * costs_out, int * status_out, int * iters_out)
@@ -570,11 +343,7 @@ void BatchShard::sync_begin(double * costs_out, int * status_out, int * iters_ou
    if (costs_out) hip_check(hipMemcpyAsync(costs_out, d_costs_.as<void>(), (size_t) n_runs*3*sizeof(double), hipMemcpyDeviceToHost, st), "costs");
    if (status_out) hip_check(hipMemcpyAsync(status_out, d_status_.as<void>(), n_runs*sizeof(int), hipMemcpyDeviceToHost, st), "status");
    if (iters_out) hip_check(hipMemcpyAsync(iters_out, d_iters_done_.as<void>(), n_runs*sizeof(int), hipMemcpyDeviceToHost, st), "iters_done");
-   if (overflow_armed_)
-   {
-      hip_check(hipMemcpyAsync(&overflow_host_, d_overflow_.as<void>(), sizeof(int), hipMemcpyDeviceToHost, st), "hmc overflow");
-      hip_check(hipMemsetAsync(d_overflow_.as<void>(), 0, sizeof(int), st), "hmc overflow");
-   }
+   hmc_->sync_begin();
 }
 
 void BatchShard::sync_end()
@@ -582,14 +351,7 @@ void BatchShard::sync_end()
    DeviceGuard guard(device);
    hip_check(hipStreamSynchronize(stream_), "hipStreamSynchronize");
    harvest_events(false);
-   if (overflow_armed_ && overflow_host_)
-   {
-      // the iterate kernel has run with a cut schedule and the generators have moved on: nothing to go back to
-      overflow_host_ = 0;
-      unusable_ = true;
-      throw std::runtime_error("hmc: a run drew more momentum resamples in one iterate call than the plan has room for (probability ~1e-12 per run and call); "
-                               "the batch is not usable any more: destroy it, create it again and iterate with fewer iterations per call!");
-   }
+   hmc_->sync_end();
 }
 
 namespace {
@@ -675,31 +437,29 @@ void BatchShard::set_traj(const double * traj)
 }
 
 // ---- multi-start ----------------------------------------------------------------------------------------------------
-void BatchShard::perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank)
+void BatchShard::launch_perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank, const int * source_of_run, PerturbUpload & up)
 {
-   DeviceGuard guard(device);
    hipStream_t st = stream_;
-   const size_t lds = orc_perturb_lds_bytes(m, n);
    // one upload: the generators, then the limits of the columns
    std::vector<double> host(gen);
    host.insert(host.end(), jl_lo_.begin(), jl_lo_.end());
    host.insert(host.end(), jl_hi_.begin(), jl_hi_.end());
-   double * d_gen = nullptr; unsigned int * d_seeds = nullptr;
-   try
-   {
-      d_gen = dev_alloc<double>(host.size());
-      d_seeds = dev_alloc<unsigned int>(n_runs);
-      hip_check(hipMemcpyAsync(d_gen, host.data(), host.size()*sizeof(double), hipMemcpyHostToDevice, st), "perturb generators");
-      hip_check(hipMemcpyAsync(d_seeds, seeds, n_runs*sizeof(unsigned int), hipMemcpyHostToDevice, st), "perturb seeds");
-      const double * U = d_gen, * V = d_gen + (size_t) rank * m, * lo = d_gen + (size_t) 2 * rank * m, * hi = lo + n;
-      hipError_t e;
-      if (params.precision == 64) e = orc_launch_perturb_f64(d_traj_.as<double>(), n_runs, n_points, n, m, d_seeds, rank, U, V, scale, lo, hi, lds, nullptr, st);
-      else e = orc_launch_perturb_f32(d_traj_.as<float>(), n_runs, n_points, n, m, d_seeds, rank, U, V, scale, lo, hi, lds, nullptr, st);
-      hip_check(e, "perturb_kernel launch");
-      hip_check(hipStreamSynchronize(st), "perturb sync");
-   }
-   catch (...) { dev_free(d_gen); dev_free(d_seeds); throw; }
-   dev_free(d_gen); dev_free(d_seeds);
+   up.gen.reset(dev_alloc<double>(host.size()));
+   up.seeds.reset(dev_alloc<unsigned int>(n_runs));
+   hip_check(hipMemcpyAsync(up.gen.as<void>(), host.data(), host.size()*sizeof(double), hipMemcpyHostToDevice, st), "perturb generators");
+   hip_check(hipMemcpyAsync(up.seeds.as<void>(), seeds, n_runs*sizeof(unsigned int), hipMemcpyHostToDevice, st), "perturb seeds");
+   const double * U = up.gen.as<double>(), * V = U + (size_t) rank * m, * lo = U + (size_t) 2 * rank * m, * hi = lo + n;
+   const hipError_t e = orc_launch_perturb(d_traj_.as<void>(), params.precision, n_runs, n_points, n, m, up.seeds.as<unsigned int>(), rank, U, V,
+      scale, lo, hi, orc_perturb_lds_bytes(m, n), source_of_run, st);
+   hip_check(e, "perturb_kernel launch");
+}
+
+void BatchShard::perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank)
+{
+   DeviceGuard guard(device);
+   PerturbUpload up;
+   launch_perturb(scale, seeds, gen, rank, nullptr, up);
+   hip_check(hipStreamSynchronize(stream_), "perturb sync");
 }
 
 void BatchShard::respawn(int n_groups, const std::vector<int> & group_offs, const std::vector<int> & members, int column, int mode, int keep,
@@ -710,14 +470,11 @@ void BatchShard::respawn(int n_groups, const std::vector<int> & group_offs, cons
    if (mode != 0 && !d_vkey_) throw std::runtime_error("respawn: no collision verdict on the device!");
    int max_group = 0;
    for (int g=0; g<n_groups; g++) max_group = std::max(max_group, group_offs[g+1] - group_offs[g]);
-   // one upload of ints (the group table, then the members), one of doubles (the generators, then the limits of the columns)
+   // one upload of ints (the group table, then the members); launch_perturb makes the one of doubles
    std::vector<int> table(group_offs);
    table.insert(table.end(), members.begin(), members.end());
-   std::vector<double> host(gen);
-   host.insert(host.end(), jl_lo_.begin(), jl_lo_.end());
-   host.insert(host.end(), jl_hi_.begin(), jl_hi_.end());
-   const bool move = scale > 0.0;
-   DevBuf d_table, d_out, d_gen, d_seeds;
+   DevBuf d_table, d_out;
+   PerturbUpload up;
    d_table.reset(dev_alloc<int>(table.size()));
    d_out.reset(dev_alloc<int>((size_t) n_runs + n_groups));      // source_of_run, then n_survivors
    hip_check(hipMemcpyAsync(d_table.as<void>(), table.data(), table.size()*sizeof(int), hipMemcpyHostToDevice, st), "respawn groups");
@@ -727,19 +484,7 @@ void BatchShard::respawn(int n_groups, const std::vector<int> & group_offs, cons
       n_groups, d_offs, d_members, max_group, d_source, d_nsurv, st), "respawn_rank_kernel launch");
    hip_check(orc_launch_respawn_copy(d_traj_.as<void>(), d_AG_.as<void>(), params.precision, d_leap_.as<int>(), d_source, n_runs, n_points, n, m, st),
       "respawn_copy_kernel launch");
-   if (move)
-   {
-      d_gen.reset(dev_alloc<double>(host.size()));
-      d_seeds.reset(dev_alloc<unsigned int>(n_runs));
-      hip_check(hipMemcpyAsync(d_gen.as<void>(), host.data(), host.size()*sizeof(double), hipMemcpyHostToDevice, st), "respawn generators");
-      hip_check(hipMemcpyAsync(d_seeds.as<void>(), seeds, n_runs*sizeof(unsigned int), hipMemcpyHostToDevice, st), "respawn seeds");
-      const double * U = d_gen.as<double>(), * V = U + (size_t) rank * m, * lo = U + (size_t) 2 * rank * m, * hi = lo + n;
-      const size_t lds = orc_perturb_lds_bytes(m, n);
-      hipError_t e;
-      if (params.precision == 64) e = orc_launch_perturb_f64(d_traj_.as<double>(), n_runs, n_points, n, m, d_seeds.as<unsigned int>(), rank, U, V, scale, lo, hi, lds, d_source, st);
-      else e = orc_launch_perturb_f32(d_traj_.as<float>(), n_runs, n_points, n, m, d_seeds.as<unsigned int>(), rank, U, V, scale, lo, hi, lds, d_source, st);
-      hip_check(e, "perturb_kernel launch");
-   }
+   if (scale > 0.0) launch_perturb(scale, seeds, gen, rank, d_source, up);
    std::vector<int> back((size_t) n_runs + n_groups);
    hip_check(hipMemcpyAsync(back.data(), d_out.as<void>(), back.size()*sizeof(int), hipMemcpyDeviceToHost, st), "respawn plan");
    hip_check(hipStreamSynchronize(st), "respawn sync");
@@ -752,22 +497,20 @@ void BatchShard::select_best(int n_groups, const int * group, bool collision_fre
    DeviceGuard guard(device);
    hipStream_t st = stream_;
    if (collision_free && !d_vkey_) throw std::runtime_error("select_best: no collision verdict on the device!");
-   int * d_group = nullptr; unsigned long long * d_key = nullptr; int * d_best = nullptr; int * d_count = nullptr;
-   try
-   {
-      d_group = dev_alloc<int>(n_runs); d_key = dev_alloc<unsigned long long>(n_groups); d_best = dev_alloc<int>(n_groups); d_count = dev_alloc<int>(n_groups);
-      hip_check(hipMemcpyAsync(d_group, group, n_runs*sizeof(int), hipMemcpyHostToDevice, st), "select groups");
-      hip_check(hipMemsetAsync(d_key, 0xff, n_groups*sizeof(unsigned long long), st), "select keys");
-      hip_check(hipMemsetAsync(d_best, 0x7f, n_groups*sizeof(int), st), "select runs");      // (0x7f7f7f7f: above every run index)
-      hip_check(hipMemsetAsync(d_count, 0, n_groups*sizeof(int), st), "select counts");
-      hip_check(orc_launch_select_best(d_costs_.as<double>(), d_status_.as<int>(), collision_free ? d_vkey_.as<unsigned long long>() : nullptr, d_group, n_runs, column, d_key, d_count, d_best, st), "select_best kernels launch");
-      hip_check(hipMemcpyAsync(key_out, d_key, n_groups*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "select keys");
-      hip_check(hipMemcpyAsync(best_out, d_best, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select runs");
-      hip_check(hipMemcpyAsync(count_out, d_count, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select counts");
-      hip_check(hipStreamSynchronize(st), "select sync");
-   }
-   catch (...) { dev_free(d_group); dev_free(d_key); dev_free(d_best); dev_free(d_count); throw; }
-   dev_free(d_group); dev_free(d_key); dev_free(d_best); dev_free(d_count);
+   DevBuf group_buf, key_buf, best_buf, count_buf;
+   group_buf.reset(dev_alloc<int>(n_runs)); key_buf.reset(dev_alloc<unsigned long long>(n_groups));
+   best_buf.reset(dev_alloc<int>(n_groups)); count_buf.reset(dev_alloc<int>(n_groups));
+   int * d_group = group_buf.as<int>(), * d_best = best_buf.as<int>(), * d_count = count_buf.as<int>();
+   unsigned long long * d_key = key_buf.as<unsigned long long>();
+   hip_check(hipMemcpyAsync(d_group, group, n_runs*sizeof(int), hipMemcpyHostToDevice, st), "select groups");
+   hip_check(hipMemsetAsync(d_key, 0xff, n_groups*sizeof(unsigned long long), st), "select keys");
+   hip_check(hipMemsetAsync(d_best, 0x7f, n_groups*sizeof(int), st), "select runs");      // (0x7f7f7f7f: above every run index)
+   hip_check(hipMemsetAsync(d_count, 0, n_groups*sizeof(int), st), "select counts");
+   hip_check(orc_launch_select_best(d_costs_.as<double>(), d_status_.as<int>(), collision_free ? d_vkey_.as<unsigned long long>() : nullptr, d_group, n_runs, column, d_key, d_count, d_best, st), "select_best kernels launch");
+   hip_check(hipMemcpyAsync(key_out, d_key, n_groups*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "select keys");
+   hip_check(hipMemcpyAsync(best_out, d_best, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select runs");
+   hip_check(hipMemcpyAsync(count_out, d_count, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select counts");
+   hip_check(hipStreamSynchronize(st), "select sync");
 }
 
 // ---- per-run parameters ---------------------------------------------------------------------------------------------
@@ -820,24 +563,12 @@ void BatchShard::gettraj_rows(const std::vector<int> & rows, double * out)
    DeviceGuard guard(device);
    hipStream_t st = stream_;
    const size_t row_len = (size_t) n_points * n;
-   int * d_rows = nullptr; double * d_out = nullptr;
-   try
-   {
-      d_rows = dev_alloc<int>(rows.size()); d_out = dev_alloc<double>(rows.size() * row_len);
-      hip_check(hipMemcpyAsync(d_rows, rows.data(), rows.size()*sizeof(int), hipMemcpyHostToDevice, st), "gather rows");
-      hip_check(orc_launch_gather_rows(d_traj_.as<void>(), params.precision, d_rows, (int) rows.size(), row_len, d_out, st), "gather_rows_kernel launch");
-      hip_check(hipMemcpyAsync(out, d_out, rows.size()*row_len*sizeof(double), hipMemcpyDeviceToHost, st), "gather download");
-      hip_check(hipStreamSynchronize(st), "gather sync");
-   }
-   catch (...) { dev_free(d_rows); dev_free(d_out); throw; }
-   dev_free(d_rows); dev_free(d_out);
-}
-
-void BatchShard::set_noise(const double * noise, int n_blocks)
-{
-   if (hmc_on_device_) throw std::runtime_error("caller-supplied noise needs the host noise streams (ORC_HMC_HOST=1, or fewer than 256 runs)!");
-   ext_noise_blocks_ = n_blocks;
-   ext_noise_.assign(noise, noise + (size_t) n_runs * n_blocks * m * n);
+   DevBuf d_rows, d_out;
+   d_rows.reset(dev_alloc<int>(rows.size())); d_out.reset(dev_alloc<double>(rows.size() * row_len));
+   hip_check(hipMemcpyAsync(d_rows.as<void>(), rows.data(), rows.size()*sizeof(int), hipMemcpyHostToDevice, st), "gather rows");
+   hip_check(orc_launch_gather_rows(d_traj_.as<void>(), params.precision, d_rows.as<int>(), (int) rows.size(), row_len, d_out.as<double>(), st), "gather_rows_kernel launch");
+   hip_check(hipMemcpyAsync(out, d_out.as<void>(), rows.size()*row_len*sizeof(double), hipMemcpyDeviceToHost, st), "gather download");
+   hip_check(hipStreamSynchronize(st), "gather sync");
 }
 
 // ================================================================ Batch ===

@@ -7,9 +7,10 @@
 // recurrence and tempering; GSL seeds 0 as 4357) and writes the noise blocks and their iterations for
 // the iterate kernel.  State layout [625][n_runs] (word i of
 // all runs contiguous; row 624 is the stream position), so that lockstep runs read coalesced.
-// A batch's stream lives either here or in the host's GslRng objects (batch.cpp picks at create).
+// A batch's stream lives either here or in the host's GslRng objects (hmc.cpp: HmcPlanner picks at create).
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "launch.h"
 #include "mt_wave.h"
 
 namespace {
@@ -81,15 +82,11 @@ hipError_t orc_launch_hmc_seed(uint32_t * state, int * next, const unsigned int 
    hipLaunchKernelGGL(hmc_seed_kernel, dim3((n_runs + 63) / 64), dim3(64), 0, stream, state, next, seeds, n_runs);
    return hipGetLastError();
 }
-hipError_t orc_launch_hmc_plan_f64(uint32_t * state, int * next, int n_runs, int iter_begin, int iter_end, int cap, size_t mn, double lambda,
-   double * noise, int * iters, int * overflow, hipStream_t stream)
+hipError_t orc_launch_hmc_plan(uint32_t * state, int * next, int n_runs, int iter_begin, int iter_end, int cap, size_t mn, double lambda,
+   int precision, void * noise, int * iters, int * overflow, hipStream_t stream)
 {
-   hipLaunchKernelGGL(hmc_plan_kernel<double>, dim3((n_runs + ORC_HMC_WAVES - 1) / ORC_HMC_WAVES), dim3(64 * ORC_HMC_WAVES), 0, stream, state, next, n_runs, iter_begin, iter_end, cap, mn, lambda, noise, iters, overflow);
-   return hipGetLastError();
-}
-hipError_t orc_launch_hmc_plan_f32(uint32_t * state, int * next, int n_runs, int iter_begin, int iter_end, int cap, size_t mn, double lambda,
-   float * noise, int * iters, int * overflow, hipStream_t stream)
-{
-   hipLaunchKernelGGL(hmc_plan_kernel<float>, dim3((n_runs + ORC_HMC_WAVES - 1) / ORC_HMC_WAVES), dim3(64 * ORC_HMC_WAVES), 0, stream, state, next, n_runs, iter_begin, iter_end, cap, mn, lambda, noise, iters, overflow);
+   const dim3 grid((n_runs + ORC_HMC_WAVES - 1) / ORC_HMC_WAVES), block(64 * ORC_HMC_WAVES);
+   if (precision == 64) hipLaunchKernelGGL(hmc_plan_kernel<double>, grid, block, 0, stream, state, next, n_runs, iter_begin, iter_end, cap, mn, lambda, (double *) noise, iters, overflow);
+   else hipLaunchKernelGGL(hmc_plan_kernel<float>, grid, block, 0, stream, state, next, n_runs, iter_begin, iter_end, cap, mn, lambda, (float *) noise, iters, overflow);
    return hipGetLastError();
 }

@@ -1,6 +1,8 @@
-// launch.h -- the launch wrappers of chomp_kernel.hip, as batch.cpp calls them (one name per wrapper, overloaded by precision).
+// launch.h -- the launch wrappers of chomp_kernel.hip, hmc_kernels.hip and multistart_kernels.hip, as the host layer calls them: the
+// iterate and seed wrappers are overloaded by precision, the others take `int precision` (64 or 32) and a `void *` array.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdint>
 #include "dev_types.h"
 
 // the row of kernel_table.h that (variant, block, precision) names; hipErrorInvalidValue when the library holds no such kernel
@@ -9,3 +11,20 @@ hipError_t orc_launch_iterate(const DevBatch<float> & b, size_t lds, hipStream_t
 // straight-line seed trajectories (instantiated for double and float)
 template <typename real>
 hipError_t orc_launch_seed(real * traj, const double * starts, const double * goals, int n_runs, int n_points, int n, int floating, hipStream_t stream);
+
+// hmc_kernels.hip: the generators' state [625][n_runs] and every run's next resample iteration; the plan of a call's iterations
+hipError_t orc_launch_hmc_seed(uint32_t * state, int * next, const unsigned int * seeds, int n_runs, hipStream_t stream);
+hipError_t orc_launch_hmc_plan(uint32_t * state, int * next, int n_runs, int iter_begin, int iter_end, int cap, size_t mn, double lambda,
+   int precision, void * noise, int * iters, int * overflow, hipStream_t stream);
+// multistart_kernels.hip
+size_t orc_perturb_lds_bytes(int m, int n);
+hipError_t orc_launch_perturb(void * traj, int precision, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
+   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
+   const int * source_of_run, hipStream_t stream);
+hipError_t orc_launch_respawn_rank(const double * costs, const int * status, const unsigned long long * verdict_key, int mode, int column, int keep,
+   int n_groups, const int * group_offs, const int * members, int max_group, int * source_of_run, int * n_survivors, hipStream_t stream);
+hipError_t orc_launch_respawn_copy(void * traj, void * AG, int precision, int * leapfrog_first, const int * source_of_run,
+   int n_runs, int n_points, int n, int m, hipStream_t stream);
+hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
+   unsigned long long * key, int * count, int * best, hipStream_t stream);
+hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);

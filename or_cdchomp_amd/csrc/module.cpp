@@ -203,11 +203,6 @@ Module::~Module()
       DeviceGuard guard(kv.first);
       (void) hipStreamDestroy(kv.second);
    }
-   for (auto & kv : plan_buffers_)
-   {
-      DeviceGuard guard(kv.first.first);
-      (void) hipFree(kv.second.noise); (void) hipFree(kv.second.iters);
-   }
 }
 
 hipEvent_t Module::acquire_event(int dev)

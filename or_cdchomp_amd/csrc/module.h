@@ -16,6 +16,8 @@
 #include <string>
 #include <vector>
 #include "stages.h"      // Robot, Sdf, SceneTable, TsrSpec, BatchParams; the stages of `create`
+#include "devbuf.h"      // DeviceGuard, hip_check, DevBuf, dev_alloc, upload
+#include "hmc.h"         // HmcPlan, PlanStore, HmcPlanner: the momentum-resampling plan of HMC runs
 #include "verdict.h"     // VerdictInputs, the sample clock, the free functions of the collision verdict
 
 template <typename real> struct DevVerdictWalk;      // verdict_device.h
@@ -34,58 +36,6 @@ struct KinBody                    // a kinbody of oriented boxes (InitFromBoxes 
    // reads from a body the robot holds (src/orcdchomp_mod.cpp:2173-2211); `link` is unused
    std::vector<Robot::Sphere> spheres;
 };
-
-// makes `device` the calling thread's current HIP device for the lifetime of the object
-// (every entry point of a batch asserts its device: several modules, or the shards of one batch,
-// may live on different GPUs of the node inside one process)
-class DeviceGuard
-{
-public:
-   explicit DeviceGuard(int device);
-   ~DeviceGuard();
-   DeviceGuard(const DeviceGuard &) = delete;
-   DeviceGuard & operator=(const DeviceGuard &) = delete;
-private:
-   int prev_ = -1;
-   bool changed_ = false;
-};
-
-void hip_check(hipError_t e, const char * what);
-// device memory released on the device it was allocated on
-std::shared_ptr<void> device_buffer(int device, size_t bytes);
-
-// Device memory with one owner: what the handle holds is freed when it is reset or destroyed, on the device that was current
-// when the handle took it (the device of the allocation).
-class DevBuf
-{
-public:
-   DevBuf() = default;
-   ~DevBuf() { reset(); }
-   DevBuf(const DevBuf &) = delete;
-   DevBuf & operator=(const DevBuf &) = delete;
-   void reset(void * p = nullptr);
-   template <typename T> T * as() const { return static_cast<T *>(p_); }
-   explicit operator bool() const { return p_ != nullptr; }
-private:
-   void * p_ = nullptr;
-   int device_ = -1;
-};
-// what a DevBuf is reset with: an array of `count` elements (at least one); below, a host vector uploaded as `real`s (waits for the copy)
-template <typename T> T * dev_alloc(size_t count)
-{
-   T * p = nullptr;
-   hip_check(hipMalloc((void **) &p, (count ? count : 1) * sizeof(T)), "hipMalloc");
-   return p;
-}
-
-template <typename real> real * upload(const std::vector<double> & v, hipStream_t s)
-{
-   std::vector<real> tmp(v.begin(), v.end());
-   real * d = dev_alloc<real>(tmp.size());
-   hip_check(hipMemcpyAsync(d, tmp.data(), tmp.size() * sizeof(real), hipMemcpyHostToDevice, s), "upload");
-   hip_check(hipStreamSynchronize(s), "upload sync");
-   return d;
-}
 
 // Which runs a device-planned collision verdict examines, and what it does about the samples nobody walks (the fields of the
 // same names in DevVerdictPlan, verdict_device.h).  The default is orc_batch_collision_verdict_device's: every run, the
@@ -131,7 +81,7 @@ public:
    void get_plan(double out[9]) const;      // kernel variant bits, threads per workgroup, LDS bytes, tile, solve mode, workgroups per CU, tiles, lanes per waypoint, first tile
    void get_state(const std::string & which, double * out);
    void get_trace(double * out);
-   void set_noise(const double * noise, int n_blocks);
+   void set_noise(const double * noise, int n_blocks) { hmc_->set_noise(noise, n_blocks); }      // caller-supplied blocks (host streams only)
    void set_traj(const double * traj);          // [n_runs][n_points][n] host -> device (warm start)
    // multi-start (multistart_kernels.hip).  m n of a run perturb stages in LDS: 8 m n + 2496 (the mt19937 state) <= 160 KB - 256
    static constexpr size_t ORC_PERTURB_MAX_MN = 20136;
@@ -187,8 +137,10 @@ private:
    template <typename real> void build_device(const Robot & robot);     // the stages of stages.h, and the uploads of what they return
    template <typename real> std::shared_ptr<void> grid_on_device(Sdf & s);      // the device's copy of a field's grid, shared by the shards
    template <typename real> void seed_runs(const Robot & robot, const double * starts, const double * goals, const double * basegoals);
-   void start_hmc(const unsigned int * seeds);
-   template <typename real> void launch(int n_iter, bool final_eval, bool carry);
+   template <typename real> void launch(int n_iter, bool final_eval, bool carry, const HmcPlan & hmc);
+   // generators, limits and seeds of a perturbation go up and perturb_kernel is launched (source_of_run: a respawn's plan, or NULL); no wait
+   struct PerturbUpload { DevBuf gen, seeds; };
+   void launch_perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank, const int * source_of_run, PerturbUpload & up);
    // what both verdicts put on the device (verdict.cpp): the tables of DevVerdictWalk, which the handles keep until the kernel has run
    struct VerdictTables { DevBuf xml, pairs, rsum, inact, depth; };
    template <typename real> void verdict_walk_args(const VerdictInputs & in, const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w);
@@ -196,9 +148,6 @@ private:
       const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
    template <typename real> bool collision_verdict_planned_typed(const VerdictInputs & in, unsigned long long * key_out, double * depth_out,
       double * time_out, int * n_samples_out, const VerdictScope & scope);
-   void plan_hmc(int iter_begin, int iter_end);
-   int hmc_room(int n_iter, const Switches & now) const;
-   void hmc_reserve(int cap, bool pending_work);
    void construct(const Robot & robot, const double * starts, const double * goals, const double * basegoals,
       const unsigned int * seeds);
    Module * mod_;
@@ -226,24 +175,8 @@ private:
    DevBuf d_Aband_, d_beta_s_, d_beta_g_, d_metric64_, d_pcr_, d_Ainv_, d_jl_lo_, d_jl_hi_;
    // TSR hard constraints (csrc/tsr.h): the device copies of the constraints, the per-run workspace
    DevBuf d_tsrs_, d_tsr_ws_, d_tsr_err_;
-   // The momentum resamples of a call: iterations [n_runs][cap] and noise [n_runs][cap][m n].  NOT owned: they point at the
-   // module's buffers of this shard's stream (plan_shared_, Module::plan_buffers) or at own_* below
-   int * d_hmc_iters_ = nullptr; void * d_noise_ = nullptr; size_t hmc_cap_iters_ = 0, noise_cap_ = 0;
-   bool plan_shared_ = false;
-   DevBuf own_hmc_iters_, own_noise_;
-   int max_resamples_ = 0;
-   hipEvent_t ev_plan_[2] = { nullptr, nullptr };   // iterate stream -> plan stream -> iterate stream
-   int overflow_host_ = 0; bool overflow_armed_ = false;   // the plan's overflow flag, read (and cleared) with the results of a call
-   bool unusable_ = false;                                  // set by an overflow: the runs' schedules were cut short, the batch has to be created again
    std::vector<double> jl_lo_, jl_hi_;
-   // hmc host state per run (src/orcdchomp_mod.cpp:948-952)
-   std::vector<GslRng> rng_;
-   // ... or, for large batches, on the device (hmc_kernels.hip): mt19937 state [625][n_runs], next resample iteration [n_runs]
-   bool hmc_on_device_ = false;
-   DevBuf d_mt_, d_mt_bak_, d_hmc_next_, d_hmc_next_bak_, d_overflow_;
-   std::vector<int> hmc_resample_iter_;
-   std::vector<double> ext_noise_; int ext_noise_blocks_ = 0;
-   std::vector<int> ext_noise_used_;   // caller-supplied blocks consumed by the current iterate call, per run
+   std::unique_ptr<HmcPlanner> hmc_;         // the momentum-resampling plan of the runs (hmc.h), made at the end of `construct`
 };
 
 // A batch as the boundary sees it: its runs are cut into contiguous blocks, one BatchShard per
@@ -411,7 +344,7 @@ public:
    // The momentum-resampling plan of an iterate call (noise [n_runs][cap][m n], resample iterations [n_runs][cap]) is written and
    // read inside that one call, so the batches that run on one stream share one pair of buffers: the stream orders their
    // calls.  (A buffer per batch held 1.8 GB for every config-4 batch a caller had created ahead of time.)
-   struct PlanBuffers { void * noise = nullptr; size_t noise_bytes = 0; int * iters = nullptr; size_t iters_count = 0; std::mutex enqueue; };
+   struct PlanBuffers { PlanStore store; std::mutex enqueue; };
    PlanBuffers & plan_buffers(int device, hipStream_t stream);
    // kernel timing (HIP events on the shards' streams), harvested from the shards
    void time_collect();

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "dev_types.h"
+#include "launch.h"
 #include "mt_wave.h"
 #include "run_candidate.h"
 
@@ -272,17 +273,12 @@ size_t orc_perturb_lds_bytes(int m, int n)
    return (size_t) m * n * sizeof(double) + 624 * sizeof(uint32_t);
 }
 // source_of_run: NULL, or the plan of a respawn (its survivors are skipped)
-hipError_t orc_launch_perturb_f64(double * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
+hipError_t orc_launch_perturb(void * traj, int precision, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
    const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
    const int * source_of_run, hipStream_t stream)
 {
-   return launch_perturb<double>(traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, source_of_run, stream);
-}
-hipError_t orc_launch_perturb_f32(float * traj, int n_runs, int n_points, int n, int m, const unsigned int * seeds, int D,
-   const double * genU, const double * genV, double scale, const double * lim_lo, const double * lim_hi, size_t lds,
-   const int * source_of_run, hipStream_t stream)
-{
-   return launch_perturb<float>(traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, source_of_run, stream);
+   if (precision == 64) return launch_perturb<double>((double *) traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, source_of_run, stream);
+   return launch_perturb<float>((float *) traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, source_of_run, stream);
 }
 // LDS of a group's workgroup: 14 bytes per member of the largest group (the caller refuses groups over
 // BatchShard::ORC_RESPAWN_MAX_GROUP, module.h: 56 KB, inside what a kernel has without asking)

@@ -114,7 +114,7 @@ struct BatchParams
 
 // The ORC_* diagnostics switches of the environment (NOTES/switches.md), read once per `create` (BatchShard::construct)
 // and handed to the stages; a shard's later calls go by what its `create` read.  (`hmc_room` and `hmc_plan_sync` alone are
-// a call's: plan_hmc reads them again, the overflow test sets ORC_HMC_ROOM between `create` and `iterate`.)
+// a call's: HmcPlanner::plan reads them again, the overflow test sets ORC_HMC_ROOM between `create` and `iterate`.)
 struct Switches
 {
    struct Int { bool set = false; int value = 0; };      // a switch with a number: is it set, and atoi of its text

@@ -118,6 +118,107 @@ def test_hmc_batches_of_one_stream_share_the_plan_buffers(monkeypatch):
     assert np.array_equal(mod.batch_gettraj(b), alone[1])
 
 
+def _replay_host_noise(oracle, seeds, n_iter, mn, lam):
+    """the blocks the host planner draws for one iterate call of n_iter iterations, per run in resample order: at a
+    resample iteration `it` m n Gaussians of sigma 1/sqrt(100 exp(0.02 it)), then one uniform u, and the next resample
+    at it + 1 + int(-log(u)/lambda); the first is at iteration 0 (src/orcdchomp_mod.cpp:2755-2768)"""
+    import ctypes as C
+    L = oracle.lib()
+    blocks = []
+    for seed in seeds:
+        r = oracle.Rng()
+        L.ora_rng_set(C.byref(r), int(seed))
+        mine, nxt = [], 0
+        for it in range(n_iter):
+            if it != nxt:
+                continue
+            sigma = 1.0 / np.sqrt(100.0 * np.exp(0.02 * it))
+            mine.append(np.array([L.ora_ran_gaussian(C.byref(r), sigma) for _ in range(mn)]))
+            nxt += 1 + int(-np.log(L.ora_rng_uniform(C.byref(r))) / lam)
+        blocks.append(mine)
+    return blocks
+
+
+@pytest.mark.parametrize("precision", [64, 32])
+def test_caller_supplied_noise_replays_the_host_streams(oracle, monkeypatch, precision):
+    """orc_batch_set_noise: a batch given the blocks its own streams would draw (replayed with the oracle's generator)
+    computes what the batch on its streams computes, bit for bit; so does one given the first block only (the later
+    resamples fall back to the stream, which was advanced all the same); the negated blocks give something else (they
+    are read).  Seeds 0..3 draw 4, 4, 4 and 3 resamples in the 12 iterations.  fp32 is compared with the fp32 batch on its
+    own streams: the host planner's (float) conversion of either source"""
+    monkeypatch.setenv("ORC_HMC_HOST", "1")
+    mod = _mk_module()
+    model = common.setup_product_wam(mod)
+    _, base, _, _ = common.wam_state()
+    n_runs, n_points, n_iter, lam = 4, 12, 12, 0.3
+    goals = common.wam_goals(n_runs, seed=20250103)
+    basegoals = np.tile(np.asarray(base), (n_runs, 1))
+    seeds = np.arange(n_runs, dtype=np.uint32)
+    kw = dict(n_points=n_points, lambda_=100.0, obs_factor=500.0, floating_base=1, use_momentum=1, use_hmc=1,
+              hmc_resample_lambda=lam, precision=precision)
+
+    def run(noise=None):
+        bid = mod.batch_create(model.name, goals, basegoals=basegoals, seeds=seeds, **kw)
+        if noise is not None:
+            mod.batch_set_noise(bid, noise)
+        costs, status = mod.batch_iterate(bid, n_iter)
+        out = (mod.batch_gettraj(bid), costs, status)
+        mod.batch_destroy(bid)
+        return out
+
+    mn = (n_points - 2) * 14
+    blocks = _replay_host_noise(oracle, seeds, n_iter, mn, lam)
+    counts = [len(b) for b in blocks]
+    print("resamples per run:", counts)
+    assert min(counts) >= 2, counts
+    noise = np.zeros((n_runs, max(counts), mn))
+    for k, mine in enumerate(blocks):
+        noise[k, :len(mine)] = mine
+    a = run()
+    assert np.all(np.isfinite(a[0])) and np.all(np.isfinite(a[1]))
+    for name, given in (("all blocks", noise), ("the first block", noise[:, :1])):
+        got = run(given)
+        assert np.array_equal(got[0], a[0]) and np.array_equal(got[1], a[1]) and np.array_equal(got[2], a[2]), name
+    d = run(-noise)
+    assert not np.array_equal(d[0], a[0])
+    monkeypatch.delenv("ORC_HMC_HOST")
+    monkeypatch.setenv("ORC_HMC_DEVICE", "1")
+    bid = mod.batch_create(model.name, goals, basegoals=basegoals, seeds=seeds, **kw)
+    with pytest.raises(RuntimeError, match="caller-supplied noise needs the host noise streams"):
+        mod.batch_set_noise(bid, noise)
+    mod.batch_destroy(bid)
+
+
+def test_synchronous_hmc_plan_retries_with_more_room(oracle, monkeypatch):
+    """ORC_HMC_PLAN_SYNC draws the plan on the shard's stream and waits; a run that needs more room than the call began
+    with makes it back the generators up, double the room and draw again.  With ORC_HMC_ROOM=1 as the first room the
+    retry runs twice in the first call (of seeds 0..7, run 0 draws three resamples in 20 iterations at lambda 0.05 and
+    run 6 two: asserted below by replaying the streams), and two calls give bit for bit what the plan stream's way
+    gives.  What the test cannot see is whether the first room really was 1: were ORC_HMC_ROOM ignored under
+    ORC_HMC_PLAN_SYNC again (as it was before hmc.cpp), the results would be the same and the retry not reached"""
+    counts = [len(b) for b in _replay_host_noise(oracle, np.arange(8), 20, 14 * 14, 0.05)]
+    assert counts[0] == 3 and counts[6] == 2, counts          # more than a room of one, and of two: the loop doubles twice
+    monkeypatch.setenv("ORC_HMC_DEVICE", "1")
+    legs = []
+    for sync in (False, True):
+        mod = _mk_module()
+        model = common.setup_product_wam(mod)
+        bid = _hmc_batch(mod, model, 8, 0, n_points=16)
+        if sync:
+            monkeypatch.setenv("ORC_HMC_PLAN_SYNC", "1")
+            monkeypatch.setenv("ORC_HMC_ROOM", "1")
+        out = []
+        for n_iter in (20, 6):
+            costs, status = mod.batch_iterate(bid, n_iter)
+            out.append((mod.batch_gettraj(bid), costs, status))
+        mod.batch_destroy(bid)
+        legs.append(out)
+    for plain, retried in zip(*legs):
+        assert np.all(np.isfinite(plain[1]))
+        for x, y in zip(plain, retried):
+            assert np.array_equal(x, y)
+
+
 def _tree_scene(mod, oracle, cube_extent):
     """four box kinbodies with their own fields (config 5), returned for the oracle as well"""
     rng = np.random.default_rng(20250104)
