@@ -5,6 +5,7 @@
 #include "module.h"
 #include "kernel_table.h"
 #include "launch.h"
+#include "trajdoc.h"      // count_int_conversions
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -14,13 +15,6 @@
 #include <exception>
 
 namespace orc {
-
-void DevBuf::reset(void * p)
-{
-   if (p_) { DeviceGuard guard(device_); (void) hipFree(p_); }
-   p_ = p; device_ = -1;
-   if (p) hip_check(hipGetDevice(&device_), "hipGetDevice");
-}
 
 BatchShard::BatchShard(Module * mod, int dev, hipStream_t stream, const Robot & robot, const BatchParams & p, int nruns,
    const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
@@ -945,24 +939,6 @@ void Batch::get_wave_hwid(unsigned int * out)
 
 // create's dat_filename (src/orcdchomp_mod.cpp:2306-2310): one file per run; a batch of several
 // runs takes a printf pattern with one %d (the run index)
-// conversions of a printf pattern: the number of integer conversions (%d, %i, %u with flags and a width), or -1
-// when the pattern holds any other conversion (a caller's pattern is never handed to printf with one)
-int count_int_conversions(const std::string & pattern)
-{
-   int count = 0;
-   for (size_t k=0; k<pattern.size(); k++)
-   {
-      if (pattern[k] != '%') continue;
-      if (k + 1 < pattern.size() && pattern[k+1] == '%') { k++; continue; }
-      size_t q = k + 1;
-      while (q < pattern.size() && (pattern[q] == '0' || pattern[q] == '-' || pattern[q] == '+' || pattern[q] == ' ')) q++;
-      while (q < pattern.size() && pattern[q] >= '0' && pattern[q] <= '9') q++;
-      if (q >= pattern.size() || (pattern[q] != 'd' && pattern[q] != 'i' && pattern[q] != 'u')) return -1;
-      count++; k = q;
-   }
-   return count;
-}
-
 void Batch::open_dat(const std::string & pattern)
 {
    // one run: the name as it is (src/orcdchomp_mod.cpp:2306-2310); a batch: a pattern with exactly one integer

@@ -1,0 +1,248 @@
+// batch.h -- a batch of CHOMP runs as the host layer holds it: the shard of its runs on one device, the batch over the shards, and
+// the small structs their calls take (batch.cpp, verdict.cpp).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstdio>
+#include <functional>
+#include <memory>
+#include <string>
+#include <vector>
+#include "stages.h"      // Robot, Sdf, SceneTable, TsrSpec, BatchParams; the stages of `create`
+#include "devbuf.h"      // DeviceGuard, hip_check, DevBuf, dev_alloc, upload
+#include "hmc.h"         // HmcPlan, PlanStore, HmcPlanner: the momentum-resampling plan of HMC runs
+#include "verdict.h"     // VerdictInputs, the sample clock, the free functions of the collision verdict
+
+template <typename real> struct DevVerdictWalk;      // verdict_device.h
+
+namespace orc {
+
+// Which runs a device-planned collision verdict examines, and what it does about the samples nobody walks (the fields of the
+// same names in DevVerdictPlan, verdict_device.h).  The default is orc_batch_collision_verdict_device's: every run, the
+// samples behind a contact counted, a run that is too long fails the call.
+struct VerdictScope
+{
+   int which = -1;                            // -1 every run; 0 the runs of `examine`; 1 the candidates (run_candidate.h)
+   const unsigned char * examine = nullptr;   // which 0: a byte per run of the BATCH, nonzero: examine it (a shard takes its slice)
+   bool count_rest = true;                    // false: n_samples of an examined run is not exact and nobody counts to 2^30
+   bool long_marks_run = false;               // true: a run that is too long reports n_samples ORC_VERDICT_TOO_LONG and the call succeeds
+};
+
+// the convergence stop of a batch's runs (orc_batch_set_convergence; dev_types.h DevBatch::conv_*): patience 0 is off
+struct ConvergenceSpec
+{
+   double rtol = 0.0;
+   int patience = 0;
+   double obs_max = HUGE_VAL;
+   // rejects a NaN or non-positive rtol and a NaN obs_max when the stop is on (throws)
+   void validate() const;
+};
+
+class Module;
+
+// a contiguous block of the runs of a batch on ONE device: n_runs independent runs sharing robot,
+// fields and parameters (struct run, src/orcdchomp_mod.cpp:887-966, once per run in the reference)
+class BatchShard
+{
+public:
+   BatchShard(Module * mod, int device, hipStream_t stream, const Robot & robot, const BatchParams & p, int n_runs,
+      const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
+      std::shared_ptr<const SceneTable> scenes, int run0);
+   ~BatchShard();
+   BatchShard(const BatchShard &) = delete;
+   BatchShard & operator=(const BatchShard &) = delete;
+   // iterations [iter_begin, iter_begin + n_iter) of an iterate call (r->iter restarts at 0 in every
+   // call, src/orcdchomp_mod.cpp:2752: the hmc schedule compares against it), then the cost-only pass
+   // `carry`: the launch continues an iterate call (runs that left their limits earlier in the call stay out)
+   void iterate_async(int n_iter, int iter_begin = 0, bool final_eval = true, bool carry = false);
+   void sync_begin(double * costs_out, int * status_out, int * iters_out);   // enqueue the copies
+   void sync_end();                                                          // wait for them
+   void gettraj(double * out);
+   void get_plan(double out[9]) const;      // kernel variant bits, threads per workgroup, LDS bytes, tile, solve mode, workgroups per CU, tiles, lanes per waypoint, first tile
+   void get_state(const std::string & which, double * out);
+   void get_trace(double * out);
+   void set_noise(const double * noise, int n_blocks) { hmc_->set_noise(noise, n_blocks); }      // caller-supplied blocks (host streams only)
+   void set_traj(const double * traj);          // [n_runs][n_points][n] host -> device (warm start)
+   // multi-start (multistart_kernels.hip).  m n of a run perturb stages in LDS: 8 m n + 2496 (the mt19937 state) <= 160 KB - 256
+   static constexpr size_t ORC_PERTURB_MAX_MN = 20136;
+   // perturb: T[moving] += scale * A^-1 xi(seed of the run), clamped to the limits;
+   // gen = the generators of A^-1, U [rank][m] then V [rank][m] (Batch::perturb builds them once for all shards)
+   void perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank);
+   // per group the lowest cost key among this shard's eligible runs, the lowest LOCAL run that has it, the eligible runs;
+   // group [n_runs] is this shard's slice; collision_free: a run whose key of the last collision_verdict_planned (kept on
+   // the device) names a contact is not eligible
+   // column: which of costs[run][0..2] is minimised (eligibility always asks for a finite TOTAL cost)
+   void select_best(int n_groups, const int * group, bool collision_free, int column, unsigned long long * key_out, int * best_out, int * count_out);
+   // respawn (orc_batch_respawn): the largest group the ranking kernel takes (14 bytes of LDS per member: 56 KB)
+   static constexpr int ORC_RESPAWN_MAX_GROUP = 4096;
+   // This shard's groups as a CSR over its LOCAL runs (group_offs [n_groups + 1], members ascending per group, every run in one
+   // group): ranks every group, makes every run that does not survive a copy of its source or the straight line, perturbs those
+   // runs when scale > 0 (seeds, gen, rank: as in perturb).  mode 1, 2: the keys of the collision_verdict_planned made just
+   // before.  One synchronisation, at the end; source_out [n_runs] (local runs, -1: the line) and n_survivors_out [n_groups]
+   // are what comes back
+   void respawn(int n_groups, const std::vector<int> & group_offs, const std::vector<int> & members, int column, int mode, int keep,
+      double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank, int * source_out, int * n_survivors_out);
+   // per-run lambda, epsilon, obs_factor, obs_factor_self of this shard's runs (orc_batch_set_run_params): table [n_runs][4] doubles,
+   // validated by Batch::set_run_params, converted to the batch's precision here and uploaded on the shard's stream (so that launches
+   // enqueued before keep the old values); NULL: the later launches read no table
+   void set_run_params(const double * table);
+   void get_run_params(double * out);       // [n_runs][4]: what the device holds, or the shared values when there is no table
+   // rows[k] (local runs) of the trajectory array as doubles: out [rows.size()][n_points][n]
+   void gettraj_rows(const std::vector<int> & rows, double * out);
+   const Metric & metric() const { return metric_; }
+   // (verdict.cpp) first contact of every run's trajectory with a field, on the device (Module::batch_collision_verdict plans the samples)
+   void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
+                          const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
+   // the same verdict with the retiming and the samples planned on the device (verdict_kernels.hip): nothing but vmax
+   // [n - col0] and the pair tables goes up, and what of key / depth / time / n_samples [n_runs] is not NULL comes back; the
+   // keys stay on the device for select_best.  Returns false when a run has too many samples (nothing is written then).
+   // scope: the runs that are examined (its `examine` is this shard's slice); a run that is not has the key ORC_VERDICT_NONE
+   bool collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
+                                  int * n_samples_out, const VerdictScope & scope = VerdictScope());
+   void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
+   void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
+   // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
+   void harvest_events(bool wait);
+
+   int n_runs, n_points, n, m;
+   BatchParams params;
+   ConvergenceSpec conv;           // sticky for the later iterate calls (Batch::set_convergence)
+   int last_n_iter = 0;
+   int device;
+   std::string robot_name;
+   std::vector<int> adofindices;
+   std::vector<int> device_sphere_order;    // XML index of device sphere k
+   std::vector<int> slot_xml;               // XML index of the sphere in lane/slot q of the active block, -1: empty
+private:
+   template <typename real> void build_device(const Robot & robot);     // the stages of stages.h, and the uploads of what they return
+   template <typename real> std::shared_ptr<void> grid_on_device(Sdf & s);      // the device's copy of a field's grid, shared by the shards
+   template <typename real> void seed_runs(const Robot & robot, const double * starts, const double * goals, const double * basegoals);
+   template <typename real> void launch(int n_iter, bool final_eval, bool carry, const HmcPlan & hmc);
+   // generators, limits and seeds of a perturbation go up and perturb_kernel is launched (source_of_run: a respawn's plan, or NULL); no wait
+   struct PerturbUpload { DevBuf gen, seeds; };
+   void launch_perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank, const int * source_of_run, PerturbUpload & up);
+   // what both verdicts put on the device (verdict.cpp): the tables of DevVerdictWalk, which the handles keep until the kernel has run
+   struct VerdictTables { DevBuf xml, pairs, rsum, inact, depth; };
+   template <typename real> void verdict_walk_args(const VerdictInputs & in, const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w);
+   template <typename real> void collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
+      const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
+   template <typename real> bool collision_verdict_planned_typed(const VerdictInputs & in, unsigned long long * key_out, double * depth_out,
+      double * time_out, int * n_samples_out, const VerdictScope & scope);
+   void construct(const Robot & robot, const double * starts, const double * goals, const double * basegoals,
+      const unsigned int * seeds);
+   Module * mod_;
+   hipStream_t stream_ = nullptr;   // the stream all work of this shard is issued on
+   Switches sw_;                    // the environment's switches as `create` found them
+   std::vector<std::shared_ptr<void>> sdf_refs_;   // the field copies the device descriptors point at
+   std::shared_ptr<const SceneTable> scenes_;      // the batch's scenes; this shard holds runs [run0_, run0_ + n_runs) of its scene_of_run
+   int run0_ = 0;
+   std::vector<std::pair<hipEvent_t, hipEvent_t>> pending_events_;
+   Metric metric_;
+   // what the stages of `create` left (stages.h)
+   ModelScalars ms_ = {};           // the device model's scalars (carried in the kernarg block)
+   TsrDims tsr_;
+   SceneDims scn_;
+   MetricDims met_;
+   IteratePlan plan_;
+   // device buffers of the shard (typed by params.precision: a cast where they are used)
+   DevBuf d_model_, d_sdfs_, d_sdfc_, d_scene_of_run_, d_scene_nsdf_;
+   DevBuf d_traj_, d_AG_, d_G_, d_Gcost_;
+   DevBuf d_costs_, d_trace_; size_t trace_cap_ = 0;
+   DevBuf d_conv_prev_, d_conv_streak_;      // [n_runs] the convergence stop's state between the launches of a call
+   DevBuf d_status_, d_iters_done_, d_leap_, d_phase_, d_hwid_;
+   DevBuf d_run_params_; bool run_params_on_ = false;      // [n_runs] RunParams<real>; kept allocated while off (launches in flight may read it)
+   DevBuf d_vkey_;                           // [n_runs] the keys of the last collision_verdict_planned
+   DevBuf d_Aband_, d_beta_s_, d_beta_g_, d_metric64_, d_pcr_, d_Ainv_, d_jl_lo_, d_jl_hi_;
+   // TSR hard constraints (csrc/tsr.h): the device copies of the constraints, the per-run workspace
+   DevBuf d_tsrs_, d_tsr_ws_, d_tsr_err_;
+   std::vector<double> jl_lo_, jl_hi_;
+   std::unique_ptr<HmcPlanner> hmc_;         // the momentum-resampling plan of the runs (hmc.h), made at the end of `construct`
+};
+
+// A batch as the boundary sees it: its runs are cut into contiguous blocks, one BatchShard per
+// entry of the module's device list (no collective, the caller's arrays are the
+// gather).  One device: one shard.
+class Batch
+{
+public:
+   Batch(Module * mod, const std::vector<int> & devices, const Robot & robot, const BatchParams & p, int n_runs,
+      const double * starts, const double * goals, const double * basegoals, const unsigned int * seeds,
+      std::shared_ptr<const SceneTable> scenes);
+   ~Batch();
+   void iterate_async(int n_iter, int iter_begin = 0, bool final_eval = true, bool carry = false);
+   void sync(double * costs_out, int * status_out, int * iters_out = nullptr);
+   void gettraj(double * out);
+   void get_plan(double out[9]);            // the plan of the first shard (all shards of a batch plan alike)
+   void get_state(const std::string & which, double * out);
+   void get_trace(double * out);
+   void set_noise(const double * noise, int n_blocks);
+   void set_traj(const double * traj);
+   // multi-start: orc_batch_perturb / _select_best / _gettraj_runs (include/orcdchomp_amd.h has the contract)
+   void perturb(double sigma, const unsigned int * seeds);
+   // what a perturbation of this batch needs: the generators of A^-1 (U [D][m], then V [D][m]) and sigma c; throws for a bad
+   // sigma and for the batches orc_batch_perturb rejects, whatever sigma is; sigma == 0: scale 0 and no generators
+   struct PerturbPlan { std::vector<double> gen; int D = 0; double scale = 0.0; };
+   PerturbPlan perturb_plan(double sigma) const;
+   // respawn (orc_batch_respawn): respawn_plan checks every argument and builds the shards' group tables without any device
+   // work (throws); respawn then runs on every shard that has a group.  The verdict, for mode 1 and 2, is taken between the two
+   struct RespawnPlan
+   {
+      int column = 0, mode = 0, keep = 1, n_groups = 0;
+      PerturbPlan perturb;
+      struct Shard { std::vector<int> groups, group_offs, members; };      // the shard's groups (the caller's numbers), their CSR over local runs
+      std::vector<Shard> shards;
+   };
+   RespawnPlan respawn_plan(int cost_column, int n_groups, const int * group_of_run, int collision_mode, int keep, double sigma,
+      const unsigned int * seeds) const;
+   void respawn(const RespawnPlan & plan, const unsigned int * seeds, int * source_of_run_out, int * n_survivors_out);
+   std::vector<int> select_groups(int n_groups, const int * group_of_run) const;   // the validated group of every run (NULL: contiguous equal blocks); throws
+   // collision_free: the runs' keys of the collision_verdict_planned made just before (they never left the device)
+   // column 0 total, 1 obs, 2 smooth: the cost that is minimised and reported (validate with select_column first)
+   void select_best(int n_groups, const std::vector<int> & group, bool collision_free, int column, int * best_run_out, double * best_cost_out, int * n_eligible_out);
+   static void select_column(int column);   // throws unless 0, 1 or 2
+   // per-run parameters: each array [n_runs] or NULL (the value of `params`); all NULL switches the table off.  Throws and changes
+   // nothing on a NaN or infinite entry or a lambda or epsilon <= 0
+   void set_run_params(const double * lambda, const double * epsilon, const double * obs_factor, const double * obs_factor_self);
+   void get_run_params(double * out);       // [n_runs][4]
+   void gettraj_runs(const int * runs, int n_sel, double * out);
+   bool iterated = false;            // an iterate call has been made: the device's costs and status are a call's results
+   void collision_verdict(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
+                          const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
+   // every shard plans and walks its own runs; outputs [n_runs] or NULL; throws when a run has too many samples (unless
+   // scope.long_marks_run).  scope.which 1 on a batch that has not been iterated throws select_best's message
+   void collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
+                                  int * n_samples_out, const VerdictScope & scope = VerdictScope());
+   // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
+   // kept until it is set again
+   int verdict_scope = 0;
+   void set_verdict_scope(int scope);        // throws unless 0 or 1
+   VerdictScope selection_scope() const;     // what that verdict is taken with
+   void get_phase_cycles(long long * out);
+   void get_wave_hwid(unsigned int * out);
+   // the convergence stop of every shard's runs for the later iterate calls (validated: throws and changes nothing on a bad spec)
+   void set_convergence(const ConvergenceSpec & c);
+   const ConvergenceSpec & convergence() const { return shards[0]->conv; }
+   // the per-iteration log of create's dat_filename (src/orcdchomp_mod.cpp:2306-2310, 2811-2818)
+   void open_dat(const std::string & pattern);
+   void write_dat(int iter_begin, int n_iter, const int * iters_done, double t_begin, double t_end);
+
+   int n_runs, n_points, n, m;
+   BatchParams params;
+   int last_n_iter = 0;
+   std::string robot_name;
+   std::vector<int> adofindices;
+   std::vector<int> device_sphere_order;
+   std::vector<int> slot_xml;
+   std::vector<Robot::Sphere> run_spheres;   // the spheres create collected (robot + held bodies): what the XML indices count through
+   std::vector<unsigned char> run_self_excl; // [n][n] pairs of them the re-check's self-collision leg never tests (Robot::run_self_pairs_excluded, taken at create)
+   std::vector<std::unique_ptr<BatchShard>> shards;
+   std::vector<int> offs;            // first run of every shard, then n_runs
+   std::shared_ptr<const SceneTable> scenes;   // the runs' obstacles as create placed them
+   bool per_run_scenes = false;      // created with a scene table (orc_batch_create_scenes): gettraj's re-check walks the run's scene
+   bool has_dat() const { return !dat_.empty(); }
+private:
+   void for_shards(const std::function<void(size_t)> & body, bool threads);
+   std::vector<FILE *> dat_;         // one per run (a single run: the reference's fp_dat)
+};
+
+} // namespace orc

@@ -31,6 +31,29 @@ void need(const void * p, const char * what)
    if (!p) throw std::runtime_error(std::string("null argument: ") + what);
 }
 const char * str(const char * s, const char * what) { need(s, what); return s; }
+
+orc::BatchParams to_params(const orc_batch_params & p)
+{
+   orc::BatchParams q;
+   q.n_points = p.n_points; q.floating_base = p.floating_base; q.lambda = p.lambda;
+   q.derivative = p.derivative; q.use_momentum = p.use_momentum; q.use_hmc = p.use_hmc;
+   q.hmc_resample_lambda = p.hmc_resample_lambda; q.epsilon = p.epsilon; q.epsilon_self = p.epsilon_self;
+   q.obs_factor = p.obs_factor; q.obs_factor_self = p.obs_factor_self; q.precision = p.precision;
+   return q;
+}
+
+// the same validation the create command performs (mod.cpp:2091-2097); no_fields: the call plans with the module's field list and
+// that list is empty (orc_batch_create_scenes brings its fields in the scene table and passes false)
+void check_create(const orc::BatchParams & q, int n_runs, const double * goals, const double * basegoals, bool no_fields)
+{
+   if (!goals) throw std::runtime_error("Did not pass either adofgoal or starttraj!");
+   if (q.floating_base && !basegoals) throw std::runtime_error("Passed floating_base with no basegoal!");
+   if (!q.floating_base && basegoals) throw std::runtime_error("Passed basegoal with no floating_base!");
+   if (no_fields) throw std::runtime_error("No signed distance fields have yet been computed!");
+   if (q.lambda < 0.01) throw std::runtime_error("lambda must be >=0.01!");
+   if (q.n_points < 3) throw std::runtime_error("n_points must be >=3!");
+   if (n_runs < 1) throw std::runtime_error("n_runs must be >=1!");
+}
 }
 
 extern "C" {
@@ -150,19 +173,19 @@ int orc_env_add_robot(orc_module * mod, const char * name, const orc_robot_desc 
       }
       r.dof_values.assign(d->n_dof, 0.0);
       for (int i=0; i<d->n_dof; i++) r.active_dofs.push_back(i);
-      mod->impl->add_robot(r);
+      mod->impl->env.add_robot(r);
    });
 }
 
 int orc_robot_set_transform(orc_module * mod, const char * name, const double pose[7])
 {
-   return guarded(mod, [&] { need(pose, "pose"); mod->impl->robot(str(name, "name")).transform = orc::Pose(pose); });
+   return guarded(mod, [&] { need(pose, "pose"); mod->impl->env.robot(str(name, "name")).transform = orc::Pose(pose); });
 }
 
 int orc_robot_set_dof_values(orc_module * mod, const char * name, const double * values, int n)
 {
    return guarded(mod, [&] {
-      orc::Robot & r = mod->impl->robot(str(name, "name"));
+      orc::Robot & r = mod->impl->env.robot(str(name, "name"));
       if (n != r.n_dof) throw std::runtime_error("wrong number of dof values!");
       if (n) need(values, "values");
       r.dof_values.assign(values, values + n);
@@ -172,7 +195,7 @@ int orc_robot_set_dof_values(orc_module * mod, const char * name, const double *
 int orc_robot_set_active_dofs(orc_module * mod, const char * name, const int * indices, int n)
 {
    return guarded(mod, [&] {
-      orc::Robot & r = mod->impl->robot(str(name, "name"));
+      orc::Robot & r = mod->impl->env.robot(str(name, "name"));
       if (n < 0) throw std::runtime_error("bad dof index!");
       if (n) need(indices, "indices");
       for (int i=0; i<n; i++) if (indices[i] < 0 || indices[i] >= r.n_dof) throw std::runtime_error("bad dof index!");
@@ -183,7 +206,7 @@ int orc_robot_set_active_dofs(orc_module * mod, const char * name, const int * i
 int orc_robot_set_velocity_limits(orc_module * mod, const char * name, const double * limits, int n)
 {
    return guarded(mod, [&] {
-      orc::Robot & r = mod->impl->robot(str(name, "name"));
+      orc::Robot & r = mod->impl->env.robot(str(name, "name"));
       if (n != r.n_dof) throw std::runtime_error("wrong number of velocity limits!");
       if (n) need(limits, "limits");
       r.limit_vel.assign(limits, limits + n);
@@ -210,7 +233,7 @@ int orc_set_workgroups_per_cu(orc_module * mod, int workgroups)
 int orc_robot_set_link_names(orc_module * mod, const char * name, const char * const * names, int n)
 {
    return guarded(mod, [&] {
-      orc::Robot & r = mod->impl->robot(str(name, "name"));
+      orc::Robot & r = mod->impl->env.robot(str(name, "name"));
       if (n != r.n_links) throw std::runtime_error("wrong number of link names!");
       need(names, "names");
       for (int i=0; i<n; i++) need(names[i], "a link name");
@@ -221,7 +244,7 @@ int orc_robot_set_link_names(orc_module * mod, const char * name, const char * c
 int orc_robot_add_manipulator(orc_module * mod, const char * name, const char * manip, int ee_link, const double tool_pose[7])
 {
    return guarded(mod, [&] {
-      orc::Robot & r = mod->impl->robot(str(name, "name"));
+      orc::Robot & r = mod->impl->env.robot(str(name, "name"));
       if (ee_link < 0 || ee_link >= r.n_links) throw std::runtime_error("manipulator end-effector link out of range!");
       orc::Robot::Manip m;
       m.name = str(manip, "manipulator name"); m.link = ee_link;
@@ -233,7 +256,7 @@ int orc_robot_add_manipulator(orc_module * mod, const char * name, const char * 
 int orc_robot_set_adjacent_links(orc_module * mod, const char * name, const int * link_pairs, int n_pairs)
 {
    return guarded(mod, [&] {
-      orc::Robot & r = mod->impl->robot(str(name, "name"));
+      orc::Robot & r = mod->impl->env.robot(str(name, "name"));
       if (n_pairs < 0 || (n_pairs > 0 && !link_pairs)) throw std::runtime_error("bad adjacent link list!");
       r.adjacent.clear();
       for (int k=0; k<n_pairs; k++)
@@ -247,13 +270,13 @@ int orc_robot_set_adjacent_links(orc_module * mod, const char * name, const int 
 
 int orc_robot_set_self_check(orc_module * mod, const char * name, int enabled)
 {
-   return guarded(mod, [&] { mod->impl->robot(str(name, "name")).self_check = enabled != 0; });
+   return guarded(mod, [&] { mod->impl->env.robot(str(name, "name")).self_check = enabled != 0; });
 }
 
 int orc_robot_set_active_manipulator(orc_module * mod, const char * name, const char * manip)
 {
    return guarded(mod, [&] {
-      orc::Robot & r = mod->impl->robot(str(name, "name"));
+      orc::Robot & r = mod->impl->env.robot(str(name, "name"));
       for (size_t k=0; k<r.manips.size(); k++)
          if (r.manips[k].name == str(manip, "manipulator name")) { r.active_manip = (int) k; return; }
       throw std::runtime_error("manipulator not found!");
@@ -275,7 +298,7 @@ int orc_env_add_kinbody_boxes(orc_module * mod, const char * name, int n_boxes, 
          for (int q=0; q<3; q++) b.half[q] = half_extents[3*i+q];
          k.boxes.push_back(b);
       }
-      mod->impl->add_kinbody(k);
+      mod->impl->env.add_kinbody(k);
    });
 }
 
@@ -287,32 +310,32 @@ int orc_env_add_kinbody_trimesh(orc_module * mod, const char * name, int n_tri, 
       if (n_tri > (1 << 26)) throw std::runtime_error("too many triangles in one mesh (at most 2^26)!");
       for (size_t i=0; i<9*(size_t) n_tri; i++) if (!std::isfinite(vertices[i])) throw std::runtime_error("mesh vertices must be finite numbers!");
       const std::string nm = str(name, "name");
-      if (mod->impl->has_body(nm))
+      if (mod->impl->env.has_body(nm))
       {
          // a kinbody of boxes gets its mesh geometry added (a body may have both kinds); a robot of that name is an error.
          // A body whose distance field exists already keeps the field of its OLD geometry (computedistancefield refuses a second
          // one: "We already have an sdf for this kinbody!"), so new geometry for it is an error here, not a stale field later
-         if (mod->impl->find_sdf(nm)) throw std::runtime_error("that kinbody has a distance field already: removefield first!");
-         orc::KinBody & k = mod->impl->kinbody(nm);
+         if (mod->impl->env.find_sdf(nm)) throw std::runtime_error("that kinbody has a distance field already: removefield first!");
+         orc::KinBody & k = mod->impl->env.kinbody(nm);
          k.tris.insert(k.tris.end(), vertices, vertices + 9*(size_t) n_tri);
          return;
       }
       orc::KinBody k;
       k.name = nm;
       k.tris.assign(vertices, vertices + 9*(size_t) n_tri);
-      mod->impl->add_kinbody(k);
+      mod->impl->env.add_kinbody(k);
    });
 }
 
 int orc_kinbody_set_transform(orc_module * mod, const char * name, const double pose[7])
 {
-   return guarded(mod, [&] { need(pose, "pose"); mod->impl->set_kinbody_transform(str(name, "name"), orc::Pose(pose)); });
+   return guarded(mod, [&] { need(pose, "pose"); mod->impl->env.set_kinbody_transform(str(name, "name"), orc::Pose(pose)); });
 }
 
 int orc_kinbody_set_spheres(orc_module * mod, const char * name, int n_spheres, const double * sphere_pos, const double * sphere_radius)
 {
    return guarded(mod, [&] {
-      orc::KinBody & k = mod->impl->kinbody(str(name, "name"));
+      orc::KinBody & k = mod->impl->env.kinbody(str(name, "name"));
       if (n_spheres < 0) throw std::runtime_error("bad number of spheres!");
       if (n_spheres) { need(sphere_pos, "sphere_pos"); need(sphere_radius, "sphere_radius"); }
       k.spheres.clear();
@@ -323,38 +346,38 @@ int orc_kinbody_set_spheres(orc_module * mod, const char * name, int n_spheres, 
          for (int q=0; q<3; q++) sp.pos[q] = sphere_pos[3*i+q];
          k.spheres.push_back(sp);
       }
-      mod->impl->refresh_grab_contacts(k.name);      // (a held body's contacts were taken with its old spheres)
+      mod->impl->env.refresh_grab_contacts(k.name);      // (a held body's contacts were taken with its old spheres)
    });
 }
 
 int orc_robot_grab(orc_module * mod, const char * robot, const char * kinbody, int link)
 {
-   return guarded(mod, [&] { mod->impl->grab(str(robot, "robot"), str(kinbody, "kinbody"), link); });
+   return guarded(mod, [&] { mod->impl->env.grab(str(robot, "robot"), str(kinbody, "kinbody"), link); });
 }
 
 int orc_robot_release(orc_module * mod, const char * robot, const char * kinbody)
 {
-   return guarded(mod, [&] { mod->impl->release(str(robot, "robot"), str(kinbody, "kinbody")); });
+   return guarded(mod, [&] { mod->impl->env.release(str(robot, "robot"), str(kinbody, "kinbody")); });
 }
 
 int orc_robot_release_all(orc_module * mod, const char * robot)
 {
-   return guarded(mod, [&] { mod->impl->release_all(str(robot, "robot")); });
+   return guarded(mod, [&] { mod->impl->env.release_all(str(robot, "robot")); });
 }
 
 int orc_body_get_transform(orc_module * mod, const char * name, double pose_out[7])
 {
    return guarded(mod, [&] {
       need(pose_out, "pose_out");
-      if (!mod->impl->has_body(str(name, "name"))) throw std::runtime_error("Could not find kinbody with that name!");
-      const orc::Pose p = mod->impl->body_transform(name);
+      if (!mod->impl->env.has_body(str(name, "name"))) throw std::runtime_error("Could not find kinbody with that name!");
+      const orc::Pose p = mod->impl->env.body_transform(name);
       for (int i=0; i<7; i++) pose_out[i] = p.v[i];
    });
 }
 
 int orc_kinbody_enable(orc_module * mod, const char * name, int enabled)
 {
-   return guarded(mod, [&] { mod->impl->kinbody(str(name, "name")).enabled = enabled != 0; });
+   return guarded(mod, [&] { mod->impl->env.kinbody(str(name, "name")).enabled = enabled != 0; });
 }
 
 int orc_scene_add_sdf(orc_module * mod, const char * kinbody, const int sizes[3], const double lengths[3],
@@ -362,12 +385,12 @@ int orc_scene_add_sdf(orc_module * mod, const char * kinbody, const int sizes[3]
 {
    return guarded(mod, [&] {
       need(kinbody, "kinbody"); need(sizes, "sizes"); need(lengths, "lengths"); need(pose, "pose"); need(data, "data");
-      if (!mod->impl->has_body(kinbody)) throw std::runtime_error("Could not find kinbody with that name!");
+      if (!mod->impl->env.has_body(kinbody)) throw std::runtime_error("Could not find kinbody with that name!");
       for (int i=0; i<3; i++) if (sizes[i] < 2 || !(lengths[i] > 0.0)) throw std::runtime_error("sdf grids need at least 2 cells per dimension and positive lengths!");
       orc::Grid g;
       for (int i=0; i<3; i++) { g.sizes[i] = sizes[i]; g.lengths[i] = lengths[i]; }
       g.data.assign(data, data + g.ncells());
-      mod->impl->add_sdf(kinbody, g, orc::Pose(pose));
+      mod->impl->env.add_sdf(kinbody, g, orc::Pose(pose));
    });
 }
 
@@ -376,7 +399,7 @@ int orc_scene_get_sdf(orc_module * mod, const char * kinbody, int sizes[3], doub
 {
    return guarded(mod, [&] {
       need(kinbody, "kinbody"); need(sizes, "sizes"); need(lengths, "lengths"); need(pose, "pose");
-      orc::Sdf * s = mod->impl->find_sdf(kinbody);
+      orc::Sdf * s = mod->impl->env.find_sdf(kinbody);
       if (!s) throw std::runtime_error("No sdf for that kinbody!");
       for (int i=0; i<3; i++) { sizes[i] = s->grid.sizes[i]; lengths[i] = s->grid.lengths[i]; }
       for (int i=0; i<7; i++) pose[i] = s->pose.v[i];
@@ -403,19 +426,8 @@ int orc_batch_create(orc_module * mod, const char * robot, const orc_batch_param
 {
    return guarded(mod, [&] {
       need(robot, "robot"); need(p, "params"); need(batch_id, "batch_id");
-      orc::BatchParams q;
-      q.n_points = p->n_points; q.floating_base = p->floating_base; q.lambda = p->lambda;
-      q.derivative = p->derivative; q.use_momentum = p->use_momentum; q.use_hmc = p->use_hmc;
-      q.hmc_resample_lambda = p->hmc_resample_lambda; q.epsilon = p->epsilon; q.epsilon_self = p->epsilon_self;
-      q.obs_factor = p->obs_factor; q.obs_factor_self = p->obs_factor_self; q.precision = p->precision;
-      // the same validation the create command performs (mod.cpp:2091-2097)
-      if (!goals) throw std::runtime_error("Did not pass either adofgoal or starttraj!");
-      if (q.floating_base && !basegoals) throw std::runtime_error("Passed floating_base with no basegoal!");
-      if (!q.floating_base && basegoals) throw std::runtime_error("Passed basegoal with no floating_base!");
-      if (mod->impl->sdfs.empty()) throw std::runtime_error("No signed distance fields have yet been computed!");
-      if (q.lambda < 0.01) throw std::runtime_error("lambda must be >=0.01!");
-      if (q.n_points < 3) throw std::runtime_error("n_points must be >=3!");
-      if (n_runs < 1) throw std::runtime_error("n_runs must be >=1!");
+      const orc::BatchParams q = to_params(*p);
+      check_create(q, n_runs, goals, basegoals, mod->impl->env.sdfs.empty());
       *batch_id = mod->impl->create_batch(robot, q, n_runs, starts, goals, basegoals, seeds);
    });
 }
@@ -427,17 +439,8 @@ int orc_batch_create_scenes(orc_module * mod, const char * robot, const orc_batc
 {
    return guarded(mod, [&] {
       need(robot, "robot"); need(p, "params"); need(batch_id, "batch_id");
-      orc::BatchParams q;
-      q.n_points = p->n_points; q.floating_base = p->floating_base; q.lambda = p->lambda;
-      q.derivative = p->derivative; q.use_momentum = p->use_momentum; q.use_hmc = p->use_hmc;
-      q.hmc_resample_lambda = p->hmc_resample_lambda; q.epsilon = p->epsilon; q.epsilon_self = p->epsilon_self;
-      q.obs_factor = p->obs_factor; q.obs_factor_self = p->obs_factor_self; q.precision = p->precision;
-      if (!goals) throw std::runtime_error("Did not pass either adofgoal or starttraj!");
-      if (q.floating_base && !basegoals) throw std::runtime_error("Passed floating_base with no basegoal!");
-      if (!q.floating_base && basegoals) throw std::runtime_error("Passed basegoal with no floating_base!");
-      if (q.lambda < 0.01) throw std::runtime_error("lambda must be >=0.01!");
-      if (q.n_points < 3) throw std::runtime_error("n_points must be >=3!");
-      if (n_runs < 1) throw std::runtime_error("n_runs must be >=1!");
+      const orc::BatchParams q = to_params(*p);
+      check_create(q, n_runs, goals, basegoals, false);
       // the scene table
       if (n_scenes < 1) throw std::runtime_error("n_scenes must be >=1!");
       need(scene_begin, "scene_begin"); need(scene_of_run, "scene_of_run");
@@ -455,13 +458,13 @@ int orc_batch_create_scenes(orc_module * mod, const char * robot, const orc_batc
          for (int k=scene_begin[sc]; k<scene_begin[sc+1]; k++)
          {
             const std::string name = str(field_kinbodies[k], "field_kinbodies entry");
-            if (!mod->impl->has_body(name)) throw std::runtime_error("Kinbody " + name + " of a scene does not exist!");
+            if (!mod->impl->env.has_body(name)) throw std::runtime_error("Kinbody " + name + " of a scene does not exist!");
             std::shared_ptr<orc::Sdf> field;
-            for (const auto & f : mod->impl->sdfs) if (f->kinbody_name == name) field = f;
+            for (const auto & f : mod->impl->env.sdfs) if (f->kinbody_name == name) field = f;
             if (!field) throw std::runtime_error("Kinbody " + name + " of a scene has no signed distance field!");
             orc::Pose pose;
             if (field_poses) for (int j=0; j<7; j++) pose.v[j] = field_poses[(size_t) k*7 + j];
-            else pose = mod->impl->body_transform(name);
+            else pose = mod->impl->env.body_transform(name);
             t->scenes[sc].push_back({ field, pose });
          }
       t->scene_of_run.assign(scene_of_run, scene_of_run + n_runs);

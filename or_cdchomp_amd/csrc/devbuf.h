@@ -1,5 +1,5 @@
 // devbuf.h -- the host layer's handles on a device: the guard that makes a device current, the check of a HIP call, device memory
-// with one owner.  Included by module.h and by the headers that hold device memory without needing the module (hmc.h).
+// with one owner.  Included by batch.h and by the headers that hold device memory without needing the module (hmc.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <memory>

@@ -1,4 +1,4 @@
-// launch.h -- the launch wrappers of chomp_kernel.hip, hmc_kernels.hip and multistart_kernels.hip, as the host layer calls them: the
+// launch.h -- the launch wrappers of chomp_kernel.hip, hmc_kernels.hip, multistart_kernels.hip and sdf_kernels.hip, as the host layer calls them: the
 // iterate and seed wrappers are overloaded by precision, the others take `int precision` (64 or 32) and a `void *` array.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -28,3 +28,8 @@ hipError_t orc_launch_respawn_copy(void * traj, void * AG, int precision, int * 
 hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
    unsigned long long * key, int * count, int * best, hipStream_t stream);
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);
+// sdf_kernels.hip: occupancy -> signed distance field; the whole field of a body from the world's boxes and triangles (host arrays in, host array out)
+hipError_t orc_sdf_from_occupancy_device(const double * occ, double * sdf_out, const int sizes[3], const double lengths[3],
+   hipStream_t st);
+hipError_t orc_sdf_build_device(const int sizes[3], const double lengths[3], const double grid_xform[12], const double grid_pose[7],
+   double cube_extent, int n_boxes, const double * boxes, int n_tris, const double * tris, double * sdf_out, hipStream_t st);

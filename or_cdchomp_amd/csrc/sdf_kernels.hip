@@ -12,6 +12,7 @@
 
 #pragma clang fp contract(off)
 
+#include "launch.h"
 #include "vox_tri.h"
 
 namespace {

@@ -38,7 +38,7 @@ struct Robot                      // what the path reads from an OpenRAVE::Robot
    bool self_check = true;                     // the sphere-pair stand-in for CheckSelfCollision in gettraj's re-check (orc_robot_set_self_check)
    // kinbodies the robot holds, in the order they were grabbed (RobotBase::Grab / GetGrabbed, src/orcdchomp_mod.cpp:2168-2171):
    // the body is rigid with `link` from the moment of the grab, `rel` = T_w_link^-1 o T_w_body at that moment
-   // touch_link / touch_body: what the body's spheres overlapped AT THE MOMENT OF THE GRAB (Module::grab; taken anew when
+   // touch_link / touch_body: what the body's spheres overlapped AT THE MOMENT OF THE GRAB (Environment::grab; taken anew when
    // set_kinbody_transform re-anchors it): links of the robot, by its own spheres, and bodies the robot held already.
    // OpenRAVE's CheckSelfCollision leaves a grabbed body out against exactly those (and against the grabbing link).
    struct Grab { std::string body; int link; Xform rel; std::vector<unsigned char> touch_link; std::vector<std::string> touch_body; };
@@ -71,7 +71,7 @@ struct Sdf                        // struct sdf, src/orcdchomp_mod.cpp:148-153
 
 // The obstacles of a batch's runs (orc_batch_create_scenes): scenes of at most ORC_MAX_SDFS field placements, every run
 // in one of them.  orc_batch_create is the one-scene case: the module's fields where their kinbodies stand, every run in
-// scene 0 (Module::current_scene).
+// scene 0 (Environment::current_scene).
 struct ScenePlacement
 {
    std::shared_ptr<Sdf> sdf;      // the module's field (shared: removefield does not pull it from under a batch)

@@ -61,10 +61,10 @@ VerdictInputs verdict_inputs(const Robot & robot, const Batch & b, bool self_che
 // OpenRAVE for environment/self collisions (mod.cpp:2958-3006).  Here the verdict comes from
 // the model the optimizer itself uses: a configuration collides when an active sphere
 // penetrates a signed distance field (interpolated field value below the sphere radius).
-bool host_recheck(Module & mod, const Batch & b, const double * traj, const std::vector<double> & dtm, bool self_check, std::string & details_out)
+bool host_recheck(const Environment & env, const Batch & b, const double * traj, const std::vector<double> & dtm, bool self_check, std::string & details_out)
 {
    const int col0 = b.params.floating_base ? 7 : 0;
-   const Robot rob = verdict_robot(mod.robot(b.robot_name), b);
+   const Robot rob = verdict_robot(env.robot(b.robot_name), b);
    std::vector<Xform> frames;
    std::vector<double> q = rob.dof_values;
    bool collides = false; std::ostringstream details;
@@ -93,12 +93,12 @@ bool host_recheck(Module & mod, const Batch & b, const double * traj, const std:
          mat3_vec(frames[sp.link].R, sp.pos, pw);
          for (int k=0; k<3; k++) pw[k] += frames[sp.link].t[k];
          // the module's fields where their kinbodies stand now; a batch with per-run scenes: the placements of run 0's scene
-         const size_t n_fields = b.per_run_scenes ? b.scenes->scenes[b.scenes->scene_of_run[0]].size() : mod.sdfs.size();
+         const size_t n_fields = b.per_run_scenes ? b.scenes->scenes[b.scenes->scene_of_run[0]].size() : env.sdfs.size();
          for (size_t fi=0; fi<n_fields; fi++)
          {
             const ScenePlacement * pl = b.per_run_scenes ? &b.scenes->scenes[b.scenes->scene_of_run[0]][fi] : nullptr;
-            const Sdf & f = pl ? *pl->sdf : *mod.sdfs[fi];
-            const Pose pose_world_gsdf = pose_compose(pl ? pl->pose_world_kinbody : mod.body_transform(f.kinbody_name), f.pose);
+            const Sdf & f = pl ? *pl->sdf : *env.sdfs[fi];
+            const Pose pose_world_gsdf = pose_compose(pl ? pl->pose_world_kinbody : env.body_transform(f.kinbody_name), f.pose);
             double pg[3], val;
             pose_apply(pose_invert(pose_world_gsdf), pw, pg);
             if (grid_interp(f.grid, pg, &val)) continue;
@@ -149,7 +149,7 @@ static void verdict_decode(unsigned long long key, int k, int * collides, int * 
 void Module::batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check)
 {
    Batch & b = batch(id);
-   const VerdictInputs in = verdict_inputs(robot(b.robot_name), b, self_check);
+   const VerdictInputs in = verdict_inputs(env.robot(b.robot_name), b, self_check);
    std::vector<double> traj((size_t) b.n_runs * b.n_points * b.n);
    b.gettraj(traj.data());
    std::vector<int> offs(b.n_runs + 1, 0), seg;
@@ -180,7 +180,7 @@ void Module::batch_collision_verdict_device(int id, int * collides, double * tim
    const VerdictScope & scope)
 {
    Batch & b = batch(id);
-   const VerdictInputs in = verdict_inputs(robot(b.robot_name), b, true);
+   const VerdictInputs in = verdict_inputs(env.robot(b.robot_name), b, true);
    const bool want_key = collides || sphere || field;
    std::vector<unsigned long long> key(want_key ? b.n_runs : 0);
    b.collision_verdict_planned(in, want_key ? key.data() : nullptr, depth, time, n_samples, scope);

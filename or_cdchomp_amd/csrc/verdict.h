@@ -7,7 +7,7 @@
 #include <vector>
 
 namespace orc {
-struct Robot; class Batch; class Module;
+struct Robot; class Batch; class Environment;
 
 // LinearTrajectoryRetimer stand-in (reference: RetimeActiveDOFTrajectory(..., "LinearTrajectoryRetimer"),
 // src/orcdchomp_mod.cpp:2905-2911): each segment is traversed at the largest constant velocity the dof velocity limits allow.
@@ -70,6 +70,6 @@ struct VerdictInputs
 // tables false: the pair tables, which only the kernels read, stay empty (gettraj's re-check walks the spheres itself)
 VerdictInputs verdict_inputs(const Robot & robot, const Batch & b, bool self_check, bool tables = true);
 // gettraj's re-check of run 0 of `b` on the host, dtm being retime_linear's: true when a sample is in contact, with the line the reference logs
-bool host_recheck(Module & mod, const Batch & b, const double * traj, const std::vector<double> & dtm, bool self_check, std::string & details);
+bool host_recheck(const Environment & env, const Batch & b, const double * traj, const std::vector<double> & dtm, bool self_check, std::string & details);
 
 } // namespace orc

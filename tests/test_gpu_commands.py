@@ -293,6 +293,146 @@ def test_starttraj_seeding(oracle):
     assert np.array_equal(c1, c2)
 
 
+def test_starttraj_single_waypoint(oracle):
+    """a document of one waypoint (count 1, deltatime 0): every row of the seeded trajectory is that waypoint"""
+    mod = bindings.bind(_mk())
+    model = common.setup_product_wam(mod)
+    wp = np.array([[0.3, -0.7, 0.2, 1.1, -0.3, 0.4, 0.1]])
+    run = mod.create(robot=model.name, starttraj=_doc(wp, [0.0]), n_points=5)
+    t = mod.batch_gettraj(int(run))[0]
+    assert t.shape == (5, 7)
+    assert np.array_equal(t, np.tile(wp, (5, 1)))
+    assert np.array_equal(t, oracle.sample_starttraj(wp, [0.0], 5))
+    mod.destroy(run=run)
+
+
+def test_starttraj_last_segment_takes_no_time(oracle):
+    """a timed document whose last waypoint has deltatime 0: the samples before the end interpolate the segments that take
+    time, the last sample is the last waypoint (OpenRAVE's Sample at the duration)"""
+    mod = bindings.bind(_mk())
+    model = common.setup_product_wam(mod)
+    rng = np.random.default_rng(29)
+    lo = np.asarray(model.limit_lower[:7]) + 0.2; hi = np.asarray(model.limit_upper[:7]) - 0.2
+    wp = rng.uniform(lo, hi, size=(4, 7))
+    wp[:, 0] = [0.0, 7.0, 8.0, 9.0]
+    dt = [0.0, 1.0, 0.5, 0.0]
+    want = oracle.sample_starttraj(wp, dt, 7)
+    assert np.allclose(want[:, 0], [0.0, 1.75, 3.5, 5.25, 7.0, 7.5, 9.0], rtol=1e-14, atol=0)
+    run = mod.create(robot=model.name, starttraj=_doc(wp, dt), n_points=7)
+    t = mod.batch_gettraj(int(run))[0]
+    mod.destroy(run=run)
+    print("starttraj, last segment of no time: max |product - oracle| %.3e" % np.abs(t - want).max())
+    assert np.allclose(t, want, rtol=1e-14, atol=1e-15)
+
+
+def _rot(q):
+    """rotation matrix of a quaternion x y z w"""
+    x, y, z, w = np.asarray(q, dtype=float) / np.linalg.norm(q)
+    return np.array([[1 - 2*(y*y + z*z), 2*(x*y - z*w), 2*(x*z + y*w)],
+                     [2*(x*y + z*w), 1 - 2*(x*x + z*z), 2*(y*z - x*w)],
+                     [2*(x*z - y*w), 2*(y*z + x*w), 1 - 2*(x*x + y*y)]])
+
+
+def _field_dims(link_aabbs, cube_extent, aabb_padding):
+    """sizes, lengths and pose of computedistancefield's grid, read from the reference (src/orcdchomp_mod.cpp:88-140,
+    377-409): link_aabbs: (pos, extents) of every enabled link with the body at the origin; a link without extents is left out"""
+    vmin = vmax = None
+    for pos, ext in link_aabbs:
+        pos = np.asarray(pos, dtype=float); ext = np.asarray(ext, dtype=float)
+        if not ext.any():
+            continue
+        vmin = pos - ext if vmin is None else np.minimum(vmin, pos - ext)
+        vmax = pos + ext if vmax is None else np.maximum(vmax, pos + ext)
+    if vmin is None:
+        apos, aext = np.zeros(3), np.zeros(3)
+    else:
+        apos = 0.5 * (vmin + vmax); aext = vmax - apos
+    sizes = np.ceil((aext + aabb_padding) / cube_extent).astype(int)
+    lengths = sizes * 2.0 * cube_extent
+    return sizes, lengths, np.r_[apos - 0.5 * lengths, 0.0, 0.0, 0.0, 1.0]
+
+
+def test_computedistancefield_boxes_and_mesh():
+    """the grid of a kinbody that has boxes and a mesh: the box around every enabled piece with the body at the origin, a box
+    without extents left out (reference src/orcdchomp_mod.cpp:88-140, 377-409)"""
+    mod = bindings.bind(_mk())
+    qz = [0.0, 0.0, np.sin(0.35), np.cos(0.35)]                        # 0.7 rad about z
+    boxes = [([0.1, -0.2, 0.05] + qz, [0.3, 0.1, 0.05]),
+             ([-0.15, 0.1, 0.3, 0, 0, 0, 1], [0.05, 0.2, 0.1]),
+             ([40.0, -30.0, 25.0, 0, 0, 0, 1], [0.0, 0.0, 0.0])]      # no extents, far outside the others: the AABB skips it
+    tris = np.array([[[-0.6, 0.0, 0.0], [0.2, 0.45, 0.1], [0.1, -0.1, 0.55]],
+                     [[0.2, 0.45, 0.1], [0.1, -0.1, 0.55], [0.3, 0.2, -0.25]]])
+    mod.add_kinbody_boxes("both", boxes)
+    mod.add_kinbody_trimesh("both", tris)
+    mod.set_kinbody_transform("both", [0.4, -0.3, 0.2, 0.0, 0.0, np.sin(0.2), np.cos(0.2)])      # the AABB is taken at the origin
+    cube_extent, aabb_padding = 0.05, 0.15
+    mod.SendCommand("computedistancefield kinbody both cube_extent %r aabb_padding %r" % (cube_extent, aabb_padding))
+    data, lengths, pose = mod.get_sdf("both")
+    v = tris.reshape(-1, 3)
+    links = [(0.5 * (v.min(axis=0) + v.max(axis=0)), 0.5 * (v.max(axis=0) - v.min(axis=0)))]
+    links += [(np.asarray(p[:3]), np.abs(_rot(p[3:])) @ np.asarray(h)) for p, h in boxes]
+    sizes, want_lengths, want_pose = _field_dims(links, cube_extent, aabb_padding)
+    assert data.size < 1 << 18                                         # (the host build)
+    assert data.shape == tuple(sizes)
+    assert np.allclose(lengths, want_lengths, rtol=1e-15, atol=0)
+    assert np.allclose(pose, want_pose, rtol=1e-14, atol=1e-15)
+    assert (data < 0).any() and (data > 0).any()                       # the body is in its field
+
+
+def test_computedistancefield_disabled_kinbody():
+    """a disabled kinbody has no enabled geometry: the grid is the padding around the origin, and every cell is free; a
+    grid of fewer than 2 cells along an axis is refused"""
+    from or_cdchomp_amd import scenes
+    mod = bindings.bind(_mk())
+    mod.add_kinbody_boxes("off", [(scenes.IDENT, [0.3, 0.2, 0.1])], transform=[1.0, 2.0, 3.0, 0, 0, 0, 1])
+    mod.enable_kinbody("off", False)
+    with pytest.raises(RuntimeError, match="Not enough memory for distance field!"):
+        mod.SendCommand("computedistancefield kinbody off cube_extent 0.05 aabb_padding 0.05")
+    mod.SendCommand("computedistancefield kinbody off cube_extent 0.05 aabb_padding 0.2")
+    data, lengths, pose = mod.get_sdf("off")
+    sizes, want_lengths, want_pose = _field_dims([], 0.05, 0.2)
+    assert data.shape == tuple(sizes) == (4, 4, 4)
+    assert np.allclose(lengths, want_lengths, rtol=1e-15, atol=0) and np.allclose(lengths, 0.4)
+    assert np.allclose(pose, want_pose, rtol=1e-14, atol=1e-15) and np.allclose(pose[:3], -0.2)
+    assert np.isinf(data).all() and (data > 0).all()
+
+
+def test_removefield_of_a_kinbody_without_field():
+    mod = bindings.bind(_mk())
+    from or_cdchomp_amd import scenes
+    mod.add_kinbody_boxes("a", [(scenes.IDENT, [0.1, 0.1, 0.1])])
+    mod.add_kinbody_boxes("b", [(scenes.IDENT, [0.1, 0.1, 0.1])], transform=[1.0, 0, 0, 0, 0, 0, 1])
+    mod.SendCommand("computedistancefield kinbody a cube_extent 0.05")
+    with pytest.raises(RuntimeError, match="No sdf for that kinbody!"):
+        mod.SendCommand("removefield kinbody b")
+    with pytest.raises(RuntimeError, match="No sdf for that kinbody!"):
+        mod.SendCommand("removefield kinbody nobody")
+    mod.SendCommand("removefield kinbody a")
+    with pytest.raises(RuntimeError, match="No sdf for that kinbody!"):
+        mod.SendCommand("removefield kinbody a")
+    with pytest.raises(RuntimeError, match="No sdf for that kinbody!"):
+        mod.get_sdf("a")
+
+
+def test_tsr_tokens_need_a_manipulator():
+    """con_tsr with one word, everyn_tsr and start_tsr address the active manipulator's end effector: a robot without
+    manipulators gets each token's own message"""
+    mod = bindings.bind(_mk())
+    model, base, dofvals, adofs = common.wam_state()
+    model.manipulators = []
+    mod.add_robot(model, transform=base, dof_values=dofvals, active_dofs=adofs)
+    tsr = robots.Tsr().serialize()
+    head = "create robot %s adofgoal '0 0 0 0 0 0 0' " % model.name
+    with pytest.raises(RuntimeError, match="con_tsr manip not found!"):
+        mod.SendCommand(head + "con_tsr 'all' '%s'" % tsr)
+    with pytest.raises(RuntimeError, match="everyn_tsr needs an active manipulator!"):
+        mod.SendCommand(head + "everyn_tsr '%s'" % tsr)
+    with pytest.raises(RuntimeError, match="start_tsr needs an active manipulator!"):
+        mod.SendCommand(head + "start_tsr '%s'" % tsr)
+    with pytest.raises(RuntimeError, match="Cannot parse everyn_tsr TSR!"):      # (the TSR is read before the manipulator is looked up)
+        mod.SendCommand(head + "everyn_tsr '0 NULL 1 2 3'")
+
+
 def _groups(text):
     """(rows [count][width], {group name's first word: (offset, dof)}) of a trajectory document"""
     import re
