@@ -1824,9 +1824,13 @@ __device__ __forceinline__ PassCosts phase_costs_body(const void * kp, KArg<real
       for (int e=tid; e<mn; e+=BLOCK)
       {
          const int i = div_n(e, rn_f), c = e - i*n;
-         const real sg = smooth_grad<real>(b, T_s, i, c);     // (A T + B)
-         const real bt = b.a_off * ((i == 0 ? T_s[c] : (real)0) + (i == m-1 ? T_s[(np-1)*n + c] : (real)0));
-         acc += (double) T_s[n + e] * (0.5 * ((double) sg + (double) bt));
+         // (A T + B) as smooth_grad forms it, but in double whatever `real` is (the same bits in fp64): this sum weighs the row's rounding
+         // by T itself, not by a change of T, and in float the second difference is rounded at a |T| 2^-24 -- 3e-6 of the smoothness cost
+         // of a 34-waypoint fp32 run, 20-40 x what the float rounding of its waypoints moves it (NOTES/first-iteration.md); a product of two
+         // floats is exact in double.  A higher derivative's band_cost_pass does the same.
+         const double sg = (double) b.a_diag * (double) T_s[(i+1)*n + c] + (double) b.a_off * ((double) T_s[i*n + c] + (double) T_s[(i+2)*n + c]);
+         const double bt = (double) b.a_off * ((i == 0 ? (double) T_s[c] : 0.0) + (i == m-1 ? (double) T_s[(np-1)*n + c] : 0.0));
+         acc += (double) T_s[n + e] * (0.5 * (sg + bt));
       }
       double ss = 0.0, sg2 = 0.0, gg = 0.0;
       if (tid < n)
