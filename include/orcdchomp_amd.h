@@ -57,7 +57,9 @@ int orc_set_num_streams(orc_module * mod, int n);
  * iterate / gettraj / destroy (src/orcdchomp_mod.h:58-66).  Same command names,
  * same argv grammar (shell-style quoting, src/libcd/util_shparse.c), same textual
  * returns.  out receives the reply (NUL terminated, truncated to out_cap).
- * Batch extensions (additive): createbatch, iteratebatch, gettrajbatch.
+ * Batch extensions (additive): createbatch, iteratebatch, gettrajbatch; and
+ * mergefields kinbody NAME fields 'A B C' cell F [bounds 'x0 y0 z0 x1 y1 z1'] (orc_scene_merge_fields with every source
+ * where it stands; reply "").
  * create ... dat_filename PATH writes the reference's per-iteration log "%d %f %f %f %f\n"
  * (iteration, seconds, cost_total, cost_obs, cost_smooth; mod.cpp:2306-2310, 2811-2818); the seconds
  * are wall seconds since the iterate call began (the reference: thread CPU seconds), a fused launch's
@@ -192,6 +194,31 @@ int orc_scene_add_sdf(orc_module * mod, const char * kinbody, const int sizes[3]
 /* copy out a computed field: sizes[3], lengths[3], pose[7] (grid wrt kinbody), data (may be NULL to query sizes) */
 int orc_scene_get_sdf(orc_module * mod, const char * kinbody, int sizes[3], double lengths[3], double pose[7],
    double * data, size_t data_cap);
+
+/* The fields of n_fields placed kinbodies baked into ONE field whose axes are the target kinbody's, on the device: the layout
+ * becomes an ordinary module field, so a scene of that one placement is under the cap of ORC_MAX_SDFS whatever n_fields is
+ * (there is no limit of eight here) and, with the target standing at the identity, runs the one-field kernels.
+ *   field_kinbodies [n_fields]: kinbodies with a field, in the order of the best-of-N field loop; one may repeat.
+ *   field_poses [n_fields][7] (x y z qx qy qz qw): the world pose to use for every source kinbody, or NULL: every kinbody
+ *     where it stands now.  Poses are used as given (pose_apply's expanded quaternion; nothing is normalised).
+ *   cell: the edge of the merged grid's cubic cells.  bounds [6] = lo[3], hi[3] in the target kinbody's frame, or NULL: the
+ *     box around the eight corners of every source's box.  sizes[d] = max(2, ceil((hi[d] - lo[d]) / cell)), lengths[d] =
+ *     sizes[d] cell, and the field's pose in the target kinbody's frame is (lo, identity quaternion): orc_host_merge_grid.
+ * Every cell holds what the best-of-N loop finds at the cell's CENTRE: the smallest value, by strict <, that the reference's
+ * interpolation (cd_grid_double_interp, src/libcd/grid.c:386-454, HUGE_VAL poisoning included) gives among the sources that
+ * contain the centre; a cell no source covers holds +inf, which every cost family reads as "no field here".  That is the one
+ * difference from a scene of the n_fields placements: the values are resampled at cell centres and interpolated from there
+ * (merged_grid_dims and merged_field of or_cdchomp_amd/module.py are the specification, orc_host_merge_fields the host twin
+ * the device agrees with bit for bit).
+ * The target must be an existing kinbody without a field (one of zero boxes is the intended target).  The field is a
+ * snapshot: moving a source afterwards does not change it, moving the target moves it, as with any field.  The host copy is
+ * read back once; the kernel's output buffer stays as the field's fp64 copy on the module's (first) device.
+ * Rejected with a nonzero return and a message, before any device work, the module unchanged: n_fields < 1; an unknown
+ * kinbody, or a source without a field; the target among the sources, or a target that already has a field; a non-finite or
+ * non-positive cell; non-finite poses or bounds, or lo >= hi; a quaternion of zero norm; a grid of 2^31 bytes or more
+ * ("signed distance field too large for this build!", here and not at create). */
+int orc_scene_merge_fields(orc_module * mod, const char * target_kinbody, int n_fields, const char * const * field_kinbodies,
+   const double * field_poses, double cell, const double * bounds);
 
 /* ---- kernel-level batch API --------------------------------------------------
  * what the command layer calls; one batch = n_runs independent CHOMP runs that
@@ -495,6 +522,16 @@ int orc_host_voxelize_boxes(const int sizes[3], const double lengths[3], const d
 /* ... and of a triangle mesh (world_vertices [n_tri][3][3]): HUGE_VAL where the cube touches a triangle */
 int orc_host_voxelize_trimesh(const int sizes[3], const double lengths[3], const double pose_world_gsdf[7], double cube_extent,
    int n_tri, const double * world_vertices, double * occupancy_out);
+/* the grid orc_scene_merge_fields merges into: source_lengths [n_sources][3] and source_poses [n_sources][7], every source
+ * grid's box and its pose in the TARGET KINBODY's frame; cell and bounds as there (with bounds the sources are not read and
+ * n_sources may be 0).  pose_out is the merged grid's pose in the target kinbody's frame.  Nonzero on what that call rejects */
+int orc_host_merge_grid(int n_sources, const double * source_lengths, const double * source_poses, double cell, const double * bounds,
+   int sizes_out[3], double lengths_out[3], double pose_out[7]);
+/* the host twin of the merge kernel: the grid (sizes, lengths) rooted at pose_world_gsdf filled from n_sources grids given by
+ * source_sizes [n][3], source_lengths [n][3], source_poses [n][7] (every source GRID's world pose) and source_data [n]
+ * (C ordered cells); data_out [sizes[0] sizes[1] sizes[2]].  Same function, same operations as the device: bit for bit */
+int orc_host_merge_fields(int n_sources, const int * source_sizes, const double * source_lengths, const double * source_poses,
+   const double * const * source_data, const int sizes[3], const double lengths[3], const double pose_world_gsdf[7], double * data_out);
 /* tokenizer of the command grammar: replaces cd_util_shparse (src/libcd/util_shparse.c:37-128).
  * tokens are written NUL-separated into out; returns the token count or -1 if out is too small */
 int orc_host_shparse(const char * in, char * out, size_t out_cap);

@@ -66,6 +66,8 @@ SYMBOLS = [
     ("orc_robot_release_all", C.c_int, [C.c_void_p, C.c_char_p]),
     ("orc_scene_add_sdf", C.c_int, [C.c_void_p, C.c_char_p, c_int_p, c_double_p, c_double_p, c_double_p]),
     ("orc_scene_get_sdf", C.c_int, [C.c_void_p, C.c_char_p, c_int_p, c_double_p, c_double_p, c_double_p, C.c_size_t]),
+    ("orc_scene_merge_fields", C.c_int, [C.c_void_p, C.c_char_p, C.c_int, C.POINTER(C.c_char_p), c_double_p, C.c_double,
+                                         c_double_p]),
     ("orc_batch_params_default", None, [C.POINTER(BatchParams)]),
     ("orc_batch_create", C.c_int, [C.c_void_p, C.c_char_p, C.POINTER(BatchParams), C.c_int, c_double_p,
                                    c_double_p, c_double_p, c_uint_p, c_int_p]),
@@ -105,6 +107,9 @@ SYMBOLS = [
     ("orc_host_voxelize_boxes", C.c_int, [c_int_p, c_double_p, c_double_p, C.c_double, C.c_int, c_double_p, c_double_p,
                                           c_double_p]),
     ("orc_host_voxelize_trimesh", C.c_int, [c_int_p, c_double_p, c_double_p, C.c_double, C.c_int, c_double_p, c_double_p]),
+    ("orc_host_merge_grid", C.c_int, [C.c_int, c_double_p, c_double_p, C.c_double, c_double_p, c_int_p, c_double_p, c_double_p]),
+    ("orc_host_merge_fields", C.c_int, [C.c_int, c_int_p, c_double_p, c_double_p, C.POINTER(c_double_p), c_int_p, c_double_p,
+                                        c_double_p, c_double_p]),
     ("orc_host_shparse", C.c_int, [C.c_char_p, C.c_char_p, C.c_size_t]),
     ("orc_host_metric", C.c_int, [C.c_int, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p,
                                   c_double_p, C.c_int, c_double_p]),

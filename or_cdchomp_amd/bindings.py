@@ -80,6 +80,15 @@ def removefield(mod, kinbody=None, releasegil=False):
     return mod.SendCommand(_Cmd("removefield").body("kinbody", kinbody).text(), releasegil)
 
 
+def mergefields(mod, kinbody=None, fields=None, cell=None, bounds=None, releasegil=False):
+    """additive (not in the reference): the fields of the kinbodies `fields`, where they stand, baked into one field of
+    `kinbody` with its axes (orc_scene_merge_fields)"""
+    c = (_Cmd("mergefields").body("kinbody", kinbody)
+         .vec("fields", None if fields is None else [_name(f) for f in fields])
+         .fmt("cell", cell, "%r").vec("bounds", None if bounds is None else [repr(float(b)) for b in bounds]))
+    return mod.SendCommand(c.text(), releasegil)
+
+
 def create(mod, robot=None, adofgoal=None, basegoal=None, floating_base=None, lambda_=None,
            starttraj=None, n_points=None,
            con_tsr=None, con_tsrs=None, start_tsr=None, start_cost=None, everyn_tsr=None,
@@ -148,7 +157,7 @@ def runchomp(mod,
 
 
 def bind(mod):                                   # orcdchomp.py:27-37
-    for fn in (computedistancefield, addfield_fromobsarray, removefield, create, iterate,
+    for fn in (computedistancefield, addfield_fromobsarray, removefield, mergefields, create, iterate,
                gettraj, destroy, runchomp):
         setattr(mod, fn.__name__, types.MethodType(fn, mod))
     return mod

@@ -411,6 +411,19 @@ int orc_scene_get_sdf(orc_module * mod, const char * kinbody, int sizes[3], doub
    });
 }
 
+int orc_scene_merge_fields(orc_module * mod, const char * target_kinbody, int n_fields, const char * const * field_kinbodies,
+   const double * field_poses, double cell, const double * bounds)
+{
+   return guarded(mod, [&] {
+      need(target_kinbody, "target_kinbody");
+      if (n_fields < 1) throw std::runtime_error("n_fields must be >=1!");
+      need(field_kinbodies, "field_kinbodies");
+      std::vector<std::string> names;
+      for (int k=0; k<n_fields; k++) names.push_back(str(field_kinbodies[k], "field_kinbodies entry"));
+      mod->impl->merge_fields(target_kinbody, names, field_poses, cell, bounds);
+   });
+}
+
 void orc_batch_params_default(orc_batch_params * p)
 {
    if (!p) return;
@@ -767,6 +780,52 @@ int orc_host_voxelize_trimesh(const int sizes[3], const double lengths[3], const
       const std::vector<double> tris(world_vertices, world_vertices + 9*(size_t)(n_tri > 0 ? n_tri : 0));
       orc::voxelize_boxes(g, orc::Pose(pose_world_gsdf), cube_extent, std::vector<orc::Box>(), tris);
       std::memcpy(occupancy_out, g.data.data(), g.ncells() * sizeof(double));
+      return 0;
+   }
+   catch (...) { return 1; }
+}
+
+int orc_host_merge_grid(int n_sources, const double * source_lengths, const double * source_poses, double cell, const double * bounds,
+   int sizes_out[3], double lengths_out[3], double pose_out[7])
+{
+   if (n_sources < 0 || !sizes_out || !lengths_out || !pose_out) return 1;
+   if (n_sources > 0 && (!source_lengths || !source_poses)) return 1;
+   try
+   {
+      std::vector<orc::MergeBox> boxes(n_sources);
+      for (int k=0; k<n_sources; k++)
+      {
+         for (int d=0; d<3; d++) boxes[k].lengths[d] = source_lengths[3*k+d];
+         boxes[k].pose = orc::Pose(source_poses + 7*k);
+      }
+      orc::Pose pose;
+      orc::merge_grid_dims(boxes, cell, bounds, sizes_out, lengths_out, pose);
+      for (int i=0; i<7; i++) pose_out[i] = pose.v[i];
+      return 0;
+   }
+   catch (...) { return 1; }
+}
+
+int orc_host_merge_fields(int n_sources, const int * source_sizes, const double * source_lengths, const double * source_poses,
+   const double * const * source_data, const int sizes[3], const double lengths[3], const double pose_world_gsdf[7], double * data_out)
+{
+   if (n_sources < 0 || !sizes || !lengths || !pose_world_gsdf || !data_out) return 1;
+   if (n_sources > 0 && (!source_sizes || !source_lengths || !source_poses || !source_data)) return 1;
+   for (int d=0; d<3; d++) if (sizes[d] < 1 || !(lengths[d] > 0.0)) return 1;
+   try
+   {
+      std::vector<OrcMergeSource> table;
+      for (int k=0; k<n_sources; k++)
+      {
+         if (!source_data[k]) return 1;
+         for (int d=0; d<3; d++) if (source_sizes[3*k+d] < 2 || !(source_lengths[3*k+d] > 0.0)) return 1;
+         table.push_back(orc::merge_affine(orc::Pose(pose_world_gsdf), orc::Pose(source_poses + 7*k), source_sizes + 3*k, source_lengths + 3*k,
+                                           source_data[k]));
+      }
+      orc::Grid g;
+      for (int d=0; d<3; d++) { g.sizes[d] = sizes[d]; g.lengths[d] = lengths[d]; }
+      orc::merge_fields_host(table, g);
+      std::memcpy(data_out, g.data.data(), g.ncells() * sizeof(double));
       return 0;
    }
    catch (...) { return 1; }

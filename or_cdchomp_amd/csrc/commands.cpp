@@ -67,6 +67,7 @@ std::string Module::send_command(const std::string & cmd)
    if (name == "computedistancefield") return cmd_computedistancefield(argv);
    if (name == "addfield_fromobsarray") return cmd_addfield_fromobsarray(argv);
    if (name == "removefield") return cmd_removefield(argv);
+   if (name == "mergefields") return cmd_mergefields(argv);
    if (name == "create") return cmd_create(argv, false);
    if (name == "createbatch") return cmd_create(argv, true);
    if (name == "iterate") return cmd_iterate(argv, false);
@@ -250,6 +251,40 @@ std::string Module::cmd_removefield(const std::vector<std::string> & argv)
    if (i < argc) bad_arguments();
    if (kb.empty()) throw std::runtime_error("Did not pass a kinbody!");
    env.remove_sdf(kb);
+   return "";
+}
+
+// additive: mergefields kinbody NAME fields 'A B C' cell F [bounds 'x0 y0 z0 x1 y1 z1'] -- orc_scene_merge_fields with every
+// source where its kinbody stands now
+std::string Module::cmd_mergefields(const std::vector<std::string> & argv)
+{
+   std::string kb;
+   std::vector<std::string> fields;
+   std::vector<double> bounds;
+   double cell = 0.0;
+   bool have_fields = false, have_cell = false, have_bounds = false;
+   const int argc = (int) argv.size();
+   int i;
+   for (i=1; i<argc; i++)
+   {
+      if (argv[i] == "kinbody" && i+1 < argc)
+      {
+         if (!kb.empty()) throw std::runtime_error("Only one kinbody can be passed!");
+         kb = argv[++i];
+      }
+      else if (argv[i] == "fields" && i+1 < argc) { fields = shparse(argv[++i]); have_fields = true; }
+      else if (argv[i] == "cell" && i+1 < argc) { cell = std::atof(argv[++i].c_str()); have_cell = true; }
+      else if (argv[i] == "bounds" && i+1 < argc)
+      {
+         bounds = parse_vector(argv[++i]);
+         if (bounds.size() != 6) throw std::runtime_error("bounds must be length 6!");
+         have_bounds = true;
+      }
+      else break;
+   }
+   if (i < argc) bad_arguments();
+   if (kb.empty() || !have_fields || !have_cell) throw std::runtime_error("Did not pass all required args!");
+   merge_fields(kb, fields, nullptr, cell, have_bounds ? bounds.data() : nullptr);
    return "";
 }
 

@@ -1,6 +1,7 @@
 // host_math.cpp -- see host_math.h
 #include "host_math.h"
 #include "vox_tri.h"
+#include "merge_interp.h"
 #include <algorithm>
 #include <cctype>
 #include <cstring>
@@ -257,35 +258,93 @@ void grid_flood_1_to_0(Grid & g, size_t start)
 
 int grid_interp(const Grid & g, const double p[3], double * value)
 {
-   int sub[3];
+   return orc_grid_interp(g.sizes, g.lengths, g.data.data(), p, value);      // (merge_interp.h: shared with the merge kernel)
+}
+
+// ================================================================ merge ===
+static void need_finite_pose(const Pose & p)
+{
+   for (int i=0; i<7; i++) if (!std::isfinite(p.v[i])) throw std::runtime_error("poses and bounds must be finite numbers!");
+   if (p.v[3] == 0.0 && p.v[4] == 0.0 && p.v[5] == 0.0 && p.v[6] == 0.0) throw std::runtime_error("a pose's quaternion has zero norm!");
+}
+
+void merge_grid_dims(const std::vector<MergeBox> & boxes, double cell, const double * bounds, int sizes[3], double lengths[3], Pose & pose_kinbody_gsdf)
+{
+   if (!std::isfinite(cell) || !(cell > 0.0)) throw std::runtime_error("cell must be a positive finite number!");
+   double lo[3], hi[3];
+   if (bounds)
+   {
+      for (int d=0; d<6; d++) if (!std::isfinite(bounds[d])) throw std::runtime_error("poses and bounds must be finite numbers!");
+      for (int d=0; d<3; d++) { lo[d] = bounds[d]; hi[d] = bounds[3+d]; }
+   }
+   else
+   {
+      if (boxes.empty()) throw std::runtime_error("n_fields must be >=1!");
+      bool init = false;
+      for (const MergeBox & b : boxes)
+      {
+         need_finite_pose(b.pose);
+         for (int d=0; d<3; d++) if (!std::isfinite(b.lengths[d])) throw std::runtime_error("poses and bounds must be finite numbers!");
+         for (int corner=0; corner<8; corner++)
+         {
+            const double c[3] = { (corner & 4) ? b.lengths[0] : 0.0, (corner & 2) ? b.lengths[1] : 0.0, (corner & 1) ? b.lengths[2] : 0.0 };
+            double w[3];
+            pose_apply(b.pose, c, w);
+            for (int d=0; d<3; d++)
+            {
+               if (!init || w[d] < lo[d]) lo[d] = w[d];
+               if (!init || w[d] > hi[d]) hi[d] = w[d];
+            }
+            init = true;
+         }
+      }
+   }
+   double n[3];
    for (int d=0; d<3; d++)
    {
-      const double x = p[d] / g.lengths[d];
-      if (x < 0.0 || x > 1.0) return 1;
-      int s = (int) std::floor(x * g.sizes[d]);
-      if (s == g.sizes[d]) s--;
-      sub[d] = s;
+      if (!std::isfinite(lo[d]) || !std::isfinite(hi[d])) throw std::runtime_error("poses and bounds must be finite numbers!");
+      if (!(lo[d] < hi[d])) throw std::runtime_error("bounds must have lo < hi in every dimension!");
+      n[d] = std::ceil((hi[d] - lo[d]) / cell);
+      if (!(n[d] >= 2.0)) n[d] = 2.0;
    }
-   const size_t stride[3] = { (size_t) g.sizes[1] * g.sizes[2], (size_t) g.sizes[2], 1 };
-   const size_t index = sub[0]*stride[0] + sub[1]*stride[1] + sub[2];
-   double v = g.data[index];
-   if (v == HUGE_VAL) { *value = HUGE_VAL; return 0; }
-   for (int d=2; d>=0; d--)
+   // (in double: the product of three cell counts that each fit an int need not)
+   if (!(n[0] * n[1] * n[2] * sizeof(double) < 2147483648.0)) throw std::runtime_error("signed distance field too large for this build!");
+   pose_kinbody_gsdf = Pose();
+   for (int d=0; d<3; d++)
    {
-      const double center = (0.5 + sub[d]) / g.sizes[d] * g.lengths[d];
-      bool prev;
-      if (sub[d] == 0) prev = false;
-      else if (sub[d] == g.sizes[d]-1) prev = true;
-      else prev = p[d] < center;
-      const double after = prev ? g.data[index] : g.data[index + stride[d]];
-      const double before = prev ? g.data[index - stride[d]] : g.data[index];
-      if (after == HUGE_VAL || before == HUGE_VAL) { *value = HUGE_VAL; return 0; }
-      double diff = after;
-      diff -= before;
-      v += diff * g.sizes[d] / g.lengths[d] * (p[d] - center);
+      sizes[d] = (int) n[d];
+      lengths[d] = sizes[d] * cell;
+      pose_kinbody_gsdf.v[d] = lo[d];
    }
-   *value = v;
-   return 0;
+}
+
+OrcMergeSource merge_affine(const Pose & pose_world_gsdf, const Pose & pose_world_gsrc, const int src_sizes[3], const double src_lengths[3],
+   const double * src_data)
+{
+   const Pose inv = pose_invert(pose_world_gsrc);
+   const Mat3 Ri = pose_rotation_expanded(inv);
+   const Mat3 A = mat3_mul(Ri, pose_rotation_expanded(pose_world_gsdf));
+   OrcMergeSource s;
+   for (int q=0; q<9; q++) s.A[q] = A.m[q];
+   double r[3];
+   mat3_vec(Ri, pose_world_gsdf.v, r);
+   for (int d=0; d<3; d++)
+   {
+      s.t[d] = r[d] + inv.v[d];
+      s.size[d] = src_sizes[d];
+      s.length[d] = src_lengths[d];
+   }
+   s.pad_ = 0;
+   s.data = src_data;
+   return s;
+}
+
+void merge_fields_host(const std::vector<OrcMergeSource> & sources, Grid & out)
+{
+   const size_t nc = out.ncells();
+   out.data.resize(nc);
+   for (size_t idx=0; idx<nc; idx++)
+      out.data[idx] = orc_merge_cell(out.sizes, out.lengths, (long) idx, sources.data(), (int) sources.size());
 }
 
 bool obb_overlap(const Xform & a, const double ha[3], const Xform & b, const double hb[3], double tol)

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <string>
 #include <vector>
+#include "merge_interp.h"
 
 namespace orc {
 
@@ -64,6 +65,22 @@ void grid_flood_1_to_0(Grid & g, size_t start);
 
 // cd_grid_double_interp on the host (src/libcd/grid.c:386-454): returns 1 when p is outside
 int grid_interp(const Grid & g, const double p[3], double * value);
+
+// ---------------------------------------------------------------- merge ---
+// the fields of placed kinbodies resampled into one grid (orc_scene_merge_fields; the specification is merged_grid_dims and
+// merged_field of or_cdchomp_amd/module.py)
+struct MergeBox { double lengths[3]; Pose pose; };      // a source grid's box and its pose in the target kinbody's frame
+// the merged grid: `bounds` [6] (lo, hi in the target kinbody's frame) or, when NULL, the box around the eight corners of every
+// source's box; sizes = max(2, ceil((hi - lo) / cell)), lengths = sizes cell, the pose (lo, identity quaternion).  Throws on a
+// non-finite or non-positive cell, non-finite numbers, a quaternion of zero norm, lo >= hi, and on a grid of 2^31 bytes or more
+void merge_grid_dims(const std::vector<MergeBox> & boxes, double cell, const double * bounds, int sizes[3], double lengths[3],
+   Pose & pose_kinbody_gsdf);
+// the record of one source (merge_interp.h): the affine target grid frame -> source grid frame, which is
+// pose_apply(pose_invert(pose_world_gsrc), pose_apply(pose_world_gsdf, .)) composed in double, and the source grid
+OrcMergeSource merge_affine(const Pose & pose_world_gsdf, const Pose & pose_world_gsrc, const int src_sizes[3], const double src_lengths[3],
+   const double * src_data);
+// the host twin of merge_fields_kernel: every cell of `out` (sizes and lengths set by the caller) by orc_merge_cell
+void merge_fields_host(const std::vector<OrcMergeSource> & sources, Grid & out);
 
 // oriented box for the primitive voxelizer
 struct Box { Xform world; double half[3]; };

@@ -1,6 +1,8 @@
 // module.cpp -- the module's device plumbing (event pool, stream pool, plan streams and buffers, timing totals) and its batches.
 // (The SendCommand layer: commands.cpp; the environment: env.cpp; the collision verdicts: verdict.cpp.)
 #include "module.h"
+#include "merge_launch.h"
+#include <cmath>
 #include <stdexcept>
 
 namespace orc {
@@ -155,6 +157,78 @@ int Module::create_batch(const std::string & rname, const BatchParams & p, int n
    const int id = next_batch_id_++;
    batches_[id] = std::move(b);
    return id;
+}
+
+// orc_scene_merge_fields.  Everything that can be refused is refused before the first device call, and the field list
+// changes in the last statement: a call that fails leaves the module as it was.
+void Module::merge_fields(const std::string & target, const std::vector<std::string> & fields, const double * field_poses,
+   double cell, const double * bounds)
+{
+   std::lock_guard<std::recursive_mutex> env_lock(env_mutex);
+   auto need_pose = [](const Pose & p) {
+      for (int i=0; i<7; i++) if (!std::isfinite(p.v[i])) throw std::runtime_error("poses and bounds must be finite numbers!");
+      if (p.v[3] == 0.0 && p.v[4] == 0.0 && p.v[5] == 0.0 && p.v[6] == 0.0) throw std::runtime_error("a pose's quaternion has zero norm!");
+   };
+   if (fields.empty()) throw std::runtime_error("n_fields must be >=1!");
+   env.kinbody(target);                                     // "Could not find kinbody with that name!"
+   if (env.find_sdf(target)) throw std::runtime_error("We already have an sdf for this kinbody!");
+   if (!std::isfinite(cell) || !(cell > 0.0)) throw std::runtime_error("cell must be a positive finite number!");
+   const Pose pose_world_target = env.body_transform(target);
+   need_pose(pose_world_target);
+   std::vector<std::shared_ptr<Sdf>> src;
+   std::vector<Pose> pose_world_gsrc;
+   std::vector<MergeBox> boxes;
+   const Pose pose_target_world = pose_invert(pose_world_target);
+   for (size_t k=0; k<fields.size(); k++)
+   {
+      const std::string & name = fields[k];
+      if (!env.has_body(name)) throw std::runtime_error("Could not find kinbody with that name!");
+      if (name == target) throw std::runtime_error("the target kinbody is among the fields to merge!");
+      std::shared_ptr<Sdf> field;
+      for (const auto & f : env.sdfs) if (f->kinbody_name == name) field = f;
+      if (!field) throw std::runtime_error("Kinbody " + name + " has no signed distance field!");
+      const Pose pose_world_kinbody = field_poses ? Pose(field_poses + 7*k) : env.body_transform(name);
+      need_pose(pose_world_kinbody);
+      need_pose(field->pose);
+      const Pose pw = pose_compose(pose_world_kinbody, field->pose);
+      MergeBox b;
+      for (int d=0; d<3; d++) b.lengths[d] = field->grid.lengths[d];
+      b.pose = pose_compose(pose_target_world, pw);
+      src.push_back(field); pose_world_gsrc.push_back(pw); boxes.push_back(b);
+   }
+   Grid g;
+   Pose pose_kinbody_gsdf;
+   merge_grid_dims(boxes, cell, bounds, g.sizes, g.lengths, pose_kinbody_gsdf);      // (with the other refusals: bounds, 2^31 bytes)
+   const Pose pose_world_gsdf = pose_compose(pose_world_target, pose_kinbody_gsdf);
+
+   // ---- the device: the sources' fp64 copies (shared with the batches, made on demand as BatchShard::grid_on_device makes
+   // them), the table, one kernel, one read-back
+   DeviceGuard guard(device);
+   std::vector<OrcMergeSource> table;
+   for (size_t k=0; k<src.size(); k++)
+   {
+      Sdf & s = *src[k];
+      std::shared_ptr<void> & buf = s.dev64[device];
+      if (!buf)
+      {
+         const size_t bytes = s.grid.ncells() * sizeof(double);
+         std::shared_ptr<void> fresh = device_buffer(device, bytes);
+         hip_check(hipMemcpy(fresh.get(), s.grid.data.data(), bytes, hipMemcpyHostToDevice), "sdf upload");
+         buf = fresh;
+      }
+      table.push_back(merge_affine(pose_world_gsdf, pose_world_gsrc[k], s.grid.sizes, s.grid.lengths, (const double *) buf.get()));
+   }
+   const size_t nc = g.ncells();
+   std::shared_ptr<void> out = device_buffer(device, nc * sizeof(double));
+   std::shared_ptr<void> dtable = device_buffer(device, table.size() * sizeof(OrcMergeSource));
+   g.data.resize(nc);
+   hip_check(hipMemcpyAsync(dtable.get(), table.data(), table.size() * sizeof(OrcMergeSource), hipMemcpyHostToDevice, stream), "merge table upload");
+   hip_check(orc_launch_merge_fields((double *) out.get(), g.sizes, g.lengths, (const OrcMergeSource *) dtable.get(), (int) table.size(), stream),
+             "merge_fields_kernel");
+   hip_check(hipMemcpyAsync(g.data.data(), out.get(), nc * sizeof(double), hipMemcpyDeviceToHost, stream), "merged field read-back");
+   hip_check(hipStreamSynchronize(stream), "merge sync");
+   env.add_sdf(target, g, pose_kinbody_gsdf);
+   env.find_sdf(target)->dev64[device] = out;               // the kernel's buffer is the field's fp64 copy here: no re-upload
 }
 
 Batch & Module::batch(int id)

@@ -55,6 +55,12 @@ public:
    void batch_collision_verdict_subset(int id, int which, const unsigned char * examine, int * collides, double * time, int * sphere,
       int * field, double * depth, int * n_samples);
 
+   // orc_scene_merge_fields / the mergefields command: the fields of `fields` (each where field_poses [n][7] puts its kinbody;
+   // NULL: where it stands) resampled on the device into one grid with the axes of `target`, a kinbody without a field, and
+   // registered as that kinbody's field; bounds [6] in the target's frame or NULL (merge_grid_dims, merge_kernels.hip)
+   void merge_fields(const std::string & target, const std::vector<std::string> & fields, const double * field_poses, double cell,
+      const double * bounds);
+
    hipStream_t stream = nullptr;     // orc_set_stream: the stream of the first device's work (NULL: its default stream)
    int device;                       // first entry of `devices`
    std::vector<int> devices;
@@ -92,6 +98,7 @@ private:
    std::string cmd_computedistancefield(const std::vector<std::string> & argv);
    std::string cmd_addfield_fromobsarray(const std::vector<std::string> & argv);
    std::string cmd_removefield(const std::vector<std::string> & argv);
+   std::string cmd_mergefields(const std::vector<std::string> & argv);
    std::string cmd_create(const std::vector<std::string> & argv, bool batch);
    std::string cmd_iterate(const std::vector<std::string> & argv, bool batch);
    std::string cmd_gettraj(const std::vector<std::string> & argv, bool batch);

@@ -372,6 +372,138 @@ def contiguous_groups(n_runs, n_groups):
     return np.repeat(np.arange(n_groups, dtype=np.int32), n_runs // n_groups)
 
 
+def pose_apply(pose, p):
+    """cd_kin_pose_compos (reference src/libcd/kin.c:180-212) as the library's pose_apply evaluates it, in scalar Python
+    doubles: the expanded quaternion products (not normalised), the factor 2 folded into the matrix, each row summed left
+    to right, then the translation.  Returns a list of 3 floats.  Pure: no library call."""
+    x, y, z, qx, qy, qz, qw = (float(v) for v in pose)
+    qx2 = qx * qx; qy2 = qy * qy; qz2 = qz * qz; qw2 = qw * qw
+    qxqy = qx * qy; qxqz = qx * qz; qxqw = qx * qw; qyqz = qy * qz; qyqw = qy * qw; qzqw = qz * qw
+    R = ((qx2 - qy2 - qz2 + qw2, 2 * (qxqy - qzqw), 2 * (qxqz + qyqw)),
+         (2 * (qxqy + qzqw), -qx2 + qy2 - qz2 + qw2, 2 * (qyqz - qxqw)),
+         (2 * (qxqz - qyqw), 2 * (qyqz + qxqw), -qx2 - qy2 + qz2 + qw2))
+    v = [float(c) for c in p]
+    t = (x, y, z)
+    return [(R[i][0] * v[0] + R[i][1] * v[1] + R[i][2] * v[2]) + t[i] for i in range(3)]
+
+
+def pose_invert(pose):
+    """cd_kin_pose_invert (reference src/libcd/kin.c:288-326) as the library evaluates it: the conjugate quaternion, and
+    minus the translation turned by it.  Returns a list of 7 floats.  Pure: no library call."""
+    q = [0.0, 0.0, 0.0, -float(pose[3]), -float(pose[4]), -float(pose[5]), float(pose[6])]
+    r = pose_apply(q, pose[:3])
+    return [-r[0], -r[1], -r[2]] + q[3:]
+
+
+def grid_interp(data, lengths, p):
+    """cd_grid_double_interp (reference src/libcd/grid.c:386-454) in scalar Python doubles, operation for operation:
+    returns (outside, value).  outside is True when a coordinate of p, divided by the grid's length, is not in [0, 1] (a NaN
+    is outside); a cell that holds +inf, or whose neighbour on the side of p does, gives +inf (the reference's poisoning);
+    the first and last cell of an axis take their neighbour inwards.  data [nx][ny][nz].  Pure: no library call."""
+    data = np.asarray(data, dtype=np.float64)
+    sizes = data.shape
+    sub = [0, 0, 0]
+    for d in range(3):
+        x = float(p[d]) / float(lengths[d])
+        if not (x >= 0.0 and x <= 1.0):
+            return True, 0.0
+        s = int(math.floor(x * sizes[d]))
+        if s == sizes[d]:
+            s -= 1
+        sub[d] = s
+    v = float(data[sub[0], sub[1], sub[2]])
+    if v == math.inf:
+        return False, math.inf
+    for d in (2, 1, 0):
+        center = (0.5 + sub[d]) / sizes[d] * float(lengths[d])
+        if sub[d] == 0:
+            prev = False
+        elif sub[d] == sizes[d] - 1:
+            prev = True
+        else:
+            prev = float(p[d]) < center
+        lo = list(sub); hi = list(sub)
+        if prev:
+            lo[d] -= 1
+        else:
+            hi[d] += 1
+        after = float(data[hi[0], hi[1], hi[2]]); before = float(data[lo[0], lo[1], lo[2]])
+        if after == math.inf or before == math.inf:
+            return False, math.inf
+        v += (after - before) * sizes[d] / float(lengths[d]) * (float(p[d]) - center)
+    return False, v
+
+
+def merged_grid_dims(source_boxes, cell, bounds=None):
+    """The grid orc_scene_merge_fields merges into (orc_host_merge_grid is the library's own).  source_boxes: per source
+    (lengths[3], pose7): its grid's box and the grid's pose in the TARGET KINBODY's frame; cell: the edge of the merged
+    grid's cubic cells; bounds: six numbers lo[3], hi[3] in the target kinbody's frame, or None: the axis-aligned box
+    around the eight corners of every source's box (pose_apply of the corner).  sizes[d] = max(2, ceil((hi[d] - lo[d]) /
+    cell)), lengths[d] = sizes[d] * cell, and the grid's pose in the target kinbody's frame is (lo, identity quaternion):
+    the merged grid's axes are the target kinbody's.  Returns (sizes [3] ints, lengths [3] floats, pose [7] floats).
+    Raises ValueError where the call is rejected.  Pure: no library call."""
+    cell = float(cell)
+    if not (math.isfinite(cell) and cell > 0.0):
+        raise ValueError("cell must be a positive finite number")
+    if bounds is not None:
+        b = [float(v) for v in bounds]
+        if len(b) != 6:
+            raise ValueError("bounds holds lo[3] and hi[3]")
+        lo, hi = b[:3], b[3:]
+    else:
+        if len(source_boxes) < 1:
+            raise ValueError("without bounds there must be a source")
+        lo = hi = None
+        for lengths, pose in source_boxes:
+            if not all(math.isfinite(float(v)) for v in list(lengths) + list(pose)):
+                raise ValueError("poses and lengths must be finite numbers")
+            for corner in range(8):
+                c = [float(lengths[0]) if corner & 4 else 0.0, float(lengths[1]) if corner & 2 else 0.0,
+                     float(lengths[2]) if corner & 1 else 0.0]
+                w = pose_apply(pose, c)
+                lo = list(w) if lo is None else [min(a, x) for a, x in zip(lo, w)]
+                hi = list(w) if hi is None else [max(a, x) for a, x in zip(hi, w)]
+    if not all(math.isfinite(v) for v in lo + hi):
+        raise ValueError("poses and bounds must be finite numbers")
+    if not all(a < b for a, b in zip(lo, hi)):
+        raise ValueError("bounds must have lo < hi in every dimension")
+    sizes = [max(2, int(math.ceil((hi[d] - lo[d]) / cell))) for d in range(3)]
+    if sizes[0] * sizes[1] * sizes[2] * 8 >= 2 ** 31:
+        raise ValueError("signed distance field too large for this build")
+    lengths = [sizes[d] * cell for d in range(3)]
+    return sizes, lengths, [lo[0], lo[1], lo[2], 0.0, 0.0, 0.0, 1.0]
+
+
+def merged_field(sources, sizes, lengths, pose_world_gsdf, interp=grid_interp):
+    """The field orc_scene_merge_fields computes (orc_host_merge_fields is the host twin, merge_fields_kernel the device's).
+    sources: an ordered list of (data [nx][ny][nz], lengths [3], pose_world_gsrc [7]); sizes, lengths, pose_world_gsdf: the
+    merged grid and its world pose.  For cell (i, j, k): c[d] = (0.5 + sub[d]) / sizes[d] * lengths[d] (the cell centre as
+    the voxelizer forms it), p_w = pose_apply(pose_world_gsdf, c), and for every source in order p_s =
+    pose_apply(pose_invert(pose_world_gsrc), p_w) and (outside, val) = interp(data, lengths, p_s); the cell is the smallest
+    val, by strict <, of the sources that are not outside, starting from +inf: the best-of-N field loop of the cost function
+    evaluated at the cell centre.  A poisoned (+inf) value never wins and a cell no source covers holds +inf.  interp:
+    grid_interp, or another reading of cd_grid_double_interp with its signature.  Returns data [sizes].  (The library composes
+    the two pose_apply calls into one affine per source, in double: the same point to a few roundings.)  Pure: no library
+    call."""
+    sizes = [int(s) for s in sizes]
+    lengths = [float(v) for v in lengths]
+    inv = [pose_invert(src[2]) for src in sources]
+    out = np.full(sizes, np.inf)
+    for i in range(sizes[0]):
+        for j in range(sizes[1]):
+            for k in range(sizes[2]):
+                sub = (i, j, k)
+                c = [(0.5 + sub[d]) / sizes[d] * lengths[d] for d in range(3)]
+                p_w = pose_apply(pose_world_gsdf, c)
+                best = math.inf
+                for (data, slen, _), pinv in zip(sources, inv):
+                    outside, val = interp(data, slen, pose_apply(pinv, p_w))
+                    if not outside and val < best:
+                        best = val
+                out[i, j, k] = best
+    return out
+
+
 class Module:
     def __init__(self, device=0):
         """device: one HIP ordinal, or a list of them (batches are then sharded over the list inside
@@ -546,6 +678,28 @@ class Module:
         self._check(self._lib.orc_scene_get_sdf(self._h, kinbody.encode(), _ip(sizes), _dp(lengths), _dp(pose),
                                                 _dp(data), data.size))
         return data, lengths, pose
+
+    def merge_fields(self, target, fields, cell, bounds=None):
+        """Bake a layout into one field (orc_scene_merge_fields; the rule is merged_grid_dims' and merged_field's): the
+        fields of `fields`, a list of (kinbody, pose7 or None: where the kinbody stands now) -- the element type of
+        batch_create's scenes --, resampled on the device into one grid with the axes of `target`, an existing kinbody
+        without a field (add_kinbody_boxes(name, []) makes one), with cubic cells of edge `cell` over `bounds` (lo[3] + hi[3]
+        in the target's frame; None: the box around all the sources).  The result is an ordinary field of `target`:
+        get_sdf(target) reads it, batch_create(scenes=[[(target, None)]], ...) plans against it."""
+        fields = list(fields)
+        _, names, poses = scenes_to_csr([fields])
+        if poses is not None:
+            for k in range(len(names)):
+                if fields[k][1] is None:
+                    poses[k] = self.body_transform(names[k])
+            poses = np.ascontiguousarray(poses)
+        cnames = (C.c_char_p * max(len(names), 1))(*[nm.encode() for nm in names])
+        bd = None if bounds is None else _f64(bounds).reshape(-1)
+        if bd is not None and bd.size != 6:
+            raise ValueError("bounds holds lo[3] and hi[3]")
+        self._check(self._lib.orc_scene_merge_fields(self._h, target.encode(), len(names), cnames,
+                                                     None if poses is None else _dp(poses), float(cell),
+                                                     None if bd is None else _dp(bd)))
 
     # ---- kernel-level batch API -------------------------------------------------------
     def batch_params(self, **kw):

@@ -20,6 +20,23 @@ def add_tabletop(mod):
         mod.add_kinbody_boxes(name, boxes, transform=IDENT)
 
 
+def merged_scenes(mod, scenes, cell, bounds=None, prefix="merged"):
+    """Every scene of `scenes` (lists of (kinbody, pose7 or None), as batch_create takes them) baked into one field with
+    the world's axes: for scene s an empty kinbody prefix + str(s) is added at the identity and the scene merged into it
+    (Module.merge_fields).  Returns [[(prefix + str(s), None)], ...], ready for batch_create(scenes=...): every scene is one
+    placement whatever it held, and runs the one-field kernels.  An empty scene stays empty (no kinbody is added)."""
+    out = []
+    for s, scene in enumerate(scenes):
+        if not scene:
+            out.append([])
+            continue
+        name = prefix + str(s)
+        mod.add_kinbody_boxes(name, [], transform=IDENT)
+        mod.merge_fields(name, scene, cell, bounds)
+        out.append([(name, None)])
+    return out
+
+
 def random_boxes(rng, n_bodies=4):
     """config 5: four box kinbodies with random poses (seeded by the caller)."""
     out = {}
