@@ -87,6 +87,37 @@ def test_perturbation_matches_the_specification(wam, n_points, derivative, n_run
     assert same(mod_seed_0(model, line[1], sigma, derivative), want[1])
 
 
+@pytest.mark.parametrize("n_points,derivative", [(32, 1), (100, 2)])
+def test_perturbation_with_a_zero_word_in_the_stream(wam, n_points, derivative):
+    """seeds whose fresh stream holds an output word of 0 inside the m n >= 210 values drawn (hmc_stream.ZERO_WORD_*: word 141,
+    the second of its pair, and word 400, the first of its pair): gsl_rng_uniform_pos skips it, and the wavefront's chunk of 64
+    pairs that meets it takes MtWave's one-at-a-time walk.  The specification and the bar of
+    test_perturbation_matches_the_specification; that the specification's own stream skips the word as the oracle's does is
+    tests/test_host_hmc_stream.py's"""
+    import hmc_stream
+    mod, model = wam
+    seeds = np.array([hmc_stream.ZERO_WORD_SECOND[0], hmc_stream.ZERO_WORD_FIRST[0], 3, hmc_stream.ZERO_WORD_SECOND[0], hmc_stream.ZERO_WORD_FIRST[0]],
+                     dtype=np.uint32)
+    n_runs = len(seeds)
+    goals = common.wam_goals(n_runs, seed=31)
+    sigma = 0.15
+    bid = mod.batch_create(model.name, goals, **dict(KW, n_points=n_points, derivative=derivative))
+    line = mod.batch_state(bid, "T")
+    mod.batch_perturb(bid, sigma, seeds)
+    got = mod.batch_state(bid, "T")
+    mod.batch_destroy(bid)
+    assert line.shape == (n_runs, n_points - 2, 7) and (n_points - 2) * 7 >= 210
+    want = spec_rows(model, line, sigma, seeds, derivative)
+    worst = 0.0
+    for k in range(n_runs):
+        d_want = want[k] - line[k]
+        assert np.abs(d_want[(n_points - 2) // 2]).max() > 0.01, "the workload must move the middle waypoint"
+        err = common.rel_l2(got[k] - line[k], d_want)
+        worst = max(worst, err)
+        assert err <= 1e-10, (k, int(seeds[k]), err)
+    print("zero-word seeds, n_points %d derivative %d: worst relative L2 of the displacement %.3e" % (n_points, derivative, worst))
+
+
 def mod_seed_0(model, line, sigma, derivative):
     """the run seeded 0, by the specification with GSL's default seed spelled out"""
     m, n = line.shape
