@@ -490,6 +490,59 @@ int orc_batch_select_best_by(orc_module * mod, int batch_id, int cost_column, in
 int orc_batch_respawn(orc_module * mod, int batch_id, int cost_column, int n_groups, const int * group_of_run,
    int collision_mode, int keep, double sigma, const unsigned int * seeds,
    int * source_of_run_out, int * n_survivors_out);
+/* ---- clearance: how far a run stays away, where the verdict only says whether it touches -----------------------------
+ * The walk of orc_batch_collision_verdict_device without its stop at the first contact: the same retiming, the same samples
+ * (verdict_samples of or_cdchomp_amd/module.py), the same FK and field lookup in the batch's precision, with the robot's
+ * self-check setting.  Over every sample of a run two minima are kept:
+ *   [0] fields: value - radius, over the live active spheres and every field of the run's scene that contains the sphere's
+ *       centre.  A +inf value (a poisoned cell, a merged field's "no field here") is never the minimum, a NaN is ignored.
+ *   [1] self: distance - (r_a + r_b), over the pairs of the verdict's self-collision leg (none with the self check off).
+ * They are the subtractions the verdict compares to zero: min(clearance) < 0 exactly when the verdict says the run collides,
+ * and then min(clearance) <= -depth.  Where a minimum is attained more than once the item of the lowest key counts
+ * (sample, XML sphere, field -- or sample, XML sphere a, XML sphere b); the reduction is deterministic (an integer minimum
+ * over the keys at the minimum, no floating-point atomic), so a run's outputs depend on its trajectory only, not on its
+ * batch, its shard or a schedule.
+ *   which 0: examine [n_runs] bytes, nonzero: examine the run (NULL is rejected).  which 1: the candidates, as
+ *   orc_batch_collision_verdict_subset's which 1 (examine must be NULL; a batch never iterated is rejected).  which 2: every
+ *   run (examine must be NULL).
+ * The walk cannot stop early, so it is bounded by the caller: a run with duration > 0 and (C-space length / 0.04 >=
+ * max_samples or a step that does not advance the clock) is TOO LONG, decided before anything of it is walked
+ * (`clearance_too_long` of module.py).  max_samples lies in [1, 2^20]; a run the rule passes has at most max_samples + 2
+ * samples.  A run of 2^20 samples occupies one workgroup for 16 384 chunks of 64 samples: measured once on an MI355X, alone
+ * in a batch of one, 0.31 s (NOTES/clearance.md); the default of the Python layer is 65 536.
+ * Outputs, clearance_out [n_runs][2] and n_samples_out [n_runs] required, the others may be NULL:
+ *   an examined run: clearance_out the two minima widened to double from the batch's precision; time_out [n_runs][2] the time
+ *     of each on the retimed trajectory; sphere_out [n_runs][2] the XML index of the sphere (of sphere a); other_out
+ *     [n_runs][2] the index of the field, or the XML index of sphere b; n_samples_out the samples walked.  A minimum over
+ *     nothing (no sample, no field that contains a sphere, no pairs) is +inf with time -1.0, sphere -1 and other -1.
+ *   a run that is not examined: clearance NaN, time -1, sphere -1, other -1, n_samples -1; its workgroup returns before it
+ *     stages anything.
+ *   a run that is too long: the same with n_samples -2, AND THE CALL SUCCEEDS.
+ * Several devices: every shard takes its slice, as the subset verdict does.
+ * Rejected with a nonzero return and a message before any device work, the batch unchanged and the module usable: an unknown
+ * batch; which outside 0..2; a NULL examine with which 0 or an examine with which 1 or 2; clearance_out or n_samples_out
+ * NULL; max_samples outside [1, 2^20]; which 1 on a batch never iterated. */
+int orc_batch_clearance(orc_module * mod, int batch_id, int which, const unsigned char * examine, int max_samples,
+   double * clearance_out /* [n_runs][2]: fields, self */, double * time_out /* [n_runs][2] */,
+   int * sphere_out /* [n_runs][2] */, int * other_out /* [n_runs][2]: field index; XML index of sphere b */,
+   int * n_samples_out /* [n_runs] */);
+/* The best run of every group among those that keep a margin.  n_groups and group_of_run as in orc_batch_select_best.  A run
+ * is eligible when all three hold: it is a candidate (status 0 or 1 and a finite total cost); it was walked, i.e. is not too
+ * long for max_samples; fmin(clearance[0], clearance[1]) >= margin.  margin 0 is orc_batch_select_best_by's
+ * require_collision_free.  cost_column 0..2: orc_batch_select_best_by's key and tie rule.  cost_column 3: the largest
+ * clearance wins, a tie goes to the lowest run index, and best_cost_out is -clearance, so "lowest wins" holds for every
+ * column.  best_run_out [n_groups] (-1 for a group without an eligible run), best_cost_out [n_groups] (+inf there),
+ * best_clearance_out [n_groups] the winner's fmin of the two minima (NaN there), n_eligible_out [n_groups]; n_samples_out
+ * [n_runs] as orc_batch_clearance(which 1) reports it; any output may be NULL.  `select_clear` of module.py is the rule.
+ * On the device: the clearance kernel runs over the candidates only, the minima stay there, a segmented arg-min reads them;
+ * n_groups rows come back, and n_samples_out if asked for.  Several devices: every shard reduces its runs and the host merges
+ * n_shards x n_groups candidates by the same rule; groups may span shards.
+ * Rejected with a nonzero return and a message before any device work, the batch unchanged and the module usable: an unknown
+ * batch; a batch never iterated; cost_column outside 0..3; a NaN margin (+-inf are accepted); max_samples outside [1, 2^20];
+ * n_groups < 1, a group_of_run entry outside [0, n_groups), or a NULL group_of_run with n_runs % n_groups != 0. */
+int orc_batch_select_clear(orc_module * mod, int batch_id, int cost_column, int n_groups, const int * group_of_run,
+   double margin, int max_samples,
+   int * best_run_out, double * best_cost_out, double * best_clearance_out, int * n_eligible_out, int * n_samples_out);
 /* The rows runs[0 .. n_sel) of what orc_batch_gettraj returns, gathered on the device and copied as n_sel n_points n
  * doubles: traj_out [n_sel][n_points][n].  An entry -1 (what orc_batch_select_best reports for a group without an
  * eligible run) gives a row of NaN; duplicates are allowed; runs that live on different shards work.  Any other entry

@@ -95,6 +95,10 @@ SYMBOLS = [
     ("orc_batch_select_best", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, c_double_p, c_int_p]),
     ("orc_batch_select_best_by", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, c_int_p, c_double_p,
                                            c_int_p]),
+    ("orc_batch_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_ubyte_p, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p,
+                                      c_int_p]),
+    ("orc_batch_select_clear", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_int, c_int_p, c_double_p,
+                                         c_double_p, c_int_p, c_int_p]),
     ("orc_batch_respawn", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, C.c_int, C.c_double, c_uint_p,
                                     c_int_p, c_int_p]),
     ("orc_batch_set_run_params", C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),

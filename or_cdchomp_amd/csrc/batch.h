@@ -99,6 +99,15 @@ public:
    // scope: the runs that are examined (its `examine` is this shard's slice); a run that is not has the key ORC_VERDICT_NONE
    bool collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
                                   int * n_samples_out, const VerdictScope & scope = VerdictScope());
+   // (clearance.cpp) the clearance of this shard's runs (clearance_kernels.hip; scope.which -1, 0, 1 as for the verdict, the other
+   // fields of the scope are not read): the two minima of every run stay on the device for select_clear, and what of clear /
+   // time [n_runs][2], key [n_runs][2] and n_samples [n_runs] is not NULL comes back
+   void clearance(const VerdictInputs & in, const VerdictScope & scope, int max_samples, double * clear_out, double * time_out,
+                  unsigned long long * key_out, int * n_samples_out);
+   // per group among this shard's runs that are candidates, were walked by the last `clearance` and clear `margin`: the lowest
+   // key (column 0..2 a cost, 3 minus the clearance), the lowest LOCAL run that has it, the winner's clearance, the eligible runs
+   void select_clear(int n_groups, const int * group, int column, double margin, unsigned long long * key_out, int * best_out,
+                     double * best_clear_out, int * count_out);
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
@@ -128,6 +137,8 @@ private:
       const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
    template <typename real> bool collision_verdict_planned_typed(const VerdictInputs & in, unsigned long long * key_out, double * depth_out,
       double * time_out, int * n_samples_out, const VerdictScope & scope);
+   template <typename real> void clearance_typed(const VerdictInputs & in, const VerdictScope & scope, int max_samples, double * clear_out,
+      double * time_out, unsigned long long * key_out, int * n_samples_out);
    void construct(const Robot & robot, const double * starts, const double * goals, const double * basegoals,
       const unsigned int * seeds);
    Module * mod_;
@@ -152,6 +163,7 @@ private:
    DevBuf d_status_, d_iters_done_, d_leap_, d_phase_, d_hwid_;
    DevBuf d_run_params_; bool run_params_on_ = false;      // [n_runs] RunParams<real>; kept allocated while off (launches in flight may read it)
    DevBuf d_vkey_;                           // [n_runs] the keys of the last collision_verdict_planned
+   DevBuf d_clear_, d_clear_ns_;             // [n_runs][2] doubles, [n_runs] ints: the minima and the sample counts of the last `clearance`
    DevBuf d_Aband_, d_beta_s_, d_beta_g_, d_metric64_, d_pcr_, d_Ainv_, d_jl_lo_, d_jl_hi_;
    // TSR hard constraints (csrc/tsr.h): the device copies of the constraints, the per-run workspace
    DevBuf d_tsrs_, d_tsr_ws_, d_tsr_err_;
@@ -212,6 +224,14 @@ public:
    // scope.long_marks_run).  scope.which 1 on a batch that has not been iterated throws select_best's message
    void collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
                                   int * n_samples_out, const VerdictScope & scope = VerdictScope());
+   // (clearance.cpp) orc_batch_clearance / orc_batch_select_clear.  clearance_check throws for what those calls reject of which,
+   // examine and max_samples, before any device work; `clearance`: every shard walks its slice, outputs as BatchShard's, over
+   // the batch's runs; select_clear: the shards' winners merged by the same rule (lower key, then lower run)
+   void clearance_check(int which, const unsigned char * examine, int max_samples) const;
+   void clearance(const VerdictInputs & in, int which, const unsigned char * examine, int max_samples, double * clear_out, double * time_out,
+                  unsigned long long * key_out, int * n_samples_out);
+   void select_clear(int n_groups, const std::vector<int> & group, int column, double margin, int * best_run_out, double * best_cost_out,
+                     double * best_clear_out, int * n_eligible_out);
    // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
    // kept until it is set again
    int verdict_scope = 0;

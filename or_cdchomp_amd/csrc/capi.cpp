@@ -669,6 +669,25 @@ int orc_batch_select_best_by(orc_module * mod, int id, int cost_column, int n_gr
    });
 }
 
+int orc_batch_clearance(orc_module * mod, int id, int which, const unsigned char * examine, int max_samples, double * clearance_out,
+   double * time_out, int * sphere_out, int * other_out, int * n_samples_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch(id);      // (an unknown batch first)
+      need(clearance_out, "clearance_out"); need(n_samples_out, "n_samples_out");
+      mod->impl->batch_clearance(id, which, examine, max_samples, clearance_out, time_out, sphere_out, other_out, n_samples_out);
+   });
+}
+
+int orc_batch_select_clear(orc_module * mod, int id, int cost_column, int n_groups, const int * group_of_run, double margin, int max_samples,
+   int * best_run_out, double * best_cost_out, double * best_clearance_out, int * n_eligible_out, int * n_samples_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch_select_clear(id, cost_column, n_groups, group_of_run, margin, max_samples, best_run_out, best_cost_out,
+         best_clearance_out, n_eligible_out, n_samples_out);
+   });
+}
+
 int orc_batch_respawn(orc_module * mod, int id, int cost_column, int n_groups, const int * group_of_run, int collision_mode, int keep,
    double sigma, const unsigned int * seeds, int * source_of_run_out, int * n_survivors_out)
 {

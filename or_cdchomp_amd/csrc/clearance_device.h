@@ -1,0 +1,41 @@
+// clearance_device.h -- the clearance of a batch's runs (clearance_kernels.hip) and the selection by margin that reads it
+// (multistart_kernels.hip), as clearance.cpp launches them.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "verdict_device.h"
+
+// The walk of the device-planned collision verdict (DevVerdictPlan) without its stop at the first contact: over every sample
+// of an examined run the smallest `value - radius` of a live active sphere in a field of the run's scene, and the smallest
+// `distance - radius sum` of a pair of the self-collision leg.  key_out and depth_out of the walk are not used.
+template <typename real>
+struct DevClearance : DevVerdictWalk<real>
+{
+   int col0;                   // first column the retiming reads (7 with a floating base)
+   const double * vmax;        // [n - col0] velocity limits of the retimed columns
+   int max_samples;            // a run with C-space length / 0.04 >= max_samples is too long: nothing of it is walked
+   // which runs are examined, as in DevVerdictPlan: all NULL: every run
+   const unsigned char * examine;
+   const int * cand_status;
+   const double * cand_costs;
+   // per run two minima, [0] over the fields and [1] over the pairs: the value widened to double (+inf: nothing to take a
+   // minimum of; NaN: the run was not walked), its key and its time on the retimed trajectory (-1 without a key).
+   //   key [0]: sample << 32 | XML sphere << 16 | field      key [1]: sample << 32 | XML sphere a << 16 | XML sphere b
+   // the lowest key among the items that attain the minimum; ORC_VERDICT_NONE without one
+   double * clear_out;              // [n_runs][2]
+   unsigned long long * ckey_out;   // [n_runs][2]
+   double * ctime_out;              // [n_runs][2]
+   int * n_samples_out;             // [n_runs] samples walked; ORC_VERDICT_SKIPPED: not examined; ORC_VERDICT_TOO_LONG
+};
+
+#define ORC_CLEARANCE_MAX_SAMPLES (1 << 20)
+
+hipError_t orc_launch_clearance(const DevClearance<double> & v, size_t lds, hipStream_t stream, int tree);
+hipError_t orc_launch_clearance(const DevClearance<float> & v, size_t lds, hipStream_t stream, int tree);
+size_t orc_clearance_lds_bytes(int n_points, int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);
+
+// The best run per group among the candidates (run_candidate.h) that were walked (n_samples >= 0) and clear `margin`
+// (fmin of a run's two minima >= margin).  column 0..2: the lowest costs[run][column]; 3: the largest clearance (the key is
+// -clearance).  key [n_groups] (all bits set), count [n_groups] (0) and best [n_groups] (above every run index) are the
+// caller's to initialise; best_clear [n_groups] is written in full: the winner's fmin, NaN without a winner.
+hipError_t orc_launch_select_clear(const double * costs, const int * status, const double * clear, const int * n_samples, const int * group,
+   int n_runs, int n_groups, int column, double margin, unsigned long long * key, int * count, int * best, double * best_clear, hipStream_t stream);

@@ -54,6 +54,13 @@ public:
    // samples behind a contact are not counted
    void batch_collision_verdict_subset(int id, int which, const unsigned char * examine, int * collides, double * time, int * sphere,
       int * field, double * depth, int * n_samples);
+   // (clearance.cpp) orc_batch_clearance: per run the smallest gap to a field [0] and between two spheres of a pair [1] over the
+   // samples the verdict looks at, with time, XML sphere and field / other sphere; which 0 examine, 1 the candidates, 2 every run
+   void batch_clearance(int id, int which, const unsigned char * examine, int max_samples, double * clearance, double * time, int * sphere,
+      int * other, int * n_samples);
+   // orc_batch_select_clear: the clearance of the candidates, then per group the best run among those that clear `margin`
+   void batch_select_clear(int id, int cost_column, int n_groups, const int * group_of_run, double margin, int max_samples,
+      int * best_run, double * best_cost, double * best_clearance, int * n_eligible, int * n_samples);
 
    // orc_scene_merge_fields / the mergefields command: the fields of `fields` (each where field_poses [n][7] puts its kinbody;
    // NULL: where it stands) resampled on the device into one grid with the axes of `target`, a kinbody without a field, and

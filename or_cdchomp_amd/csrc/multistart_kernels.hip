@@ -1,6 +1,7 @@
 // multistart_kernels.hip -- multi-start batches: perturbed seed trajectories, the best run per problem, the rows of the
 // winners, the losing runs respawned from the winners, all on the device (orc_batch_perturb, orc_batch_select_best,
-// orc_batch_gettraj_runs, orc_batch_respawn).
+// orc_batch_gettraj_runs, orc_batch_respawn), and the best run per problem among those that clear a margin
+// (orc_batch_select_clear).
 //
 // The reference has no multi-start; K runs of one planning problem start from one straight line (seed_traj_kernel) and are
 // K identical runs unless something diversifies them.  perturb_kernel adds to the moving waypoints of every run a smooth
@@ -16,6 +17,7 @@
 #include "launch.h"
 #include "mt_wave.h"
 #include "run_candidate.h"
+#include "clearance_device.h"
 
 namespace {
 
@@ -128,6 +130,47 @@ __global__ void select_run_kernel(const double * costs, const int * status, cons
    const int r = blockIdx.x * blockDim.x + threadIdx.x;
    if (r >= n_runs || !run_eligible(costs, status, verdict_key, r)) return;
    if (cost_key(costs[(size_t) r*3 + column]) == key[group[r]]) atomicMin(&best[group[r]], r);
+}
+
+// ---- the best run per group by margin (orc_batch_select_clear) --------------------------------------------------------
+// clear [n_runs][2] and n_samples [n_runs] are what clearance_kernel (clearance_kernels.hip) left of the candidates.  A run
+// is eligible when it is a candidate, was walked (not too long) and its smaller minimum is at least `margin`.
+__device__ __forceinline__ bool run_clear(const double * costs, const int * status, const double * clear, const int * n_samples, double margin, int r, double & c)
+{
+   c = fmin(clear[(size_t) r*2], clear[(size_t) r*2 + 1]);
+   return orc_run_candidate(status[r], costs[(size_t) r*3]) && n_samples[r] >= 0 && c >= margin;
+}
+// column 0..2: the cost; 3: the clearance, the largest first
+__device__ __forceinline__ unsigned long long clear_key(const double * costs, int column, int r, double c)
+{
+   return cost_key(column < 3 ? costs[(size_t) r*3 + column] : -c);
+}
+// pass 1: the lowest key of every group's eligible runs and their number
+__global__ void select_clear_cost_kernel(const double * costs, const int * status, const double * clear, const int * n_samples, const int * group,
+   int n_runs, int column, double margin, unsigned long long * key, int * count)
+{
+   const int r = blockIdx.x * blockDim.x + threadIdx.x;
+   double c;
+   if (r >= n_runs || !run_clear(costs, status, clear, n_samples, margin, r, c)) return;
+   atomicMin(&key[group[r]], clear_key(costs, column, r, c));
+   atomicAdd(&count[group[r]], 1);
+}
+// pass 2: the lowest index among the runs that have it
+__global__ void select_clear_run_kernel(const double * costs, const int * status, const double * clear, const int * n_samples, const int * group,
+   int n_runs, int column, double margin, const unsigned long long * key, int * best)
+{
+   const int r = blockIdx.x * blockDim.x + threadIdx.x;
+   double c;
+   if (r >= n_runs || !run_clear(costs, status, clear, n_samples, margin, r, c)) return;
+   if (clear_key(costs, column, r, c) == key[group[r]]) atomicMin(&best[group[r]], r);
+}
+// pass 3: the winners' clearance
+__global__ void select_clear_margin_kernel(const double * clear, const int * count, const int * best, int n_groups, double * best_clear)
+{
+   const int g = blockIdx.x * blockDim.x + threadIdx.x;
+   if (g >= n_groups) return;
+   const int r = best[g];
+   best_clear[g] = count[g] > 0 ? fmin(clear[(size_t) r*2], clear[(size_t) r*2 + 1]) : __longlong_as_double(0x7ff8000000000000LL);
 }
 
 // ---- rows of the trajectory array, as doubles -----------------------------------------------------------------------
@@ -310,6 +353,15 @@ hipError_t orc_launch_select_best(const double * costs, const int * status, cons
    const dim3 grid((n_runs + 255) / 256), block(256);
    hipLaunchKernelGGL(select_cost_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, column, key, count);
    hipLaunchKernelGGL(select_run_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, column, key, best);
+   return hipGetLastError();
+}
+hipError_t orc_launch_select_clear(const double * costs, const int * status, const double * clear, const int * n_samples, const int * group,
+   int n_runs, int n_groups, int column, double margin, unsigned long long * key, int * count, int * best, double * best_clear, hipStream_t stream)
+{
+   const dim3 grid((n_runs + 255) / 256), block(256);
+   hipLaunchKernelGGL(select_clear_cost_kernel, grid, block, 0, stream, costs, status, clear, n_samples, group, n_runs, column, margin, key, count);
+   hipLaunchKernelGGL(select_clear_run_kernel, grid, block, 0, stream, costs, status, clear, n_samples, group, n_runs, column, margin, key, best);
+   hipLaunchKernelGGL(select_clear_margin_kernel, dim3((n_groups + 255) / 256), block, 0, stream, clear, count, best, n_groups, best_clear);
    return hipGetLastError();
 }
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream)

@@ -255,6 +255,82 @@ def select_best(costs, status, collides, group_of_run, n_groups, column=0):
     return best_run, best_cost, n_eligible
 
 
+def clearance_too_long(traj, vmax, col0, max_samples):
+    """Whether orc_batch_clearance finds one trajectory [n_points][n] too long for `max_samples`: the rule its kernel decides
+    before anything is walked, in the scalar Python doubles of verdict_samples (the same sums, in the same order):
+    duration > 0 and (total_dist / 0.04 >= max_samples or step_time <= 0).  A trajectory it passes has at most max_samples + 2
+    samples.  Pure: no library call."""
+    T = np.asarray(traj, dtype=np.float64)
+    if T.ndim != 2 or T.shape[0] < 2:
+        raise ValueError("a trajectory is [n_points][n] with at least two points")
+    n_points, n = T.shape
+    col0 = int(col0)
+    vm = [float(x) for x in np.asarray(vmax, dtype=np.float64).reshape(-1)]
+    if not 0 <= col0 < n or len(vm) != n - col0:
+        raise ValueError("vmax has an entry for every column from col0 on")
+    rows = [[float(x) for x in row] for row in T]
+    total_dist = 0.0
+    duration = 0.0
+    for i in range(1, n_points):
+        dt = 0.0
+        d2 = 0.0
+        for j in range(col0, n):
+            v = vm[j - col0] if vm[j - col0] > 0.0 else 1.0
+            c = abs(rows[i][j] - rows[i - 1][j]) / v
+            dt = c if dt < c else dt
+            d = rows[i - 1][j] - rows[i][j]
+            d2 += d * d
+        total_dist += math.sqrt(d2)
+        duration += dt
+    step_time = duration * 0.04 / total_dist if total_dist > 0.0 else duration + 1.0
+    return bool(duration > 0.0 and (total_dist / 0.04 >= float(max_samples) or step_time <= 0.0))
+
+
+def select_clear(costs, status, clearance, n_samples, group_of_run, n_groups, margin, column):
+    """The rule of orc_batch_select_clear.  costs [n_runs][3] rows as batch_iterate returns them, status [n_runs], clearance
+    [n_runs][2] and n_samples [n_runs] as batch_clearance(runs="candidates") returns them, group_of_run [n_runs] with entries
+    in [0, n_groups).  A run is eligible when it is a candidate (candidates), was walked (n_samples >= 0) and
+    fmin(clearance[run]) >= margin.  column 0..2: the eligible run of lowest costs[run][column] wins; column 3: the one of
+    largest clearance, its cost is -clearance; a tie goes to the lowest run index, and -0 ties with +0.  Returns (best_run
+    int32 [n_groups], -1 for a group without an eligible run; best_cost [n_groups], +inf there; best_clearance [n_groups], NaN
+    there; n_eligible int32 [n_groups]).  Pure numpy."""
+    costs = np.asarray(costs, dtype=np.float64)
+    if column not in (0, 1, 2, 3):
+        raise ValueError("column is 0 (total), 1 (obs), 2 (smooth) or 3 (clearance)")
+    if costs.ndim != 2 or costs.shape[1] != 3:
+        raise ValueError("costs are the [n_runs][3] cost rows")
+    margin = float(margin)
+    if margin != margin:
+        raise ValueError("margin is NaN")
+    n_runs = costs.shape[0]
+    status = np.asarray(status).reshape(-1)
+    group = np.asarray(group_of_run).reshape(-1)
+    clear = np.asarray(clearance, dtype=np.float64).reshape(-1, 2)
+    ns = np.asarray(n_samples).reshape(-1)
+    if status.shape[0] != n_runs or group.shape[0] != n_runs or clear.shape[0] != n_runs or ns.shape[0] != n_runs:
+        raise ValueError("costs, status, clearance, n_samples and group_of_run have one entry per run")
+    if n_groups < 1 or (n_runs and (group.min() < 0 or group.max() >= n_groups)):
+        raise ValueError("group_of_run entries must lie in [0, n_groups)")
+    cand = candidates(costs[:, 0], status)
+    best_run = np.full(n_groups, -1, dtype=np.int32)
+    best_cost = np.full(n_groups, np.inf)
+    best_clear = np.full(n_groups, np.nan)
+    n_eligible = np.zeros(n_groups, dtype=np.int32)
+    for r in range(n_runs):
+        c = float(np.fmin(clear[r, 0], clear[r, 1]))
+        if not (cand[r] and ns[r] >= 0 and c >= margin):
+            continue
+        g = int(group[r])
+        key = (costs[r, column] if column < 3 else -c) + 0.0
+        n_eligible[g] += 1
+        # the device's order: cost_key, in which a NaN cost is above every number and ties keep the earlier run
+        if best_run[g] < 0 or cost_key(key) < cost_key(best_cost[g]):
+            best_run[g] = r
+            best_cost[g] = key
+            best_clear[g] = c
+    return best_run, best_cost, best_clear, n_eligible
+
+
 def cost_key(c):
     """A cost as the unsigned key of the same order that the device compares (cost_key of csrc/multistart_kernels.hip): the
     bits of c + 0.0, so that -0 is +0, inverted for a negative number and with the sign bit set otherwise.  Python int."""
@@ -963,6 +1039,62 @@ class Module:
             return dict(collides=col, time=tim, sphere=sph, field=fld, depth=dep, n_samples=cnt)
         self._check(self._lib.orc_batch_collision_verdict(self._h, bid, _ip(col), _dp(tim), _ip(sph), _ip(fld), _dp(dep)))
         return dict(collides=col, time=tim, sphere=sph, field=fld, depth=dep)
+
+    def batch_clearance(self, bid, runs=None, max_samples=65536):
+        """How far every run stays from the fields of its scene and from itself, on the device (orc_batch_clearance): the
+        walk of batch_collision_verdict(on_device=True) without its stop at a contact.  runs: None (every run), "candidates"
+        (candidates(costs, status) of the last iterate call) or a boolean / 0-1 array [n_runs].  Returns a dict of arrays:
+        clearance [n_runs][2] (the smallest value - radius over spheres and fields; the smallest distance - radius sum over
+        the self-collision pairs), time [n_runs][2], sphere [n_runs][2], other [n_runs][2] (the field; the other sphere),
+        n_samples [n_runs].  A minimum over nothing is +inf with time -1 and sphere, other -1.  A run that is not examined
+        reports NaN / -1 and n_samples -1; one that clearance_too_long(traj, vmax, col0, max_samples) marks the same with
+        n_samples -2."""
+        n_runs = self.batch_dims(bid)[0]
+        if runs is None:
+            which, ex = 2, None
+        elif isinstance(runs, str):
+            if runs != "candidates":
+                raise ValueError('runs is None, an array [n_runs] or "candidates"')
+            which, ex = 1, None
+        else:
+            ex = np.ascontiguousarray(np.asarray(runs).reshape(-1) != 0, dtype=np.uint8)
+            if ex.size != n_runs:
+                raise ValueError("runs has %d entries for %d runs" % (ex.size, n_runs))
+            which = 0
+        clr = np.zeros((n_runs, 2)); tim = np.zeros((n_runs, 2))
+        sph = np.zeros((n_runs, 2), dtype=np.int32); oth = np.zeros((n_runs, 2), dtype=np.int32)
+        cnt = np.zeros(n_runs, dtype=np.int32)
+        self._check(self._lib.orc_batch_clearance(self._h, bid, which, None if ex is None else ex.ctypes.data_as(_capi.c_ubyte_p),
+                                                  int(max_samples), _dp(clr), _dp(tim), _ip(sph), _ip(oth), _ip(cnt)))
+        return dict(clearance=clr, time=tim, sphere=sph, other=oth, n_samples=cnt)
+
+    def batch_select_clear(self, bid, groups=None, n_groups=None, margin=0.0, by="total", max_samples=65536):
+        """The best run of every group among the candidates that keep `margin` metres of clearance, on the device
+        (orc_batch_select_clear; the rule is select_clear's).  by: "total", "obs", "smooth" (the cost that is minimised) or
+        "clearance" (the largest clearance wins; the cost returned is -clearance).  groups and n_groups as in
+        batch_select_best.  Returns (best_run int32 [n_groups], -1 for a group without an eligible run; best_cost [n_groups],
+        +inf there; best_clearance [n_groups], NaN there; n_eligible int32 [n_groups]; n_samples int32 [n_runs], as
+        batch_clearance(runs="candidates") reports it)."""
+        if by not in ("total", "obs", "smooth", "clearance"):
+            raise ValueError('by is "total", "obs", "smooth" or "clearance"')
+        n_runs = self.batch_dims(bid)[0]
+        gp = None
+        if groups is not None:
+            gp = np.ascontiguousarray(groups, dtype=np.int32).reshape(-1)
+            if gp.size != n_runs:
+                raise ValueError("groups has %d entries for %d runs" % (gp.size, n_runs))
+            if n_groups is None:
+                n_groups = int(gp.max()) + 1
+        elif n_groups is None:
+            n_groups = 1
+        n_groups = int(n_groups)
+        size = max(n_groups, 1)
+        best = np.zeros(size, dtype=np.int32); cost = np.zeros(size); clr = np.zeros(size); cnt = np.zeros(size, dtype=np.int32)
+        ns = np.zeros(n_runs, dtype=np.int32)
+        self._check(self._lib.orc_batch_select_clear(self._h, bid, ("total", "obs", "smooth", "clearance").index(by), n_groups,
+                                                     None if gp is None else _ip(gp), float(margin), int(max_samples),
+                                                     _ip(best), _dp(cost), _dp(clr), _ip(cnt), _ip(ns)))
+        return best[:n_groups], cost[:n_groups], clr[:n_groups], cnt[:n_groups], ns
 
     def batch_plan(self, bid):
         """what the planner chose for this batch (orc_batch_get_state "plan")"""
