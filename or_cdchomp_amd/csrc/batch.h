@@ -1,5 +1,5 @@
 // batch.h -- a batch of CHOMP runs as the host layer holds it: the shard of its runs on one device, the batch over the shards, and
-// the small structs their calls take (batch.cpp, verdict.cpp).
+// the small structs their calls take (batch.cpp, verdict.cpp, clearance.cpp, multistart.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -12,6 +12,7 @@
 #include "devbuf.h"      // DeviceGuard, hip_check, DevBuf, dev_alloc, upload
 #include "hmc.h"         // HmcPlan, PlanStore, HmcPlanner: the momentum-resampling plan of HMC runs
 #include "verdict.h"     // VerdictInputs, the sample clock, the free functions of the collision verdict
+#include "multistart.h"  // SelectCriterion, SelectResult, PerturbPlan, RespawnPlan: what the multi-start calls pass each other
 
 template <typename real> struct DevVerdictWalk;      // verdict_device.h
 
@@ -63,19 +64,14 @@ public:
    void get_trace(double * out);
    void set_noise(const double * noise, int n_blocks) { hmc_->set_noise(noise, n_blocks); }      // caller-supplied blocks (host streams only)
    void set_traj(const double * traj);          // [n_runs][n_points][n] host -> device (warm start)
-   // multi-start (multistart_kernels.hip).  m n of a run perturb stages in LDS: 8 m n + 2496 (the mt19937 state) <= 160 KB - 256
-   static constexpr size_t ORC_PERTURB_MAX_MN = 20136;
+   // multi-start (multistart.cpp, multistart_kernels.hip)
    // perturb: T[moving] += scale * A^-1 xi(seed of the run), clamped to the limits;
    // gen = the generators of A^-1, U [rank][m] then V [rank][m] (Batch::perturb builds them once for all shards)
    void perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank);
-   // per group the lowest cost key among this shard's eligible runs, the lowest LOCAL run that has it, the eligible runs;
-   // group [n_runs] is this shard's slice; collision_free: a run whose key of the last collision_verdict_planned (kept on
-   // the device) names a contact is not eligible
-   // column: which of costs[run][0..2] is minimised (eligibility always asks for a finite TOTAL cost)
-   void select_best(int n_groups, const int * group, bool collision_free, int column, unsigned long long * key_out, int * best_out, int * count_out);
-   // respawn (orc_batch_respawn): the largest group the ranking kernel takes (14 bytes of LDS per member: 56 KB)
-   static constexpr int ORC_RESPAWN_MAX_GROUP = 4096;
-   // This shard's groups as a CSR over its LOCAL runs (group_offs [n_groups + 1], members ascending per group, every run in one
+   // the winners among this shard's runs (LOCAL runs); group [n_runs] is this shard's slice.  collision_free reads the keys the
+   // last collision_verdict_planned kept on the device, by_margin the minima the last `clearance` kept there
+   SelectResult select(int n_groups, const int * group, const SelectCriterion & c);
+   // respawn (orc_batch_respawn).  This shard's groups as a CSR over its LOCAL runs (group_offs [n_groups + 1], members ascending per group, every run in one
    // group): ranks every group, makes every run that does not survive a copy of its source or the straight line, perturbs those
    // runs when scale > 0 (seeds, gen, rank: as in perturb).  mode 1, 2: the keys of the collision_verdict_planned made just
    // before.  One synchronisation, at the end; source_out [n_runs] (local runs, -1: the line) and n_survivors_out [n_groups]
@@ -100,14 +96,10 @@ public:
    bool collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
                                   int * n_samples_out, const VerdictScope & scope = VerdictScope());
    // (clearance.cpp) the clearance of this shard's runs (clearance_kernels.hip; scope.which -1, 0, 1 as for the verdict, the other
-   // fields of the scope are not read): the two minima of every run stay on the device for select_clear, and what of clear /
+   // fields of the scope are not read): the two minima of every run stay on the device for `select`, and what of clear /
    // time [n_runs][2], key [n_runs][2] and n_samples [n_runs] is not NULL comes back
    void clearance(const VerdictInputs & in, const VerdictScope & scope, int max_samples, double * clear_out, double * time_out,
                   unsigned long long * key_out, int * n_samples_out);
-   // per group among this shard's runs that are candidates, were walked by the last `clearance` and clear `margin`: the lowest
-   // key (column 0..2 a cost, 3 minus the clearance), the lowest LOCAL run that has it, the winner's clearance, the eligible runs
-   void select_clear(int n_groups, const int * group, int column, double margin, unsigned long long * key_out, int * best_out,
-                     double * best_clear_out, int * count_out);
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
@@ -189,28 +181,20 @@ public:
    void get_trace(double * out);
    void set_noise(const double * noise, int n_blocks);
    void set_traj(const double * traj);
-   // multi-start: orc_batch_perturb / _select_best / _gettraj_runs (include/orcdchomp_amd.h has the contract)
+   // multi-start (multistart.cpp): orc_batch_perturb / _select_best / _select_clear / _respawn / _gettraj_runs (include/orcdchomp_amd.h
+   // has the contract)
    void perturb(double sigma, const unsigned int * seeds);
-   // what a perturbation of this batch needs: the generators of A^-1 (U [D][m], then V [D][m]) and sigma c; throws for a bad
-   // sigma and for the batches orc_batch_perturb rejects, whatever sigma is; sigma == 0: scale 0 and no generators
-   struct PerturbPlan { std::vector<double> gen; int D = 0; double scale = 0.0; };
+   // throws for a bad sigma and for the batches orc_batch_perturb rejects, whatever sigma is
    PerturbPlan perturb_plan(double sigma) const;
    // respawn (orc_batch_respawn): respawn_plan checks every argument and builds the shards' group tables without any device
    // work (throws); respawn then runs on every shard that has a group.  The verdict, for mode 1 and 2, is taken between the two
-   struct RespawnPlan
-   {
-      int column = 0, mode = 0, keep = 1, n_groups = 0;
-      PerturbPlan perturb;
-      struct Shard { std::vector<int> groups, group_offs, members; };      // the shard's groups (the caller's numbers), their CSR over local runs
-      std::vector<Shard> shards;
-   };
    RespawnPlan respawn_plan(int cost_column, int n_groups, const int * group_of_run, int collision_mode, int keep, double sigma,
       const unsigned int * seeds) const;
    void respawn(const RespawnPlan & plan, const unsigned int * seeds, int * source_of_run_out, int * n_survivors_out);
    std::vector<int> select_groups(int n_groups, const int * group_of_run) const;   // the validated group of every run (NULL: contiguous equal blocks); throws
-   // collision_free: the runs' keys of the collision_verdict_planned made just before (they never left the device)
-   // column 0 total, 1 obs, 2 smooth: the cost that is minimised and reported (validate with select_column first)
-   void select_best(int n_groups, const std::vector<int> & group, bool collision_free, int column, int * best_run_out, double * best_cost_out, int * n_eligible_out);
+   // every shard's winners merged (merge_winners), with the batch's runs; the verdict or the clearance the criterion reads was
+   // made just before and never left the device (validate a column 0..2 with select_column first)
+   SelectResult select(int n_groups, const std::vector<int> & group, const SelectCriterion & c);
    static void select_column(int column);   // throws unless 0, 1 or 2
    // per-run parameters: each array [n_runs] or NULL (the value of `params`); all NULL switches the table off.  Throws and changes
    // nothing on a NaN or infinite entry or a lambda or epsilon <= 0
@@ -226,12 +210,10 @@ public:
                                   int * n_samples_out, const VerdictScope & scope = VerdictScope());
    // (clearance.cpp) orc_batch_clearance / orc_batch_select_clear.  clearance_check throws for what those calls reject of which,
    // examine and max_samples, before any device work; `clearance`: every shard walks its slice, outputs as BatchShard's, over
-   // the batch's runs; select_clear: the shards' winners merged by the same rule (lower key, then lower run)
+   // the batch's runs
    void clearance_check(int which, const unsigned char * examine, int max_samples) const;
    void clearance(const VerdictInputs & in, int which, const unsigned char * examine, int max_samples, double * clear_out, double * time_out,
                   unsigned long long * key_out, int * n_samples_out);
-   void select_clear(int n_groups, const std::vector<int> & group, int column, double margin, int * best_run_out, double * best_cost_out,
-                     double * best_clear_out, int * n_eligible_out);
    // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
    // kept until it is set again
    int verdict_scope = 0;

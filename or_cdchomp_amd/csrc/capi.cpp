@@ -648,24 +648,14 @@ int orc_batch_perturb(orc_module * mod, int id, double sigma, const unsigned int
 int orc_batch_select_best(orc_module * mod, int id, int n_groups, const int * group_of_run, int require_collision_free,
    int * best_run_out, double * best_cost_out, int * n_eligible_out)
 {
-   return guarded(mod, [&] {
-      orc::Batch & b = mod->impl->batch(id);
-      const std::vector<int> group = b.select_groups(n_groups, group_of_run);      // (the arguments first: the verdict below walks every trajectory)
-      // the verdict's keys stay on the device, where the selection reads them
-      if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b.selection_scope());
-      b.select_best(n_groups, group, require_collision_free != 0, 0, best_run_out, best_cost_out, n_eligible_out);
-   });
+   return orc_batch_select_best_by(mod, id, 0, n_groups, group_of_run, require_collision_free, best_run_out, best_cost_out, n_eligible_out);
 }
 
 int orc_batch_select_best_by(orc_module * mod, int id, int cost_column, int n_groups, const int * group_of_run, int require_collision_free,
    int * best_run_out, double * best_cost_out, int * n_eligible_out)
 {
    return guarded(mod, [&] {
-      orc::Batch & b = mod->impl->batch(id);
-      orc::Batch::select_column(cost_column);      // (the arguments first, as in orc_batch_select_best)
-      const std::vector<int> group = b.select_groups(n_groups, group_of_run);
-      if (require_collision_free) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b.selection_scope());
-      b.select_best(n_groups, group, require_collision_free != 0, cost_column, best_run_out, best_cost_out, n_eligible_out);
+      mod->impl->batch_select_best(id, cost_column, n_groups, group_of_run, require_collision_free != 0, best_run_out, best_cost_out, n_eligible_out);
    });
 }
 
@@ -692,12 +682,7 @@ int orc_batch_respawn(orc_module * mod, int id, int cost_column, int n_groups, c
    double sigma, const unsigned int * seeds, int * source_of_run_out, int * n_survivors_out)
 {
    return guarded(mod, [&] {
-      orc::Batch & b = mod->impl->batch(id);
-      // every argument first, on the host: a rejected call costs no kernel and changes no bit
-      const orc::Batch::RespawnPlan plan = b.respawn_plan(cost_column, n_groups, group_of_run, collision_mode, keep, sigma, seeds);
-      // the verdict of the current trajectories; its keys stay on the device, where the ranking reads them
-      if (collision_mode != 0) mod->impl->batch_collision_verdict_device(id, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, b.selection_scope());
-      b.respawn(plan, seeds, source_of_run_out, n_survivors_out);
+      mod->impl->batch_respawn(id, cost_column, n_groups, group_of_run, collision_mode, keep, sigma, seeds, source_of_run_out, n_survivors_out);
    });
 }
 

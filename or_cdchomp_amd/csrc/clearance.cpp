@@ -1,11 +1,8 @@
-// clearance.cpp -- host side of the clearance of a batch's runs and of the selection by margin (orc_batch_clearance,
-// orc_batch_select_clear): the checks of their arguments, the launches of clearance_kernels.hip and of the selection kernels
-// of multistart_kernels.hip on every shard, and the merge of the shards' winners.  The tables the walk reads are the collision
-// verdict's (verdict.cpp: verdict_inputs, BatchShard::verdict_walk_args).
+// clearance.cpp -- host side of the clearance of a batch's runs (orc_batch_clearance; the selection by margin that reads it is
+// multistart.cpp's): the checks of its arguments and the launches of clearance_kernels.hip on every shard.  The tables the walk
+// reads are the collision verdict's (verdict.cpp: verdict_inputs, BatchShard::verdict_walk_args).
 #include "module.h"
 #include "clearance_device.h"
-#include <cmath>
-#include <cstring>
 #include <stdexcept>
 
 namespace orc {
@@ -39,20 +36,6 @@ void Module::batch_clearance(int id, int which, const unsigned char * examine, i
    std::vector<unsigned long long> key((sphere || other) ? (size_t) b.n_runs * 2 : 0);
    b.clearance(in, which, examine, max_samples, clearance, time, key.empty() ? nullptr : key.data(), n_samples);
    clearance_decode(key, sphere, other);
-}
-
-void Module::batch_select_clear(int id, int cost_column, int n_groups, const int * group_of_run, double margin, int max_samples,
-   int * best_run, double * best_cost, double * best_clearance, int * n_eligible, int * n_samples)
-{
-   Batch & b = batch(id);
-   // every argument first, on the host: a rejected call costs no kernel
-   if (cost_column < 0 || cost_column > 3) throw std::runtime_error("select_clear: cost_column must be 0 (total), 1 (obs), 2 (smooth) or 3 (clearance)!");
-   if (std::isnan(margin)) throw std::runtime_error("select_clear: margin is NaN!");
-   const std::vector<int> group = b.select_groups(n_groups, group_of_run);
-   b.clearance_check(1, nullptr, max_samples);
-   const VerdictInputs in = verdict_inputs(env.robot(b.robot_name), b, true);
-   b.clearance(in, 1, nullptr, max_samples, nullptr, nullptr, nullptr, n_samples);      // (the minima stay on the device)
-   b.select_clear(n_groups, group, cost_column, margin, best_run, best_cost, best_clearance, n_eligible);
 }
 
 void Batch::clearance(const VerdictInputs & in, int which, const unsigned char * examine, int max_samples, double * clear_out, double * time_out,
@@ -113,67 +96,6 @@ void BatchShard::clearance(const VerdictInputs & in, const VerdictScope & scope,
    DeviceGuard guard(device);
    if (params.precision == 64) clearance_typed<double>(in, scope, max_samples, clear_out, time_out, key_out, n_samples_out);
    else clearance_typed<float>(in, scope, max_samples, clear_out, time_out, key_out, n_samples_out);
-}
-
-void BatchShard::select_clear(int n_groups, const int * group, int column, double margin, unsigned long long * key_out, int * best_out,
-   double * best_clear_out, int * count_out)
-{
-   DeviceGuard guard(device);
-   hipStream_t st = stream_;
-   if (!d_clear_) throw std::runtime_error("select_clear: no clearance on the device!");
-   DevBuf group_buf, key_buf, best_buf, count_buf, clear_buf;
-   group_buf.reset(dev_alloc<int>(n_runs)); key_buf.reset(dev_alloc<unsigned long long>(n_groups));
-   best_buf.reset(dev_alloc<int>(n_groups)); count_buf.reset(dev_alloc<int>(n_groups)); clear_buf.reset(dev_alloc<double>(n_groups));
-   int * d_group = group_buf.as<int>(), * d_best = best_buf.as<int>(), * d_count = count_buf.as<int>();
-   unsigned long long * d_key = key_buf.as<unsigned long long>();
-   hip_check(hipMemcpyAsync(d_group, group, n_runs*sizeof(int), hipMemcpyHostToDevice, st), "select groups");
-   hip_check(hipMemsetAsync(d_key, 0xff, n_groups*sizeof(unsigned long long), st), "select keys");
-   hip_check(hipMemsetAsync(d_best, 0x7f, n_groups*sizeof(int), st), "select runs");      // (0x7f7f7f7f: above every run index)
-   hip_check(hipMemsetAsync(d_count, 0, n_groups*sizeof(int), st), "select counts");
-   hip_check(orc_launch_select_clear(d_costs_.as<double>(), d_status_.as<int>(), d_clear_.as<double>(), d_clear_ns_.as<int>(), d_group, n_runs, n_groups,
-      column, margin, d_key, d_count, d_best, clear_buf.as<double>(), st), "select_clear kernels launch");
-   hip_check(hipMemcpyAsync(key_out, d_key, n_groups*sizeof(unsigned long long), hipMemcpyDeviceToHost, st), "select keys");
-   hip_check(hipMemcpyAsync(best_out, d_best, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select runs");
-   hip_check(hipMemcpyAsync(count_out, d_count, n_groups*sizeof(int), hipMemcpyDeviceToHost, st), "select counts");
-   hip_check(hipMemcpyAsync(best_clear_out, clear_buf.as<void>(), n_groups*sizeof(double), hipMemcpyDeviceToHost, st), "select clearance");
-   hip_check(hipStreamSynchronize(st), "select sync");
-}
-
-void Batch::select_clear(int n_groups, const std::vector<int> & group, int column, double margin, int * best_run_out, double * best_cost_out,
-   double * best_clear_out, int * n_eligible_out)
-{
-   const size_t S = shards.size();
-   std::vector<unsigned long long> key(S * n_groups);
-   std::vector<int> best(S * n_groups), count(S * n_groups);
-   std::vector<double> clear(S * n_groups);
-   for_shards([&](size_t k) {
-      shards[k]->select_clear(n_groups, group.data() + offs[k], column, margin, key.data() + k * n_groups, best.data() + k * n_groups,
-                              clear.data() + k * n_groups, count.data() + k * n_groups);
-   }, true);
-   // the merge of n_shards x n_groups candidates: the lower key, then the lower run (the shards hold ascending runs)
-   for (int g=0; g<n_groups; g++)
-   {
-      unsigned long long bk = ~0ull; int br = -1, cnt = 0; double bc = std::nan("");
-      for (size_t k=0; k<S; k++)
-      {
-         const size_t q = k * n_groups + g;
-         cnt += count[q];
-         if (count[q] > 0 && key[q] < bk) { bk = key[q]; br = offs[k] + best[q]; bc = clear[q]; }
-      }
-      if (best_run_out) best_run_out[g] = br;
-      if (n_eligible_out) n_eligible_out[g] = cnt;
-      if (best_clear_out) best_clear_out[g] = bc;
-      if (best_cost_out)
-      {
-         double cost = HUGE_VAL;
-         if (br >= 0)
-         {
-            const unsigned long long bits = (bk >> 63) ? (bk & 0x7fffffffffffffffull) : ~bk;      // (cost_key of multistart_kernels.hip, undone)
-            std::memcpy(&cost, &bits, sizeof(double));
-         }
-         best_cost_out[g] = cost;
-      }
-   }
 }
 
 } // namespace orc

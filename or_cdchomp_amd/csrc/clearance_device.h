@@ -1,5 +1,5 @@
-// clearance_device.h -- the clearance of a batch's runs (clearance_kernels.hip) and the selection by margin that reads it
-// (multistart_kernels.hip), as clearance.cpp launches them.
+// clearance_device.h -- the clearance of a batch's runs (clearance_kernels.hip), as clearance.cpp launches it.  The selection by
+// margin that reads it is orc_launch_select's (launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "verdict_device.h"
@@ -32,10 +32,3 @@ struct DevClearance : DevVerdictWalk<real>
 hipError_t orc_launch_clearance(const DevClearance<double> & v, size_t lds, hipStream_t stream, int tree);
 hipError_t orc_launch_clearance(const DevClearance<float> & v, size_t lds, hipStream_t stream, int tree);
 size_t orc_clearance_lds_bytes(int n_points, int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);
-
-// The best run per group among the candidates (run_candidate.h) that were walked (n_samples >= 0) and clear `margin`
-// (fmin of a run's two minima >= margin).  column 0..2: the lowest costs[run][column]; 3: the largest clearance (the key is
-// -clearance).  key [n_groups] (all bits set), count [n_groups] (0) and best [n_groups] (above every run index) are the
-// caller's to initialise; best_clear [n_groups] is written in full: the winner's fmin, NaN without a winner.
-hipError_t orc_launch_select_clear(const double * costs, const int * status, const double * clear, const int * n_samples, const int * group,
-   int n_runs, int n_groups, int column, double margin, unsigned long long * key, int * count, int * best, double * best_clear, hipStream_t stream);

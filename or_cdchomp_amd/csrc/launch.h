@@ -25,8 +25,18 @@ hipError_t orc_launch_respawn_rank(const double * costs, const int * status, con
    int n_groups, const int * group_offs, const int * members, int max_group, int * source_of_run, int * n_survivors, hipStream_t stream);
 hipError_t orc_launch_respawn_copy(void * traj, void * AG, int precision, int * leapfrog_first, const int * source_of_run,
    int n_runs, int n_points, int n, int m, hipStream_t stream);
-hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
-   unsigned long long * key, int * count, int * best, hipStream_t stream);
+// The rule of a selection, in the kernarg block of its kernels: which runs are eligible and what is minimised among them.
+struct SelectRule
+{
+   const double * costs; const int * status;   // [n_runs][3], [n_runs]: what the last iterate call left (a candidate: run_candidate.h)
+   const unsigned long long * verdict_key;     // [n_runs] keys of the collision verdict: a run with a contact is not eligible; NULL: not asked for
+   const double * clear; const int * n_samples;   // [n_runs][2], [n_runs] of the last clearance: a run that was not walked or whose
+   double margin;                              // fmin of the two is under `margin` is not eligible; both NULL: no margin
+   int column;                                 // the key: costs[run][column] for 0..2; 3 (with clear): minus the clearance, the largest first
+};
+// the best run per group: the lowest key, the eligible runs, the lowest run that has the key, (a rule with clear) its clearance
+hipError_t orc_launch_select(const SelectRule & rule, const int * group, int n_runs, int n_groups, unsigned long long * key, int * count, int * best,
+   double * best_clear, hipStream_t stream);
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream);
 // sdf_kernels.hip: occupancy -> signed distance field; the whole field of a body from the world's boxes and triangles (host arrays in, host array out)
 hipError_t orc_sdf_from_occupancy_device(const double * occ, double * sdf_out, const int sizes[3], const double lengths[3],

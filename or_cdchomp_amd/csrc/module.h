@@ -46,7 +46,7 @@ public:
    // collides (0/1), time of the first contact on the retimed trajectory, XML sphere, field, depth
    void batch_collision_verdict(int id, int * collides, double * time, int * sphere, int * field, double * depth, bool self_check = true);
    // the same verdict planned on the device (no trajectory is read back); every output may be NULL: the keys stay on the
-   // device for Batch::select_best.  n_samples: the samples of every run's retimed trajectory
+   // device for Batch::select and BatchShard::respawn (multistart.cpp).  n_samples: the samples of every run's retimed trajectory
    void batch_collision_verdict_device(int id, int * collides, double * time, int * sphere, int * field, double * depth, int * n_samples,
       const VerdictScope & scope = VerdictScope());
    // ... of a subset of the runs (orc_batch_collision_verdict_subset): which 0 the runs with a nonzero byte in examine [n_runs],
@@ -58,6 +58,12 @@ public:
    // samples the verdict looks at, with time, XML sphere and field / other sphere; which 0 examine, 1 the candidates, 2 every run
    void batch_clearance(int id, int which, const unsigned char * examine, int max_samples, double * clearance, double * time, int * sphere,
       int * other, int * n_samples);
+   // (multistart.cpp) orc_batch_select_best[_by], _respawn, _select_clear: each checks every argument on the host, then takes the
+   // verdict with Batch::selection_scope() (collision_free; collision_mode 1, 2) or the clearance, then selects or respawns on the device
+   void batch_select_best(int id, int cost_column, int n_groups, const int * group_of_run, bool collision_free, int * best_run, double * best_cost,
+      int * n_eligible);
+   void batch_respawn(int id, int cost_column, int n_groups, const int * group_of_run, int collision_mode, int keep, double sigma,
+      const unsigned int * seeds, int * source_of_run, int * n_survivors);
    // orc_batch_select_clear: the clearance of the candidates, then per group the best run among those that clear `margin`
    void batch_select_clear(int id, int cost_column, int n_groups, const int * group_of_run, double margin, int max_samples,
       int * best_run, double * best_cost, double * best_clearance, int * n_eligible, int * n_samples);

@@ -17,7 +17,7 @@
 #include "launch.h"
 #include "mt_wave.h"
 #include "run_candidate.h"
-#include "clearance_device.h"
+#include "cost_key.h"
 
 namespace {
 
@@ -100,71 +100,41 @@ void perturb_kernel(real * traj, int n_points, int n, int m, const unsigned int 
    }
 }
 
-// ---- the best run per group -------------------------------------------------------------------------------------
-// doubles as unsigned keys of the same order (-0 made +0 first: equal costs must tie)
-__device__ __forceinline__ unsigned long long cost_key(double c)
+// ---- the best run per group (orc_batch_select_best[_by], orc_batch_select_clear) ----------------------------------------
+// Is run r eligible under the rule (launch.h: SelectRule), and with what key?  A candidate (run_candidate.h); with verdict_key
+// (verdict_kernels.hip) one without a contact; with clear (what clearance_kernel left of the candidates) one that was walked
+// (not too long) and whose smaller minimum is at least `margin`.  The key is that of the column's cost (0 total, 1 obs,
+// 2 smooth) or, column 3, of minus the clearance: the largest first.  Eligibility does not depend on the column.
+__device__ __forceinline__ bool select_key(const SelectRule & s, int r, unsigned long long & key)
 {
-   const unsigned long long b = (unsigned long long) __double_as_longlong(c + 0.0);
-   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-// verdict_key: the runs' keys of the collision verdict (verdict_kernels.hip), or NULL when the verdict is not asked for
-__device__ __forceinline__ bool run_eligible(const double * costs, const int * status, const unsigned long long * verdict_key, int r)
-{
-   return orc_run_candidate(status[r], costs[(size_t) r*3]) && !(verdict_key && verdict_key[r] != ORC_VERDICT_NONE);
-}
-
-// column: which of a run's costs (0 total, 1 obs, 2 smooth) is the key that is minimised; eligibility does not depend on it
-// pass 1: the lowest cost key of every group's eligible runs and their number
-__global__ void select_cost_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
-   unsigned long long * key, int * count)
-{
-   const int r = blockIdx.x * blockDim.x + threadIdx.x;
-   if (r >= n_runs || !run_eligible(costs, status, verdict_key, r)) return;
-   atomicMin(&key[group[r]], cost_key(costs[(size_t) r*3 + column]));
-   atomicAdd(&count[group[r]], 1);
-}
-// pass 2: the lowest index among the runs that have it
-__global__ void select_run_kernel(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
-   const unsigned long long * key, int * best)
-{
-   const int r = blockIdx.x * blockDim.x + threadIdx.x;
-   if (r >= n_runs || !run_eligible(costs, status, verdict_key, r)) return;
-   if (cost_key(costs[(size_t) r*3 + column]) == key[group[r]]) atomicMin(&best[group[r]], r);
-}
-
-// ---- the best run per group by margin (orc_batch_select_clear) --------------------------------------------------------
-// clear [n_runs][2] and n_samples [n_runs] are what clearance_kernel (clearance_kernels.hip) left of the candidates.  A run
-// is eligible when it is a candidate, was walked (not too long) and its smaller minimum is at least `margin`.
-__device__ __forceinline__ bool run_clear(const double * costs, const int * status, const double * clear, const int * n_samples, double margin, int r, double & c)
-{
-   c = fmin(clear[(size_t) r*2], clear[(size_t) r*2 + 1]);
-   return orc_run_candidate(status[r], costs[(size_t) r*3]) && n_samples[r] >= 0 && c >= margin;
-}
-// column 0..2: the cost; 3: the clearance, the largest first
-__device__ __forceinline__ unsigned long long clear_key(const double * costs, int column, int r, double c)
-{
-   return cost_key(column < 3 ? costs[(size_t) r*3 + column] : -c);
+   if (!orc_run_candidate(s.status[r], s.costs[(size_t) r*3]) || (s.verdict_key && s.verdict_key[r] != ORC_VERDICT_NONE)) return false;
+   double c = 0.0;
+   if (s.clear)
+   {
+      c = fmin(s.clear[(size_t) r*2], s.clear[(size_t) r*2 + 1]);
+      if (!(s.n_samples[r] >= 0 && c >= s.margin)) return false;
+   }
+   key = cost_key(s.column < 3 ? s.costs[(size_t) r*3 + s.column] : -c);
+   return true;
 }
 // pass 1: the lowest key of every group's eligible runs and their number
-__global__ void select_clear_cost_kernel(const double * costs, const int * status, const double * clear, const int * n_samples, const int * group,
-   int n_runs, int column, double margin, unsigned long long * key, int * count)
+__global__ void select_cost_kernel(SelectRule rule, const int * group, int n_runs, unsigned long long * key, int * count)
 {
    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-   double c;
-   if (r >= n_runs || !run_clear(costs, status, clear, n_samples, margin, r, c)) return;
-   atomicMin(&key[group[r]], clear_key(costs, column, r, c));
+   unsigned long long k;
+   if (r >= n_runs || !select_key(rule, r, k)) return;
+   atomicMin(&key[group[r]], k);
    atomicAdd(&count[group[r]], 1);
 }
 // pass 2: the lowest index among the runs that have it
-__global__ void select_clear_run_kernel(const double * costs, const int * status, const double * clear, const int * n_samples, const int * group,
-   int n_runs, int column, double margin, const unsigned long long * key, int * best)
+__global__ void select_run_kernel(SelectRule rule, const int * group, int n_runs, const unsigned long long * key, int * best)
 {
    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-   double c;
-   if (r >= n_runs || !run_clear(costs, status, clear, n_samples, margin, r, c)) return;
-   if (clear_key(costs, column, r, c) == key[group[r]]) atomicMin(&best[group[r]], r);
+   unsigned long long k;
+   if (r >= n_runs || !select_key(rule, r, k)) return;
+   if (k == key[group[r]]) atomicMin(&best[group[r]], r);
 }
-// pass 3: the winners' clearance
+// pass 3 (a rule with clear): the winners' clearance
 __global__ void select_clear_margin_kernel(const double * clear, const int * count, const int * best, int n_groups, double * best_clear)
 {
    const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -310,7 +280,7 @@ hipError_t launch_perturb(real * traj, int n_runs, int n_points, int n, int m, c
 
 } // namespace
 
-// LDS of one run's workgroup: xi, then the generator's state (the caller refuses m n > BatchShard::ORC_PERTURB_MAX_MN, module.h)
+// LDS of one run's workgroup: xi, then the generator's state (the caller refuses m n > ORC_PERTURB_MAX_MN, multistart.h)
 size_t orc_perturb_lds_bytes(int m, int n)
 {
    return (size_t) m * n * sizeof(double) + 624 * sizeof(uint32_t);
@@ -324,7 +294,7 @@ hipError_t orc_launch_perturb(void * traj, int precision, int n_runs, int n_poin
    return launch_perturb<float>((float *) traj, n_runs, n_points, n, m, seeds, D, genU, genV, scale, lim_lo, lim_hi, lds, source_of_run, stream);
 }
 // LDS of a group's workgroup: 14 bytes per member of the largest group (the caller refuses groups over
-// BatchShard::ORC_RESPAWN_MAX_GROUP, module.h: 56 KB, inside what a kernel has without asking)
+// ORC_RESPAWN_MAX_GROUP, multistart.h: 56 KB, inside what a kernel has without asking)
 size_t orc_respawn_rank_lds_bytes(int max_group)
 {
    return ((size_t) max_group * 14 + 15) & ~(size_t) 15;
@@ -346,22 +316,15 @@ hipError_t orc_launch_respawn_copy(void * traj, void * AG, int precision, int * 
    else hipLaunchKernelGGL(respawn_copy_kernel<float>, dim3(n_runs), dim3(256), 0, stream, (float *) traj, (float *) AG, leapfrog_first, source_of_run, n_points, n, m);
    return hipGetLastError();
 }
-// key [n_groups] (all bits set), count [n_groups] (0) and best [n_groups] (INT_MAX) are the caller's to initialise
-hipError_t orc_launch_select_best(const double * costs, const int * status, const unsigned long long * verdict_key, const int * group, int n_runs, int column,
-   unsigned long long * key, int * count, int * best, hipStream_t stream)
+// key [n_groups] (all bits set), count [n_groups] (0) and best [n_groups] (above every run index) are the caller's to initialise;
+// best_clear [n_groups] is written in full when the rule has clear (the winner's fmin, NaN without a winner), else not at all
+hipError_t orc_launch_select(const SelectRule & rule, const int * group, int n_runs, int n_groups, unsigned long long * key, int * count, int * best,
+   double * best_clear, hipStream_t stream)
 {
    const dim3 grid((n_runs + 255) / 256), block(256);
-   hipLaunchKernelGGL(select_cost_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, column, key, count);
-   hipLaunchKernelGGL(select_run_kernel, grid, block, 0, stream, costs, status, verdict_key, group, n_runs, column, key, best);
-   return hipGetLastError();
-}
-hipError_t orc_launch_select_clear(const double * costs, const int * status, const double * clear, const int * n_samples, const int * group,
-   int n_runs, int n_groups, int column, double margin, unsigned long long * key, int * count, int * best, double * best_clear, hipStream_t stream)
-{
-   const dim3 grid((n_runs + 255) / 256), block(256);
-   hipLaunchKernelGGL(select_clear_cost_kernel, grid, block, 0, stream, costs, status, clear, n_samples, group, n_runs, column, margin, key, count);
-   hipLaunchKernelGGL(select_clear_run_kernel, grid, block, 0, stream, costs, status, clear, n_samples, group, n_runs, column, margin, key, best);
-   hipLaunchKernelGGL(select_clear_margin_kernel, dim3((n_groups + 255) / 256), block, 0, stream, clear, count, best, n_groups, best_clear);
+   hipLaunchKernelGGL(select_cost_kernel, grid, block, 0, stream, rule, group, n_runs, key, count);
+   hipLaunchKernelGGL(select_run_kernel, grid, block, 0, stream, rule, group, n_runs, key, best);
+   if (rule.clear) hipLaunchKernelGGL(select_clear_margin_kernel, dim3((n_groups + 255) / 256), block, 0, stream, rule.clear, count, best, n_groups, best_clear);
    return hipGetLastError();
 }
 hipError_t orc_launch_gather_rows(const void * traj, int precision, const int * rows, int n_sel, size_t row_len, double * out, hipStream_t stream)

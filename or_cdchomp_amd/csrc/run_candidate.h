@@ -1,5 +1,5 @@
 // run_candidate.h -- which runs of a batch an iterate call left worth asking about: the half of a run's eligibility that does
-// not need the collision verdict.  multistart_kernels.hip (run_eligible, respawn_rank_kernel) adds the verdict to it;
+// not need the collision verdict.  multistart_kernels.hip (select_key, respawn_rank_kernel) adds the verdict or the margin to it;
 // verdict_kernels.hip decides with it which runs the verdict is taken of at all (DevVerdictPlan::cand_status), so the two
 // cannot disagree about a run.  or_cdchomp_amd/module.py `candidates` is its specification.
 #pragma once

@@ -332,7 +332,7 @@ def select_clear(costs, status, clearance, n_samples, group_of_run, n_groups, ma
 
 
 def cost_key(c):
-    """A cost as the unsigned key of the same order that the device compares (cost_key of csrc/multistart_kernels.hip): the
+    """A cost as the unsigned key of the same order that the device compares (cost_key of csrc/cost_key.h): the
     bits of c + 0.0, so that -0 is +0, inverted for a negative number and with the sign bit set otherwise.  Python int."""
     b = int((np.float64(c) + np.float64(0.0)).view(np.uint64))
     return (~b) & 0xFFFFFFFFFFFFFFFF if b >> 63 else b | 0x8000000000000000

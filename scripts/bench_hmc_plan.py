@@ -5,7 +5,8 @@ Child processes alternated parent, this (the parent's library through ORC_LIB), 
   async       the same two batches in a process of this script: host time of one batch_iterate_async call of 100 iterations
               (plan and launch enqueued) and wall time of a step of both, medians of STEPS steps
   multistart  the 8 192-run block of scripts/bench_multistart.py: batch_perturb, and batch_select_best(collision_free=False) +
-              batch_gettraj_runs after 100 iterations, medians of five calls
+              batch_gettraj_runs after 100 iterations, batch_select_clear (whole, and less the batch_clearance of the candidates
+              timed beside it) and batch_respawn (mode 0, keep 16 of 128), medians of five calls (NOTES/multistart-host.md)
   headline    (--headline N) bench.py's headline configuration, parent / this alternated N times
 Writes profiles/hmc_plan_<build>.json (adding to the legs an earlier call left there) and prints one line.
    python scripts/bench_hmc_plan.py --parent-lib FILE [--reps 5] [--headline 2] [--legs config4,async,multistart]"""
@@ -76,8 +77,29 @@ def child_multistart():
         rows = mod.batch_gettraj_runs(bid, best)
         if rnd:
             select.append(time.perf_counter() - t0)
+    # the selection by margin: its time is the clearance walk of the candidates, so that walk alone is timed beside it
+    mod.batch_set_verdict_scope(bid, "candidates")
+    clear, walk = [], []
+    for rnd in range(6):
+        t0 = time.perf_counter()
+        sel = mod.batch_select_clear(bid, n_groups=ms.N_PROBLEMS, margin=0.0)
+        t1 = time.perf_counter()
+        mod.batch_clearance(bid, runs="candidates")
+        if rnd:
+            clear.append(t1 - t0); walk.append(time.perf_counter() - t1)
+    # the respawn last (it changes the runs): mode 0, no verdict in its time; iterate(0) makes the costs valid again
+    respawn = []
+    for rnd in range(6):
+        t0 = time.perf_counter()
+        source, kept = mod.batch_respawn(bid, 16, ms.SIGMA, seeds, n_groups=ms.N_PROBLEMS, collision="ignore")
+        if rnd:
+            respawn.append(time.perf_counter() - t0)
+        mod.batch_iterate(bid, 0)
     mod.close()
-    return dict(perturb_s=med(perturb), select_gettraj_s=med(select), winners=[int(x) for x in best], rows_sum=float(np.nansum(rows)))
+    return dict(perturb_s=med(perturb), select_gettraj_s=med(select), select_clear_s=med(clear), clearance_s=med(walk),
+                select_clear_less_clearance_s=med(clear) - med(walk), respawn_s=med(respawn),
+                winners=[int(x) for x in best] + [int(x) for x in sel[0]] + [int(x) for x in source],
+                rows_sum=float(np.nansum(rows)) + float(np.nansum(sel[2])))
 
 
 def run_child(leg, parent_lib, bench_args=()):

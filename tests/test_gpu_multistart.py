@@ -272,6 +272,7 @@ K = 8
 N_PROBLEMS = 30          # config 2's own goals, K perturbed starts each; then a group that ends in the table and a group of identical runs
 N_GROUPS = N_PROBLEMS + 2
 N_RUNS = N_GROUPS * K
+TIE_GOAL = 14 * K        # the one problem of the workload whose goal the straight line reaches without a contact
 
 
 def multistart_workload():
@@ -392,6 +393,31 @@ def test_shards_agree(wam, wam2):
     for a, b in zip(*res):
         assert np.array_equal(a[0], b[0]) and same(a[1], b[1]) and np.array_equal(a[2], b[2])
     assert (res[0][1][0] >= 0).all()
+
+
+def test_an_exact_tie_across_the_shards(wam2):
+    """four identical runs, two on each shard: every key the shards report is the same, so the winner is the merge's own
+    rule (the lower key, then the lower run), for select_best and select_clear, one group and two interleaved ones"""
+    mod, model = wam2
+    goals, _ = multistart_workload()
+    bid = mod.batch_create(model.name, np.tile(goals[TIE_GOAL], (4, 1)), **KW)
+    costs, status = mod.batch_iterate(bid, 0)
+    assert same(costs, np.tile(costs[0], (4, 1))) and (status == 0).all(), (costs, status)
+    assert not mod.batch_collision_verdict(bid)["collides"].any()
+    clear = mod.batch_clearance(bid)["clearance"]
+    assert same(clear, np.tile(clear[0], (4, 1)))
+    interleaved = np.array([1, 0, 1, 0], dtype=np.int32)
+    for grp, runs, n_eligible in ((None, [0], [4]), (interleaved, [1, 0], [2, 2])):
+        for column, by in enumerate(("total", "obs", "smooth")):
+            for cf in (False, True):
+                got = mod.batch_select_best(bid, groups=grp, n_groups=len(runs), collision_free=cf, by=by)
+                assert np.array_equal(got[0], runs) and np.array_equal(got[2], n_eligible), (by, cf, got)
+                assert same(got[1], np.full(len(runs), costs[0, column])), (by, cf, got)
+        for by in ("total", "obs", "smooth", "clearance"):
+            got = mod.batch_select_clear(bid, groups=grp, n_groups=len(runs), margin=-INF, by=by)
+            assert np.array_equal(got[0], runs) and np.array_equal(got[3], n_eligible), (by, got)
+            assert same(got[2], np.full(len(runs), clear[0].min())), (by, got)
+    mod.batch_destroy(bid)
 
 
 # ---- 7. errors -------------------------------------------------------------------------------------------------------
