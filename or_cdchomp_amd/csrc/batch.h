@@ -15,6 +15,7 @@
 #include "multistart.h"  // SelectCriterion, SelectResult, PerturbPlan, RespawnPlan: what the multi-start calls pass each other
 
 template <typename real> struct DevVerdictWalk;      // verdict_device.h
+template <typename real> struct DevVerdictPlanned;
 
 namespace orc {
 
@@ -122,9 +123,12 @@ private:
    // generators, limits and seeds of a perturbation go up and perturb_kernel is launched (source_of_run: a respawn's plan, or NULL); no wait
    struct PerturbUpload { DevBuf gen, seeds; };
    void launch_perturb(double scale, const unsigned int * seeds, const std::vector<double> & gen, int rank, const int * source_of_run, PerturbUpload & up);
-   // what both verdicts put on the device (verdict.cpp): the tables of DevVerdictWalk, which the handles keep until the kernel has run
-   struct VerdictTables { DevBuf xml, pairs, rsum, inact, depth; };
+   // what the verdicts and the clearance put on the device (verdict.cpp): the tables of DevVerdictWalk and, for a device-planned
+   // walk, of DevVerdictPlanned, which the handles keep until the kernel has run
+   struct VerdictTables { DevBuf xml, pairs, rsum, inact, depth, vmax, examine; };
    template <typename real> void verdict_walk_args(const VerdictInputs & in, const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w);
+   template <typename real> size_t verdict_planned_args(const char * who, const char * tag, size_t (*kernel_lds)(int, int, int, int, int, size_t, int), const VerdictInputs & in,
+      const VerdictScope & scope, VerdictTables & t, DevVerdictPlanned<real> & v);
    template <typename real> void collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,
       const VerdictInputs & in, unsigned long long * key_out, double * depth_out);
    template <typename real> bool collision_verdict_planned_typed(const VerdictInputs & in, unsigned long long * key_out, double * depth_out,
@@ -208,6 +212,8 @@ public:
    // scope.long_marks_run).  scope.which 1 on a batch that has not been iterated throws select_best's message
    void collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
                                   int * n_samples_out, const VerdictScope & scope = VerdictScope());
+   // the checks of a device-planned walk's scope that the verdict and the clearance share (verdict.cpp; throws)
+   void verdict_scope_check(const char * who, int which, const unsigned char * examine, const char * unmasked, const char * other) const;
    // (clearance.cpp) orc_batch_clearance / orc_batch_select_clear.  clearance_check throws for what those calls reject of which,
    // examine and max_samples, before any device work; `clearance`: every shard walks its slice, outputs as BatchShard's, over
    // the batch's runs

@@ -1,6 +1,7 @@
 // clearance.cpp -- host side of the clearance of a batch's runs (orc_batch_clearance; the selection by margin that reads it is
-// multistart.cpp's): the checks of its arguments and the launches of clearance_kernels.hip on every shard.  The tables the walk
-// reads are the collision verdict's (verdict.cpp: verdict_inputs, BatchShard::verdict_walk_args).
+// multistart.cpp's): the checks of its arguments and the launches of clearance_kernels.hip on every shard.  What it shares with
+// the device-planned collision verdict is verdict.cpp's: verdict_inputs, Batch::verdict_scope_check and
+// BatchShard::verdict_planned_args, which puts the tables, vmax and the scope on the device.
 #include "module.h"
 #include "clearance_device.h"
 #include <stdexcept>
@@ -10,10 +11,8 @@ namespace orc {
 void Batch::clearance_check(int which, const unsigned char * examine, int max_samples) const
 {
    if (which < 0 || which > 2) throw std::runtime_error("clearance: which is 0 (the runs of examine), 1 (the candidates) or 2 (every run)!");
-   if (which == 0 && !examine) throw std::runtime_error("clearance: which 0 needs examine [n_runs]!");
-   if (which != 0 && examine) throw std::runtime_error("clearance: which 1 (the candidates) and 2 (every run) take no examine!");
-   if (max_samples < 1 || max_samples > ORC_CLEARANCE_MAX_SAMPLES) throw std::runtime_error("clearance: max_samples must lie in [1, 1048576]!");
-   if (which == 1 && !iterated) throw std::runtime_error("select_best: the batch has not been iterated (orc_batch_iterate with 0 iterations makes its costs valid)!");
+   const bool cap_ok = max_samples >= 1 && max_samples <= ORC_CLEARANCE_MAX_SAMPLES;
+   verdict_scope_check("clearance", which, examine, "which 1 (the candidates) and 2 (every run) take", cap_ok ? nullptr : "clearance: max_samples must lie in [1, 1048576]!");
 }
 
 // key: sample << 32 | XML sphere << 16 | field, or the other sphere of a pair
@@ -57,29 +56,15 @@ void BatchShard::clearance_typed(const VerdictInputs & in, const VerdictScope & 
    unsigned long long * key_out, int * n_samples_out)
 {
    hipStream_t st = stream_;
-   hip_check(hipStreamSynchronize(st), "clearance: pending work");
-   if (n_points < 2 || (int) in.vmax.size() != n - in.col0) throw std::runtime_error("clearance: bad trajectory dimensions!");
-   const auto lds_bytes = [this](int chunk) { return orc_clearance_lds_bytes(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
    VerdictTables t;
    DevClearance<real> v;
-   verdict_walk_args<real>(in, lds_bytes, t, v);
-   const size_t lds = lds_bytes(v.chunk);
-   if (lds > 160*1024 - 256) throw std::runtime_error("trajectory too long for the batched collision verdict!");
-   DevBuf d_time, d_key, d_vmax, d_examine;
+   const size_t lds = verdict_planned_args<real>("clearance", "clearance", orc_clearance_lds_bytes, in, scope, t, v);
+   DevBuf d_time, d_key;
    const size_t n2 = (size_t) n_runs * 2;
    d_time.reset(dev_alloc<double>(n2)); d_key.reset(dev_alloc<unsigned long long>(n2));
    if (!d_clear_) { d_clear_.reset(dev_alloc<double>(n2)); d_clear_ns_.reset(dev_alloc<int>(n_runs)); }
-   d_vmax.reset(upload<double>(in.vmax, st));
    v.key_out = nullptr; v.depth_out = nullptr;      // (the walk's outputs of the verdict: not written here)
-   v.col0 = in.col0; v.vmax = d_vmax.as<const double>(); v.max_samples = max_samples;
-   v.examine = nullptr; v.cand_status = nullptr; v.cand_costs = nullptr;
-   if (scope.which == 0)
-   {
-      d_examine.reset(dev_alloc<unsigned char>(n_runs));
-      hip_check(hipMemcpyAsync(d_examine.as<void>(), scope.examine, n_runs, hipMemcpyHostToDevice, st), "clearance runs");
-      v.examine = d_examine.as<unsigned char>();
-   }
-   else if (scope.which == 1) { v.cand_status = d_status_.as<int>(); v.cand_costs = d_costs_.as<double>(); }      // (what the last iterate call left)
+   v.max_samples = max_samples;
    v.clear_out = d_clear_.as<double>(); v.ckey_out = d_key.as<unsigned long long>(); v.ctime_out = d_time.as<double>();
    v.n_samples_out = d_clear_ns_.as<int>();
    hip_check(orc_launch_clearance(v, lds, st, plan_.variant & ORC_VAR_TREE), "clearance_kernel launch");

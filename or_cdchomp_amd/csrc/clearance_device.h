@@ -4,19 +4,14 @@
 #include <hip/hip_runtime.h>
 #include "verdict_device.h"
 
-// The walk of the device-planned collision verdict (DevVerdictPlan) without its stop at the first contact: over every sample
-// of an examined run the smallest `value - radius` of a live active sphere in a field of the run's scene, and the smallest
-// `distance - radius sum` of a pair of the self-collision leg.  key_out and depth_out of the walk are not used.
+// The device-planned walk (DevVerdictPlanned, verdict_planned.h) without the verdict's stop at the first contact: over every
+// sample of an examined run the smallest `value - radius` of a live active sphere in a field of the run's scene, and the
+// smallest `distance - radius sum` of a pair of the self-collision leg.  key_out and depth_out of the walk are not used;
+// n_samples_out: the samples walked.
 template <typename real>
-struct DevClearance : DevVerdictWalk<real>
+struct DevClearance : DevVerdictPlanned<real>
 {
-   int col0;                   // first column the retiming reads (7 with a floating base)
-   const double * vmax;        // [n - col0] velocity limits of the retimed columns
    int max_samples;            // a run with C-space length / 0.04 >= max_samples is too long: nothing of it is walked
-   // which runs are examined, as in DevVerdictPlan: all NULL: every run
-   const unsigned char * examine;
-   const int * cand_status;
-   const double * cand_costs;
    // per run two minima, [0] over the fields and [1] over the pairs: the value widened to double (+inf: nothing to take a
    // minimum of; NaN: the run was not walked), its key and its time on the retimed trajectory (-1 without a key).
    //   key [0]: sample << 32 | XML sphere << 16 | field      key [1]: sample << 32 | XML sphere a << 16 | XML sphere b
@@ -24,7 +19,6 @@ struct DevClearance : DevVerdictWalk<real>
    double * clear_out;              // [n_runs][2]
    unsigned long long * ckey_out;   // [n_runs][2]
    double * ctime_out;              // [n_runs][2]
-   int * n_samples_out;             // [n_runs] samples walked; ORC_VERDICT_SKIPPED: not examined; ORC_VERDICT_TOO_LONG
 };
 
 #define ORC_CLEARANCE_MAX_SAMPLES (1 << 20)

@@ -1,10 +1,11 @@
 // clearance_kernels.hip -- the clearance of a batch's runs (orc_batch_clearance, orc_batch_select_clear): how far every run
 // stays from the fields of its scene and from itself, at exactly the samples the collision verdict looks at.
 //
-// clearance_kernel has the shape of collision_verdict_planned_kernel (verdict_kernels.hip): one workgroup per run, a fifth
-// wavefront that retimes the run and steps the sample times a chunk ahead (verdict_plan.h: the host's arithmetic, rounding
-// for rounding), four wavefronts that interpolate the rows, run FK and look the spheres up (verdict_walk.h).  Where the
-// verdict stops at the first contact, this walk goes to the end and every thread keeps a running minimum of the gap of its
+// clearance_kernel is, like collision_verdict_planned_kernel (verdict_kernels.hip), a shell around the planned walk of
+// verdict_planned.h: one workgroup per run, a fifth wavefront that retimes the run and steps the sample times a chunk ahead
+// (verdict_plan.h: the host's arithmetic, rounding for rounding), four wavefronts that interpolate the rows, run FK and
+// look the spheres up (verdict_walk.h) -- one text for both kernels, so both look at the same samples.  Where the verdict's
+// policy stops at the first contact, this one never stops and every thread keeps a running minimum of the gap of its
 // items: `value - radius` over the live spheres in every field that contains them, `distance - radius sum` over the pairs of
 // the self-collision leg -- the subtractions the verdict compares to zero.  A walk without a stop needs a bound of its own:
 // the caller's max_samples stands where the verdict has 2^30, decided by the planner's first lane before anything is walked.
@@ -19,9 +20,7 @@
 #include "clearance_device.h"
 #include "run_candidate.h"
 
-#define ORC_CL_WORKERS ORC_BLOCK            // threads that walk the samples (verdict_walk.h)
-#define ORC_CL_BLOCK   (ORC_BLOCK + 64)     // ... and the planner's wavefront
-#define ORC_CL_HEADER  64                   // bytes: the two keys, the sample counts of the two chunk buffers, the too-long flag, four wave minima
+#define ORC_CL_HEADER  64                   // bytes of the kernel's LDS header: the two keys, the plan's flags (verdict_planned.h), four wave minima
 
 #pragma clang fp contract(off)
 namespace {
@@ -36,6 +35,7 @@ namespace {
 #include "sdf_lookup.h"
 #include "fk.h"
 #include "verdict_walk.h"
+#include "verdict_planned.h"
 
 // a thread's running minimum of one leg: the items reach a thread in ascending key order, so `<` keeps the lowest key
 template <typename real>
@@ -115,99 +115,41 @@ __device__ __forceinline__ void clearance_not_walked(const DevClearance<real> & 
 }
 
 template <typename real, bool TREE>
-__global__ __launch_bounds__(ORC_CL_BLOCK)
+__global__ __launch_bounds__(ORC_VP_BLOCK)
 void clearance_kernel(DevClearance<real> v)
 {
    extern __shared__ __align__(16) unsigned char smem_raw[];
    const DevModel<real> & gmod = *v.model;
    const int run = blockIdx.x, tid = threadIdx.x;
-   const bool planner = tid >= ORC_CL_WORKERS;
-   // ---- is the run examined at all?  One answer for the workgroup, before anything is staged and before the first barrier
-   if (v.examine || v.cand_status)
+   const bool planner = tid >= ORC_VP_WORKERS;
+   if (!planned_examined<real>(v, run))
    {
-      const int walk = v.examine ? (v.examine[run] != 0) : (orc_run_candidate(v.cand_status[run], v.cand_costs[(size_t) run*3]) ? 1 : 0);
-      if (!__builtin_amdgcn_readfirstlane(walk))
-      {
-         if (tid == 0) clearance_not_walked(v, run, ORC_VERDICT_SKIPPED);
-         return;
-      }
+      if (tid == 0) clearance_not_walked(v, run, ORC_VERDICT_SKIPPED);
+      return;
    }
    const int n = v.n, np = v.n_points, chunk = v.chunk;
    const DevSdf<real> * sdfs; int n_fields;
    verdict_scene<real>(v, run, sdfs, n_fields);
    unsigned long long * key_s = (unsigned long long *) smem_raw;     // [2]: the lowest key at the minimum, fields and pairs
-   int * cnt_s = (int *)(smem_raw + 16);                             // [2]: samples in either chunk buffer
-   int * long_s = (int *)(smem_raw + 24);                            // [1]: the run has too many samples
    double * wmin_s = (double *)(smem_raw + 32);                      // [4]: the wavefronts' minima of the leg being reduced
-   double * times_s = (double *)(smem_raw + ORC_CL_HEADER);          // [2][chunk]
-   double * u_s = times_s + 2*chunk;                                 // [2][chunk]
-   double * dtm_s = u_s + 2*chunk;                                   // [np]
-   double * tstart_s = dtm_s + np;                                   // [np]
-   int * seg_s = (int *)(tstart_s + np);                             // [2][chunk]
-   const VerdictLds<real> L = verdict_lds((unsigned char *)(seg_s + 2*chunk), gmod, n, chunk);
-   verdict_stage<real, ORC_CL_BLOCK>(gmod, v.slot_xml, L, tid);
-   if (tid == 0) { key_s[0] = ORC_VERDICT_NONE; key_s[1] = ORC_VERDICT_NONE; dtm_s[0] = 0.0; }
-   const ModelView<real> mod = verdict_model_view(gmod, n, L);
+   const PlannedLds<real> P = planned_lds(smem_raw, ORC_CL_HEADER, gmod, np, n, chunk);
+   verdict_stage<real, ORC_VP_BLOCK>(gmod, v.slot_xml, P.walk, tid);
+   if (tid == 0) { key_s[0] = ORC_VERDICT_NONE; key_s[1] = ORC_VERDICT_NONE; }
+   const ModelView<real> mod = verdict_model_view(gmod, n, P.walk);
 
    const real * traj = v.traj + (size_t) run * np * n;
-   // ---- the plan's prologue: a lane per segment, then one lane for the sums that have an order
-   for (int i=1+tid; i<np; i+=ORC_CL_BLOCK) plan_segment(traj, i, n, v.col0, v.vmax, dtm_s[i], tstart_s[i]);
-   __syncthreads();
-   double time = 0.0, step_time = 0.0, duration = 0.0;      // the planner's first lane keeps the clock
-   int planned = 0;
-   if (tid == ORC_CL_WORKERS)
-   {
-      double total_dist;
-      plan_totals(np, dtm_s, tstart_s, total_dist, duration);
-      step_time = plan_step_time(total_dist, duration);
-      // the verdict's rule with the caller's cap: decided before anything is walked.  A run it passes has at most
-      // max_samples + 2 samples, and its step advances the clock, so the loop below ends
-      const bool too_long = duration > 0.0 && (total_dist / 0.04 >= (double) v.max_samples || step_time <= 0.0);
-      long_s[0] = too_long ? 1 : 0;
-      planned = too_long ? 0 : plan_times(time, step_time, duration, times_s, chunk);
-      cnt_s[0] = planned;
-   }
-   __syncthreads();
-   if (long_s[0])      // (workgroup-uniform)
+   PlannedClock c;
+   // (the verdict's rule with the caller's cap: a run it passes has at most max_samples + 2 samples, so a walk without a stop ends)
+   if (planned_prologue<real>(v, traj, v.max_samples, tid, P, c))
    {
       if (tid == 0) clearance_not_walked(v, run, ORC_VERDICT_TOO_LONG);
       return;
    }
-   if (planner && tid - ORC_CL_WORKERS < cnt_s[0])
-   {
-      const int k = tid - ORC_CL_WORKERS;
-      seg_s[k] = plan_locate(times_s[k], np, dtm_s, tstart_s, u_s[k]);
-   }
-   __syncthreads();
-
+   // the walk's policy: the minima of a chunk, and no stop
    ClearMin<real> best[2];      // [0] fields, [1] pairs
    for (int leg=0; leg<2; leg++) { best[leg].val = M<real>::inf(); best[leg].key = ORC_VERDICT_NONE; best[leg].time = -1.0; }
-   for (int ci=0; ; ci++)
-   {
-      const int buf = (ci & 1) * chunk, nbuf = chunk - buf;
-      const int count = cnt_s[ci & 1];
-      if (count == 0) break;
-      if (tid == ORC_CL_WORKERS)
-      {
-         const int more = plan_times(time, step_time, duration, times_s + nbuf, chunk);
-         cnt_s[(ci + 1) & 1] = more;
-         planned += more;
-      }
-      if (!planner) verdict_rows(traj, seg_s, u_s, buf, count, n, tid, L);
-      __syncthreads();
-      if (planner && tid - ORC_CL_WORKERS < cnt_s[(ci + 1) & 1])
-      {
-         const int k = nbuf + tid - ORC_CL_WORKERS;
-         seg_s[k] = plan_locate(times_s[k], np, dtm_s, tstart_s, u_s[k]);
-      }
-      verdict_renormalise(mod, count, tid, L);      // (tid < count: workers)
-      __syncthreads();
-      if (!planner) verdict_fk<real, TREE>(mod, count, tid, L);
-      __syncthreads();
-      if (!planner) clearance_tests<real>(v, mod, sdfs, n_fields, ci * chunk, count, tid, L, times_s + buf, best[0], best[1]);
-      __syncthreads();      // (the next pass writes the rows, and the pass after it this chunk's times)
-      if (count < chunk) break;
-   }
+   planned_walk<real, TREE, false>(v, mod, traj, tid, P, c, nullptr, [&](int sbase, int count, const double * times) {
+      clearance_tests<real>(v, mod, sdfs, n_fields, sbase, count, tid, P.walk, times, best[0], best[1]); });
 
    // ---- the workgroup's two minima, and at each the lowest key
    for (int leg=0; leg<2; leg++)
@@ -239,7 +181,7 @@ void clearance_kernel(DevClearance<real> v)
          v.ctime_out[(size_t) run*2 + leg] = best[leg].time;
       }
    }
-   if (tid == ORC_CL_WORKERS) v.n_samples_out[run] = planned;
+   if (tid == ORC_VP_WORKERS) v.n_samples_out[run] = c.planned;
 }
 
 } // namespace
@@ -247,22 +189,9 @@ void clearance_kernel(DevClearance<real> v)
 template <typename real>
 static hipError_t launch_clearance_t(const DevClearance<real> & v, size_t lds, hipStream_t stream, int tree)
 {
-   static std::atomic<unsigned long long> attr_set{0ull};      // (the dynamic-LDS attribute is per device and per kernel)
-   if (v.n_points < 2 || v.chunk < 4 || v.chunk > 64 || (v.chunk & 3)) return hipErrorInvalidValue;
+   if (!planned_args_ok<real>(v)) return hipErrorInvalidValue;
    if (v.max_samples < 1 || v.max_samples > ORC_CLEARANCE_MAX_SAMPLES) return hipErrorInvalidValue;
-   int dev = 0;
-   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-   if (!((attr_set.load() >> dev) & 1ull))
-   {
-      hipError_t e = hipFuncSetAttribute((const void *) clearance_kernel<real, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void *) clearance_kernel<real, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160*1024 - 256);
-      if (e != hipSuccess) return e;
-      attr_set.fetch_or(1ull << dev);
-   }
-   if (lds > 160*1024 - 256) return hipErrorInvalidValue;
-   if (tree) hipLaunchKernelGGL((clearance_kernel<real, true>), dim3(v.n_runs), dim3(ORC_CL_BLOCK), lds, stream, v);
-   else hipLaunchKernelGGL((clearance_kernel<real, false>), dim3(v.n_runs), dim3(ORC_CL_BLOCK), lds, stream, v);
-   return hipGetLastError();
+   return launch_verdict_kernels<DevClearance<real>, clearance_kernel<real, true>, clearance_kernel<real, false>>(v, ORC_VP_BLOCK, lds, stream, tree);
 }
 hipError_t orc_launch_clearance(const DevClearance<double> & v, size_t lds, hipStream_t stream, int tree) { return launch_clearance_t<double>(v, lds, stream, tree); }
 hipError_t orc_launch_clearance(const DevClearance<float> & v, size_t lds, hipStream_t stream, int tree) { return launch_clearance_t<float>(v, lds, stream, tree); }
@@ -270,6 +199,5 @@ hipError_t orc_launch_clearance(const DevClearance<float> & v, size_t lds, hipSt
 // dynamic LDS of clearance_kernel (the carve-up at its top): the header, the plan's arrays, then what the walk holds
 size_t orc_clearance_lds_bytes(int n_points, int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk)
 {
-   const size_t plan = (size_t) ORC_CL_HEADER + ((size_t) 4*chunk + (size_t) 2*n_points) * sizeof(double) + (size_t) 2*chunk * sizeof(int);
-   return plan + verdict_walk_lds_bytes(n, Sa, Sa_real, nj, real_size, chunk);
+   return planned_lds_bytes(ORC_CL_HEADER, n_points, n, Sa, Sa_real, nj, real_size, chunk);
 }

@@ -1,5 +1,7 @@
 // verdict.cpp -- host side of the collision verdict: gettraj's re-check of one run, and the batched verdicts of
-// Module, Batch and BatchShard, which plan the samples here or leave that to the device and launch verdict_kernels.hip.
+// Module, Batch and BatchShard, which plan the samples here or leave that to the device and launch verdict_kernels.hip; and what
+// the clearance (clearance.cpp) shares with the device-planned verdict: the checks of a scope and the kernel arguments of a
+// planned walk.
 #include "module.h"
 #include "verdict_device.h"
 #include <cstdlib>
@@ -221,13 +223,22 @@ void Batch::collision_verdict(const std::vector<int> & soffs, const std::vector<
    }, true);
 }
 
+// what a device-planned walk rejects of its scope, the verdict's or the clearance's (`who`), before any device work; `unmasked`
+// names the values of which that go without examine.  `other`: NULL, or what the caller found wrong with another argument,
+// which ranks behind a wrong mask and before the batch's state
+void Batch::verdict_scope_check(const char * who, int which, const unsigned char * examine, const char * unmasked, const char * other) const
+{
+   if (which == 0 && !examine) throw std::runtime_error(std::string(who) + ": which 0 needs examine [n_runs]!");
+   if (which > 0 && examine) throw std::runtime_error(std::string(who) + ": " + unmasked + " no examine!");      // (the verdict's 1; the clearance's 1 and 2; not the verdict's -1, as before)
+   if (other) throw std::runtime_error(other);
+   if (which == 1 && !iterated) throw std::runtime_error("select_best: the batch has not been iterated (orc_batch_iterate with 0 iterations makes its costs valid)!");
+}
+
 void Batch::collision_verdict_planned(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
    int * n_samples_out, const VerdictScope & scope)
 {
    // (scope.which is -1, 0 or 1: the callers' own values, Module::batch_collision_verdict_subset checks the C caller's)
-   if (scope.which == 0 && !scope.examine) throw std::runtime_error("collision verdict: which 0 needs examine [n_runs]!");
-   if (scope.which == 1 && scope.examine) throw std::runtime_error("collision verdict: which 1 (the candidates) takes no examine!");
-   if (scope.which == 1 && !iterated) throw std::runtime_error("select_best: the batch has not been iterated (orc_batch_iterate with 0 iterations makes its costs valid)!");
+   verdict_scope_check("collision verdict", scope.which, scope.examine, "which 1 (the candidates) takes", nullptr);
    std::vector<int> ok(shards.size(), 1);
    for_shards([&](size_t k) {
       const int r0 = offs[k];
@@ -252,7 +263,7 @@ void BatchShard::verdict_walk_args(const VerdictInputs & in, const std::function
    hip_check(hipMemsetAsync(t.depth.as<void>(), 0, n_runs*sizeof(double), st), "verdict depth");
    t.rsum.reset(upload<real>(in.rsum, st)); t.inact.reset(upload<real>(in.inact_pos, st));
    int chunk = 64;
-   while (chunk > 4 && lds_bytes(chunk) > 160*1024 - 256) chunk -= 4;
+   while (chunk > 4 && lds_bytes(chunk) > ORC_VERDICT_LDS_LIMIT) chunk -= 4;
    w.model = d_model_.as<const DevModel<real>>(); w.sdfs = d_sdfs_.as<const DevSdf<real>>(); w.n_sdfs = scn_.n_sdfs;
    w.scene_of_run = d_scene_of_run_.as<int>(); w.scene_nsdf = d_scene_nsdf_.as<int>();
    w.n_runs = n_runs; w.n_points = n_points; w.n = n; w.chunk = chunk; w.traj = d_traj_.as<const real>();
@@ -260,9 +271,6 @@ void BatchShard::verdict_walk_args(const VerdictInputs & in, const std::function
    w.n_pairs = (int) in.rsum.size(); w.pairs = t.pairs.as<int>(); w.pair_rsum = t.rsum.as<const real>(); w.inact_pos = t.inact.as<const real>();
    w.depth_out = t.depth.as<double>();
 }
-
-template void BatchShard::verdict_walk_args<double>(const VerdictInputs &, const std::function<size_t(int)> &, VerdictTables &, DevVerdictWalk<double> &);      // (clearance.cpp calls them too)
-template void BatchShard::verdict_walk_args<float>(const VerdictInputs &, const std::function<size_t(int)> &, VerdictTables &, DevVerdictWalk<float> &);
 
 // first contact of every run's trajectory with a field, in the run's precision
 template <typename real>
@@ -296,37 +304,51 @@ void BatchShard::collision_verdict(const std::vector<int> & offs, const std::vec
    else collision_verdict_typed<float>(offs, seg, u, in, key_out, depth_out);
 }
 
+// What the two device-planned walks share (verdict_planned.h; `who`, `tag`: the verdict or the clearance, for its messages): the
+// walk's tables and vmax go up, the scope becomes the kernel's pointers, and `v` is filled but for n_samples_out.  Returns the
+// kernel's dynamic LDS by the kernel's own formula: the plan's arrays sit there too, and grow with n_points.
+template <typename real>
+size_t BatchShard::verdict_planned_args(const char * who, const char * tag, size_t (*kernel_lds)(int, int, int, int, int, size_t, int), const VerdictInputs & in,
+   const VerdictScope & scope, VerdictTables & t, DevVerdictPlanned<real> & v)
+{
+   hipStream_t st = stream_;
+   hip_check(hipStreamSynchronize(st), (std::string(tag) + ": pending work").c_str());
+   if (n_points < 2 || (int) in.vmax.size() != n - in.col0) throw std::runtime_error(std::string(who) + ": bad trajectory dimensions!");
+   const auto lds_bytes = [&](int chunk) { return kernel_lds(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
+   verdict_walk_args<real>(in, lds_bytes, t, v);
+   const size_t lds = lds_bytes(v.chunk);
+   if (lds > ORC_VERDICT_LDS_LIMIT) throw std::runtime_error("trajectory too long for the batched collision verdict!");
+   t.vmax.reset(upload<double>(in.vmax, st));
+   v.col0 = in.col0; v.vmax = t.vmax.as<const double>();
+   v.examine = nullptr; v.cand_status = nullptr; v.cand_costs = nullptr;
+   if (scope.which == 0)
+   {
+      t.examine.reset(dev_alloc<unsigned char>(n_runs));
+      hip_check(hipMemcpyAsync(t.examine.as<void>(), scope.examine, n_runs, hipMemcpyHostToDevice, st), (std::string(tag) + " runs").c_str());
+      v.examine = t.examine.as<unsigned char>();
+   }
+   else if (scope.which == 1) { v.cand_status = d_status_.as<int>(); v.cand_costs = d_costs_.as<double>(); }      // (what the last iterate call left)
+   return lds;
+}
+
+template size_t BatchShard::verdict_planned_args<double>(const char *, const char *, size_t (*)(int, int, int, int, int, size_t, int), const VerdictInputs &, const VerdictScope &, VerdictTables &, DevVerdictPlanned<double> &);      // (clearance.cpp calls them)
+template size_t BatchShard::verdict_planned_args<float>(const char *, const char *, size_t (*)(int, int, int, int, int, size_t, int), const VerdictInputs &, const VerdictScope &, VerdictTables &, DevVerdictPlanned<float> &);
+
 // ... with the samples planned by the kernel itself: the trajectories stay where they are
 template <typename real>
 bool BatchShard::collision_verdict_planned_typed(const VerdictInputs & in, unsigned long long * key_out, double * depth_out, double * time_out,
    int * n_samples_out, const VerdictScope & scope)
 {
    hipStream_t st = stream_;
-   hip_check(hipStreamSynchronize(st), "verdict: pending work");
-   if (n_points < 2 || (int) in.vmax.size() != n - in.col0) throw std::runtime_error("collision verdict: bad trajectory dimensions!");
-   // (the plan's arrays sit in the LDS too)
-   const auto lds_bytes = [this](int chunk) { return orc_verdict_planned_lds_bytes(n_points, n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
    VerdictTables t;
    DevVerdictPlan<real> v;
-   verdict_walk_args<real>(in, lds_bytes, t, v);
-   const size_t lds = lds_bytes(v.chunk);
-   if (lds > 160*1024 - 256) throw std::runtime_error("trajectory too long for the batched collision verdict!");
-   DevBuf d_time, d_ns, d_flag, d_vmax, d_examine;
+   const size_t lds = verdict_planned_args<real>("collision verdict", "verdict", orc_verdict_planned_lds_bytes, in, scope, t, v);
+   DevBuf d_time, d_ns, d_flag;
    d_time.reset(dev_alloc<double>(n_runs)); d_ns.reset(dev_alloc<int>(n_runs)); d_flag.reset(dev_alloc<int>(1));
    if (!d_vkey_) d_vkey_.reset(dev_alloc<unsigned long long>(n_runs));
    hip_check(hipMemsetAsync(d_flag.as<void>(), 0, sizeof(int), st), "verdict flag");
-   d_vmax.reset(upload<double>(in.vmax, st));
-   v.col0 = in.col0; v.vmax = d_vmax.as<const double>();
    v.key_out = d_vkey_.as<unsigned long long>(); v.time_out = d_time.as<double>();
    v.n_samples_out = d_ns.as<int>(); v.too_long = d_flag.as<int>();
-   v.examine = nullptr; v.cand_status = nullptr; v.cand_costs = nullptr;
-   if (scope.which == 0)
-   {
-      d_examine.reset(dev_alloc<unsigned char>(n_runs));
-      hip_check(hipMemcpyAsync(d_examine.as<void>(), scope.examine, n_runs, hipMemcpyHostToDevice, st), "verdict runs");
-      v.examine = d_examine.as<unsigned char>();
-   }
-   else if (scope.which == 1) { v.cand_status = d_status_.as<int>(); v.cand_costs = d_costs_.as<double>(); }      // (what the last iterate call left)
    v.count_rest = scope.count_rest ? 1 : 0; v.long_marks_run = scope.long_marks_run ? 1 : 0;
    hip_check(orc_launch_verdict_planned(v, lds, st, plan_.variant & ORC_VAR_TREE), "collision_verdict_planned_kernel launch");
    int too_long = 0;

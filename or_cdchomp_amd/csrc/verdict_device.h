@@ -39,22 +39,28 @@ struct DevVerdict : DevVerdictWalk<real>
    const real * u;             // [samples] position on the segment, 0..1
 };
 
-// ... with the retiming and the sample planning on the device: what DevVerdict takes as offs / seg / u, the kernel derives
-// from the trajectory and vmax
+// ... with the retiming and the sample planning on the device (verdict_planned.h): what DevVerdict takes as offs / seg / u, the
+// workgroup derives from the trajectory and vmax.  What the two kernels made of that walk share of their arguments:
 template <typename real>
-struct DevVerdictPlan : DevVerdictWalk<real>
+struct DevVerdictPlanned : DevVerdictWalk<real>
 {
    int col0;                   // first column the retiming reads (7 with a floating base)
    const double * vmax;        // [n - col0] velocity limits of the retimed columns
-   double * time_out;          // [n_runs] the first contact's time on the retimed trajectory, -1 without a contact
-   int * n_samples_out;        // [n_runs] samples the run's trajectory has (all of them, also when the walk stops at a contact)
-   int * too_long;             // [1] set when a run has 2^30 samples or more: nothing of that run is walked (the caller zeroes it)
-   // Which runs are examined (orc_batch_collision_verdict_subset, orc_batch_set_verdict_scope); all NULL / 1 / 0: every run,
-   // as orc_batch_collision_verdict_device.  A run that is not examined stages and walks nothing: key ORC_VERDICT_NONE, time
-   // -1, n_samples ORC_VERDICT_SKIPPED, its depth left as the caller zeroed it.
+   // Which runs are examined (orc_batch_collision_verdict_subset, orc_batch_set_verdict_scope, orc_batch_clearance); all NULL:
+   // every run.  A run that is not examined stages and walks nothing and reports n_samples ORC_VERDICT_SKIPPED.
    const unsigned char * examine;   // [n_runs] nonzero: examine the run; NULL: every run, or the candidates below
    const int * cand_status;    // [n_runs] with examine NULL: the runs orc_run_candidate (run_candidate.h) passes on the status ...
    const double * cand_costs;  // [n_runs][3] ... and the costs an iterate call left; both NULL: every run
+   int * n_samples_out;        // [n_runs] samples of the run's trajectory; ORC_VERDICT_SKIPPED: not examined; ORC_VERDICT_TOO_LONG
+};
+
+// the first contact of every examined run (collision_verdict_planned_kernel).  A run that is not examined or too long has key
+// ORC_VERDICT_NONE and time -1, its depth left as the caller zeroed it.
+template <typename real>
+struct DevVerdictPlan : DevVerdictPlanned<real>
+{
+   double * time_out;          // [n_runs] the first contact's time on the retimed trajectory, -1 without a contact
+   int * too_long;             // [1] set when a run has 2^30 samples or more: nothing of that run is walked (the caller zeroes it)
    int count_rest;             // 1: the samples behind a contact are counted (n_samples_out is exact); 0: n_samples_out is what was
                                // planned when the walk stopped, and "too long" is only what is decided before anything is walked
    int long_marks_run;         // 0: a run that is too long sets *too_long; 1: it reports like a run that is not examined, with
@@ -70,3 +76,6 @@ hipError_t orc_launch_verdict_planned(const DevVerdictPlan<float> & v, size_t ld
 // dynamic LDS of collision_verdict_kernel and of collision_verdict_planned_kernel
 size_t orc_verdict_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);
 size_t orc_verdict_planned_lds_bytes(int n_points, int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk);
+
+// the most dynamic LDS a workgroup of these kernels takes (a CU has 160 KB): `chunk` is chosen under it, the launcher (verdict_planned.h) refuses more
+#define ORC_VERDICT_LDS_LIMIT (160*1024 - 256)

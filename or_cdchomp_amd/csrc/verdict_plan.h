@@ -1,6 +1,6 @@
 // verdict_plan.h -- the plan of a run's samples on the device: the host's arithmetic (verdict.h retime_linear, SampleClock),
-// rounding for rounding, as the planner wavefront of collision_verdict_planned_kernel (verdict_kernels.hip) and of
-// clearance_kernel (clearance_kernels.hip) runs it.  module.py verdict_samples is its specification: doubles for either
+// rounding for rounding, as the planner wavefront of the planned walk (verdict_planned.h: collision_verdict_planned_kernel and
+// clearance_kernel) runs it.  module.py verdict_samples is its specification: doubles for either
 // precision, no fused multiply-add, the sums in index order, time advanced by repeated addition.
 //
 // Included inside the including file's namespace after <hip/hip_runtime.h> and <math.h>, with `#pragma clang fp contract(off)`
@@ -43,6 +43,13 @@ __device__ __forceinline__ void plan_totals(int np, const double * dtm, double *
 __device__ __forceinline__ double plan_step_time(double total_dist, double duration)
 {
    return total_dist > 0.0 ? duration * 0.04 / total_dist : duration + 1.0;
+}
+
+// A run of `cap` samples or more is too long, and so is one whose step does not advance the clock (an underflow: the walk
+// would never end).  Decided before anything is walked; a run this passes has at most cap + 2 samples.
+__device__ __forceinline__ bool plan_too_long(double total_dist, double step_time, double duration, int cap)
+{
+   return duration > 0.0 && (total_dist / 0.04 >= (double) cap || step_time <= 0.0);
 }
 
 // the next samples' times, `cap` at most; returns their number

@@ -5,6 +5,7 @@ specification (or_cdchomp_amd.module.verdict_samples), on every kind of batch th
 import numpy as np
 import pytest
 
+import clearance as CL
 import common
 import or_cdchomp_amd
 from or_cdchomp_amd import _capi, robots, scenes
@@ -295,6 +296,22 @@ def test_degenerate_trajectories(wam):
     for key in dev:
         assert same(dev[key][others], before[key][others]), key
     assert dev["collides"][6:].all()
+    mod.batch_destroy(bid)
+
+
+def test_chunk_edges(wam):
+    """the synthetic runs of tests/clearance.py, whose sample counts sit on the chunk's edges: a walk without a contact whose
+    samples are exactly two chunks ends on an empty chunk, not on a partial one; one of no sample; one that ends on the
+    second sample of a chunk"""
+    mod, model, vmax = wam
+    runs = CL.synthetic_runs(robots.WAM_START)
+    bid = mod.batch_create(model.name, common.wam_goals(len(runs), seed=1), **dict(KW, n_points=CL.SYNTH_POINTS))
+    mod.batch_set_traj(bid, runs)
+    host, dev, back = compare(mod, bid, vmax, 0)
+    m, z = CL.SYNTH_NAMES.index("chunk multiple"), CL.SYNTH_NAMES.index("zero length")
+    assert dev["n_samples"][m] == 2 * CHUNK and host["collides"][m] == 0, "two full chunks, walked to the end"
+    assert dev["n_samples"][z] == 0 and host["collides"][z] == 0
+    assert host["collides"][CL.SYNTH_NAMES.index("penetrates")] == 1
     mod.batch_destroy(bid)
 
 
