@@ -390,7 +390,8 @@ int orc_batch_set_verdict_scope(orc_module * mod, int batch_id, int scope);
  * the launch's last iteration, ORC_WAVE_ROTATE); "plan" (8 numbers: kernel variant bits -- 512 = the dense pair-list family, 1 = a tree --, threads per
  * workgroup, LDS bytes per workgroup, tile, solve mode (2 closed-form scans, 3 band-inverse generators, 1 dense), workgroups
  * per CU, tiles, lanes per waypoint; a ninth, the moving waypoints of the first tile, when cap_doubles >= 9);
- * "run_params" ([n_runs][4]: lambda, epsilon, obs_factor, obs_factor_self as the device holds them, orc_batch_set_run_params) */
+ * "run_params" ([n_runs][4]: lambda, epsilon, obs_factor, obs_factor_self as the device holds them, orc_batch_set_run_params);
+ * "config_chunk" (1 number: the consecutive queries a workgroup of orc_batch_config_clearance's kernel takes for this batch) */
 int orc_batch_get_state(orc_module * mod, int batch_id, const char * which, double * out, size_t cap_doubles);
 int orc_batch_dims(orc_module * mod, int batch_id, int * n_runs, int * n_points, int * n);
 /* overwrite the trajectories of a batch (warm start; what `create starttraj` does for one run,
@@ -526,6 +527,36 @@ int orc_batch_clearance(orc_module * mod, int batch_id, int which, const unsigne
    double * clearance_out /* [n_runs][2]: fields, self */, double * time_out /* [n_runs][2] */,
    int * sphere_out /* [n_runs][2] */, int * other_out /* [n_runs][2]: field index; XML index of sphere b */,
    int * n_samples_out /* [n_runs] */);
+/* The clearance of single configurations, on the device: the per-sample body of orc_batch_clearance's walk -- FK, every live
+ * active sphere against every field of a scene, the self-collision pairs -- without a trajectory and a sample clock around it.
+ * A configuration is one row of the batch's trajectories, n columns as orc_batch_dims reports (a floating base: columns 0..6
+ * the pose, its quaternion renormalised as the walk renormalises a sample's); a precision-32 batch narrows the row to float
+ * on upload, as orc_batch_set_traj does.  Query q is tested against the scene of run run_of_q[q] (NULL: run 0 for every
+ * query) with what orc_batch_clearance would use at this moment: the batch's robot model, held bodies, live mask and pair
+ * tables, and the robot's self-check setting.
+ * orc_batch_config_clearance uploads configs [n_q][n].  orc_batch_waypoint_clearance reads T[run_of_q[q]][point_of_q[q]] of
+ * the device's trajectories and uploads the two index arrays only; with both NULL, n_q must be n_runs * n_points and the
+ * queries are every waypoint in storage order, the profile [n_runs][n_points].
+ * Per query, any output may be NULL:
+ *   clearance_out [n_q][2]: [0] the smallest value - radius over the live active spheres and the fields that contain them,
+ *     [1] the smallest distance - (r_a + r_b) over the pairs; the subtractions of orc_batch_clearance, widened to double.  A
+ *     trajectory with exactly one sample (0 < C-space length < 0.04) has the clearance of its first row, bit for bit.
+ *   sphere_out / other_out [n_q][2]: XML sphere and field, XML spheres a and b, of the item of lowest key (sphere << 16 |
+ *     other) among those that attain the minimum.
+ *   A minimum over nothing (an empty scene, a configuration outside every field, the self check off) is +inf with -1, -1; a
+ *   NaN gap is never a minimum.  A row with a non-finite entry is not evaluated: NaN and -1, -1 on both legs.
+ * A query's answer depends on its row and its run only: not on its place in the list, on n_q, on the shard or on a schedule
+ * (each query is reduced by one wavefront with shuffles; no atomic).  The calls leave no state: trajectories, momentum, costs,
+ * status, verdict keys and the minima orc_batch_select_clear cached are untouched.  They are ordered on the shards' streams
+ * like orc_batch_clearance: after orc_batch_iterate_async they see the trajectories that launch leaves.  Several devices: every
+ * shard takes the queries whose run it owns; a list may interleave shards freely.
+ * Rejected with a nonzero return and a message before any device work, the batch unchanged and the module usable: an unknown
+ * batch; n_q < 1 or n_q > 2^22; configs NULL; a run_of_q entry outside [0, n_runs); a point_of_q entry outside [0, n_points);
+ * exactly one of run_of_q / point_of_q NULL; both NULL with n_q != n_runs * n_points. */
+int orc_batch_config_clearance(orc_module * mod, int batch_id, int n_q, const int * run_of_q,
+   const double * configs /* [n_q][n] */, double * clearance_out /* [n_q][2] */, int * sphere_out, int * other_out /* [n_q][2] each */);
+int orc_batch_waypoint_clearance(orc_module * mod, int batch_id, int n_q, const int * run_of_q, const int * point_of_q,
+   double * clearance_out, int * sphere_out, int * other_out);
 /* The best run of every group among those that keep a margin.  n_groups and group_of_run as in orc_batch_select_best.  A run
  * is eligible when all three hold: it is a candidate (status 0 or 1 and a finite total cost); it was walked, i.e. is not too
  * long for max_samples; fmin(clearance[0], clearance[1]) >= margin.  margin 0 is orc_batch_select_best_by's

@@ -97,6 +97,8 @@ SYMBOLS = [
                                            c_int_p]),
     ("orc_batch_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_ubyte_p, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p,
                                       c_int_p]),
+    ("orc_batch_config_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, c_int_p, c_int_p]),
+    ("orc_batch_waypoint_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p]),
     ("orc_batch_select_clear", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_int, c_int_p, c_double_p,
                                          c_double_p, c_int_p, c_int_p]),
     ("orc_batch_respawn", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, C.c_int, C.c_double, c_uint_p,

@@ -1,5 +1,5 @@
 // batch.h -- a batch of CHOMP runs as the host layer holds it: the shard of its runs on one device, the batch over the shards, and
-// the small structs their calls take (batch.cpp, verdict.cpp, clearance.cpp, multistart.cpp).
+// the small structs their calls take (batch.cpp, verdict.cpp, clearance.cpp, config_clearance.cpp, multistart.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -101,6 +101,13 @@ public:
    // time [n_runs][2], key [n_runs][2] and n_samples [n_runs] is not NULL comes back
    void clearance(const VerdictInputs & in, const VerdictScope & scope, int max_samples, double * clear_out, double * time_out,
                   unsigned long long * key_out, int * n_samples_out);
+   // (config_clearance.cpp) the clearance of n_q single rows against the scenes of this shard's runs (config_kernels.hip):
+   // configs [n_q][n] with run_of_q [n_q] (LOCAL runs); or configs NULL, waypoints of the device's trajectories: run_of_q and
+   // point_of_q [n_q], or both NULL and n_q = n_runs * n_points, every waypoint in storage order.  What of clear [n_q][2] and
+   // key [n_q][2] (config_device.h) is not NULL comes back; nothing is kept on the device
+   void config_clearance(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
+                         double * clear_out, unsigned int * key_out);
+   int config_chunk() const;                 // the queries a workgroup of that kernel takes: the walk's rule for `chunk` with this kernel's LDS
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
@@ -135,6 +142,8 @@ private:
       double * time_out, int * n_samples_out, const VerdictScope & scope);
    template <typename real> void clearance_typed(const VerdictInputs & in, const VerdictScope & scope, int max_samples, double * clear_out,
       double * time_out, unsigned long long * key_out, int * n_samples_out);
+   template <typename real> void config_clearance_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q,
+      const double * configs, double * clear_out, unsigned int * key_out);
    void construct(const Robot & robot, const double * starts, const double * goals, const double * basegoals,
       const unsigned int * seeds);
    Module * mod_;
@@ -220,6 +229,12 @@ public:
    void clearance_check(int which, const unsigned char * examine, int max_samples) const;
    void clearance(const VerdictInputs & in, int which, const unsigned char * examine, int max_samples, double * clear_out, double * time_out,
                   unsigned long long * key_out, int * n_samples_out);
+   // (config_clearance.cpp) orc_batch_config_clearance / orc_batch_waypoint_clearance.  config_clearance_check throws for what
+   // those calls reject, before any device work; `config_clearance`: every shard takes the queries whose run it owns, in their
+   // order, and the results go back to the caller's order; outputs [n_q][2] or NULL
+   void config_clearance_check(bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs) const;
+   void config_clearance(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q,
+                         const double * configs, double * clear_out, unsigned int * key_out);
    // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
    // kept until it is set again
    int verdict_scope = 0;

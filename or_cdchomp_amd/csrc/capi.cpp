@@ -609,6 +609,12 @@ int orc_batch_get_state(orc_module * mod, int id, const char * which, double * o
          std::copy(plan, plan + (cap < 9 ? 8 : 9), out);      // (the first tile's size: appended, read when there is room)
          return;
       }
+      if (std::string(which) == "config_chunk")      // the queries a workgroup of config_clearance_kernel takes for this batch
+      {
+         if (cap < 1) throw std::runtime_error("buffer too small!");
+         out[0] = (double) b.shards[0]->config_chunk();
+         return;
+      }
       if (std::string(which) == "run_params")
       {
          if (cap < (size_t) b.n_runs * 4) throw std::runtime_error("buffer too small!");
@@ -667,6 +673,18 @@ int orc_batch_clearance(orc_module * mod, int id, int which, const unsigned char
       need(clearance_out, "clearance_out"); need(n_samples_out, "n_samples_out");
       mod->impl->batch_clearance(id, which, examine, max_samples, clearance_out, time_out, sphere_out, other_out, n_samples_out);
    });
+}
+
+int orc_batch_config_clearance(orc_module * mod, int id, int n_q, const int * run_of_q, const double * configs, double * clearance_out,
+   int * sphere_out, int * other_out)
+{
+   return guarded(mod, [&] { mod->impl->batch_config_clearance(id, false, n_q, run_of_q, nullptr, configs, clearance_out, sphere_out, other_out); });
+}
+
+int orc_batch_waypoint_clearance(orc_module * mod, int id, int n_q, const int * run_of_q, const int * point_of_q, double * clearance_out,
+   int * sphere_out, int * other_out)
+{
+   return guarded(mod, [&] { mod->impl->batch_config_clearance(id, true, n_q, run_of_q, point_of_q, nullptr, clearance_out, sphere_out, other_out); });
 }
 
 int orc_batch_select_clear(orc_module * mod, int id, int cost_column, int n_groups, const int * group_of_run, double margin, int max_samples,

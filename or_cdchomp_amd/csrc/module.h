@@ -58,6 +58,11 @@ public:
    // samples the verdict looks at, with time, XML sphere and field / other sphere; which 0 examine, 1 the candidates, 2 every run
    void batch_clearance(int id, int which, const unsigned char * examine, int max_samples, double * clearance, double * time, int * sphere,
       int * other, int * n_samples);
+   // (config_clearance.cpp) orc_batch_config_clearance / orc_batch_waypoint_clearance: the two minima of a single row, n_q rows
+   // that are uploaded (configs [n_q][n]) or waypoints of the device's trajectories (waypoints: configs is not read); run_of_q
+   // names the run whose scene a query is tested against; outputs [n_q][2], any may be NULL
+   void batch_config_clearance(int id, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
+      double * clearance, int * sphere, int * other);
    // (multistart.cpp) orc_batch_select_best[_by], _respawn, _select_clear: each checks every argument on the host, then takes the
    // verdict with Batch::selection_scope() (collision_free; collision_mode 1, 2) or the clearance, then selects or respawns on the device
    void batch_select_best(int id, int cost_column, int n_groups, const int * group_of_run, bool collision_free, int * best_run, double * best_cost,

@@ -272,6 +272,9 @@ void BatchShard::verdict_walk_args(const VerdictInputs & in, const std::function
    w.depth_out = t.depth.as<double>();
 }
 
+template void BatchShard::verdict_walk_args<double>(const VerdictInputs &, const std::function<size_t(int)> &, VerdictTables &, DevVerdictWalk<double> &);      // (config_clearance.cpp calls them)
+template void BatchShard::verdict_walk_args<float>(const VerdictInputs &, const std::function<size_t(int)> &, VerdictTables &, DevVerdictWalk<float> &);
+
 // first contact of every run's trajectory with a field, in the run's precision
 template <typename real>
 void BatchShard::collision_verdict_typed(const std::vector<int> & offs, const std::vector<int> & seg, const std::vector<double> & u,

@@ -1068,6 +1068,79 @@ class Module:
                                                   int(max_samples), _dp(clr), _dp(tim), _ip(sph), _ip(oth), _ip(cnt)))
         return dict(clearance=clr, time=tim, sphere=sph, other=oth, n_samples=cnt)
 
+    def batch_config_clearance(self, bid, configs, runs=None):
+        """The clearance of given configurations, on the device (orc_batch_config_clearance): the per-sample body of
+        batch_clearance's walk without a trajectory around it.  configs [n_q][n] (or one row [n]), rows as batch_gettraj
+        returns them; runs: the run whose scene each is tested against, an int array [n_q], one int for all, or None for
+        run 0.  Returns a dict: clearance [n_q][2] (fields; self), sphere [n_q][2], other [n_q][2] (the field; the other
+        sphere).  A minimum over nothing is +inf with -1, -1; a row with a non-finite entry reports NaN with -1, -1."""
+        n_runs, _, n = self.batch_dims(bid)
+        cf = np.ascontiguousarray(configs, dtype=np.float64)
+        if cf.ndim == 1:
+            cf = cf.reshape(1, -1)
+        if cf.ndim != 2 or cf.shape[1] != n or cf.shape[0] < 1:
+            raise ValueError("configs is [n_q][%d], n_q >= 1" % n)
+        n_q = cf.shape[0]
+        rq = None
+        if runs is not None:
+            rq = np.asarray(runs)
+            rq = np.full(n_q, int(rq), dtype=np.int32) if rq.ndim == 0 else np.ascontiguousarray(rq, dtype=np.int32).reshape(-1)
+            if rq.size != n_q:
+                raise ValueError("runs has %d entries for %d configurations" % (rq.size, n_q))
+            if ((rq < 0) | (rq >= n_runs)).any():
+                raise ValueError("a run lies outside [0, %d)" % n_runs)
+        clr = np.zeros((n_q, 2)); sph = np.zeros((n_q, 2), dtype=np.int32); oth = np.zeros((n_q, 2), dtype=np.int32)
+        self._check(self._lib.orc_batch_config_clearance(self._h, bid, n_q, None if rq is None else _ip(rq), _dp(cf), _dp(clr),
+                                                         _ip(sph), _ip(oth)))
+        return dict(clearance=clr, sphere=sph, other=oth)
+
+    def batch_config_chunk(self, bid):
+        """how many consecutive queries a workgroup of the configuration-clearance kernel takes for this batch (64, or what
+        the LDS of a CU holds of the robot); a query's answer does not depend on it"""
+        out = np.zeros(1)
+        self._check(self._lib.orc_batch_get_state(self._h, bid, b"config_chunk", _dp(out), out.size))
+        return int(out[0])
+
+    def batch_waypoint_clearance(self, bid, runs=None, points=None):
+        """The clearance of waypoints of the batch's trajectories as they stand on the device
+        (orc_batch_waypoint_clearance); nothing is uploaded but indices.  runs and points None: the whole profile, arrays
+        [n_runs][n_points][2].  points an int or a sequence with runs None: those waypoints of every run,
+        [n_runs][len(points)][2]; a negative index counts from the end, so points=(0, -1) is "starts and goals".  runs and
+        points both arrays [n_q]: those waypoints, [n_q][2].  Returns a dict: clearance, sphere, other, as
+        batch_config_clearance."""
+        n_runs, n_points, _ = self.batch_dims(bid)
+        if points is None and runs is not None:
+            raise ValueError("runs needs points: both None is the whole profile")
+        shape = (n_runs, n_points)
+        rq = pq = None
+        if points is not None:
+            pq = np.asarray(points)
+            if pq.dtype.kind not in "iu":
+                raise ValueError("points is an int or a sequence of ints")
+            pq = pq.astype(np.int64).reshape(-1)
+            if ((pq < -n_points) | (pq >= n_points)).any():
+                raise ValueError("a point lies outside [-%d, %d)" % (n_points, n_points))
+            pq = np.where(pq < 0, pq + n_points, pq)
+            if runs is None:
+                if pq.size < 1:
+                    raise ValueError("points is empty")
+                shape = (n_runs, pq.size)
+                rq = np.repeat(np.arange(n_runs), pq.size)
+                pq = np.tile(pq, n_runs)
+            else:
+                rq = np.ascontiguousarray(runs, dtype=np.int32).reshape(-1)
+                if rq.size != pq.size or rq.size < 1:
+                    raise ValueError("runs has %d entries for %d points" % (rq.size, pq.size))
+                if ((rq < 0) | (rq >= n_runs)).any():
+                    raise ValueError("a run lies outside [0, %d)" % n_runs)
+                shape = (rq.size,)
+            rq = np.ascontiguousarray(rq, dtype=np.int32); pq = np.ascontiguousarray(pq, dtype=np.int32)
+        n_q = int(np.prod(shape))
+        clr = np.zeros(shape + (2,)); sph = np.zeros(shape + (2,), dtype=np.int32); oth = np.zeros(shape + (2,), dtype=np.int32)
+        self._check(self._lib.orc_batch_waypoint_clearance(self._h, bid, n_q, None if rq is None else _ip(rq),
+                                                           None if pq is None else _ip(pq), _dp(clr), _ip(sph), _ip(oth)))
+        return dict(clearance=clr, sphere=sph, other=oth)
+
     def batch_select_clear(self, bid, groups=None, n_groups=None, margin=0.0, by="total", max_samples=65536):
         """The best run of every group among the candidates that keep `margin` metres of clearance, on the device
         (orc_batch_select_clear; the rule is select_clear's).  by: "total", "obs", "smooth" (the cost that is minimised) or
