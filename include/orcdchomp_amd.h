@@ -391,7 +391,8 @@ int orc_batch_set_verdict_scope(orc_module * mod, int batch_id, int scope);
  * workgroup, LDS bytes per workgroup, tile, solve mode (2 closed-form scans, 3 band-inverse generators, 1 dense), workgroups
  * per CU, tiles, lanes per waypoint; a ninth, the moving waypoints of the first tile, when cap_doubles >= 9);
  * "run_params" ([n_runs][4]: lambda, epsilon, obs_factor, obs_factor_self as the device holds them, orc_batch_set_run_params);
- * "config_chunk" (1 number: the consecutive queries a workgroup of orc_batch_config_clearance's kernel takes for this batch) */
+ * "config_chunk" (1 number: the consecutive queries a workgroup of orc_batch_config_clearance's kernel takes for this batch);
+ * "penetration_chunk" (1 number: the same of orc_batch_config_penetration's kernel) */
 int orc_batch_get_state(orc_module * mod, int batch_id, const char * which, double * out, size_t cap_doubles);
 int orc_batch_dims(orc_module * mod, int batch_id, int * n_runs, int * n_points, int * n);
 /* overwrite the trajectories of a batch (warm start; what `create starttraj` does for one run,
@@ -557,6 +558,27 @@ int orc_batch_config_clearance(orc_module * mod, int batch_id, int n_q, const in
    const double * configs /* [n_q][n] */, double * clearance_out /* [n_q][2] */, int * sphere_out, int * other_out /* [n_q][2] each */);
 int orc_batch_waypoint_clearance(orc_module * mod, int batch_id, int n_q, const int * run_of_q, const int * point_of_q,
    double * clearance_out, int * sphere_out, int * other_out);
+/* Which way is out: the penetration cost of single configurations and its gradient, on the device.  The queries, their rows,
+ * runs and waypoints are those of the two clearance calls above, and so are the rules for n_q, run_of_q, point_of_q and configs.
+ * With gap the quantity those calls take the minimum of, per query:
+ *   cost_out [n_q][2]: [0] 1/2 sum max(0, margin_field - gap)^2 over the live active spheres and the fields that contain them,
+ *     [1] 1/2 sum max(0, margin_self - gap)^2 over the pairs.  An item whose gap is not below its margin adds nothing: a
+ *     poisoned (+inf) value, a NaN, a sphere outside a field.  The margins are rounded to the batch's precision.
+ *   grad_out [n_q][n]: d(cost[0] + cost[1]) / d row[c], what a finite difference of the cost over the caller's row measures.  A
+ *     field's slope is that of the cell the lookup interpolates in.  An inactive sphere is a constant; a pair whose centres
+ *     coincide adds to the cost and not to the gradient.  A floating base: columns 0..2 take the force, columns 3..6 the
+ *     derivative through the renormalisation of the quaternion (a factor 1 / |quaternion| of the caller's row); the 0.01 by
+ *     which the optimizer scales its base block is not applied.
+ *   clearance_out, sphere_out, other_out [n_q][2]: orc_batch_config_clearance's, bit for bit.
+ * A row with a non-finite entry: NaN costs, NaN gradient, NaN minima and -1, -1.  Any output may be NULL.
+ * As with the clearance calls, a query's answer depends on its row, its run and the margins only (every sum has a fixed order;
+ * no atomic), the calls leave no state, and they are ordered on the shards' streams.  Rejected in addition to what those calls
+ * reject: a margin that is negative, infinite or NaN. */
+int orc_batch_config_penetration(orc_module * mod, int batch_id, int n_q, const int * run_of_q, const double * configs /* [n_q][n] */,
+   double margin_field, double margin_self, double * cost_out /* [n_q][2] */, double * grad_out /* [n_q][n] */,
+   double * clearance_out /* [n_q][2] */, int * sphere_out, int * other_out /* [n_q][2] each */);
+int orc_batch_waypoint_penetration(orc_module * mod, int batch_id, int n_q, const int * run_of_q, const int * point_of_q,
+   double margin_field, double margin_self, double * cost_out, double * grad_out, double * clearance_out, int * sphere_out, int * other_out);
 /* The best run of every group among those that keep a margin.  n_groups and group_of_run as in orc_batch_select_best.  A run
  * is eligible when all three hold: it is a candidate (status 0 or 1 and a finite total cost); it was walked, i.e. is not too
  * long for max_samples; fmin(clearance[0], clearance[1]) >= margin.  margin 0 is orc_batch_select_best_by's

@@ -99,6 +99,10 @@ SYMBOLS = [
                                       c_int_p]),
     ("orc_batch_config_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, c_int_p, c_int_p]),
     ("orc_batch_waypoint_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p]),
+    ("orc_batch_config_penetration", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, C.c_double, C.c_double, c_double_p, c_double_p,
+                                               c_double_p, c_int_p, c_int_p]),
+    ("orc_batch_waypoint_penetration", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, C.c_double, C.c_double, c_double_p, c_double_p,
+                                                 c_double_p, c_int_p, c_int_p]),
     ("orc_batch_select_clear", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_int, c_int_p, c_double_p,
                                          c_double_p, c_int_p, c_int_p]),
     ("orc_batch_respawn", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, C.c_int, C.c_double, c_uint_p,

@@ -1,5 +1,5 @@
 // batch.h -- a batch of CHOMP runs as the host layer holds it: the shard of its runs on one device, the batch over the shards, and
-// the small structs their calls take (batch.cpp, verdict.cpp, clearance.cpp, config_clearance.cpp, multistart.cpp).
+// the small structs their calls take (batch.cpp, verdict.cpp, clearance.cpp, config_clearance.cpp, penetration.cpp, multistart.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -38,6 +38,15 @@ struct ConvergenceSpec
    double obs_max = HUGE_VAL;
    // rejects a NaN or non-positive rtol and a NaN obs_max when the stop is on (throws)
    void validate() const;
+};
+
+// where a penetration call's results go (penetration.cpp): cost [n_q][2], grad [n_q][n], clear [n_q][2], key [n_q][2]
+// (config_device.h); any may be NULL
+struct PenetrationOut
+{
+   double * cost = nullptr, * grad = nullptr, * clear = nullptr;
+   unsigned int * key = nullptr;
+   PenetrationOut from(size_t first, int n) const;
 };
 
 class Module;
@@ -108,6 +117,11 @@ public:
    void config_clearance(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
                          double * clear_out, unsigned int * key_out);
    int config_chunk() const;                 // the queries a workgroup of that kernel takes: the walk's rule for `chunk` with this kernel's LDS
+   // (penetration.cpp) the penetration cost and its gradient of the same queries (penetration_kernels.hip), with the two minima
+   // and keys of config_clearance; nothing is kept on the device
+   void config_penetration(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
+                           double margin_field, double margin_self, const PenetrationOut & out);
+   int penetration_chunk() const;            // the queries a workgroup of that kernel takes
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
@@ -144,6 +158,8 @@ private:
       double * time_out, unsigned long long * key_out, int * n_samples_out);
    template <typename real> void config_clearance_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q,
       const double * configs, double * clear_out, unsigned int * key_out);
+   template <typename real> void config_penetration_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q,
+      const double * configs, double margin_field, double margin_self, const PenetrationOut & out);
    void construct(const Robot & robot, const double * starts, const double * goals, const double * basegoals,
       const unsigned int * seeds);
    Module * mod_;
@@ -235,6 +251,10 @@ public:
    void config_clearance_check(bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs) const;
    void config_clearance(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q,
                          const double * configs, double * clear_out, unsigned int * key_out);
+   // (penetration.cpp) orc_batch_config_penetration / orc_batch_waypoint_penetration: the queries dealt as config_clearance deals
+   // them (the caller has made config_clearance_check and checked the margins)
+   void config_penetration(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q,
+                           const double * configs, double margin_field, double margin_self, const PenetrationOut & out);
    // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
    // kept until it is set again
    int verdict_scope = 0;

@@ -615,6 +615,12 @@ int orc_batch_get_state(orc_module * mod, int id, const char * which, double * o
          out[0] = (double) b.shards[0]->config_chunk();
          return;
       }
+      if (std::string(which) == "penetration_chunk")      // ... of penetration_kernel
+      {
+         if (cap < 1) throw std::runtime_error("buffer too small!");
+         out[0] = (double) b.shards[0]->penetration_chunk();
+         return;
+      }
       if (std::string(which) == "run_params")
       {
          if (cap < (size_t) b.n_runs * 4) throw std::runtime_error("buffer too small!");
@@ -685,6 +691,24 @@ int orc_batch_waypoint_clearance(orc_module * mod, int id, int n_q, const int * 
    int * sphere_out, int * other_out)
 {
    return guarded(mod, [&] { mod->impl->batch_config_clearance(id, true, n_q, run_of_q, point_of_q, nullptr, clearance_out, sphere_out, other_out); });
+}
+
+int orc_batch_config_penetration(orc_module * mod, int id, int n_q, const int * run_of_q, const double * configs, double margin_field,
+   double margin_self, double * cost_out, double * grad_out, double * clearance_out, int * sphere_out, int * other_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch_config_penetration(id, false, n_q, run_of_q, nullptr, configs, margin_field, margin_self, cost_out, grad_out, clearance_out,
+         sphere_out, other_out);
+   });
+}
+
+int orc_batch_waypoint_penetration(orc_module * mod, int id, int n_q, const int * run_of_q, const int * point_of_q, double margin_field,
+   double margin_self, double * cost_out, double * grad_out, double * clearance_out, int * sphere_out, int * other_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch_config_penetration(id, true, n_q, run_of_q, point_of_q, nullptr, margin_field, margin_self, cost_out, grad_out, clearance_out,
+         sphere_out, other_out);
+   });
 }
 
 int orc_batch_select_clear(orc_module * mod, int id, int cost_column, int n_groups, const int * group_of_run, double margin, int max_samples,

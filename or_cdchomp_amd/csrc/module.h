@@ -63,6 +63,10 @@ public:
    // names the run whose scene a query is tested against; outputs [n_q][2], any may be NULL
    void batch_config_clearance(int id, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
       double * clearance, int * sphere, int * other);
+   // (penetration.cpp) orc_batch_config_penetration / orc_batch_waypoint_penetration: the same queries; per query the penetration
+   // cost of the two legs at the two margins [n_q][2], its gradient with respect to the row [n_q][n], and the outputs above
+   void batch_config_penetration(int id, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
+      double margin_field, double margin_self, double * cost, double * grad, double * clearance, int * sphere, int * other);
    // (multistart.cpp) orc_batch_select_best[_by], _respawn, _select_clear: each checks every argument on the host, then takes the
    // verdict with Batch::selection_scope() (collision_free; collision_mode 1, 2) or the clearance, then selects or respawns on the device
    void batch_select_best(int id, int cost_column, int n_groups, const int * group_of_run, bool collision_free, int * best_run, double * best_cost,

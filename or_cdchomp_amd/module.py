@@ -11,7 +11,7 @@ import math
 
 import numpy as np
 
-from . import _capi
+from . import _capi, pushout
 
 
 def _dp(a):
@@ -1068,12 +1068,8 @@ class Module:
                                                   int(max_samples), _dp(clr), _dp(tim), _ip(sph), _ip(oth), _ip(cnt)))
         return dict(clearance=clr, time=tim, sphere=sph, other=oth, n_samples=cnt)
 
-    def batch_config_clearance(self, bid, configs, runs=None):
-        """The clearance of given configurations, on the device (orc_batch_config_clearance): the per-sample body of
-        batch_clearance's walk without a trajectory around it.  configs [n_q][n] (or one row [n]), rows as batch_gettraj
-        returns them; runs: the run whose scene each is tested against, an int array [n_q], one int for all, or None for
-        run 0.  Returns a dict: clearance [n_q][2] (fields; self), sphere [n_q][2], other [n_q][2] (the field; the other
-        sphere).  A minimum over nothing is +inf with -1, -1; a row with a non-finite entry reports NaN with -1, -1."""
+    def _config_queries(self, bid, configs, runs):
+        """the arguments of the calls that take configurations: (configs [n_q][n] of doubles, runs int32 [n_q] or None)"""
         n_runs, _, n = self.batch_dims(bid)
         cf = np.ascontiguousarray(configs, dtype=np.float64)
         if cf.ndim == 1:
@@ -1089,25 +1085,11 @@ class Module:
                 raise ValueError("runs has %d entries for %d configurations" % (rq.size, n_q))
             if ((rq < 0) | (rq >= n_runs)).any():
                 raise ValueError("a run lies outside [0, %d)" % n_runs)
-        clr = np.zeros((n_q, 2)); sph = np.zeros((n_q, 2), dtype=np.int32); oth = np.zeros((n_q, 2), dtype=np.int32)
-        self._check(self._lib.orc_batch_config_clearance(self._h, bid, n_q, None if rq is None else _ip(rq), _dp(cf), _dp(clr),
-                                                         _ip(sph), _ip(oth)))
-        return dict(clearance=clr, sphere=sph, other=oth)
+        return cf, rq
 
-    def batch_config_chunk(self, bid):
-        """how many consecutive queries a workgroup of the configuration-clearance kernel takes for this batch (64, or what
-        the LDS of a CU holds of the robot); a query's answer does not depend on it"""
-        out = np.zeros(1)
-        self._check(self._lib.orc_batch_get_state(self._h, bid, b"config_chunk", _dp(out), out.size))
-        return int(out[0])
-
-    def batch_waypoint_clearance(self, bid, runs=None, points=None):
-        """The clearance of waypoints of the batch's trajectories as they stand on the device
-        (orc_batch_waypoint_clearance); nothing is uploaded but indices.  runs and points None: the whole profile, arrays
-        [n_runs][n_points][2].  points an int or a sequence with runs None: those waypoints of every run,
-        [n_runs][len(points)][2]; a negative index counts from the end, so points=(0, -1) is "starts and goals".  runs and
-        points both arrays [n_q]: those waypoints, [n_q][2].  Returns a dict: clearance, sphere, other, as
-        batch_config_clearance."""
+    def _waypoint_queries(self, bid, runs, points):
+        """the arguments of the calls that take waypoints: (runs, points: int32 [n_q], or both None for the profile; the
+        shape of the answer without its last axis)"""
         n_runs, n_points, _ = self.batch_dims(bid)
         if points is None and runs is not None:
             raise ValueError("runs needs points: both None is the whole profile")
@@ -1135,11 +1117,99 @@ class Module:
                     raise ValueError("a run lies outside [0, %d)" % n_runs)
                 shape = (rq.size,)
             rq = np.ascontiguousarray(rq, dtype=np.int32); pq = np.ascontiguousarray(pq, dtype=np.int32)
+        return rq, pq, shape
+
+    def batch_config_clearance(self, bid, configs, runs=None):
+        """The clearance of given configurations, on the device (orc_batch_config_clearance): the per-sample body of
+        batch_clearance's walk without a trajectory around it.  configs [n_q][n] (or one row [n]), rows as batch_gettraj
+        returns them; runs: the run whose scene each is tested against, an int array [n_q], one int for all, or None for
+        run 0.  Returns a dict: clearance [n_q][2] (fields; self), sphere [n_q][2], other [n_q][2] (the field; the other
+        sphere).  A minimum over nothing is +inf with -1, -1; a row with a non-finite entry reports NaN with -1, -1."""
+        cf, rq = self._config_queries(bid, configs, runs)
+        n_q = cf.shape[0]
+        clr = np.zeros((n_q, 2)); sph = np.zeros((n_q, 2), dtype=np.int32); oth = np.zeros((n_q, 2), dtype=np.int32)
+        self._check(self._lib.orc_batch_config_clearance(self._h, bid, n_q, None if rq is None else _ip(rq), _dp(cf), _dp(clr),
+                                                         _ip(sph), _ip(oth)))
+        return dict(clearance=clr, sphere=sph, other=oth)
+
+    def batch_config_chunk(self, bid):
+        """how many consecutive queries a workgroup of the configuration-clearance kernel takes for this batch (64, or what
+        the LDS of a CU holds of the robot); a query's answer does not depend on it"""
+        out = np.zeros(1)
+        self._check(self._lib.orc_batch_get_state(self._h, bid, b"config_chunk", _dp(out), out.size))
+        return int(out[0])
+
+    def batch_waypoint_clearance(self, bid, runs=None, points=None):
+        """The clearance of waypoints of the batch's trajectories as they stand on the device
+        (orc_batch_waypoint_clearance); nothing is uploaded but indices.  runs and points None: the whole profile, arrays
+        [n_runs][n_points][2].  points an int or a sequence with runs None: those waypoints of every run,
+        [n_runs][len(points)][2]; a negative index counts from the end, so points=(0, -1) is "starts and goals".  runs and
+        points both arrays [n_q]: those waypoints, [n_q][2].  Returns a dict: clearance, sphere, other, as
+        batch_config_clearance."""
+        rq, pq, shape = self._waypoint_queries(bid, runs, points)
         n_q = int(np.prod(shape))
         clr = np.zeros(shape + (2,)); sph = np.zeros(shape + (2,), dtype=np.int32); oth = np.zeros(shape + (2,), dtype=np.int32)
         self._check(self._lib.orc_batch_waypoint_clearance(self._h, bid, n_q, None if rq is None else _ip(rq),
                                                            None if pq is None else _ip(pq), _dp(clr), _ip(sph), _ip(oth)))
         return dict(clearance=clr, sphere=sph, other=oth)
+
+    @staticmethod
+    def _margins(margin):
+        m = np.asarray(margin, dtype=np.float64).reshape(-1)
+        if m.size == 1:
+            m = np.repeat(m, 2)
+        if m.size != 2 or not np.isfinite(m).all() or (m < 0).any():
+            raise ValueError("margin is (fields, self): finite and not negative")
+        return float(m[0]), float(m[1])
+
+    def batch_config_penetration(self, bid, configs, runs=None, margin=(0.02, 0.0)):
+        """Which way is out of contact, on the device (orc_batch_config_penetration): configs and runs as in
+        batch_config_clearance; margin (fields, self) in metres.  Returns a dict: cost [n_q][2], the penetration cost
+        1/2 sum max(0, margin - gap)^2 of the field leg and of the self-collision leg; grad [n_q][n], the derivative of their
+        sum with respect to the row; clearance, sphere, other as batch_config_clearance returns them, bit for bit.  A row
+        with a non-finite entry reports NaN everywhere and -1, -1."""
+        cf, rq = self._config_queries(bid, configs, runs)
+        mf, ms = self._margins(margin)
+        n_q, n = cf.shape
+        cst = np.zeros((n_q, 2)); grd = np.zeros((n_q, n)); clr = np.zeros((n_q, 2))
+        sph = np.zeros((n_q, 2), dtype=np.int32); oth = np.zeros((n_q, 2), dtype=np.int32)
+        self._check(self._lib.orc_batch_config_penetration(self._h, bid, n_q, None if rq is None else _ip(rq), _dp(cf), mf, ms, _dp(cst),
+                                                           _dp(grd), _dp(clr), _ip(sph), _ip(oth)))
+        return dict(cost=cst, grad=grd, clearance=clr, sphere=sph, other=oth)
+
+    def batch_penetration_chunk(self, bid):
+        """how many consecutive queries a workgroup of the penetration kernel takes for this batch; a query's answer does
+        not depend on it"""
+        out = np.zeros(1)
+        self._check(self._lib.orc_batch_get_state(self._h, bid, b"penetration_chunk", _dp(out), out.size))
+        return int(out[0])
+
+    def batch_waypoint_penetration(self, bid, runs=None, points=None, margin=(0.02, 0.0)):
+        """batch_config_penetration of waypoints of the batch's trajectories as they stand on the device
+        (orc_batch_waypoint_penetration); runs and points as in batch_waypoint_clearance, and the arrays of the answer are
+        shaped the same way, grad with n as its last axis."""
+        rq, pq, shape = self._waypoint_queries(bid, runs, points)
+        mf, ms = self._margins(margin)
+        n = self.batch_dims(bid)[2]
+        n_q = int(np.prod(shape))
+        cst = np.zeros(shape + (2,)); grd = np.zeros(shape + (n,)); clr = np.zeros(shape + (2,))
+        sph = np.zeros(shape + (2,), dtype=np.int32); oth = np.zeros(shape + (2,), dtype=np.int32)
+        self._check(self._lib.orc_batch_waypoint_penetration(self._h, bid, n_q, None if rq is None else _ip(rq),
+                                                             None if pq is None else _ip(pq), mf, ms, _dp(cst), _dp(grd), _dp(clr),
+                                                             _ip(sph), _ip(oth)))
+        return dict(cost=cst, grad=grd, clearance=clr, sphere=sph, other=oth)
+
+    def batch_push_out(self, bid, configs, runs=None, margin=(0.02, 0.0), slack=2e-3, max_steps=20, step_cap=0.2, lower=None,
+                       upper=None):
+        """Move configurations in contact out to `margin` (pushout.push_out around batch_config_penetration): configs and
+        runs as in batch_config_penetration, lower and upper [n] the limits a row is clipped to (None: none).  Returns (rows
+        [n_q][n], steps int32 [n_q], status int32 [n_q]: 0 clear, 1 the gradient vanished while in contact, 2 out of steps)."""
+        cf, rq = self._config_queries(bid, configs, runs)
+
+        def evaluate(rows, m, index):      # (the rows still active: their runs go with them)
+            return self.batch_config_penetration(bid, rows, runs=None if rq is None else rq[index], margin=m)
+
+        return pushout.push_out(evaluate, cf, margin, slack, max_steps, step_cap, lower, upper, indexed=True)
 
     def batch_select_clear(self, bid, groups=None, n_groups=None, margin=0.0, by="total", max_samples=65536):
         """The best run of every group among the candidates that keep `margin` metres of clearance, on the device
