@@ -392,7 +392,9 @@ int orc_batch_set_verdict_scope(orc_module * mod, int batch_id, int scope);
  * per CU, tiles, lanes per waypoint; a ninth, the moving waypoints of the first tile, when cap_doubles >= 9);
  * "run_params" ([n_runs][4]: lambda, epsilon, obs_factor, obs_factor_self as the device holds them, orc_batch_set_run_params);
  * "config_chunk" (1 number: the consecutive queries a workgroup of orc_batch_config_clearance's kernel takes for this batch);
- * "penetration_chunk" (1 number: the same of orc_batch_config_penetration's kernel) */
+ * "penetration_chunk" (1 number: the same of orc_batch_config_penetration's kernel);
+ * "project_state" (2 numbers: 1 when a lane's state of orc_batch_project_tsr's kernel lives in LDS for this batch, 0 when it
+ * lives in the call's workspace, for TSRs of up to 3 and of up to 6 enforced rows) */
 int orc_batch_get_state(orc_module * mod, int batch_id, const char * which, double * out, size_t cap_doubles);
 int orc_batch_dims(orc_module * mod, int batch_id, int * n_runs, int * n_points, int * n);
 /* overwrite the trajectories of a batch (warm start; what `create starttraj` does for one run,
@@ -579,6 +581,43 @@ int orc_batch_config_penetration(orc_module * mod, int batch_id, int n_q, const 
    double * clearance_out /* [n_q][2] */, int * sphere_out, int * other_out /* [n_q][2] each */);
 int orc_batch_waypoint_penetration(orc_module * mod, int batch_id, int n_q, const int * run_of_q, const int * point_of_q,
    double margin_field, double margin_self, double * cost_out, double * grad_out, double * clearance_out, int * sphere_out, int * other_out);
+/* ---- task space regions at single configurations: batched inverse kinematics for goals -----------------------------
+ * "The hand at this pose" as configurations.  A TSR is what con_tsr, everyn_tsr and start_tsr of `create` take (struct tsr,
+ * src/orcdchomp_mod.h:80-87), with the end effector it is about: */
+typedef struct orc_tsr
+{
+   int ee_link;        /* link index; -1: the robot's active manipulator (its link and tool; `tool` below is ignored) */
+   double tool[7];     /* end effector in the link frame */
+   double T0w[7], Twe[7];
+   double Bw[6][2];    /* x y z roll pitch yaw; a row is enforced iff Bw[i] == {0,0}, exactly as create's con_tsr (mod.cpp:2466-2480) */
+} orc_tsr;
+/* The value and the Jacobian of TSRs at given configurations, on the device; stateless.  Row q is configs[q] (the batch's
+ * columns: 7 of a floating base, whose quaternion is used as given, then the active dofs) with tsrs[tsr_of_q[q]], or tsrs[0]
+ * when tsr_of_q is NULL.  h_out [n_q][6]: the k enforced entries of the TSR's xyzrpy value in con_tsr's order (that of the Bw rows: x y z
+ * roll pitch yaw), jac_out [n_q][6][n] (or NULL) their Jacobian rows; rows from k on are
+ * zero.  These are the h and J the constraint step of iterate sees for a trajectory row: the same device function
+ * (tsr_eval_point), the batch's model -- robot, base pose, active dofs, precision -- as `create` folded it.  A row with a
+ * non-finite entry has NaN in its k rows.
+ * Rejected with a nonzero return and a message before any device work, the module usable: an unknown batch; n_q < 1 or
+ * n_q > 2^22; n_tsr < 1; a tsr_of_q entry outside [0, n_tsr); NULL tsrs, configs or h_out; an ee_link outside the robot's
+ * links; ee_link -1 on a robot without a manipulator; a TSR with no enforced row or a non-finite pose; a robot whose
+ * active dofs are no longer the batch's. */
+int orc_batch_config_tsr(orc_module * mod, int batch_id, int n_tsr, const orc_tsr * tsrs, int n_q, const int * tsr_of_q /* NULL: tsr 0 */,
+   const double * configs /* [n_q][n] */, double * h_out /* [n_q][6] */, double * jac_out /* [n_q][6][n] or NULL */);
+/* Projects every row onto its TSR, the whole iteration on the device (one lane per row).  At iterate q with r = max_i |h_i|:
+ * r <= tol: done, status 0.  Otherwise (J J^T + mu I_k) y = h by Cholesky in the order of the rows, dq = -J^T y, shortened to
+ * step_cap in the 2-norm, q <- clip(q + dq, lower, upper) (lower, upper [n] or NULL: no box).  Status 1: a pivot that is not
+ * positive and finite, or a step that moves no entry; 2: out of steps; 3: a row with a non-finite entry (every output of the
+ * row NaN, 0 steps).  A row that is not done comes back as the visited iterate of smallest r, never worse than the input; a
+ * row within tol, and every row when max_steps is 0, comes back bit for bit with 0 steps, and so does every entry that a
+ * projection leaves where it was (a dof that does not move the link), in a precision-32 batch too.  resid_out is r of the returned
+ * row.  The arithmetic is in the batch's precision, the outputs are doubles; or_cdchomp_amd/project.py is the rule.
+ * A row's answer depends on the row, its TSR and the parameters only: not on its place, on n_q, or on the shard.
+ * Rejected as above, and: a NULL output; a NaN or non-positive tol or step_cap; a NaN or negative mu; max_steps outside
+ * [0, 256]; lower[c] > upper[c]; a floating-base batch (the update of a quaternion column is not defined here). */
+int orc_batch_project_tsr(orc_module * mod, int batch_id, int n_tsr, const orc_tsr * tsrs, int n_q, const int * tsr_of_q,
+   const double * configs, const double * lower, const double * upper /* [n] each or NULL */, int max_steps, double tol, double mu,
+   double step_cap, double * configs_out /* [n_q][n] */, double * resid_out /* [n_q] */, int * steps_out, int * status_out);
 /* The best run of every group among those that keep a margin.  n_groups and group_of_run as in orc_batch_select_best.  A run
  * is eligible when all three hold: it is a candidate (status 0 or 1 and a finite total cost); it was walked, i.e. is not too
  * long for max_samples; fmin(clearance[0], clearance[1]) >= margin.  margin 0 is orc_batch_select_best_by's

@@ -32,6 +32,12 @@ class BatchParams(C.Structure):
                 ("obs_factor_self", C.c_double), ("precision", C.c_int)]
 
 
+class Tsr(C.Structure):
+    """orc_tsr: poses are [x y z qx qy qz qw]; a Bw row [0 0] is enforced"""
+    _fields_ = [("ee_link", C.c_int), ("tool", C.c_double * 7), ("T0w", C.c_double * 7), ("Twe", C.c_double * 7),
+                ("Bw", (C.c_double * 2) * 6)]
+
+
 # every symbol include/orcdchomp_amd.h declares: (name, restype, argtypes)
 SYMBOLS = [
     ("orc_module_new", C.c_void_p, [C.c_int]),
@@ -103,6 +109,9 @@ SYMBOLS = [
                                                c_double_p, c_int_p, c_int_p]),
     ("orc_batch_waypoint_penetration", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, C.c_double, C.c_double, c_double_p, c_double_p,
                                                  c_double_p, c_int_p, c_int_p]),
+    ("orc_batch_config_tsr", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Tsr), C.c_int, c_int_p, c_double_p, c_double_p, c_double_p]),
+    ("orc_batch_project_tsr", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Tsr), C.c_int, c_int_p, c_double_p, c_double_p, c_double_p,
+                                        C.c_int, C.c_double, C.c_double, C.c_double, c_double_p, c_double_p, c_int_p, c_int_p]),
     ("orc_batch_select_clear", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_int, c_int_p, c_double_p,
                                          c_double_p, c_int_p, c_int_p]),
     ("orc_batch_respawn", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, C.c_int, C.c_double, c_uint_p,

@@ -1,5 +1,6 @@
 // batch.h -- a batch of CHOMP runs as the host layer holds it: the shard of its runs on one device, the batch over the shards, and
-// the small structs their calls take (batch.cpp, verdict.cpp, clearance.cpp, config_clearance.cpp, penetration.cpp, multistart.cpp).
+// the small structs their calls take (batch.cpp, verdict.cpp, clearance.cpp, config_clearance.cpp, penetration.cpp, project.cpp,
+// multistart.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -47,6 +48,22 @@ struct PenetrationOut
    double * cost = nullptr, * grad = nullptr, * clear = nullptr;
    unsigned int * key = nullptr;
    PenetrationOut from(size_t first, int n) const;
+};
+
+// the parameters of a projection onto TSRs (project.cpp; or_cdchomp_amd/project.py is the rule); lower, upper [n] or NULL
+struct ProjectSpec
+{
+   int max_steps = 30;
+   double tol = 1e-6, mu = 1e-8, step_cap = 0.5;
+   const double * lower = nullptr, * upper = nullptr;
+};
+// where the results of the two TSR calls go: h [n_q][6], jac [n_q][6][n] (the evaluation); rows [n_q][n], resid, steps, status
+// [n_q] (the projection); any may be NULL
+struct ProjectOut
+{
+   double * h = nullptr, * jac = nullptr, * rows = nullptr, * resid = nullptr;
+   int * steps = nullptr, * status = nullptr;
+   ProjectOut from(size_t first, int n) const;
 };
 
 class Module;
@@ -122,6 +139,12 @@ public:
    void config_penetration(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
                            double margin_field, double margin_self, const PenetrationOut & out);
    int penetration_chunk() const;            // the queries a workgroup of that kernel takes
+   // (project.cpp) the constraints `specs` (ee_link resolved, one point each) folded with `robot` as `create` folds a batch's, and
+   // at n_q rows configs [n_q][n] with tsr_of_q [n_q] (NULL: specs[0]): their value and Jacobian (ps NULL), or the projection
+   // onto them (project_kernels.hip); nothing is kept on the device
+   void project_tsr(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
+                    const ProjectSpec * ps, const ProjectOut & out);
+   int project_state_in_lds(int kmax) const; // 1: a lane's state of that kernel (kmax 3 or 6 rows) lives in LDS for this batch, 0: in the call's workspace
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
    // kernel timing: completed event pairs are added to the module's totals (all of them when `wait`)
@@ -160,6 +183,8 @@ private:
       const double * configs, double * clear_out, unsigned int * key_out);
    template <typename real> void config_penetration_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q,
       const double * configs, double margin_field, double margin_self, const PenetrationOut & out);
+   template <typename real> void project_tsr_typed(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q,
+      const double * configs, const ProjectSpec * ps, const ProjectOut & out);
    void construct(const Robot & robot, const double * starts, const double * goals, const double * basegoals,
       const unsigned int * seeds);
    Module * mod_;
@@ -255,6 +280,10 @@ public:
    // them (the caller has made config_clearance_check and checked the margins)
    void config_penetration(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q,
                            const double * configs, double margin_field, double margin_self, const PenetrationOut & out);
+   // (project.cpp) orc_batch_config_tsr / orc_batch_project_tsr: every shard takes an even contiguous slice of the queries (the
+   // caller, Module::project_check, has checked the arguments)
+   void project_tsr(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
+                    const ProjectSpec * ps, const ProjectOut & out);
    // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
    // kept until it is set again
    int verdict_scope = 0;

@@ -621,6 +621,12 @@ int orc_batch_get_state(orc_module * mod, int id, const char * which, double * o
          out[0] = (double) b.shards[0]->penetration_chunk();
          return;
       }
+      if (std::string(which) == "project_state")      // where a lane's state of project_tsr_kernel lives: [0] up to 3 enforced rows, [1] up to 6
+      {
+         if (cap < 2) throw std::runtime_error("buffer too small!");
+         out[0] = (double) b.shards[0]->project_state_in_lds(3); out[1] = (double) b.shards[0]->project_state_in_lds(6);
+         return;
+      }
       if (std::string(which) == "run_params")
       {
          if (cap < (size_t) b.n_runs * 4) throw std::runtime_error("buffer too small!");
@@ -708,6 +714,44 @@ int orc_batch_waypoint_penetration(orc_module * mod, int id, int n_q, const int 
    return guarded(mod, [&] {
       mod->impl->batch_config_penetration(id, true, n_q, run_of_q, point_of_q, nullptr, margin_field, margin_self, cost_out, grad_out, clearance_out,
          sphere_out, other_out);
+   });
+}
+
+namespace {
+// the caller's TSRs as the host layer holds them (ee_link -1, the active manipulator, is resolved by Module::project_check)
+std::vector<orc::TsrSpec> to_tsrs(int n_tsr, const orc_tsr * tsrs)
+{
+   if (n_tsr < 1) throw std::runtime_error("n_tsr must be >= 1!");
+   need(tsrs, "tsrs");
+   std::vector<orc::TsrSpec> out(n_tsr);
+   for (int t=0; t<n_tsr; t++)
+   {
+      out[t].ee_link = tsrs[t].ee_link;
+      out[t].tool = orc::Pose(tsrs[t].tool); out[t].T0w = orc::Pose(tsrs[t].T0w); out[t].Twe = orc::Pose(tsrs[t].Twe);
+      for (int r=0; r<6; r++) { out[t].Bw[r][0] = tsrs[t].Bw[r][0]; out[t].Bw[r][1] = tsrs[t].Bw[r][1]; }
+   }
+   return out;
+}
+}
+
+int orc_batch_config_tsr(orc_module * mod, int id, int n_tsr, const orc_tsr * tsrs, int n_q, const int * tsr_of_q, const double * configs,
+   double * h_out, double * jac_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch(id);      // (an unknown batch first)
+      mod->impl->batch_config_tsr(id, to_tsrs(n_tsr, tsrs), n_q, tsr_of_q, configs, h_out, jac_out);
+   });
+}
+
+int orc_batch_project_tsr(orc_module * mod, int id, int n_tsr, const orc_tsr * tsrs, int n_q, const int * tsr_of_q, const double * configs,
+   const double * lower, const double * upper, int max_steps, double tol, double mu, double step_cap, double * configs_out,
+   double * resid_out, int * steps_out, int * status_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch(id);
+      orc::ProjectSpec ps;
+      ps.max_steps = max_steps; ps.tol = tol; ps.mu = mu; ps.step_cap = step_cap; ps.lower = lower; ps.upper = upper;
+      mod->impl->batch_project_tsr(id, to_tsrs(n_tsr, tsrs), n_q, tsr_of_q, configs, ps, configs_out, resid_out, steps_out, status_out);
    });
 }
 

@@ -67,6 +67,15 @@ public:
    // cost of the two legs at the two margins [n_q][2], its gradient with respect to the row [n_q][n], and the outputs above
    void batch_config_penetration(int id, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
       double margin_field, double margin_self, double * cost, double * grad, double * clearance, int * sphere, int * other);
+   // (project.cpp) orc_batch_config_tsr: the enforced entries of a TSR's xyzrpy value [n_q][6] and their Jacobian rows [n_q][6][n]
+   // (or NULL) at n_q rows, tsrs[tsr_of_q[q]] at row q (tsr_of_q NULL: tsrs[0]; ee_link -1: the active manipulator);
+   // orc_batch_project_tsr: the rows projected onto their TSRs on the device.  project_check throws for what both reject
+   void batch_config_tsr(int id, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q, const double * configs, double * h_out,
+      double * jac_out);
+   void batch_project_tsr(int id, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q, const double * configs, const ProjectSpec & ps,
+      double * rows_out, double * resid_out, int * steps_out, int * status_out);
+   std::vector<TsrSpec> project_check(const char * who, const Batch & b, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q,
+      const double * configs) const;
    // (multistart.cpp) orc_batch_select_best[_by], _respawn, _select_clear: each checks every argument on the host, then takes the
    // verdict with Batch::selection_scope() (collision_free; collision_mode 1, 2) or the clearance, then selects or respawns on the device
    void batch_select_best(int id, int cost_column, int n_groups, const int * group_of_run, bool collision_free, int * best_run, double * best_cost,

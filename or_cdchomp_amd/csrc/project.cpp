@@ -1,0 +1,200 @@
+// project.cpp -- host side of the TSR calls on single configurations (orc_batch_config_tsr, orc_batch_project_tsr): the checks of
+// their arguments, the constraints folded with the batch's robot and joint tree through fold_tsrs (one constraint on one point
+// each), the queries dealt to the shards in even contiguous slices (a row names no run: any split does), the launches of
+// project_kernels.hip.  The model is the one `create` put on the device; nothing is kept there after the call.
+#include "module.h"
+#include "project_device.h"
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <stdexcept>
+
+namespace orc {
+
+ProjectOut ProjectOut::from(size_t first, int n) const
+{
+   ProjectOut o;
+   o.h = h ? h + 6*first : nullptr; o.jac = jac ? jac + (size_t) 6*n*first : nullptr;
+   o.rows = rows ? rows + (size_t) n*first : nullptr; o.resid = resid ? resid + first : nullptr;
+   o.steps = steps ? steps + first : nullptr; o.status = status ? status + first : nullptr;
+   return o;
+}
+
+// what both calls reject, before any device work; returns the constraints with `ee_link -1` resolved to the active manipulator
+std::vector<TsrSpec> Module::project_check(const char * who, const Batch & b, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q,
+   const double * configs) const
+{
+   const std::string w = std::string(who) + ": ";
+   const int n_tsr = (int) tsrs.size();
+   if (n_tsr < 1) throw std::runtime_error(w + "n_tsr must be >= 1!");
+   if (n_q < 1 || n_q > ORC_PROJECT_MAX_Q) throw std::runtime_error(w + "n_q must lie in [1, 4194304]!");
+   if (!configs) throw std::runtime_error(w + "configs [n_q][n] is NULL!");
+   for (int q=0; tsr_of_q && q<n_q; q++)
+      if (tsr_of_q[q] < 0 || tsr_of_q[q] >= n_tsr) throw std::runtime_error(w + "a tsr_of_q entry lies outside [0, n_tsr)!");
+   const Robot & robot = env.robot(b.robot_name);
+   if (robot.active_dofs != b.adofindices) throw std::runtime_error(w + "the robot's active dofs are not those the batch was created with!");
+   std::vector<TsrSpec> out = tsrs;
+   for (TsrSpec & t : out)
+   {
+      if (t.ee_link == -1)
+      {
+         if (robot.manips.empty()) throw std::runtime_error(w + "ee_link -1 names the active manipulator, and the robot has none!");
+         t.ee_link = robot.manips[robot.active_manip].link; t.tool = robot.manips[robot.active_manip].tool;
+      }
+      if (t.ee_link < 0 || t.ee_link >= robot.n_links) throw std::runtime_error(w + "ee_link lies outside the robot's links!");
+      int k = 0;
+      for (int r=0; r<6; r++) k += (t.Bw[r][0] == 0.0 && t.Bw[r][1] == 0.0) ? 1 : 0;
+      if (k == 0) throw std::runtime_error(w + "a TSR enforces no row (every Bw row has a range)!");
+      for (int e=0; e<7; e++)
+         if (!std::isfinite(t.tool.v[e]) || !std::isfinite(t.T0w.v[e]) || !std::isfinite(t.Twe.v[e])) throw std::runtime_error(w + "a TSR's poses must be finite numbers!");
+      t.point = 0;      // (fold_tsrs: one constraint on one point)
+   }
+   return out;
+}
+
+void Module::batch_config_tsr(int id, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q, const double * configs,
+   double * h_out, double * jac_out)
+{
+   Batch & b = batch(id);
+   const std::vector<TsrSpec> specs = project_check("config tsr", b, tsrs, n_q, tsr_of_q, configs);
+   if (!h_out) throw std::runtime_error("config tsr: h_out [n_q][6] is NULL!");
+   ProjectOut out;
+   out.h = h_out; out.jac = jac_out;
+   b.project_tsr(env.robot(b.robot_name), specs, n_q, tsr_of_q, configs, nullptr, out);
+}
+
+void Module::batch_project_tsr(int id, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q, const double * configs,
+   const ProjectSpec & ps, double * rows_out, double * resid_out, int * steps_out, int * status_out)
+{
+   Batch & b = batch(id);
+   const std::vector<TsrSpec> specs = project_check("project tsr", b, tsrs, n_q, tsr_of_q, configs);
+   if (!rows_out || !resid_out || !steps_out || !status_out) throw std::runtime_error("project tsr: configs_out, resid_out, steps_out and status_out are required!");
+   if (!(ps.tol > 0.0)) throw std::runtime_error("project tsr: tol must be a positive number!");
+   if (!(ps.step_cap > 0.0)) throw std::runtime_error("project tsr: step_cap must be a positive number!");
+   if (!(ps.mu >= 0.0)) throw std::runtime_error("project tsr: mu must be a number >= 0!");
+   if (ps.max_steps < 0 || ps.max_steps > ORC_PROJECT_MAX_STEPS) throw std::runtime_error("project tsr: max_steps must lie in [0, 256]!");
+   for (int c=0; c<b.n; c++)
+   {
+      const double lo = ps.lower ? ps.lower[c] : -HUGE_VAL, hi = ps.upper ? ps.upper[c] : HUGE_VAL;
+      if (std::isnan(lo) || std::isnan(hi) || lo > hi) throw std::runtime_error("project tsr: lower[c] <= upper[c] must hold for every column!");
+   }
+   if (b.params.floating_base) throw std::runtime_error("project tsr: a floating-base batch is not projected (its quaternion columns have no update rule here)!");
+   ProjectOut out;
+   out.rows = rows_out; out.resid = resid_out; out.steps = steps_out; out.status = status_out;
+   b.project_tsr(env.robot(b.robot_name), specs, n_q, tsr_of_q, configs, &ps, out);
+}
+
+void Batch::project_tsr(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
+   const ProjectSpec * ps, const ProjectOut & out)
+{
+   // shard k takes the queries [n_q k / S, n_q (k + 1) / S): slices of the caller's arrays, nothing is gathered
+   const size_t S = shards.size();
+   for_shards([&](size_t k) {
+      const size_t q0 = (size_t) n_q * k / S, q1 = (size_t) n_q * (k + 1) / S;
+      if (q1 == q0) return;
+      shards[k]->project_tsr(robot, specs, (int)(q1 - q0), tsr_of_q ? tsr_of_q + q0 : nullptr, configs + q0 * n, ps, out.from(q0, n));
+   }, true);
+}
+
+template <typename real>
+void BatchShard::project_tsr_typed(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
+   const ProjectSpec * ps, const ProjectOut & out)
+{
+   hipStream_t st = stream_;
+   // the constraints on the device's joint order: fold_tsrs' path, for a trajectory of one moving point
+   const JointTree tree = fold_joint_tree(robot, params.floating_base != 0);
+   if (tree.nj() != ms_.nj) throw std::runtime_error("project tsr: the robot's joint tree is not the one the batch was created with!");
+   BatchParams one = params;
+   one.tsrs = specs;
+   const FoldedTsrs<real> ft = fold_tsrs<real>(robot, one, tree, 1, n);
+   int kmax = 3;
+   for (const DevTsr<real> & t : ft.tsrs) if (t.k > 3) kmax = 6;
+
+   DevProject<real> v;
+   std::memset(&v, 0, sizeof(v));
+   v.model = d_model_.as<const DevModel<real>>();
+   v.n_q = n_q; v.n = n; v.max_steps = ps ? ps->max_steps : -1;
+   v.stride = orc_project_stride(n, kmax);
+   DevBuf d_tsrs, d_of, d_cfg, d_lo, d_hi, d_ws, d_aws, d_h, d_jac, d_rows, d_resid, d_steps, d_status;
+   d_tsrs.reset(dev_alloc<DevTsr<real>>(ft.tsrs.size()));
+   hip_check(hipMemcpyAsync(d_tsrs.as<void>(), ft.tsrs.data(), ft.tsrs.size()*sizeof(DevTsr<real>), hipMemcpyHostToDevice, st), "project tsrs");
+   v.tsrs = d_tsrs.as<const DevTsr<real>>();
+   if (tsr_of_q)
+   {
+      d_of.reset(dev_alloc<int>(n_q));
+      hip_check(hipMemcpyAsync(d_of.as<void>(), tsr_of_q, (size_t) n_q*sizeof(int), hipMemcpyHostToDevice, st), "project tsr_of_q");
+      v.tsr_of_q = d_of.as<int>();
+   }
+   const size_t count = (size_t) n_q * n;
+   std::vector<real> narrowed;      // (a precision-32 batch: narrowed as set_traj narrows; it lives until the copy is done)
+   {
+      d_cfg.reset(dev_alloc<real>(count));
+      const void * src = configs;
+      if (sizeof(real) != sizeof(double)) { narrowed.assign(configs, configs + count); src = narrowed.data(); }
+      hip_check(hipMemcpyAsync(d_cfg.as<void>(), src, count*sizeof(real), hipMemcpyHostToDevice, st), "project rows");
+      v.configs = d_cfg.as<const real>();
+   }
+   // a lane's state: in LDS when a workgroup's states fit, else in a workspace of the call
+   if ((size_t) ORC_PROJECT_LANES * v.stride * sizeof(real) > ORC_PROJECT_LDS_BYTES)
+   {
+      d_ws.reset(dev_alloc<real>((size_t) n_q * v.stride));
+      v.ws = d_ws.as<real>();
+   }
+   d_aws.reset(dev_alloc<real>((size_t) ms_.nj * 6 * n_q));
+   v.aws = d_aws.as<real>();
+   std::vector<real> lo, hi;
+   if (ps)
+   {
+      v.tol = (real) ps->tol; v.mu = (real) ps->mu; v.step_cap = (real) ps->step_cap;
+      lo.resize(n); hi.resize(n);
+      for (int c=0; c<n; c++)
+      {
+         lo[c] = ps->lower ? (real) ps->lower[c] : -std::numeric_limits<real>::infinity();
+         hi[c] = ps->upper ? (real) ps->upper[c] : std::numeric_limits<real>::infinity();
+         // (precision 32: a limit that rounds outwards is taken one step inwards, so that a clipped row lies inside the caller's box)
+         if (ps->lower && (double) lo[c] < ps->lower[c]) lo[c] = std::nextafter(lo[c], std::numeric_limits<real>::infinity());
+         if (ps->upper && (double) hi[c] > ps->upper[c]) hi[c] = std::nextafter(hi[c], -std::numeric_limits<real>::infinity());
+      }
+      d_lo.reset(dev_alloc<real>(n)); d_hi.reset(dev_alloc<real>(n));
+      hip_check(hipMemcpyAsync(d_lo.as<void>(), lo.data(), n*sizeof(real), hipMemcpyHostToDevice, st), "project lower");
+      hip_check(hipMemcpyAsync(d_hi.as<void>(), hi.data(), n*sizeof(real), hipMemcpyHostToDevice, st), "project upper");
+      v.lower = d_lo.as<const real>(); v.upper = d_hi.as<const real>();
+      d_rows.reset(dev_alloc<double>(count)); d_resid.reset(dev_alloc<double>(n_q));
+      d_steps.reset(dev_alloc<int>(n_q)); d_status.reset(dev_alloc<int>(n_q));
+      // (the answer of a row that never improves on its input is the input: the caller's own doubles)
+      hip_check(hipMemcpyAsync(d_rows.as<void>(), configs, count*sizeof(double), hipMemcpyHostToDevice, st), "project rows out");
+      v.rows_out = d_rows.as<double>(); v.resid_out = d_resid.as<double>(); v.steps_out = d_steps.as<int>(); v.status_out = d_status.as<int>();
+   }
+   else
+   {
+      d_h.reset(dev_alloc<double>((size_t) n_q * 6)); d_jac.reset(dev_alloc<double>(count * 6));
+      hip_check(hipMemsetAsync(d_h.as<void>(), 0, (size_t) n_q*6*sizeof(double), st), "config tsr h");
+      hip_check(hipMemsetAsync(d_jac.as<void>(), 0, count*6*sizeof(double), st), "config tsr jac");
+      v.h_out = d_h.as<double>(); v.jac_out = d_jac.as<double>();
+   }
+   hip_check(orc_launch_project(v, kmax, st), "project_tsr_kernel launch");
+   if (out.h) hip_check(hipMemcpyAsync(out.h, d_h.as<void>(), (size_t) n_q*6*sizeof(double), hipMemcpyDeviceToHost, st), "config tsr h");
+   if (out.jac) hip_check(hipMemcpyAsync(out.jac, d_jac.as<void>(), count*6*sizeof(double), hipMemcpyDeviceToHost, st), "config tsr jac");
+   if (out.rows) hip_check(hipMemcpyAsync(out.rows, d_rows.as<void>(), count*sizeof(double), hipMemcpyDeviceToHost, st), "project rows");
+   if (out.resid) hip_check(hipMemcpyAsync(out.resid, d_resid.as<void>(), (size_t) n_q*sizeof(double), hipMemcpyDeviceToHost, st), "project residuals");
+   if (out.steps) hip_check(hipMemcpyAsync(out.steps, d_steps.as<void>(), (size_t) n_q*sizeof(int), hipMemcpyDeviceToHost, st), "project steps");
+   if (out.status) hip_check(hipMemcpyAsync(out.status, d_status.as<void>(), (size_t) n_q*sizeof(int), hipMemcpyDeviceToHost, st), "project statuses");
+   hip_check(hipStreamSynchronize(st), "project sync");
+}
+
+void BatchShard::project_tsr(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
+   const ProjectSpec * ps, const ProjectOut & out)
+{
+   DeviceGuard guard(device);
+   if (params.precision == 64) project_tsr_typed<double>(robot, specs, n_q, tsr_of_q, configs, ps, out);
+   else project_tsr_typed<float>(robot, specs, n_q, tsr_of_q, configs, ps, out);
+}
+
+// where a lane's state lives for this batch's model and `kmax` enforced rows: 1 in LDS, 0 in the call's workspace
+int BatchShard::project_state_in_lds(int kmax) const
+{
+   const size_t real_size = params.precision == 64 ? sizeof(double) : sizeof(float);
+   return (size_t) ORC_PROJECT_LANES * orc_project_stride(n, kmax) * real_size <= ORC_PROJECT_LDS_BYTES ? 1 : 0;
+}
+
+} // namespace orc

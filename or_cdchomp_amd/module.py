@@ -11,7 +11,7 @@ import math
 
 import numpy as np
 
-from . import _capi, pushout
+from . import _capi, project, pushout
 
 
 def _dp(a):
@@ -593,6 +593,9 @@ class Module:
         if not self._h:
             raise RuntimeError(self._lib.orc_last_error(None).decode())
         self._keep = []
+        self._models = {}      # the robots add_robot was given, by name: what names a link or a manipulator, and the limits
+        self._adofs = {}       # their active dofs as set through this object
+        self._batch_robot = {} # batch id -> (robot name, its active dofs at batch_create)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -647,7 +650,8 @@ class Module:
         d.sphere_link = _ip(a["sphere_link"]); d.sphere_pos = _dp(a["sphere_pos"])
         d.sphere_radius = _dp(a["sphere_radius"])
         self._check(self._lib.orc_env_add_robot(self._h, model.name.encode(), C.byref(d)))
-        names = (C.c_char_p * len(model.link_names))(*[nm.encode() for nm in model.link_names])
+        self._models[model.name] = model
+        names =(C.c_char_p * len(model.link_names))(*[nm.encode() for nm in model.link_names])
         self._check(self._lib.orc_robot_set_link_names(self._h, model.name.encode(), names, len(model.link_names)))
         for mname, link, tool in getattr(model, "manipulators", []):
             self.add_manipulator(model.name, mname, model.link_names.index(link), tool)
@@ -684,6 +688,7 @@ class Module:
     def set_active_dofs(self, name, indices):
         idx = np.ascontiguousarray(indices, dtype=np.int32)
         self._check(self._lib.orc_robot_set_active_dofs(self._h, name.encode(), _ip(idx), len(idx)))
+        self._adofs[name] = [int(i) for i in idx]
 
     def set_velocity_limits(self, name, limits):
         v = _f64(limits)
@@ -822,11 +827,13 @@ class Module:
                 None if st is None else _dp(st), _dp(goals), None if bg is None else _dp(bg),
                 None if sd is None else sd.ctypes.data_as(_capi.c_uint_p),
                 len(begin) - 1, _ip(begin), cnames, None if poses is None else _dp(poses), _ip(sor), C.byref(bid)))
+            self._batch_robot[bid.value] = (robot, self._adofs.get(robot))
             return bid.value
         self._check(self._lib.orc_batch_create(
             self._h, robot.encode(), C.byref(p), n_runs,
             None if st is None else _dp(st), _dp(goals), None if bg is None else _dp(bg),
             None if sd is None else sd.ctypes.data_as(_capi.c_uint_p), C.byref(bid)))
+        self._batch_robot[bid.value] = (robot, self._adofs.get(robot))
         return bid.value
 
     def batch_dims(self, bid):
@@ -1211,6 +1218,135 @@ class Module:
 
         return pushout.push_out(evaluate, cf, margin, slack, max_steps, step_cap, lower, upper, indexed=True)
 
+    def _batch_model(self, bid):
+        """(model, active dofs or None) of the batch's robot: what batch_create recorded, or the only robot there is"""
+        name, adofs = self._batch_robot.get(bid, (None, None))
+        if name is None and len(self._models) == 1:
+            name = next(iter(self._models))
+            adofs = self._adofs.get(name)
+        if name not in self._models:
+            raise ValueError("the robot of batch %d is not known to this object: address the end effector by a link index, and pass "
+                             "lower and upper" % bid)
+        return self._models[name], adofs
+
+    def _tsr_records(self, bid, tsrs, link, manip):
+        """robots.Tsr objects as an array of orc_tsr.  The end effector is addressed as the head of `con_tsr '...'` addresses it:
+        neither link nor manip: the active manipulator; manip NAME: that manipulator's link and tool; link NAME (or a link
+        index): that link's frame."""
+        if isinstance(tsrs, tuple) and len(tsrs) == 2 and isinstance(tsrs[0], C.Array):
+            return tsrs      # (records made before: batch_tsr_records)
+        tsrs = list(tsrs) if isinstance(tsrs, (list, tuple)) else [tsrs]
+        if not tsrs:
+            raise ValueError("tsrs is empty")
+        if link is not None and manip is not None:
+            raise ValueError("link and manip exclude each other")
+        ee, tool = -1, [0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0]
+        if manip is not None:
+            model, _ = self._batch_model(bid)
+            found = [m for m in model.manipulators if m[0] == manip]
+            if not found:
+                raise ValueError("con_tsr manip not found!")
+            ee, tool = model.link_names.index(found[0][1]), [float(v) for v in found[0][2]]
+        elif link is not None:
+            if isinstance(link, str):
+                model, _ = self._batch_model(bid)
+                if link not in model.link_names:
+                    raise ValueError("con_tsr link not found!")
+                link = model.link_names.index(link)
+            ee = int(link)
+            if ee < 0:
+                raise ValueError("con_tsr link not found!")
+        rec = (_capi.Tsr * len(tsrs))()
+        ks = np.zeros(len(tsrs), dtype=np.int32)
+        for t, tsr in enumerate(tsrs):
+            T0w, Twe = tsr.poses()
+            rec[t].ee_link = ee
+            for i in range(7):
+                rec[t].tool[i] = tool[i]; rec[t].T0w[i] = float(T0w[i]); rec[t].Twe[i] = float(Twe[i])
+            for r in range(6):
+                rec[t].Bw[r][0] = float(tsr.Bw[r, 0]); rec[t].Bw[r][1] = float(tsr.Bw[r, 1])
+            ks[t] = int(((tsr.Bw[:, 0] == 0.0) & (tsr.Bw[:, 1] == 0.0)).sum())
+        return rec, ks
+
+    def batch_tsr_records(self, bid, tsrs, link=None, manip=None):
+        """the form batch_config_tsr and batch_project_tsr turn their tsrs into, made once for many calls: pass the result as
+        `tsrs` (link and manip are then those given here)"""
+        return self._tsr_records(bid, tsrs, link, manip)
+
+    def _tsr_queries(self, bid, configs, tsr_of, n_tsr):
+        n = self.batch_dims(bid)[2]
+        cf = np.ascontiguousarray(configs, dtype=np.float64)
+        if cf.ndim == 1:
+            cf = cf.reshape(1, -1)
+        if cf.ndim != 2 or cf.shape[1] != n or cf.shape[0] < 1:
+            raise ValueError("configs is [n_q][%d], n_q >= 1" % n)
+        tq = None
+        if tsr_of is not None:
+            tq = np.ascontiguousarray(tsr_of, dtype=np.int32).reshape(-1)
+            if tq.size != cf.shape[0]:
+                raise ValueError("tsr_of has %d entries for %d configurations" % (tq.size, cf.shape[0]))
+            if ((tq < 0) | (tq >= n_tsr)).any():
+                raise ValueError("a tsr_of entry lies outside [0, %d)" % n_tsr)
+        return cf, tq
+
+    def batch_config_tsr(self, bid, tsrs, configs, tsr_of=None, link=None, manip=None):
+        """The value and the Jacobian of task space regions at given configurations, on the device (orc_batch_config_tsr).
+        tsrs: robots.Tsr objects (or one); configs [n_q][n] (or one row), rows as batch_gettraj returns them; tsr_of [n_q]: the
+        TSR of every row (None: the first); link / manip: the end effector, as the head of `con_tsr '...'` names it (neither:
+        the active manipulator).  Returns a dict: h [n_q][6], the k enforced entries of the xyzrpy value in the order of the Bw
+        rows; jac [n_q][6][n], their Jacobian rows; k int32 [n_q]; rows from k on are zero.  These are the h and J the
+        constraint step of batch_iterate sees for a trajectory row."""
+        rec, ks = self._tsr_records(bid, tsrs, link, manip)
+        cf, tq = self._tsr_queries(bid, configs, tsr_of, len(rec))
+        n_q, n = cf.shape
+        h = np.zeros((n_q, 6)); jac = np.zeros((n_q, 6, n))
+        self._check(self._lib.orc_batch_config_tsr(self._h, bid, len(rec), rec, n_q, None if tq is None else _ip(tq), _dp(cf), _dp(h),
+                                                   _dp(jac)))
+        return dict(h=h, jac=jac, k=ks[tq] if tq is not None else np.full(n_q, ks[0], dtype=np.int32))
+
+    def batch_project_tsr(self, bid, tsrs, configs, tsr_of=None, link=None, manip=None, lower="limits", upper="limits", tol=1e-6,
+                          mu=1e-8, step_cap=0.5, max_steps=30, clearance=False, runs=None):
+        """Project configurations onto task space regions, the whole iteration on the device (orc_batch_project_tsr; the rule is
+        project.project): batched inverse kinematics with thousands of seeds at once.  tsrs, configs, tsr_of, link and manip as
+        in batch_config_tsr; lower, upper [n]: the box every step is clipped to ("limits": the robot's joint limits of the
+        batch's active dofs; None: no box).  Returns (rows [n_q][n], resid [n_q], steps int32 [n_q], status int32 [n_q]: 0
+        within tol, 1 a singular system or a step that moves nothing, 2 out of steps, 3 a row with a non-finite entry).  A row
+        that is not done is the visited iterate of smallest residual.  clearance=True appends batch_config_clearance's dict of
+        the returned rows (runs: the run whose scene each is tested against, as there): what keeps the collision-free
+        solutions."""
+        rec, _ = self._tsr_records(bid, tsrs, link, manip)
+        cf, tq = self._tsr_queries(bid, configs, tsr_of, len(rec))
+        n_q, n = cf.shape
+        box = []
+        for name, side in (("limit_lower", lower), ("limit_upper", upper)):
+            if isinstance(side, str):
+                if side != "limits":
+                    raise ValueError('lower and upper are arrays [n], None or "limits"')
+                model, adofs = self._batch_model(bid)
+                lim = np.asarray(getattr(model, name), dtype=np.float64)
+                side = lim[adofs] if adofs is not None else lim
+            if side is not None:
+                side = np.ascontiguousarray(side, dtype=np.float64).reshape(-1)
+                if side.size != n:
+                    raise ValueError("lower and upper have %d entries, one per column" % n)
+            box.append(side)
+        rows = np.zeros((n_q, n)); resid = np.zeros(n_q)
+        steps = np.zeros(n_q, dtype=np.int32); status = np.zeros(n_q, dtype=np.int32)
+        self._check(self._lib.orc_batch_project_tsr(self._h, bid, len(rec), rec, n_q, None if tq is None else _ip(tq), _dp(cf),
+                                                    None if box[0] is None else _dp(box[0]), None if box[1] is None else _dp(box[1]),
+                                                    int(max_steps), float(tol), float(mu), float(step_cap), _dp(rows), _dp(resid),
+                                                    _ip(steps), _ip(status)))
+        if clearance:
+            return rows, resid, steps, status, self.batch_config_clearance(bid, rows, runs=runs)
+        return rows, resid, steps, status
+
+    def batch_project_state(self, bid):
+        """where a lane's state of the projection kernel lives for this batch: (TSRs of up to 3 enforced rows, of up to 6), each
+        "lds" or "global"; a row's answer does not depend on it"""
+        out = np.zeros(2)
+        self._check(self._lib.orc_batch_get_state(self._h, bid, b"project_state", _dp(out), out.size))
+        return tuple("lds" if v else "global" for v in out)
+
     def batch_select_clear(self, bid, groups=None, n_groups=None, margin=0.0, by="total", max_samples=65536):
         """The best run of every group among the candidates that keep `margin` metres of clearance, on the device
         (orc_batch_select_clear; the rule is select_clear's).  by: "total", "obs", "smooth" (the cost that is minimised) or
@@ -1257,6 +1393,7 @@ class Module:
 
     def batch_destroy(self, bid):
         self._check(self._lib.orc_batch_destroy(self._h, bid))
+        self._batch_robot.pop(bid, None)
 
     def kernel_time(self, reset=False):
         ms = C.c_double(); n = C.c_int()

@@ -37,6 +37,28 @@ def quat_mul(a, b):
             aw * bw - ax * bx - ay * by - az * bz]
 
 
+def pose_from_dR(d, R):
+    """[x y z qx qy qz qw] of a translation and a 3x3 rotation: cd_kin_pose_from_dR (reference src/libcd/kin.c:510-517) as
+    `create` applies it to a TSR's frames (the largest of the four squared components from the diagonal, ties to the later)"""
+    R = np.asarray(R, dtype=np.float64).reshape(3, 3)
+    d4 = [1.0 + R[0, 0] - R[1, 1] - R[2, 2], 1.0 - R[0, 0] + R[1, 1] - R[2, 2], 1.0 - R[0, 0] - R[1, 1] + R[2, 2],
+          1.0 + R[0, 0] + R[1, 1] + R[2, 2]]
+    q = [0.0] * 4
+    if d4[0] > d4[1] and d4[0] > d4[2] and d4[0] > d4[3]:
+        q[0] = math.sqrt(0.25 * d4[0]); v4 = 0.25 / q[0]
+        q[1] = v4 * (R[1, 0] + R[0, 1]); q[2] = v4 * (R[0, 2] + R[2, 0]); q[3] = v4 * (R[2, 1] - R[1, 2])
+    elif d4[1] > d4[2] and d4[1] > d4[3]:
+        q[1] = math.sqrt(0.25 * d4[1]); v4 = 0.25 / q[1]
+        q[0] = v4 * (R[1, 0] + R[0, 1]); q[2] = v4 * (R[2, 1] + R[1, 2]); q[3] = v4 * (R[0, 2] - R[2, 0])
+    elif d4[2] > d4[3]:
+        q[2] = math.sqrt(0.25 * d4[2]); v4 = 0.25 / q[2]
+        q[0] = v4 * (R[0, 2] + R[2, 0]); q[1] = v4 * (R[2, 1] + R[1, 2]); q[3] = v4 * (R[1, 0] - R[0, 1])
+    else:
+        q[3] = math.sqrt(0.25 * d4[3]); v4 = 0.25 / q[3]
+        q[0] = v4 * (R[2, 1] - R[1, 2]); q[1] = v4 * (R[0, 2] - R[2, 0]); q[2] = v4 * (R[1, 0] - R[0, 1])
+    return np.array([float(d[0]), float(d[1]), float(d[2])] + q)
+
+
 class RobotModel:
     def __init__(self, name):
         self.name = name
@@ -245,6 +267,10 @@ class Tsr:
         self.Bw = np.zeros((6, 2)) if Bw is None else np.asarray(Bw, dtype=np.float64).reshape(6, 2)
         self.manipindex = manipindex
         self.bodyandlink = bodyandlink
+
+    def poses(self):
+        """(T0w, Twe) as poses [x y z qx qy qz qw], the form `create` turns the wire format into"""
+        return pose_from_dR(self.T0w_d, self.T0w_R), pose_from_dR(self.Twe_d, self.Twe_R)
 
     def serialize(self):
         vals = []
