@@ -394,7 +394,10 @@ int orc_batch_set_verdict_scope(orc_module * mod, int batch_id, int scope);
  * "config_chunk" (1 number: the consecutive queries a workgroup of orc_batch_config_clearance's kernel takes for this batch);
  * "penetration_chunk" (1 number: the same of orc_batch_config_penetration's kernel);
  * "project_state" (2 numbers: 1 when a lane's state of orc_batch_project_tsr's kernel lives in LDS for this batch, 0 when it
- * lives in the call's workspace, for TSRs of up to 3 and of up to 6 enforced rows) */
+ * lives in the call's workspace, for TSRs of up to 3 and of up to 6 enforced rows);
+ * "tsr_plan" (11 numbers: constraints, constrained rows in all (cons_k), 1 when the constraint step is solved point by point
+ * (tsr_structured), n_max (tsr_nmax), then orc_host_tsr_form's six for this batch, the first of them -1 when every step is the
+ * dense one, and m, the moving waypoints: n_points - 2, or n_points - 1 with start_tsr) */
 int orc_batch_get_state(orc_module * mod, int batch_id, const char * which, double * out, size_t cap_doubles);
 int orc_batch_dims(orc_module * mod, int batch_id, int * n_runs, int * n_points, int * n);
 /* overwrite the trajectories of a batch (warm start; what `create starttraj` does for one run,
@@ -694,6 +697,11 @@ int orc_host_metric_free_start(int m, int derivative, double dt, double * A_out,
 /* rank of the semiseparable form of A^-1 the device applies for this metric (0: none -- derivative 1 has its closed
  * form, derivative > 4 the dense inverse); -1 on bad arguments */
 int orc_host_metric_semisep_rank(int m, int derivative, double dt, int free_start);
+/* which form of the structured constraint solve the iterate kernel takes for `threads` per workgroup, m moving waypoints, n
+ * columns and n_max = n + (most constrained rows on one point): the kernel's own decision (csrc/tsr_form.h).  out: lanes per
+ * row of the register form (16, 32; 0: the one-wavefront LDS form), registers per lane, 1 for the augmented block, the meet
+ * form (tsr_meet_regs<2>, <4>; 0: tsr_meet), the substitution form's two template numbers.  Nonzero on bad arguments */
+int orc_host_tsr_form(int threads, int m, int n, int n_max, int out[6]);
 /* GSL's default generator restated (src/orcdchomp_mod.cpp:2303-2304,2763,2767): n gaussians with
  * the given sigma from seed, then one uniform; out_gauss[n], out_uniform[1] */
 int orc_host_gsl_stream(unsigned long seed, double sigma, int n, double * out_gauss, double * out_uniform);

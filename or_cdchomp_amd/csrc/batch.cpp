@@ -379,6 +379,17 @@ void BatchShard::get_plan(double out[9]) const
    out[8] = plan_.tile_first;
 }
 
+void BatchShard::get_tsr_plan(double out[11]) const
+{
+   // the decision phase_tsr makes from the same four numbers (tsr_form.h); without the structured solve every step is tsr_dense_step
+   const TsrForm f = tsr_form(plan_.block, m, n, plan_.tsr_nmax);
+   const bool st = plan_.tsr_structured != 0;
+   out[0] = tsr_.n_tsrs; out[1] = tsr_.cons_k; out[2] = plan_.tsr_structured; out[3] = plan_.tsr_nmax;
+   out[4] = st ? f.width : -1; out[5] = st ? f.regs : 0; out[6] = st ? f.aug : 0; out[7] = st ? f.meet : 0;
+   out[8] = st ? f.subst_w : 0; out[9] = st ? f.subst_u : 0;
+   out[10] = m;
+}
+
 void BatchShard::get_state(const std::string & which, double * out)
 {
    DeviceGuard guard(device);
@@ -588,6 +599,7 @@ void Batch::gettraj(double * out)
 }
 
 void Batch::get_plan(double out[9]) { shards[0]->get_plan(out); }
+void Batch::get_tsr_plan(double out[11]) { shards[0]->get_tsr_plan(out); }
 
 void Batch::get_state(const std::string & which, double * out)
 {

@@ -13,6 +13,7 @@
 #include "devbuf.h"      // DeviceGuard, hip_check, DevBuf, dev_alloc, upload
 #include "hmc.h"         // HmcPlan, PlanStore, HmcPlanner: the momentum-resampling plan of HMC runs
 #include "verdict.h"     // VerdictInputs, the sample clock, the free functions of the collision verdict
+#include "tsr_form.h"    // TsrForm, tsr_form: the constraint step's form, the iterate kernel's own decision
 #include "multistart.h"  // SelectCriterion, SelectResult, PerturbPlan, RespawnPlan: what the multi-start calls pass each other
 
 template <typename real> struct DevVerdictWalk;      // verdict_device.h
@@ -87,6 +88,7 @@ public:
    void sync_end();                                                          // wait for them
    void gettraj(double * out);
    void get_plan(double out[9]) const;      // kernel variant bits, threads per workgroup, LDS bytes, tile, solve mode, workgroups per CU, tiles, lanes per waypoint, first tile
+   void get_tsr_plan(double out[11]) const; // constraints, rows in all, structured solve or not, N at its largest; tsr_form's fields (width -1: the dense step); m
    void get_state(const std::string & which, double * out);
    void get_trace(double * out);
    void set_noise(const double * noise, int n_blocks) { hmc_->set_noise(noise, n_blocks); }      // caller-supplied blocks (host streams only)
@@ -231,6 +233,7 @@ public:
    void sync(double * costs_out, int * status_out, int * iters_out = nullptr);
    void gettraj(double * out);
    void get_plan(double out[9]);            // the plan of the first shard (all shards of a batch plan alike)
+   void get_tsr_plan(double out[11]);       // ... and what the constraint step will run
    void get_state(const std::string & which, double * out);
    void get_trace(double * out);
    void set_noise(const double * noise, int n_blocks);

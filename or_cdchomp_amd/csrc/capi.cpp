@@ -609,6 +609,12 @@ int orc_batch_get_state(orc_module * mod, int id, const char * which, double * o
          std::copy(plan, plan + (cap < 9 ? 8 : 9), out);      // (the first tile's size: appended, read when there is room)
          return;
       }
+      if (std::string(which) == "tsr_plan")      // which form of the constraint step this batch runs (tsr_form.h)
+      {
+         if (cap < 11) throw std::runtime_error("buffer too small!");
+         b.get_tsr_plan(out);
+         return;
+      }
       if (std::string(which) == "config_chunk")      // the queries a workgroup of config_clearance_kernel takes for this batch
       {
          if (cap < 1) throw std::runtime_error("buffer too small!");
@@ -970,6 +976,14 @@ int orc_host_metric_semisep_rank(int m, int derivative, double dt, int free_star
       return M.ss_rank;
    }
    catch (...) { return -1; }
+}
+
+int orc_host_tsr_form(int threads, int m, int n, int n_max, int out[6])
+{
+   if (!out || threads < 1 || m < 1 || n < 1 || n_max <= n) return 1;
+   const TsrForm f = tsr_form(threads, m, n, n_max);
+   out[0] = f.width; out[1] = f.regs; out[2] = f.aug; out[3] = f.meet; out[4] = f.subst_w; out[5] = f.subst_u;
+   return 0;
 }
 
 int orc_host_verdict_samples(const double * traj, int n_points, int n, int col0, const double * vmax, int cap,

@@ -912,6 +912,13 @@ template <typename real, typename BT>
 __device__ __forceinline__ real smooth_grad(const BT & b, const real * T_s, int i, int c)
 {
    const int n = b.n;
+   // In double whatever `real` is (the same bits in fp64; a product of two floats is exact in double), and rounded once: the row is a
+   // second difference, its terms of size a |T|, its value a |T''| dt^2, and float rounds it at a |T| 2^-24.  Of the gradient that is as
+   // much as the waypoints' own float rounding moves it; but A^-1 takes A dT back to dT, while it passes this error on at its full
+   // size: A^-1 G of a 34-waypoint fp32 run was off by 4e-5 of its largest row, 56 x what the float rounding of the waypoints moves it
+   // (NOTES/first-iteration.md).  phase_costs_body forms the row the same way.
+   if (sizeof(real) == 4)
+      return (real)((double) b.a_diag * (double) T_s[(i+1)*n + c] + (double) b.a_off * ((double) T_s[i*n + c] + (double) T_s[(i+2)*n + c]));
    return b.a_diag * T_s[(i+1)*n + c] + b.a_off * (T_s[i*n + c] + T_s[(i+2)*n + c]);
 }
 // The two passes over the trajectory that need A T + B, for a metric that is not that one (a higher derivative; derivative 1

@@ -17,6 +17,7 @@
 #include <utility>
 
 #include "tsr_point.h"      // tsr_eval_point: con_tsr at one trajectory row
+#include "tsr_form.h"       // tsr_form: which form of the structured solve runs (shared with the host)
 
 // (constraint, point) of block o in the reference's list order (the list grows at its head,
 // chomp.c:231-232: the last constraint added comes first, its points from m-1 down to 0)
@@ -869,11 +870,7 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp, const int t
       __syncthreads();
       const int Nm = b.tsr_nmax, wave = tid >> 6;
       int shape = 0;                             // the register form's padded width, 0: the LDS form (one wavefront)
-      // a block [S | r] of N = n + (constrained rows of the point) rows needs N + 1 columns: rows of 16 lanes up to N = 15
-      // (a 7-dof arm with up to eight constrained rows on a point), rows of 32 lanes up to N = 24
-      if (BLOCK >= 128 && m >= 4 && n <= 23)
-         shape = (Nm <= 15) ? 16 : ((Nm <= 24) ? 32 : 0);
-      if (Nm - n > 16) shape = 0;      // (the row lists of a point hold 16 entries: more constrained rows on one point take the dense path)
+      ORC_TSR_FORM_WIDTH(shape, BLOCK, m, n, Nm)      // (tsr_form.h, with the ladders' rungs below: the host reports these decisions)
       if (!shape)
       {
          if (tid < 64) tsr_block_thomas<real>(b, E, hws, Jws, Cst, E.redi);
@@ -890,22 +887,22 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp, const int t
          real * meet = (real *)((int *) E.ax_s + 64);      // [2][n]: delta_{mid-1}, delta_mid
          if (wave == 0)
          {
-            if (shape == 16 && Nm <= 8 && Nm + n + 1 <= 16) tsr_eliminate_regs<real, 16, 2, +1, true>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);      // (the augmented block fits as well: see AUG)
-            else if (shape == 16 && Nm <= 8) tsr_eliminate_regs<real, 16, 2, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);            // (four rows per register)
-            else if (shape == 16 && Nm <= 12) tsr_eliminate_regs<real, 16, 3, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);     // (a WAM point with up to five constrained rows)
-            else if (shape == 16) tsr_eliminate_regs<real, 16, 4, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);
-            else if (Nm <= 16) tsr_eliminate_regs<real, 32, 8, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);                    // (two rows per register)
-            else if (Nm <= 20) tsr_eliminate_regs<real, 32, 10, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);
+            if (tsr_form_is_16_2_aug(shape, n, Nm)) tsr_eliminate_regs<real, 16, 2, +1, true>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);      // (the augmented block fits as well: see AUG)
+            else if (tsr_form_is_16_2(shape, Nm)) tsr_eliminate_regs<real, 16, 2, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);            // (four rows per register)
+            else if (tsr_form_is_16_3(shape, Nm)) tsr_eliminate_regs<real, 16, 3, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);     // (a WAM point with up to five constrained rows)
+            else if (tsr_form_is_16_4(shape)) tsr_eliminate_regs<real, 16, 4, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);
+            else if (tsr_form_is_32_8(Nm)) tsr_eliminate_regs<real, 32, 8, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);                    // (two rows per register)
+            else if (tsr_form_is_32_10(Nm)) tsr_eliminate_regs<real, 32, 10, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);
             else tsr_eliminate_regs<real, 32, 12, +1>(b, E, hws, Jws, Cst, E.redi, 0, mid, rows);
          }
          else if (wave == 1)
          {
-            if (shape == 16 && Nm <= 8 && Nm + n + 1 <= 16) tsr_eliminate_regs<real, 16, 2, -1, true>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
-            else if (shape == 16 && Nm <= 8) tsr_eliminate_regs<real, 16, 2, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
-            else if (shape == 16 && Nm <= 12) tsr_eliminate_regs<real, 16, 3, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
-            else if (shape == 16) tsr_eliminate_regs<real, 16, 4, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
-            else if (Nm <= 16) tsr_eliminate_regs<real, 32, 8, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
-            else if (Nm <= 20) tsr_eliminate_regs<real, 32, 10, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
+            if (tsr_form_is_16_2_aug(shape, n, Nm)) tsr_eliminate_regs<real, 16, 2, -1, true>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
+            else if (tsr_form_is_16_2(shape, Nm)) tsr_eliminate_regs<real, 16, 2, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
+            else if (tsr_form_is_16_3(shape, Nm)) tsr_eliminate_regs<real, 16, 3, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
+            else if (tsr_form_is_16_4(shape)) tsr_eliminate_regs<real, 16, 4, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
+            else if (tsr_form_is_32_8(Nm)) tsr_eliminate_regs<real, 32, 8, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
+            else if (tsr_form_is_32_10(Nm)) tsr_eliminate_regs<real, 32, 10, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
             else tsr_eliminate_regs<real, 32, 12, -1>(b, E, hws, Jws, Cst, E.redi, m - 1, mid - 1, rows);
          }
          __threadfence_block();
@@ -913,8 +910,8 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp, const int t
          ORC_TMARK(2);
          if (wave == 0 && !E.redi[0])
          {
-            if (n <= 7) tsr_meet_regs<real, 2>(b, Cst, mid, meet, E.redi);
-            else if (n <= 15) tsr_meet_regs<real, 4>(b, Cst, mid, meet, E.redi);
+            if (tsr_form_is_meet_2(n)) tsr_meet_regs<real, 2>(b, Cst, mid, meet, E.redi);
+            else if (tsr_form_is_meet_4(n)) tsr_meet_regs<real, 4>(b, Cst, mid, meet, E.redi);
             else tsr_meet<real>(b, Cst, mid, meet, E.redi);
          }
          __threadfence_block();
@@ -927,16 +924,16 @@ __device__ __attribute__((noinline)) void phase_tsr(const void * kp, const int t
             if (wave == 0)
             {
                if (tid < n) Tw[n + (mid - 1)*n + tid] -= meet[tid];
-               if (n <= 7) tsr_substitute<real, -1, 8, 1>(b, E, Cst, meet, mid - 2, -1);
-               else if (n <= 15) tsr_substitute<real, -1, 16, 4>(b, E, Cst, meet, mid - 2, -1);
+               if (tsr_form_is_meet_2(n)) tsr_substitute<real, -1, 8, 1>(b, E, Cst, meet, mid - 2, -1);
+               else if (tsr_form_is_meet_4(n)) tsr_substitute<real, -1, 16, 4>(b, E, Cst, meet, mid - 2, -1);
                else tsr_substitute<real, -1, 0, 1>(b, E, Cst, meet, mid - 2, -1);
             }
             else if (wave == 1)
             {
                const int ln = tid & 63;
                if (ln < n) Tw[n + mid*n + ln] -= meet[n + ln];
-               if (n <= 7) tsr_substitute<real, +1, 8, 1>(b, E, Cst, meet + n, mid + 1, m);
-               else if (n <= 15) tsr_substitute<real, +1, 16, 4>(b, E, Cst, meet + n, mid + 1, m);
+               if (tsr_form_is_meet_2(n)) tsr_substitute<real, +1, 8, 1>(b, E, Cst, meet + n, mid + 1, m);
+               else if (tsr_form_is_meet_4(n)) tsr_substitute<real, +1, 16, 4>(b, E, Cst, meet + n, mid + 1, m);
                else tsr_substitute<real, +1, 0, 1>(b, E, Cst, meet + n, mid + 1, m);
             }
          }

@@ -1383,11 +1383,21 @@ class Module:
                 "tile_first")
         return {k: int(v) for k, v in zip(keys, out)}
 
+    def batch_tsr_plan(self, bid):
+        """which form of the constraint step this batch runs (orc_batch_get_state "tsr_plan"; csrc/tsr_form.h): n_tsrs, cons_k,
+        structured, n_max, then width (16 or 32 lanes per row of the register form, 0 the one-wavefront LDS form, -1 the dense
+        step), regs, aug, meet (tsr_meet_regs<2>, <4>; 0 tsr_meet), subst (tsr_substitute's two template numbers) and m, the moving
+        waypoints"""
+        out = np.zeros(11)
+        self._check(self._lib.orc_batch_get_state(self._h, bid, b"tsr_plan", _dp(out), out.size))
+        v = [int(x) for x in out]
+        return dict(n_tsrs=v[0], cons_k=v[1], structured=v[2], n_max=v[3], width=v[4], regs=v[5], aug=v[6], meet=v[7], subst=(v[8], v[9]), m=v[10])
+
     def batch_state(self, bid, which):
-        """"G", "AG", "T": [n_runs][m][n]; "run_params": [n_runs][4] lambda, epsilon, obs_factor, obs_factor_self as the
+        """"G", "AG", "T": [n_runs][m][n] (m moving waypoints: n_points - 2, n_points - 1 with start_tsr); "run_params": [n_runs][4] lambda, epsilon, obs_factor, obs_factor_self as the
         device holds them (run_params_table)"""
         n_runs, n_points, n = self.batch_dims(bid)
-        out = np.zeros((n_runs, 4)) if which == "run_params" else np.zeros((n_runs, n_points - 2, n))
+        out = np.zeros((n_runs, 4)) if which == "run_params" else np.zeros((n_runs, self.batch_tsr_plan(bid)["m"], n))
         self._check(self._lib.orc_batch_get_state(self._h, bid, which.encode(), _dp(out), out.size))
         return out
 
