@@ -621,6 +621,31 @@ int orc_batch_config_tsr(orc_module * mod, int batch_id, int n_tsr, const orc_ts
 int orc_batch_project_tsr(orc_module * mod, int batch_id, int n_tsr, const orc_tsr * tsrs, int n_q, const int * tsr_of_q,
    const double * configs, const double * lower, const double * upper /* [n] each or NULL */, int max_steps, double tol, double mu,
    double step_cap, double * configs_out /* [n_q][n] */, double * resid_out /* [n_q] */, int * steps_out, int * status_out);
+/* Projects every row onto its TSR and moves it out of contact at once, on the device; or_cdchomp_amd/project_clear.py is the
+ * rule.  Row q is tested against the scene of run run_of_q[q] as orc_batch_config_penetration tests it.  Per round
+ * it = 0 .. max_steps the penetration cost U = cost[0] + cost[1], its gradient g and the two clearances are taken at the
+ * iterate at the margins (margin_field + slack, margin_self + slack), and h, J and r = max_i |h_i| as orc_batch_project_tsr
+ * takes them.  The iterate is `on` when r <= tol and `clear` when clearance[0] >= margin_field and clearance[1] >= margin_self
+ * (a NaN is never clear).  Its key is class 0 (on and clear), class 1 (on, compared by U) or class 2 (anything else, compared
+ * by r): the lower class wins, within a class the smaller value, a NaN is never better and anything beats a NaN, the earlier
+ * iterate keeps a tie; the best iterate is what comes back.  On and clear: status 0.  it == max_steps: status 2.  Otherwise
+ * one step: A = J J^T + mu I_k factored by orc_batch_project_tsr's Cholesky, dq = -J^T A^-1 h; where U is finite and positive
+ * and g finite, g_N = g - J^T A^-1 (J g), s = g_N . g_N, and where s is finite and positive p = -(2U / s) g_N, shortened to
+ * push_cap in the 2-norm, is added to dq; dq is shortened to step_cap, q <- clip(q + dq, lower, upper).  Status 1: a pivot that
+ * is not positive and finite, or a step that moves no entry; 3: a row with a non-finite entry (every output of the row NaN, 0
+ * steps).  A row that starts on its TSR and clear, and every row when max_steps is 0, comes back bit for bit with 0 steps, and so
+ * does every entry the loop leaves where it was, in a precision-32 batch too.  resid_out is r and clearance_out [n_q][2] the
+ * clearance of the returned row; steps_out counts the steps taken.  The arithmetic is in the batch's precision, the outputs
+ * are doubles.  One launch of orc_batch_config_penetration's kernel and one of the step kernel per round, on the stream of the
+ * shard that owns the row's run.
+ * A row's answer depends on the row, its TSR, its run and the parameters only: not on its place, on n_q, or on the shard.
+ * Rejected with a nonzero return and a message before any device work, the module usable: everything orc_batch_project_tsr
+ * rejects (a floating-base batch included; clearance_out may not be NULL either); everything orc_batch_config_penetration
+ * rejects about run_of_q and the margins; a NaN or non-positive push_cap; a NaN, negative or infinite slack. */
+int orc_batch_project_tsr_clear(orc_module * mod, int batch_id, int n_tsr, const orc_tsr * tsrs, int n_q, const int * tsr_of_q,
+   const int * run_of_q /* NULL: run 0 */, const double * configs, const double * lower, const double * upper, int max_steps,
+   double tol, double mu, double step_cap, double push_cap, double margin_field, double margin_self, double slack,
+   double * configs_out, double * resid_out, double * clearance_out /* [n_q][2] */, int * steps_out, int * status_out);
 /* The best run of every group among those that keep a margin.  n_groups and group_of_run as in orc_batch_select_best.  A run
  * is eligible when all three hold: it is a candidate (status 0 or 1 and a finite total cost); it was walked, i.e. is not too
  * long for max_samples; fmin(clearance[0], clearance[1]) >= margin.  margin 0 is orc_batch_select_best_by's

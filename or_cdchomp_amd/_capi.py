@@ -112,6 +112,9 @@ SYMBOLS = [
     ("orc_batch_config_tsr", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Tsr), C.c_int, c_int_p, c_double_p, c_double_p, c_double_p]),
     ("orc_batch_project_tsr", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Tsr), C.c_int, c_int_p, c_double_p, c_double_p, c_double_p,
                                         C.c_int, C.c_double, C.c_double, C.c_double, c_double_p, c_double_p, c_int_p, c_int_p]),
+    ("orc_batch_project_tsr_clear", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Tsr), C.c_int, c_int_p, c_int_p, c_double_p, c_double_p,
+                                              c_double_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                              C.c_double, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]),
     ("orc_batch_select_clear", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_double, C.c_int, c_int_p, c_double_p,
                                          c_double_p, c_int_p, c_int_p]),
     ("orc_batch_respawn", C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_int_p, C.c_int, C.c_int, C.c_double, c_uint_p,

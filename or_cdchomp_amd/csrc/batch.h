@@ -1,6 +1,6 @@
 // batch.h -- a batch of CHOMP runs as the host layer holds it: the shard of its runs on one device, the batch over the shards, and
 // the small structs their calls take (batch.cpp, verdict.cpp, clearance.cpp, config_clearance.cpp, penetration.cpp, project.cpp,
-// multistart.cpp).
+// project_clear.cpp, multistart.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -18,6 +18,7 @@
 
 template <typename real> struct DevVerdictWalk;      // verdict_device.h
 template <typename real> struct DevVerdictPlanned;
+template <typename real> struct DevPenetration;      // penetration_device.h
 
 namespace orc {
 
@@ -65,6 +66,19 @@ struct ProjectOut
    double * h = nullptr, * jac = nullptr, * rows = nullptr, * resid = nullptr;
    int * steps = nullptr, * status = nullptr;
    ProjectOut from(size_t first, int n) const;
+};
+
+// the parameters of a projection onto TSRs and out of contact (project_clear.cpp; or_cdchomp_amd/project_clear.py is the rule)
+struct ProjectClearSpec
+{
+   ProjectSpec project;          // max_steps, tol, mu, step_cap, lower, upper: as the projection's
+   double push_cap = 0.2, margin_field = 0.02, margin_self = 0.0, slack = 2e-3;
+};
+// where its results go: rows [n_q][n], resid [n_q], clear [n_q][2], steps, status [n_q]; none is NULL
+struct ProjectClearOut
+{
+   double * rows = nullptr, * resid = nullptr, * clear = nullptr;
+   int * steps = nullptr, * status = nullptr;
 };
 
 class Module;
@@ -146,6 +160,11 @@ public:
    // onto them (project_kernels.hip); nothing is kept on the device
    void project_tsr(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
                     const ProjectSpec * ps, const ProjectOut & out);
+   // (project_clear.cpp) the projection of n_q rows onto `specs` and out of contact with the scenes of this shard's runs
+   // (run_of_q: LOCAL runs, NULL: run 0): rounds of penetration_kernel and project_clear_step_kernel on the shard's stream
+   // (project_clear_kernels.hip); nothing is kept on the device
+   void project_tsr_clear(const Robot & robot, const VerdictInputs & in, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q,
+                          const int * run_of_q, const double * configs, const ProjectClearSpec & ps, const ProjectClearOut & out);
    int project_state_in_lds(int kmax) const; // 1: a lane's state of that kernel (kmax 3 or 6 rows) lives in LDS for this batch, 0: in the call's workspace
    void get_phase_cycles(long long * out);   // [n_runs][8], diagnostics (ORC_PHASE_TIMERS=1)
    void get_wave_hwid(unsigned int * out);   // [n_runs][8][2], diagnostics (ORC_PHASE_TIMERS=1): DevBatch::wave_hwid of the last launch
@@ -185,6 +204,12 @@ private:
       const double * configs, double * clear_out, unsigned int * key_out);
    template <typename real> void config_penetration_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q,
       const double * configs, double margin_field, double margin_self, const PenetrationOut & out);
+   // what a launch of penetration_kernel needs beside its queries and outputs: the walk's tables (verdict_walk_args) and the
+   // pairs by sphere go up, `v` gets them and its chunk; returns the launch's LDS bytes (throws when the robot does not fit)
+   struct PenetrationTables { VerdictTables walk; DevBuf pair_offs, pair_list; std::vector<int> host_offs, host_list; };
+   template <typename real> size_t penetration_setup(const VerdictInputs & in, PenetrationTables & t, DevPenetration<real> & v);
+   template <typename real> void project_tsr_clear_typed(const Robot & robot, const VerdictInputs & in, const std::vector<TsrSpec> & specs, int n_q,
+      const int * tsr_of_q, const int * run_of_q, const double * configs, const ProjectClearSpec & ps, const ProjectClearOut & out);
    template <typename real> void project_tsr_typed(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q,
       const double * configs, const ProjectSpec * ps, const ProjectOut & out);
    void construct(const Robot & robot, const double * starts, const double * goals, const double * basegoals,
@@ -287,6 +312,10 @@ public:
    // caller, Module::project_check, has checked the arguments)
    void project_tsr(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
                     const ProjectSpec * ps, const ProjectOut & out);
+   // (project_clear.cpp) orc_batch_project_tsr_clear: a row goes to the shard that owns its run, as config_penetration deals
+   // them (the caller, Module::batch_project_tsr_clear, has checked the arguments)
+   void project_tsr_clear(const Robot & robot, const VerdictInputs & in, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q,
+                          const int * run_of_q, const double * configs, const ProjectClearSpec & ps, const ProjectClearOut & out);
    // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;
    // kept until it is set again
    int verdict_scope = 0;

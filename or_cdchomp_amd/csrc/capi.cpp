@@ -761,6 +761,23 @@ int orc_batch_project_tsr(orc_module * mod, int id, int n_tsr, const orc_tsr * t
    });
 }
 
+int orc_batch_project_tsr_clear(orc_module * mod, int id, int n_tsr, const orc_tsr * tsrs, int n_q, const int * tsr_of_q, const int * run_of_q,
+   const double * configs, const double * lower, const double * upper, int max_steps, double tol, double mu, double step_cap, double push_cap,
+   double margin_field, double margin_self, double slack, double * configs_out, double * resid_out, double * clearance_out, int * steps_out,
+   int * status_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch(id);
+      orc::ProjectClearSpec ps;
+      ps.project.max_steps = max_steps; ps.project.tol = tol; ps.project.mu = mu; ps.project.step_cap = step_cap;
+      ps.project.lower = lower; ps.project.upper = upper;
+      ps.push_cap = push_cap; ps.margin_field = margin_field; ps.margin_self = margin_self; ps.slack = slack;
+      orc::ProjectClearOut out;
+      out.rows = configs_out; out.resid = resid_out; out.clear = clearance_out; out.steps = steps_out; out.status = status_out;
+      mod->impl->batch_project_tsr_clear(id, to_tsrs(n_tsr, tsrs), n_q, tsr_of_q, run_of_q, configs, ps, out);
+   });
+}
+
 int orc_batch_select_clear(orc_module * mod, int id, int cost_column, int n_groups, const int * group_of_run, double margin, int max_samples,
    int * best_run_out, double * best_cost_out, double * best_clearance_out, int * n_eligible_out, int * n_samples_out)
 {

@@ -76,6 +76,11 @@ public:
       double * rows_out, double * resid_out, int * steps_out, int * status_out);
    std::vector<TsrSpec> project_check(const char * who, const Batch & b, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q,
       const double * configs) const;
+   void project_spec_check(const char * who, const Batch & b, const ProjectSpec & ps) const;      // ... and of a projection's parameters
+   // (project_clear.cpp) orc_batch_project_tsr_clear: the rows projected onto their TSRs and moved out of contact with the scenes of
+   // their runs at once (or_cdchomp_amd/project_clear.py is the rule); rejects what the projection and the penetration call reject
+   void batch_project_tsr_clear(int id, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q, const int * run_of_q,
+      const double * configs, const ProjectClearSpec & ps, const ProjectClearOut & out);
    // (multistart.cpp) orc_batch_select_best[_by], _respawn, _select_clear: each checks every argument on the host, then takes the
    // verdict with Batch::selection_scope() (collision_free; collision_mode 1, 2) or the clearance, then selects or respawns on the device
    void batch_select_best(int id, int cost_column, int n_groups, const int * group_of_run, bool collision_free, int * best_run, double * best_cost,

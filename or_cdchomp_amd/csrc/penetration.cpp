@@ -125,20 +125,37 @@ static void pairs_by_sphere(const std::vector<int> & pairs, int Sa, unsigned lon
    }
 }
 
+// the part of a launch that does not depend on the queries (project_clear.cpp launches the kernel once per round after one set-up)
+template <typename real>
+size_t BatchShard::penetration_setup(const VerdictInputs & in, PenetrationTables & t, DevPenetration<real> & v)
+{
+   hipStream_t st = stream_;
+   const auto lds_bytes = [this](int chunk) { return orc_penetration_lds_bytes(n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
+   verdict_walk_args<real>(in, lds_bytes, t.walk, v);
+   const size_t lds = lds_bytes(v.chunk);
+   if (lds > ORC_VERDICT_LDS_LIMIT) throw std::runtime_error("penetration: the robot does not fit the kernel's shared memory!");
+   v.key_out = nullptr; v.depth_out = nullptr;      // (the walk's outputs of the verdict: not written here)
+   std::vector<int> & poffs = t.host_offs, & plist = t.host_list;      // (they live until the caller has synchronised)
+   pairs_by_sphere(in.pairs, ms_.Sa, ms_.live_mask, poffs, plist);
+   t.pair_offs.reset(dev_alloc<int>(poffs.size())); t.pair_list.reset(dev_alloc<int>(plist.size() + 1));
+   hip_check(hipMemcpyAsync(t.pair_offs.as<void>(), poffs.data(), poffs.size()*sizeof(int), hipMemcpyHostToDevice, st), "penetration pair offsets");
+   if (!plist.empty()) hip_check(hipMemcpyAsync(t.pair_list.as<void>(), plist.data(), plist.size()*sizeof(int), hipMemcpyHostToDevice, st), "penetration pair list");
+   v.sph_pair_offs = t.pair_offs.as<int>(); v.sph_pair_list = t.pair_list.as<int>();
+   return lds;
+}
+template size_t BatchShard::penetration_setup<double>(const VerdictInputs &, PenetrationTables &, DevPenetration<double> &);      // (project_clear.cpp calls them)
+template size_t BatchShard::penetration_setup<float>(const VerdictInputs &, PenetrationTables &, DevPenetration<float> &);
+
 template <typename real>
 void BatchShard::config_penetration_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
    double margin_field, double margin_self, const PenetrationOut & out)
 {
    hipStream_t st = stream_;
-   const auto lds_bytes = [this](int chunk) { return orc_penetration_lds_bytes(n, ms_.Sa, ms_.Sa_real, ms_.nj, sizeof(real), chunk); };
-   VerdictTables t;
+   PenetrationTables t;
    DevPenetration<real> v;
-   verdict_walk_args<real>(in, lds_bytes, t, v);
-   const size_t lds = lds_bytes(v.chunk);
-   if (lds > ORC_VERDICT_LDS_LIMIT) throw std::runtime_error("penetration: the robot does not fit the kernel's shared memory!");
-   DevBuf d_run, d_point, d_cfg, d_cost, d_grad, d_clr, d_key, d_poffs, d_plist;
+   const size_t lds = penetration_setup<real>(in, t, v);
+   DevBuf d_run, d_point, d_cfg, d_cost, d_grad, d_clr, d_key;
    const size_t n2 = (size_t) n_q * 2, ng = (size_t) n_q * n;
-   v.key_out = nullptr; v.depth_out = nullptr;      // (the walk's outputs of the verdict: not written here)
    v.n_q = n_q; v.run_of_q = nullptr; v.point_of_q = nullptr; v.configs = nullptr;
    v.margin_field = (real) margin_field; v.margin_self = (real) margin_self;
    if (run_of_q)
@@ -163,12 +180,6 @@ void BatchShard::config_penetration_typed(const VerdictInputs & in, int n_q, con
       hip_check(hipMemcpyAsync(d_cfg.as<void>(), src, count*sizeof(real), hipMemcpyHostToDevice, st), "penetration rows");
       v.configs = d_cfg.as<const real>();
    }
-   std::vector<int> poffs, plist;
-   pairs_by_sphere(in.pairs, ms_.Sa, ms_.live_mask, poffs, plist);
-   d_poffs.reset(dev_alloc<int>(poffs.size())); d_plist.reset(dev_alloc<int>(plist.size() + 1));
-   hip_check(hipMemcpyAsync(d_poffs.as<void>(), poffs.data(), poffs.size()*sizeof(int), hipMemcpyHostToDevice, st), "penetration pair offsets");
-   if (!plist.empty()) hip_check(hipMemcpyAsync(d_plist.as<void>(), plist.data(), plist.size()*sizeof(int), hipMemcpyHostToDevice, st), "penetration pair list");
-   v.sph_pair_offs = d_poffs.as<int>(); v.sph_pair_list = d_plist.as<int>();
    d_cost.reset(dev_alloc<double>(n2)); d_grad.reset(dev_alloc<double>(ng)); d_clr.reset(dev_alloc<double>(n2)); d_key.reset(dev_alloc<unsigned int>(n2));
    hip_check(hipMemsetAsync(d_grad.as<void>(), 0, ng*sizeof(double), st), "penetration gradient");
    v.cost_out = d_cost.as<double>(); v.grad_out = d_grad.as<double>(); v.clear_out = d_clr.as<double>(); v.ckey_out = d_key.as<unsigned int>();

@@ -52,6 +52,22 @@ std::vector<TsrSpec> Module::project_check(const char * who, const Batch & b, co
    return out;
 }
 
+// what the projections reject of their parameters (orc_batch_project_tsr, orc_batch_project_tsr_clear), before any device work
+void Module::project_spec_check(const char * who, const Batch & b, const ProjectSpec & ps) const
+{
+   const std::string w = std::string(who) + ": ";
+   if (!(ps.tol > 0.0)) throw std::runtime_error(w + "tol must be a positive number!");
+   if (!(ps.step_cap > 0.0)) throw std::runtime_error(w + "step_cap must be a positive number!");
+   if (!(ps.mu >= 0.0)) throw std::runtime_error(w + "mu must be a number >= 0!");
+   if (ps.max_steps < 0 || ps.max_steps > ORC_PROJECT_MAX_STEPS) throw std::runtime_error(w + "max_steps must lie in [0, 256]!");
+   for (int c=0; c<b.n; c++)
+   {
+      const double lo = ps.lower ? ps.lower[c] : -HUGE_VAL, hi = ps.upper ? ps.upper[c] : HUGE_VAL;
+      if (std::isnan(lo) || std::isnan(hi) || lo > hi) throw std::runtime_error(w + "lower[c] <= upper[c] must hold for every column!");
+   }
+   if (b.params.floating_base) throw std::runtime_error(w + "a floating-base batch is not projected (its quaternion columns have no update rule here)!");
+}
+
 void Module::batch_config_tsr(int id, const std::vector<TsrSpec> & tsrs, int n_q, const int * tsr_of_q, const double * configs,
    double * h_out, double * jac_out)
 {
@@ -69,16 +85,7 @@ void Module::batch_project_tsr(int id, const std::vector<TsrSpec> & tsrs, int n_
    Batch & b = batch(id);
    const std::vector<TsrSpec> specs = project_check("project tsr", b, tsrs, n_q, tsr_of_q, configs);
    if (!rows_out || !resid_out || !steps_out || !status_out) throw std::runtime_error("project tsr: configs_out, resid_out, steps_out and status_out are required!");
-   if (!(ps.tol > 0.0)) throw std::runtime_error("project tsr: tol must be a positive number!");
-   if (!(ps.step_cap > 0.0)) throw std::runtime_error("project tsr: step_cap must be a positive number!");
-   if (!(ps.mu >= 0.0)) throw std::runtime_error("project tsr: mu must be a number >= 0!");
-   if (ps.max_steps < 0 || ps.max_steps > ORC_PROJECT_MAX_STEPS) throw std::runtime_error("project tsr: max_steps must lie in [0, 256]!");
-   for (int c=0; c<b.n; c++)
-   {
-      const double lo = ps.lower ? ps.lower[c] : -HUGE_VAL, hi = ps.upper ? ps.upper[c] : HUGE_VAL;
-      if (std::isnan(lo) || std::isnan(hi) || lo > hi) throw std::runtime_error("project tsr: lower[c] <= upper[c] must hold for every column!");
-   }
-   if (b.params.floating_base) throw std::runtime_error("project tsr: a floating-base batch is not projected (its quaternion columns have no update rule here)!");
+   project_spec_check("project tsr", b, ps);
    ProjectOut out;
    out.rows = rows_out; out.resid = resid_out; out.steps = steps_out; out.status = status_out;
    b.project_tsr(env.robot(b.robot_name), specs, n_q, tsr_of_q, configs, &ps, out);

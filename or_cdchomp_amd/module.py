@@ -1304,19 +1304,8 @@ class Module:
                                                    _dp(jac)))
         return dict(h=h, jac=jac, k=ks[tq] if tq is not None else np.full(n_q, ks[0], dtype=np.int32))
 
-    def batch_project_tsr(self, bid, tsrs, configs, tsr_of=None, link=None, manip=None, lower="limits", upper="limits", tol=1e-6,
-                          mu=1e-8, step_cap=0.5, max_steps=30, clearance=False, runs=None):
-        """Project configurations onto task space regions, the whole iteration on the device (orc_batch_project_tsr; the rule is
-        project.project): batched inverse kinematics with thousands of seeds at once.  tsrs, configs, tsr_of, link and manip as
-        in batch_config_tsr; lower, upper [n]: the box every step is clipped to ("limits": the robot's joint limits of the
-        batch's active dofs; None: no box).  Returns (rows [n_q][n], resid [n_q], steps int32 [n_q], status int32 [n_q]: 0
-        within tol, 1 a singular system or a step that moves nothing, 2 out of steps, 3 a row with a non-finite entry).  A row
-        that is not done is the visited iterate of smallest residual.  clearance=True appends batch_config_clearance's dict of
-        the returned rows (runs: the run whose scene each is tested against, as there): what keeps the collision-free
-        solutions."""
-        rec, _ = self._tsr_records(bid, tsrs, link, manip)
-        cf, tq = self._tsr_queries(bid, configs, tsr_of, len(rec))
-        n_q, n = cf.shape
+    def _project_box(self, bid, lower, upper, n):
+        """[lower, upper] of a projection as arrays [n] or None ("limits": the robot's joint limits of the batch's active dofs)"""
         box = []
         for name, side in (("limit_lower", lower), ("limit_upper", upper)):
             if isinstance(side, str):
@@ -1330,6 +1319,22 @@ class Module:
                 if side.size != n:
                     raise ValueError("lower and upper have %d entries, one per column" % n)
             box.append(side)
+        return box
+
+    def batch_project_tsr(self, bid, tsrs, configs, tsr_of=None, link=None, manip=None, lower="limits", upper="limits", tol=1e-6,
+                          mu=1e-8, step_cap=0.5, max_steps=30, clearance=False, runs=None):
+        """Project configurations onto task space regions, the whole iteration on the device (orc_batch_project_tsr; the rule is
+        project.project): batched inverse kinematics with thousands of seeds at once.  tsrs, configs, tsr_of, link and manip as
+        in batch_config_tsr; lower, upper [n]: the box every step is clipped to ("limits": the robot's joint limits of the
+        batch's active dofs; None: no box).  Returns (rows [n_q][n], resid [n_q], steps int32 [n_q], status int32 [n_q]: 0
+        within tol, 1 a singular system or a step that moves nothing, 2 out of steps, 3 a row with a non-finite entry).  A row
+        that is not done is the visited iterate of smallest residual.  clearance=True appends batch_config_clearance's dict of
+        the returned rows (runs: the run whose scene each is tested against, as there): what keeps the collision-free
+        solutions."""
+        rec, _ = self._tsr_records(bid, tsrs, link, manip)
+        cf, tq = self._tsr_queries(bid, configs, tsr_of, len(rec))
+        n_q, n = cf.shape
+        box = self._project_box(bid, lower, upper, n)
         rows = np.zeros((n_q, n)); resid = np.zeros(n_q)
         steps = np.zeros(n_q, dtype=np.int32); status = np.zeros(n_q, dtype=np.int32)
         self._check(self._lib.orc_batch_project_tsr(self._h, bid, len(rec), rec, n_q, None if tq is None else _ip(tq), _dp(cf),
@@ -1339,6 +1344,31 @@ class Module:
         if clearance:
             return rows, resid, steps, status, self.batch_config_clearance(bid, rows, runs=runs)
         return rows, resid, steps, status
+
+    def batch_project_tsr_clear(self, bid, tsrs, configs, tsr_of=None, runs=None, link=None, manip=None, lower="limits", upper="limits",
+                                margin=(0.02, 0.0), slack=2e-3, tol=1e-6, mu=1e-8, step_cap=0.5, push_cap=0.2, max_steps=40):
+        """Project configurations onto task space regions and out of contact at once, on the device
+        (orc_batch_project_tsr_clear; the rule is project_clear.project_clear): a task step plus the push-out step in the null
+        space of the TSR's Jacobian.  tsrs, configs, tsr_of, link, manip, lower, upper, tol, mu and step_cap as in
+        batch_project_tsr; runs, margin and slack as in batch_push_out; push_cap: the longest push of a step.  Returns a dict:
+        configs [n_q][n], the best iterate of every row (on its TSR and clear; else on its TSR, of smallest penetration cost;
+        else of smallest residual); resid [n_q] and clearance [n_q][2] of that iterate; steps int32 [n_q]; status int32 [n_q]:
+        0 on the TSR and clear, 1 a singular system or a step that moves nothing, 2 out of steps, 3 a row with a non-finite
+        entry."""
+        rec, _ = self._tsr_records(bid, tsrs, link, manip)
+        cf, tq = self._tsr_queries(bid, configs, tsr_of, len(rec))
+        _, rq = self._config_queries(bid, cf, runs)
+        mf, ms = self._margins(margin)
+        n_q, n = cf.shape
+        box = self._project_box(bid, lower, upper, n)
+        rows = np.zeros((n_q, n)); resid = np.zeros(n_q); clr = np.zeros((n_q, 2))
+        steps = np.zeros(n_q, dtype=np.int32); status = np.zeros(n_q, dtype=np.int32)
+        self._check(self._lib.orc_batch_project_tsr_clear(self._h, bid, len(rec), rec, n_q, None if tq is None else _ip(tq),
+                                                          None if rq is None else _ip(rq), _dp(cf),
+                                                          None if box[0] is None else _dp(box[0]), None if box[1] is None else _dp(box[1]),
+                                                          int(max_steps), float(tol), float(mu), float(step_cap), float(push_cap), mf, ms,
+                                                          float(slack), _dp(rows), _dp(resid), _dp(clr), _ip(steps), _ip(status)))
+        return dict(configs=rows, resid=resid, clearance=clr, steps=steps, status=status)
 
     def batch_project_state(self, bid):
         """where a lane's state of the projection kernel lives for this batch: (TSRs of up to 3 enforced rows, of up to 6), each
