@@ -53,32 +53,30 @@ enum : int
 template <typename real>
 struct DevJoint
 {
+   // (frames are canonical, fold.cpp: the moved frame of every joint is turned so that the joint's axis is its z)
    real Rfix[9];      // rotation   from-frame -> joint frame (row major)
    real tfix[3];      // translation from-frame -> joint frame
-   real axis[3];      // unit axis in the joint frame
+   real axis[3];      // unit axis in the joint frame: (0, 0, 1); the FK walk does not read it, tsr_point.h keeps the general form
    int type;          // 1 revolute, 2 prismatic
    int col;           // column of the trajectory / gradient this joint owns
    int load_slot;     // -2 base frame, -1 previous joint's moved frame, k>=0 saved slot k
    int save_slot;     // -1 none, k>=0: keep the moved frame in slot k
    int sph_begin;     // active spheres [sph_begin, sph_end) ride on this joint's moved frame
    int sph_end;
-   int rfix_identity; // Rfix == I (skips a 3x3 product)
-   int axis_kind;     // 1/2/3: the axis is +-x/+-y/+-z of the joint frame (cheap column rotation), 0 general
-   real axis_sign;    // +-1 for axis_kind != 0
    int aff_begin;     // the active spheres this joint moves are [aff_begin, aff_end) when DevModel::jt_scan != 0
    int aff_end;
-   int packed;        // the walk's control word in one LDS read: type | axis_kind<<2 | rfix_identity<<4 | (axis_sign<0)<<5 | sph_begin<<8 | sph_end<<16 | col<<24
+   int packed;        // the walk's control word in one LDS read: type | sph_begin<<8 | sph_end<<16 | col<<24
    int packed2;       // (load_slot + 2) | (save_slot + 2) << 4: the tree's frame traffic, scalar like `packed`
 };
 
-// What the FK walk reads of one joint (fk.h), as one record: a burst of scalar loads per joint (32 words in fp32),
+// What the FK walk reads of one joint (fk.h), as one record: a burst of scalar loads per joint (29 words in fp32),
 // the spheres riding on the joint's link included (their table entries used to be loaded one sphere at a time,
 // each load a scalar-cache round trip in the middle of the joint's step)
 template <typename real>
 struct DevFkJoint
 {
-   real Rfix[9], tfix[3], axis[3];
-   int ctl;             // spheres on the link: count (bits 0-7), index of the first in the sorted order (8-15); load_slot + 2 (16-19), save_slot + 2 (20-23); revolute (24); column (25-31)
+   real Rfix[9], tfix[3];      // (canonical frames: the axis is z of the joint frame)
+   int ctl;            // spheres on the link: count (bits 0-7), index of the first in the sorted order (8-15); load_slot + 2 (16-19), save_slot + 2 (20-23); revolute (24); column (25-31)
    real sph[4][3];      // centres of the first four of them in the link frame (more: DevModel::sph_pos from the fifth on)
    int slot[4];         // their slots of the position buffer
 };

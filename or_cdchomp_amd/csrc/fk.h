@@ -6,7 +6,7 @@
 //   pos_s[lane][sphere][3]   sphere centres in the world
 //   ax_s [lane][joint][6]    world joint axis and anchor (what J^T needs instead of 3 x n Jacobians)
 // Row k of a frame (R[k][0..2], t[k]) evolves independently of the other two rows under every
-// operation of the walk (R <- R*Rfix, R <- R*Rot(axis,q), t <- R*tfix + t, p = R*lp + t), so three
+// operation of the walk (R <- R*Rfix, R <- R*Rot(z,q), t <- R*tfix + t, p = R*lp + t), so three
 // lanes share a waypoint, one row each, and each evaluates its share of the sin/cos (lane k of the
 // triad evaluates joints k, k+3, ...; the values travel through the waypoint's ax_s slots).  A
 // wavefront walks 20 waypoints with a third of the arithmetic per lane, where one lane per waypoint
@@ -70,20 +70,36 @@ __device__ __forceinline__ void sincos_joint(float x, float * sn, float * cs)
 template <typename real>
 struct FrameRow { real r[3]; real t; };
 
+__device__ __forceinline__ double fk_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+__device__ __forceinline__ float fk_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
 // apply the joint of record J to row `cur` (in place); emit component k of the world axis / anchor and of the
 // centres of the spheres riding on the joint's link.  `store` is false on the idle lane.
 // The step is ONE instruction stream for every kind of joint (round 2; the walk used to branch on the
 // joint's type, on coordinate axes and on identity transforms -- a dozen scalar branches per joint, and
 // an FK pass is issue-bound on the length of its stream, two thirds of which were scalar):
-//    r' = r Rfix,  tj = r.tfix + t,  aw = r'.a                       (world axis, anchor)
-//    r  <- r' Rot(a, q) = r' c + (1 - c)(r'.a) a - s (a x r')          (Rodrigues for a row vector)
+//    r' = r Rfix,  tj = r.tfix + t,  aw = r'[2]                      (world axis, anchor)
+//    r  <- r' Rot(z, q) = (r'[0] c + s r'[1],  r'[1] c - s r'[0],  r'[2] c + r'[2] (1 - c))
 //    t  <- tj + qp aw
-// with (s, c, qp) = (sin q, cos q, 0) for a revolute and (0, 1, q) for a prismatic joint, prepared with
-// the sin/cos.  The record (DevFkJoint) is in scalar registers: fixed transform, axis and the table entries of
-// up to four spheres enter the products as scalar operands.
+// with (s, c, 1 - c, qp) = (sin q, cos q, 1 - cos q, 0) for a revolute and (0, 1, 0, q) for a prismatic joint, prepared
+// with the sin/cos.
+// Every joint turns about z of its own frame: the fold (fold.cpp, canonical_rotation) hands the walk frames turned that
+// way, with the spheres' centres expressed in them, so the general Rodrigues step -- r'.a, (1 - c)(r'.a) a and
+// a x r' -- is left with three operations of its sixteen (NOTES/fk-canonical.md).
+// The row along the axis is r'[2] up to one rounding.  It is formed as the general step formed it,
+// r' c + (1 - c)(r'.a) a, and the four sums of the turn name their fused multiply-adds as the compiler's contraction
+// made them of the general step's expressions.  For a robot whose axes are coordinate axes the fold's C is a signed
+// permutation and every other sum of the step has the general step's terms, so such a robot computes what it computed
+// with the general step: a run that bounces off its joint limits amplifies a last-bit difference to order one.
+// That equality is measured (the WAM's bench lines, NOTES/fk-canonical.md), NOT an invariant this code guarantees: it
+// rests on how the compiler contracts the sums left alone here (rp, tj, the sphere centres: the product in the second
+// place is rounded, the others are fused) and on which of a robot's offsets are zero.  The 30-joint tree does not keep
+// its bits.
+// The record (DevFkJoint) is in scalar registers: fixed transform and the table entries of up to four spheres
+// enter the products as scalar operands.
 template <typename real, bool LAZY, typename JT>
 __device__ __forceinline__ void fk_joint_row(const ModelView<real> & mod, const JT & J, const __attribute__((address_space(4))) DevFkJoint<real> * src,
-   FrameRow<real> & cur, real qp, real sn, real cs, bool store, real * axo_k, real * pos_k)
+   FrameRow<real> & cur, real qp, real sn, real cs, real om, bool store, real * axo_k, real * pos_k)
 {
    // joint frame in the world: cur o (Rfix, tfix)
    const real tj = cur.r[0]*J.tfix[0] + cur.r[1]*J.tfix[1] + cur.r[2]*J.tfix[2] + cur.t;
@@ -91,21 +107,21 @@ __device__ __forceinline__ void fk_joint_row(const ModelView<real> & mod, const 
 #pragma unroll
    for (int c=0; c<3; c++)
       rp[c] = cur.r[0]*J.Rfix[0*3+c] + cur.r[1]*J.Rfix[1*3+c] + cur.r[2]*J.Rfix[2*3+c];
-   const real aw = rp[0]*J.axis[0] + rp[1]*J.axis[1] + rp[2]*J.axis[2];
+   const real aw = rp[2];
    if (store) { axo_k[0] = aw; axo_k[3] = tj; }
-   const real d = aw * ((real)1 - cs);
-   const real x0 = J.axis[1]*rp[2] - J.axis[2]*rp[1], x1 = J.axis[2]*rp[0] - J.axis[0]*rp[2], x2 = J.axis[0]*rp[1] - J.axis[1]*rp[0];
-   cur.r[0] = (rp[0]*cs + d*J.axis[0]) - sn*x0;
-   cur.r[1] = (rp[1]*cs + d*J.axis[1]) - sn*x1;
-   cur.r[2] = (rp[2]*cs + d*J.axis[2]) - sn*x2;
-   cur.t = tj + qp*aw;
+   // (the roundings of the general step, as the compiler contracted it: the products with c and with 1 - c are rounded, the
+   // products with s and with qp are fused into the sums)
+   cur.r[0] = fk_fma(sn, rp[1], rp[0]*cs);
+   cur.r[1] = fk_fma(-sn, rp[0], rp[1]*cs);
+   cur.r[2] = fk_fma(rp[2], cs, rp[2]*om);
+   cur.t = fk_fma(aw, qp, tj);
 #ifndef ORC_ABLATE_FKSPH
    if (store)
    {
       const int count = J.ctl & 255;
       if (LAZY)
       {
-         // fp64: the sphere part of the record is fetched here, after the frame (the whole record is 59 words)
+         // fp64: the sphere part of the record is fetched here, after the frame (the whole record is 53 words)
          if (count > 0)
          {
             real lp[4][3]; int off[4];
@@ -144,7 +160,7 @@ __device__ __forceinline__ DevFkJoint<real> fk_record(const __attribute__((addre
 #pragma unroll
    for (int q=0; q<9; q++) d.Rfix[q] = src->Rfix[q];
 #pragma unroll
-   for (int q=0; q<3; q++) { d.tfix[q] = src->tfix[q]; d.axis[q] = src->axis[q]; }
+   for (int q=0; q<3; q++) d.tfix[q] = src->tfix[q];
    d.ctl = src->ctl;
    if (SPHERES)
 #pragma unroll
@@ -165,9 +181,10 @@ __device__ __forceinline__ DevFkJoint<real> fk_record(const __attribute__((addre
 // [j_begin, j_end), whose axes, anchors and sphere centres it stores; `first`: this walk also stores what belongs
 // to no joint (the spheres of a floating base, the row's static and empty slots).  The whole robot: (0, 0, nj, true).
 // The sin/cos of a waypoint's own joints are shared by its triad: lane k evaluates joints j_begin + k, + k + 3, ...
-// and leaves (s, c, qp) in the joint's own slot of ax_wp, which the walk overwrites with the joint's axis
-// and anchor when it gets there (the three lanes sit in one wavefront, whose LDS operations execute in
-// program order: every lane has read the slot before any lane writes it).
+// and leaves (s, c, qp, 1 - c) in the first four of the six numbers of the joint's own slot of ax_wp.  The walk overwrites
+// the slot with the joint's axis (numbers 0 .. 2, one per lane) and anchor (3 .. 5) when it gets there; 1 - c sits in the
+// first anchor number, which lane 0 writes.  The three lanes sit in one wavefront, whose LDS operations execute in
+// program order: every lane has read its four numbers before any lane writes the slot.
 // A joint's record is fetched one step ahead of its use (scalar loads; the joint's step itself then waits for
 // nothing but its three staged numbers).
 // TREE = the joint tree branches (saved frames).
@@ -246,12 +263,12 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
       // a prismatic joint: no rotation, the frame moves q along the axis; a revolute one: no translation
       const bool revolute = ((pkm & 3) == 1);
       snm = revolute ? snm : (real)0; csm = revolute ? csm : (real)1; qm = revolute ? (real)0 : qm;
-      if (valid && j < j_end) { real * st = ax_wp + jm*6; st[0] = snm; st[1] = csm; st[2] = qm; }
+      if (valid && j < j_end) { real * st = ax_wp + jm*6; st[0] = snm; st[1] = csm; st[2] = qm; st[3] = (real)1 - csm; }
    }
    __builtin_amdgcn_wave_barrier();
    const int n_steps = n_anc + (j_end - j_begin);
    auto joint_of = [&](int idx) { return (idx < n_anc) ? idx : j_begin + (idx - n_anc); };
-   // (fp32: 2 x 32 scalar registers hold this joint's record and the next; an fp64 record is 59 words, and two of
+   // (fp32: 2 x 29 scalar registers hold this joint's record and the next; an fp64 record is 53 words, and two of
    // them cost more in scalar spills than the fetch ahead gains: measured on BASELINE configs[1] and [3])
    constexpr bool AHEAD = sizeof(real) == 4;
    DevFkJoint<real> nxt;
@@ -262,11 +279,11 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
       const bool own = (idx >= n_anc);                                    // (wave-uniform)
       // the joint's staged numbers first: the wait for them (LDS) then does not also wait for the scalar loads of
       // the record fetched ahead, which are issued behind it (both count on lgkmcnt, and scalar loads return out of order)
-      real sn = 0, cs = 0, qp = 0;
+      real sn = 0, cs = 0, qp = 0, om = 0;
       if (own)
       {
          const real * st = ax_wp + j*6;
-         sn = st[0]; cs = st[1]; qp = st[2];
+         sn = st[0]; cs = st[1]; qp = st[2]; om = st[3];
       }
       DevFkJoint<real> J;
       if (AHEAD)
@@ -280,7 +297,7 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
          const bool revolute = ((J.ctl >> 24) & 1) != 0;
          const real q = row[(J.ctl >> 25) & 127];
          sincos_joint(q, &sn, &cs);
-         sn = revolute ? sn : (real)0; cs = revolute ? cs : (real)1; qp = revolute ? (real)0 : q;
+         sn = revolute ? sn : (real)0; cs = revolute ? cs : (real)1; qp = revolute ? (real)0 : q; om = (real)1 - cs;
       }
       if (TREE)
       {
@@ -292,7 +309,7 @@ __device__ __forceinline__ void fk_waypoint_triad(const ModelView<real> & mod, c
          else if (load_slot == 2) cur = sv2;
          else if (load_slot == 3) cur = sv3;
       }
-      fk_joint_row<real, !AHEAD>(mod, J, mod.fkj + j, cur, qp, sn, cs, valid && own, ax_wp + j*6 + kk, pos_k);
+      fk_joint_row<real, !AHEAD>(mod, J, mod.fkj + j, cur, qp, sn, cs, om, valid && own, ax_wp + j*6 + kk, pos_k);
       if (TREE)
       {
          const int save_slot = ((J.ctl >> 20) & 15) - 2;

@@ -64,6 +64,7 @@ JointTree fold_joint_tree(const Robot & robot, bool floating_base)
    }
    const int nj = T.nj();
    if (nj > ORC_MAX_JOINTS) throw std::runtime_error("too many active joints for this build!");
+   for (int k=0; k<nj; k++) T.canon.push_back(canonical_rotation(&robot.axis[3*T.jlink[k]]));
    T.jparent.resize(nj);
    for (int k=0; k<nj; k++)
    {
@@ -148,6 +149,69 @@ void point_in(const Robot & robot, int from_link, int li, const double * pin, do
       for (int q=0; q<3; q++) pt[q] = r[q] + x.t[q];
    }
    pout[0] = pt[0]; pout[1] = pt[1]; pout[2] = pt[2];
+}
+
+// ================================================================ canonical joint frames ===
+// The FK walk (fk.h) turns every joint about z.  The fold re-expresses the moved frame F_j of every optimized joint as
+// F'_j = F_j C_j with a constant rotation C_j, C_j e_z = axis_j (C = I for the base):
+//    Rfix'_j = C_parent^T Rfix_j C_j,   tfix'_j = C_parent^T tfix_j,   axis'_j = (0, 0, 1),
+// and everything that is stored in a joint's moved frame (sphere centres, the TSR's link frame) is multiplied by C_j^T on the
+// host.  World quantities -- sphere centres, joint axes, anchors, the end effector's pose -- are what they were.
+Mat3 canonical_rotation(const double axis[3])
+{
+   Mat3 C;
+   for (int q=0; q<9; q++) C.m[q] = 0.0;
+   // +- a coordinate axis: a signed permutation of determinant +1, so that the fold's products stay exact
+   // (columns: +x (y z x), -x (z y -x), +y (z x y), -y (x z -y), +z (x y z), -z (x -y -z))
+   for (int q=0; q<3; q++)
+      if (std::fabs(axis[q]) == 1.0 && axis[(q+1)%3] == 0.0 && axis[(q+2)%3] == 0.0)
+      {
+         const bool neg = axis[q] < 0.0;
+         const int c0 = neg ? (q == 2 ? 0 : (q+2)%3) : (q+1)%3, c1 = neg ? (q == 2 ? 1 : (q+1)%3) : (q+2)%3;
+         C.m[c0*3+0] = 1.0; C.m[c1*3+1] = (neg && q == 2) ? -1.0 : 1.0; C.m[q*3+2] = axis[q];
+         return C;
+      }
+   // a general axis, in extended precision: z = the axis; x = the coordinate axis along which the axis has its smallest component
+   // (the first of equals), made orthogonal to z; y = z x x.  One more Gram-Schmidt pass, then rounded.
+   long double z[3] = { axis[0], axis[1], axis[2] }, x[3] = { 0.0L, 0.0L, 0.0L }, y[3];
+   auto dot = [](const long double * a, const long double * b) { return a[0]*b[0] + a[1]*b[1] + a[2]*b[2]; };
+   auto unit = [&dot](long double * a) { const long double n = std::sqrt(dot(a, a)); for (int q=0; q<3; q++) a[q] /= n; };
+   if (!(dot(z, z) > 0.0L)) throw std::runtime_error("a joint axis of zero length!");
+   unit(z);
+   int least = 0;
+   for (int q=1; q<3; q++) if (std::fabs(z[q]) < std::fabs(z[least])) least = q;
+   x[least] = 1.0L;
+   for (int pass=0; pass<2; pass++)
+   {
+      const long double xz = dot(x, z);
+      for (int q=0; q<3; q++) x[q] -= xz * z[q];
+      unit(x);
+   }
+   y[0] = z[1]*x[2] - z[2]*x[1]; y[1] = z[2]*x[0] - z[0]*x[2]; y[2] = z[0]*x[1] - z[1]*x[0];
+   unit(y);
+   for (int q=0; q<3; q++) { C.m[q*3+0] = (double) x[q]; C.m[q*3+1] = (double) y[q]; C.m[q*3+2] = (double) z[q]; }
+   return C;
+}
+
+namespace { const Mat3 IDENTITY3 = { { 1.0, 0.0, 0.0,  0.0, 1.0, 0.0,  0.0, 0.0, 1.0 } }; }
+const Mat3 & JointTree::canonical(int k) const { return (k >= 0) ? canon[k] : IDENTITY3; }
+
+namespace {
+// C^T v and C^T R D, summed in extended precision and rounded once (a signed permutation leaves every entry as it was)
+void canon_vec(const Mat3 & C, const double v[3], double out[3])
+{
+   for (int c=0; c<3; c++) out[c] = (double)((long double) C.m[0*3+c]*v[0] + (long double) C.m[1*3+c]*v[1] + (long double) C.m[2*3+c]*v[2]);
+}
+Mat3 canon_mat(const Mat3 & C, const Mat3 & R, const Mat3 & D)
+{
+   long double RD[9];
+   for (int r=0; r<3; r++) for (int c=0; c<3; c++)
+      RD[r*3+c] = (long double) R.m[r*3+0]*D.m[0*3+c] + (long double) R.m[r*3+1]*D.m[1*3+c] + (long double) R.m[r*3+2]*D.m[2*3+c];
+   Mat3 out;
+   for (int r=0; r<3; r++) for (int c=0; c<3; c++)
+      out.m[r*3+c] = (double)((long double) C.m[0*3+r]*RD[0*3+c] + (long double) C.m[1*3+r]*RD[1*3+c] + (long double) C.m[2*3+r]*RD[2*3+c]);
+   return out;
+}
 }
 
 // ================================================================ lanes of the self-collision term ===
@@ -433,18 +497,13 @@ void fold_joints(DevModel<real> & M, const Robot & robot, const JointTree & T)
       const int li = T.jlink[jk];
       // from-frame: the moved frame of the parent optimized joint's link (or the base)
       const Xform fix = fixed_between(robot, (T.jparent[jk] < 0) ? -1 : T.jlink[T.jparent[jk]], li);
-      bool ident = true;
-      for (int q=0; q<9; q++)
-      {
-         J.Rfix[q] = (real) fix.R.m[q];
-         if (fix.R.m[q] != ((q % 4 == 0) ? 1.0 : 0.0)) ident = false;
-      }
-      for (int q=0; q<3; q++) { J.tfix[q] = (real) fix.t[q]; J.axis[q] = (real) robot.axis[3*li+q]; }
-      J.rfix_identity = ident ? 1 : 0;
-      J.axis_kind = 0; J.axis_sign = (real) 1;
-      for (int q=0; q<3; q++)
-         if (std::fabs(robot.axis[3*li+q]) == 1.0 && robot.axis[3*li+(q+1)%3] == 0.0 && robot.axis[3*li+(q+2)%3] == 0.0)
-         { J.axis_kind = q + 1; J.axis_sign = (real) robot.axis[3*li+q]; }
+      // ... both in their canonical form (above): the joint turns about z of its own frame
+      const Mat3 & Cp = T.canonical(T.jparent[jk]);
+      const Mat3 Rc = canon_mat(Cp, fix.R, T.canonical(jk));
+      double tc[3];
+      canon_vec(Cp, fix.t, tc);
+      for (int q=0; q<9; q++) J.Rfix[q] = (real) Rc.m[q];
+      for (int q=0; q<3; q++) { J.tfix[q] = (real) tc[q]; J.axis[q] = (real)((q == 2) ? 1 : 0); }
       J.type = robot.joint_type[li];
       J.col = T.jcol[jk];
       J.load_slot = T.load_slot[jk];
@@ -465,9 +524,10 @@ void fold_active_spheres(DevModel<real> & M, const Robot & robot, const JointTre
    {
       const Robot::Sphere & sp = robot.spheres[act[s].xml];
       const int ap = act[s].attach_pos;
-      // position in the attach frame (frozen intermediate joints folded in)
-      double pl[3];
-      point_in(robot, (ap < 0) ? -1 : T.jlink[T.order[ap]], sp.link, sp.pos, pl);
+      // position in the attach frame (frozen intermediate joints folded in), the frame in its canonical form
+      double pt[3], pl[3];
+      point_in(robot, (ap < 0) ? -1 : T.jlink[T.order[ap]], sp.link, sp.pos, pt);
+      canon_vec(T.canonical((ap < 0) ? -1 : T.order[ap]), pt, pl);
       for (int q=0; q<3; q++) M.sph_pos[s][q] = (real) pl[q];
       M.sph_radius[s] = (real) sp.radius;
       M.sph_link[s] = sp.link;
@@ -486,8 +546,7 @@ void fold_active_spheres(DevModel<real> & M, const Robot & robot, const JointTre
    for (int k=0; k<nj; k++)
    {
       DevJoint<real> & J = M.joints[k];
-      J.packed = (J.type & 3) | ((J.axis_kind & 3) << 2) | ((J.rfix_identity & 1) << 4) | ((J.axis_sign < 0 ? 1 : 0) << 5)
-               | ((J.sph_begin & 255) << 8) | ((J.sph_end & 255) << 16) | ((J.col & 127) << 24);
+      J.packed = (J.type & 3) | ((J.sph_begin & 255) << 8) | ((J.sph_end & 255) << 16) | ((J.col & 127) << 24);
       J.packed2 = ((J.load_slot + 2) & 15) | (((J.save_slot + 2) & 15) << 4);
       M.jpacked[k] = J.packed; M.jpacked2[k] = J.packed2;
    }
@@ -567,7 +626,7 @@ void fold_lanes(DevModel<real> & M, const Robot & robot, const Lanes & L, const 
       { M.pr_ab[e] = L.ptab.ab[e]; M.pr_gat[2*e] = L.ptab.gat[2*e]; M.pr_gat[2*e+1] = L.ptab.gat[2*e+1]; M.pr_rsum[e] = (real) L.ptab.rsum[e]; }
 }
 
-// the FK walk's records (DevFkJoint): fixed transform, axis, control word and the first four spheres of the link; and the cut
+// the FK walk's records (DevFkJoint): fixed transform (the axis is z), control word and the first four spheres of the link; and the cut
 // of the walk.  A chain that then branches: joints 0 .. c are each other's parents, c has several children and everything
 // after c hangs below it.  The walk is cut at the child of c that balances [0, cut) against (chain + [cut, nj)).
 template <typename real>
@@ -579,7 +638,7 @@ void fold_fk_walk(DevModel<real> & M, const JointTree & T, const Switches & sw)
       const DevJoint<real> & J = M.joints[k];
       DevFkJoint<real> & F = M.fkj[k];
       for (int q=0; q<9; q++) F.Rfix[q] = J.Rfix[q];
-      for (int q=0; q<3; q++) { F.tfix[q] = J.tfix[q]; F.axis[q] = J.axis[q]; }
+      for (int q=0; q<3; q++) F.tfix[q] = J.tfix[q];
       const int count = J.sph_end - J.sph_begin;
       F.ctl = (count & 255) | ((J.sph_begin & 255) << 8) | (((J.load_slot + 2) & 15) << 16) | (((J.save_slot + 2) & 15) << 20)
             | ((J.type == 1 ? 1 : 0) << 24) | ((J.col & 127) << 25);
@@ -719,8 +778,13 @@ FoldedTsrs<real> fold_tsrs(const Robot & robot, const BatchParams & params, cons
       x.t[0] = x.t[1] = x.t[2] = 0.0;
       const int from_link = (at < 0) ? -1 : tree.jlink[at];
       for (int cur=sp.ee_link; cur!=from_link && cur>=0; cur=robot.parent[cur]) x = xform_mul(local_moved(robot, cur), x);
-      for (int q=0; q<9; q++) T.Xl_R[q] = (real) x.R.m[q];
-      for (int q=0; q<3; q++) T.Xl_t[q] = (real) x.t[q];
+      // (the walk's frame of that joint is canonical; the constraint reads the link's true pose)
+      const Mat3 & Ca = tree.canonical(at);
+      const Mat3 Rc = canon_mat(Ca, x.R, tree.canonical(-1));
+      double tc[3];
+      canon_vec(Ca, x.t, tc);
+      for (int q=0; q<9; q++) T.Xl_R[q] = (real) Rc.m[q];
+      for (int q=0; q<3; q++) T.Xl_t[q] = (real) tc[q];
       const Pose tw = pose_invert(sp.T0w), eo = pose_invert(sp.Twe);
       for (int q=0; q<7; q++) { T.tool[q] = (real) sp.tool.v[q]; T.table_world[q] = (real) tw.v[q]; T.ee_obj[q] = (real) eo.v[q]; }
       T.k = 0;

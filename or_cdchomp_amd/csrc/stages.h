@@ -141,11 +141,18 @@ struct JointTree
    std::vector<int> roots;
    std::vector<int> order, pos_in_order;      // the walk: joint at position p; position of joint k
    std::vector<int> load_slot, save_slot;     // per joint: -2 a root, -1 the frame just computed / nothing to save, else the slot
+   std::vector<Mat3> canon;                   // per joint: its canonical rotation C, C e_z = axis (below); built once with the tree
    int nj() const { return (int) jlink.size(); }
+   // C of optimized joint k; the identity for -1 (the base, fixed or floating)
+   const Mat3 & canonical(int k) const;
    // nearest optimized-joint ancestor-or-self of a link (-1: rigid with the base)
    int attach_of(const Robot & robot, int link) const;
 };
 JointTree fold_joint_tree(const Robot & robot, bool floating_base);
+// The canonical form of a joint's moved frame: F' = F C with the constant rotation C, C e_z = axis, so that the FK walk turns
+// every joint about z (fk.h).  A signed permutation for +- a coordinate axis (the fold's products then stay exact), else built
+// in extended precision, orthonormal to rounding, the free turn about z fixed by the axis alone.
+Mat3 canonical_rotation(const double axis[3]);
 // frozen local transforms of the robot's current configuration.  Everything that is folded into the device model is a
 // product of link-local transforms, so no frame is ever inverted (the base rotation need not be orthonormal)
 Xform local_moved(const Robot & robot, int li);
