@@ -543,6 +543,34 @@ void Batch::for_shards(const std::function<void(size_t)> & body, bool threads)
    for (std::exception_ptr & e : errs) if (e) std::rethrow_exception(e);
 }
 
+void Batch::deal_by_run(int n_q, const int * run_of_q, bool profile, const std::vector<DealColumn> & ins, const std::vector<DealColumn> & outs,
+   const DealCall & call)
+{
+   // the caller's own arrays from query `first` on (a NULL stays NULL)
+   const auto from = [](const std::vector<DealColumn> & cols, size_t first) {
+      std::vector<void *> p;
+      for (const DealColumn & c : cols) p.push_back(c.data ? (unsigned char *) c.data + first*c.bytes() : nullptr);
+      return p;
+   };
+   if (shards.size() == 1)      // one shard owns every run: the gather would be the identity, and copy n_q rows to say so
+   {
+      call(0, n_q, run_of_q, from(ins, 0), from(outs, 0));
+      return;
+   }
+   for_shards([&](size_t k) {
+      if (profile)      // every waypoint in storage order: a shard's queries are its slice
+      {
+         const size_t w0 = (size_t) offs[k] * n_points;
+         call(k, (offs[k+1] - offs[k]) * n_points, nullptr, from(ins, w0), from(outs, w0));
+         return;
+      }
+      const Deal d = deal_gather(n_q, run_of_q, offs[k], offs[k+1], ins, outs);
+      if (d.at.empty()) return;
+      call(k, (int) d.at.size(), d.run.data(), d.in_ptr, d.out_ptr);
+      deal_scatter(d, outs);
+   }, true);
+}
+
 void Batch::iterate_async(int n_iter, int iter_begin, bool final_eval, bool carry)
 {
    if (n_iter < 0) throw std::runtime_error("n_iter must be >=0!");

@@ -15,6 +15,7 @@
 #include "verdict.h"     // VerdictInputs, the sample clock, the free functions of the collision verdict
 #include "tsr_form.h"    // TsrForm, tsr_form: the constraint step's form, the iterate kernel's own decision
 #include "multistart.h"  // SelectCriterion, SelectResult, PerturbPlan, RespawnPlan: what the multi-start calls pass each other
+#include "deal.h"        // DealColumn, deal_gather, deal_scatter: the queries of a single-row call dealt to the shards
 
 template <typename real> struct DevVerdictWalk;      // verdict_device.h
 template <typename real> struct DevVerdictPlanned;
@@ -49,8 +50,12 @@ struct PenetrationOut
 {
    double * cost = nullptr, * grad = nullptr, * clear = nullptr;
    unsigned int * key = nullptr;
-   PenetrationOut from(size_t first, int n) const;
 };
+// what the calls with margins reject of them (penetration.cpp; who: the call's name in what it throws)
+void margins_check(const char * who, double margin_field, double margin_self);
+// key [count] of a single-row call (config_device.h) as the boundary returns it: the XML sphere, and the field or the other
+// sphere of a pair; -1 and -1 without an item (config_clearance.cpp; sphere, other: [count] or NULL)
+void unpack_keys(const unsigned int * key, size_t count, int * sphere, int * other);
 
 // the parameters of a projection onto TSRs (project.cpp; or_cdchomp_amd/project.py is the rule); lower, upper [n] or NULL
 struct ProjectSpec
@@ -298,22 +303,29 @@ public:
    void clearance_check(int which, const unsigned char * examine, int max_samples) const;
    void clearance(const VerdictInputs & in, int which, const unsigned char * examine, int max_samples, double * clear_out, double * time_out,
                   unsigned long long * key_out, int * n_samples_out);
+   // The queries of a single-row call dealt to the shards (batch.cpp, deal.h).  Per shard: the queries whose run (run_of_q, NULL:
+   // run 0) it owns, in their order, with the run rebased; the input columns `ins` gathered; call(shard, count, run, in, out) with
+   // the columns' data in their order (NULL for a NULL column); the output columns `outs` scattered back to the caller's order.
+   // Nothing is copied when one shard owns every run, nor in the profile form (`profile`: query q is waypoint q in storage
+   // order, n_points per run, and a shard's queries are a contiguous slice of the caller's arrays; run is NULL then)
+   using DealCall = std::function<void(size_t, int, const int *, const std::vector<void *> &, const std::vector<void *> &)>;
+   void deal_by_run(int n_q, const int * run_of_q, bool profile, const std::vector<DealColumn> & ins, const std::vector<DealColumn> & outs, const DealCall & call);
    // (config_clearance.cpp) orc_batch_config_clearance / orc_batch_waypoint_clearance.  config_clearance_check throws for what
    // those calls reject, before any device work; `config_clearance`: every shard takes the queries whose run it owns, in their
    // order, and the results go back to the caller's order; outputs [n_q][2] or NULL
    void config_clearance_check(bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs) const;
    void config_clearance(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q,
                          const double * configs, double * clear_out, unsigned int * key_out);
-   // (penetration.cpp) orc_batch_config_penetration / orc_batch_waypoint_penetration: the queries dealt as config_clearance deals
-   // them (the caller has made config_clearance_check and checked the margins)
+   // (penetration.cpp) orc_batch_config_penetration / orc_batch_waypoint_penetration: the queries dealt by run (the caller has
+   // made config_clearance_check and margins_check)
    void config_penetration(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q,
                            const double * configs, double margin_field, double margin_self, const PenetrationOut & out);
    // (project.cpp) orc_batch_config_tsr / orc_batch_project_tsr: every shard takes an even contiguous slice of the queries (the
    // caller, Module::project_check, has checked the arguments)
    void project_tsr(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
                     const ProjectSpec * ps, const ProjectOut & out);
-   // (project_clear.cpp) orc_batch_project_tsr_clear: a row goes to the shard that owns its run, as config_penetration deals
-   // them (the caller, Module::batch_project_tsr_clear, has checked the arguments)
+   // (project_clear.cpp) orc_batch_project_tsr_clear: a row goes to the shard that owns its run (the caller,
+   // Module::batch_project_tsr_clear, has checked the arguments)
    void project_tsr_clear(const Robot & robot, const VerdictInputs & in, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q,
                           const int * run_of_q, const double * configs, const ProjectClearSpec & ps, const ProjectClearOut & out);
    // the runs the verdict inside select_best and respawn examines (orc_batch_set_verdict_scope): 0 every run, 1 the candidates;

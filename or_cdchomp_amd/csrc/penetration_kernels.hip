@@ -2,16 +2,17 @@
 // (orc_batch_config_penetration, orc_batch_waypoint_penetration): config_clearance_kernel's sibling.  Per query, one stateless
 // evaluation: U_f over the spheres and fields, U_s over the pairs, d(U_f + U_s)/d row, and the two minima and keys of the sibling.
 //
-// Staging, the copy of the rows, verdict_renormalise and verdict_fk are the sibling's (config_kernels.hip), and the wavefront that
-// ran FK for a query evaluates it alone.  Its lanes change roles twice:
+// Staging, the copy of the rows, verdict_renormalise and verdict_fk are the sibling's (config_query_prologue of config_query.h,
+// with one real per query of its own in the LDS header), and the wavefront that ran FK for a query evaluates it alone.  Its
+// lanes change roles twice:
 //   lane = sphere slot   the slot's fields in scene order, then the slot's pairs in list order (the pairs by sphere: a CSR the
 //                        host builds from the pair table).  The lane ends with its sphere's total force f = dU/dp and its
 //                        share of the two costs.
 //   lane = joint         the sum of (p x C f, f) over the spheres the joint moves (DevModel::sph_affects), slot by slot through
 //                        lane reads, contracted with the axis and anchor verdict_fk left in ax_s.
 //   every lane           butterfly sums of the costs and, for a floating base, of the wrench.
-// The two minima and their keys are the sibling's to the bit.  They are taken by the sibling's own loop (pen_minima: config_tests
-// word for word, lanes striding over the items), not from the gaps the cost pass forms: the lookup is compiled with contraction
+// The two minima and their keys are the sibling's to the bit.  They are taken by the sibling's own loop (config_tests of
+// config_query.h, lanes striding over the items), not from the gaps the cost pass forms: the lookup is compiled with contraction
 // allowed, and where its slope is live (here, for the force) the compiler fuses and vectorises its sums differently than where it
 // is dead (there) -- in fp32 the two gaps differ in the last bit.  A second lookup per item is the price of the same bits.
 // Every sum has a fixed order that depends on the robot alone, and there is no atomic: a query's answer depends on its row, its
@@ -33,33 +34,7 @@ namespace {
 #include "sdf_lookup.h"
 #include "fk.h"
 #include "verdict_walk.h"
-
-// a lane's running minimum of one leg, the offer and the report: config_kernels.hip's, word for word (that file is a
-// translation unit of its own; the minima must be its bits)
-template <typename real>
-struct PenMin
-{
-   real val;
-   unsigned int key;
-};
-
-template <typename real>
-__device__ __forceinline__ void pen_offer(PenMin<real> & m, real gap, int a, int b)
-{
-   const unsigned int key = ((unsigned int) a << 16) | (unsigned int) b;
-   if (gap < m.val || (gap == m.val && key < m.key && m.key != ORC_CONFIG_NONE))
-   {
-      m.val = gap;
-      m.key = key;
-   }
-}
-
-template <typename real>
-__device__ __forceinline__ real pen_wave_min(real x)
-{
-   for (int d=32; d>=1; d>>=1) x = M<real>::min_(x, __shfl_xor(x, d));
-   return x;
-}
+#include "config_query.h"
 
 // the wavefront's sum in the butterfly's order: every lane ends with the same bits
 template <typename real>
@@ -74,51 +49,6 @@ __device__ __forceinline__ float pen_lane(float x, int o) { return __int_as_floa
 __device__ __forceinline__ double pen_lane(double x, int o)
 {
    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), o), __builtin_amdgcn_readlane(__double2loint(x), o));
-}
-
-template <typename real>
-__device__ __forceinline__ void pen_report(const PenMin<real> & m, int lane, double * clear_out, unsigned int * key_out)
-{
-   const real lowest = pen_wave_min<real>(m.val);
-   unsigned int key = (m.key != ORC_CONFIG_NONE && m.val == lowest) ? m.key : ORC_CONFIG_NONE;
-   for (int d=32; d>=1; d>>=1) { const unsigned int o = __shfl_xor(key, d); key = o < key ? o : key; }
-   if (lane == 0)
-   {
-      *clear_out = (key == ORC_CONFIG_NONE) ? (double) M<real>::inf() : (double) lowest;
-      *key_out = key;
-   }
-}
-
-// config_tests of config_kernels.hip, word for word: the minima of query s (sample s of the chunk) by one wavefront
-template <typename real>
-__device__ __forceinline__ void pen_minima(const DevVerdictWalk<real> & v, const ModelView<real> & mod, const DevSdf<real> * sdfs, int n_fields,
-   int s, int lane, const VerdictLds<real> & L, PenMin<real> & fld, PenMin<real> & slf)
-{
-   const int Sa = mod.Sa;
-   for (int item=lane; item<Sa*n_fields; item+=64)
-   {
-      const int slot = item / n_fields, i = item - slot*n_fields;
-      if (!((mod.live_mask >> slot) & 1ull)) continue;
-      const real * p = L.pos_s + s*L.pstr + slot*3;
-      const real radius = L.srad_s[slot];
-      const DevSdf<real> & F = sdfs[i];
-      real gp[3], gg[3], val;
-#pragma unroll
-      for (int k=0; k<3; k++)
-         gp[k] = F.Rgw[k*3+0]*p[0] + F.Rgw[k*3+1]*p[1] + F.Rgw[k*3+2]*p[2] + F.tgw[k];
-      if (sdf_lookup(F, gp, val, gg)) continue;                 // outside this field
-      pen_offer<real>(fld, val - radius, L.xml_s[slot], i);
-   }
-   for (int pi=lane; pi<v.n_pairs; pi+=64)
-   {
-      const int ea = v.pairs[pi*4+0], eb = v.pairs[pi*4+1];
-      const real * pa = (ea >= 0) ? L.pos_s + s*L.pstr + ea*3 : v.inact_pos + (-1 - ea)*3;
-      const real * pb = (eb >= 0) ? L.pos_s + s*L.pstr + eb*3 : v.inact_pos + (-1 - eb)*3;
-      const real dx = pa[0]-pb[0], dy = pa[1]-pb[1], dz = pa[2]-pb[2];
-      const real dist = M<real>::sqrt_(dx*dx + dy*dy + dz*dz);
-      const real rs = v.pair_rsum[pi];
-      pen_offer<real>(slf, dist - rs, v.pairs[pi*4+2], v.pairs[pi*4+3]);
-   }
 }
 
 // lane = sphere slot: the slot's items of query s.  f: dU/dp of the sphere, cost [2] the lane's share of U_f and U_s
@@ -175,59 +105,13 @@ void penetration_kernel(DevPenetration<real> v)
 {
    extern __shared__ __align__(16) unsigned char smem_raw[];
    const DevModel<real> & gmod = *v.model;
-   const int tid = threadIdx.x, lane = tid & 63;
-   const int n = v.n, np = v.n_points, chunk = v.chunk;
-   const int q0 = blockIdx.x * chunk;
-   const int count = (v.n_q - q0 < chunk) ? v.n_q - q0 : chunk;      // (the launcher's grid: count >= 1)
-   int * run_s = (int *) smem_raw;                 // [chunk] the query's run
-   int * bad_s = run_s + chunk;                    // [chunk] nonzero: the row has a non-finite entry
-   real * qinv_s = (real *)(smem_raw + (size_t) chunk * 8);      // [chunk] a floating base: 1 / |quaternion| of the caller's row
-   const VerdictLds<real> L = verdict_lds(smem_raw + (size_t) chunk * (8 + sizeof(real)), gmod, n, chunk);
-   verdict_stage<real, ORC_BLOCK>(gmod, v.slot_xml, L, tid);
-   const ModelView<real> mod = verdict_model_view(gmod, n, L);
-   const bool profile = !v.configs && !v.point_of_q;
-   if (tid < count)
-   {
-      const int q = q0 + tid;
-      run_s[tid] = profile ? q / np : (v.run_of_q ? v.run_of_q[q] : 0);
-   }
-   // the rows, copied
-   for (int e=tid; e<count*n; e+=ORC_BLOCK)
-   {
-      const int s = e / n, c = e - s*n, q = q0 + s;
-      real x;
-      if (v.configs) x = v.configs[(size_t) q*n + c];
-      else
-      {
-         const int run = profile ? q / np : v.run_of_q[q];
-         const int point = profile ? q - run*np : v.point_of_q[q];
-         x = v.traj[((size_t) run*np + point)*n + c];
-      }
-      L.rows_s[s*n + c] = x;
-   }
-   __syncthreads();
-   // a row with a non-finite entry is not evaluated: decided here, before FK, which then runs on a harmless row in its place
-   if (tid < count)
-   {
-      real * row = L.rows_s + tid*n;
-      bool bad = false;
-      for (int c=0; c<n; c++) bad = bad || !(M<real>::fabs_(row[c]) < M<real>::inf());
-      bad_s[tid] = bad ? 1 : 0;
-      if (bad)
-      {
-         for (int c=0; c<n; c++) row[c] = (real)0;
-         if (mod.floating) row[6] = (real)1;
-      }
-      qinv_s[tid] = mod.floating ? (real)1 / M<real>::sqrt_(row[3]*row[3] + row[4]*row[4] + row[5]*row[5] + row[6]*row[6]) : (real)1;
-   }
-   verdict_renormalise(mod, count, tid, L);      // (tid < count: the thread that looked at the row)
-   __syncthreads();
-   verdict_fk<real, TREE>(mod, count, tid, L);
-   // what the wavefront's lanes stored for its 20 queries is read by its other lanes: a wavefront's LDS operations execute in
-   // program order, and the compiler keeps them on their side of this point
-   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-   __builtin_amdgcn_wave_barrier();
-   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+   const int lane = threadIdx.x & 63, n = v.n;
+   real * qinv_s = (real *)(smem_raw + config_query_header_bytes(v.chunk, 0));      // [chunk] a floating base: 1 / |quaternion| of the caller's row
+   const ConfigQuery<real> Q = config_query_prologue<real, TREE>(v, smem_raw, sizeof(real), [qinv_s](int s, const real * row, const ModelView<real> & mod) {
+      qinv_s[s] = mod.floating ? (real)1 / M<real>::sqrt_(row[3]*row[3] + row[4]*row[4] + row[5]*row[5] + row[6]*row[6]) : (real)1;
+   });
+   const VerdictLds<real> & L = Q.L;
+   const ModelView<real> & mod = Q.mod;
    // C (top of the file), row major; symmetric
    real C[9] = { (real)1, (real)0, (real)0, (real)0, (real)1, (real)0, (real)0, (real)0, (real)1 };
    if (!mod.floating)
@@ -243,12 +127,10 @@ void penetration_kernel(DevPenetration<real> v)
    const int Sa = mod.Sa, nj = mod.nj;
    const bool live = (lane < Sa) && ((mod.live_mask >> lane) & 1ull);
    const double nan = __longlong_as_double(0x7ff8000000000000LL);
-   const int s_begin = (tid >> 6) * 20;
-   const int s_end = (s_begin + 20 < count) ? s_begin + 20 : count;
-   for (int s=s_begin; s<s_end; s++)
+   for (int s=Q.s_begin; s<Q.s_end; s++)
    {
-      const size_t q = (size_t)(q0 + s);
-      if (bad_s[s])      // (wave-uniform)
+      const size_t q = (size_t)(Q.q0 + s);
+      if (Q.bad_s[s])      // (wave-uniform)
       {
          if (lane < 2)
          {
@@ -260,10 +142,10 @@ void penetration_kernel(DevPenetration<real> v)
          continue;
       }
       const DevSdf<real> * sdfs; int n_fields;
-      verdict_scene<real>(v, __builtin_amdgcn_readfirstlane(run_s[s]), sdfs, n_fields);
-      PenMin<real> best[2];      // [0] fields, [1] pairs
+      verdict_scene<real>(v, __builtin_amdgcn_readfirstlane(Q.run_s[s]), sdfs, n_fields);
+      ConfigMin<real> best[2];      // [0] fields, [1] pairs
       for (int leg=0; leg<2; leg++) { best[leg].val = M<real>::inf(); best[leg].key = ORC_CONFIG_NONE; }
-      pen_minima<real>(v, mod, sdfs, n_fields, s, lane, L, best[0], best[1]);
+      config_tests<real>(v, mod, sdfs, n_fields, s, lane, L, best[0], best[1]);
       // ---- lane = sphere slot
       real p[3] = { (real)0, (real)0, (real)0 }, f[3] = { (real)0, (real)0, (real)0 }, cost[2] = { (real)0, (real)0 };
       if (live)
@@ -274,7 +156,7 @@ void penetration_kernel(DevPenetration<real> v)
       }
       for (int leg=0; leg<2; leg++)
       {
-         pen_report<real>(best[leg], lane, v.clear_out + q*2 + leg, v.ckey_out + q*2 + leg);
+         config_report<real>(best[leg], lane, v.clear_out + q*2 + leg, v.ckey_out + q*2 + leg);
          const real total = pen_wave_sum<real>(cost[leg]);
          if (lane == 0) v.cost_out[q*2 + leg] = (double) total;
       }
@@ -343,36 +225,14 @@ void penetration_kernel(DevPenetration<real> v)
 
 } // namespace
 
-// One launcher for the two instantiations of a precision (launch_config_clearance_t of config_kernels.hip)
 template <typename real>
 static hipError_t launch_penetration_t(const DevPenetration<real> & v, size_t lds, hipStream_t stream, int tree)
 {
-   static std::atomic<unsigned long long> attr_set{0ull};
-   if (v.chunk < 4 || v.chunk > 64 || (v.chunk & 3)) return hipErrorInvalidValue;
-   if (v.n_q < 1 || v.n_q > ORC_CONFIG_MAX_Q || v.n_points < 1) return hipErrorInvalidValue;
-   if (!v.configs && ((v.run_of_q == nullptr) != (v.point_of_q == nullptr))) return hipErrorInvalidValue;
-   if (!v.configs && !v.point_of_q && v.n_q > v.n_runs * v.n_points) return hipErrorInvalidValue;
    if (!v.sph_pair_offs || !v.sph_pair_list || !v.cost_out || !v.grad_out || !v.clear_out || !v.ckey_out) return hipErrorInvalidValue;
-   if (lds > ORC_VERDICT_LDS_LIMIT) return hipErrorInvalidValue;
-   int dev = 0;
-   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-   if (!((attr_set.load() >> dev) & 1ull))
-   {
-      hipError_t e = hipFuncSetAttribute((const void *) penetration_kernel<real, true>, hipFuncAttributeMaxDynamicSharedMemorySize, ORC_VERDICT_LDS_LIMIT);
-      if (e == hipSuccess) e = hipFuncSetAttribute((const void *) penetration_kernel<real, false>, hipFuncAttributeMaxDynamicSharedMemorySize, ORC_VERDICT_LDS_LIMIT);
-      if (e != hipSuccess) return e;
-      attr_set.fetch_or(1ull << dev);
-   }
-   const int blocks = (v.n_q + v.chunk - 1) / v.chunk;
-   if (tree) hipLaunchKernelGGL((penetration_kernel<real, true>), dim3(blocks), dim3(ORC_BLOCK), lds, stream, v);
-   else hipLaunchKernelGGL((penetration_kernel<real, false>), dim3(blocks), dim3(ORC_BLOCK), lds, stream, v);
-   return hipGetLastError();
+   return launch_config_query<DevPenetration<real>, penetration_kernel<real, true>, penetration_kernel<real, false>>(v, lds, stream, tree);
 }
 hipError_t orc_launch_penetration(const DevPenetration<double> & v, size_t lds, hipStream_t stream, int tree) { return launch_penetration_t<double>(v, lds, stream, tree); }
 hipError_t orc_launch_penetration(const DevPenetration<float> & v, size_t lds, hipStream_t stream, int tree) { return launch_penetration_t<float>(v, lds, stream, tree); }
 
-// dynamic LDS of penetration_kernel (the carve-up at its top): two ints and one real per query, then what the walk holds
-size_t orc_penetration_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk)
-{
-   return (size_t) chunk * (8 + real_size) + verdict_walk_lds_bytes(n, Sa, Sa_real, nj, real_size, chunk);
-}
+// dynamic LDS of penetration_kernel: the queries' header with one real per query, then what the walk holds
+size_t orc_penetration_lds_bytes(int n, int Sa, int Sa_real, int nj, size_t real_size, int chunk) { return config_query_lds_bytes(n, Sa, Sa_real, nj, real_size, chunk, real_size); }

@@ -4,9 +4,9 @@
 // project_kernels.hip.  The model is the one `create` put on the device; nothing is kept there after the call.
 #include "module.h"
 #include "project_device.h"
+#include "query_upload.h"
 #include <cmath>
 #include <cstring>
-#include <limits>
 #include <stdexcept>
 
 namespace orc {
@@ -107,86 +107,42 @@ template <typename real>
 void BatchShard::project_tsr_typed(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
    const ProjectSpec * ps, const ProjectOut & out)
 {
-   hipStream_t st = stream_;
-   // the constraints on the device's joint order: fold_tsrs' path, for a trajectory of one moving point
-   const JointTree tree = fold_joint_tree(robot, params.floating_base != 0);
-   if (tree.nj() != ms_.nj) throw std::runtime_error("project tsr: the robot's joint tree is not the one the batch was created with!");
-   BatchParams one = params;
-   one.tsrs = specs;
-   const FoldedTsrs<real> ft = fold_tsrs<real>(robot, one, tree, 1, n);
-   int kmax = 3;
-   for (const DevTsr<real> & t : ft.tsrs) if (t.k > 3) kmax = 6;
-
+   QueryUpload<real> up(stream_, "project");
+   int kmax;
    DevProject<real> v;
    std::memset(&v, 0, sizeof(v));
+   v.tsrs = up.constraints("project tsr", robot, params, ms_.nj, n, specs, kmax);
    v.model = d_model_.as<const DevModel<real>>();
    v.n_q = n_q; v.n = n; v.max_steps = ps ? ps->max_steps : -1;
    v.stride = orc_project_stride(n, kmax);
-   DevBuf d_tsrs, d_of, d_cfg, d_lo, d_hi, d_ws, d_aws, d_h, d_jac, d_rows, d_resid, d_steps, d_status;
-   d_tsrs.reset(dev_alloc<DevTsr<real>>(ft.tsrs.size()));
-   hip_check(hipMemcpyAsync(d_tsrs.as<void>(), ft.tsrs.data(), ft.tsrs.size()*sizeof(DevTsr<real>), hipMemcpyHostToDevice, st), "project tsrs");
-   v.tsrs = d_tsrs.as<const DevTsr<real>>();
-   if (tsr_of_q)
-   {
-      d_of.reset(dev_alloc<int>(n_q));
-      hip_check(hipMemcpyAsync(d_of.as<void>(), tsr_of_q, (size_t) n_q*sizeof(int), hipMemcpyHostToDevice, st), "project tsr_of_q");
-      v.tsr_of_q = d_of.as<int>();
-   }
+   v.tsr_of_q = up.ints(tsr_of_q, n_q, "tsr_of_q");
    const size_t count = (size_t) n_q * n;
-   std::vector<real> narrowed;      // (a precision-32 batch: narrowed as set_traj narrows; it lives until the copy is done)
-   {
-      d_cfg.reset(dev_alloc<real>(count));
-      const void * src = configs;
-      if (sizeof(real) != sizeof(double)) { narrowed.assign(configs, configs + count); src = narrowed.data(); }
-      hip_check(hipMemcpyAsync(d_cfg.as<void>(), src, count*sizeof(real), hipMemcpyHostToDevice, st), "project rows");
-      v.configs = d_cfg.as<const real>();
-   }
-   // a lane's state: in LDS when a workgroup's states fit, else in a workspace of the call
-   if ((size_t) ORC_PROJECT_LANES * v.stride * sizeof(real) > ORC_PROJECT_LDS_BYTES)
-   {
-      d_ws.reset(dev_alloc<real>((size_t) n_q * v.stride));
-      v.ws = d_ws.as<real>();
-   }
-   d_aws.reset(dev_alloc<real>((size_t) ms_.nj * 6 * n_q));
-   v.aws = d_aws.as<real>();
-   std::vector<real> lo, hi;
+   v.configs = up.rows(configs, count);
+   v.ws = up.lane_state(n_q, n, kmax);
+   v.aws = up.template alloc<real>((size_t) ms_.nj * 6 * n_q);
    if (ps)
    {
       v.tol = (real) ps->tol; v.mu = (real) ps->mu; v.step_cap = (real) ps->step_cap;
-      lo.resize(n); hi.resize(n);
-      for (int c=0; c<n; c++)
-      {
-         lo[c] = ps->lower ? (real) ps->lower[c] : -std::numeric_limits<real>::infinity();
-         hi[c] = ps->upper ? (real) ps->upper[c] : std::numeric_limits<real>::infinity();
-         // (precision 32: a limit that rounds outwards is taken one step inwards, so that a clipped row lies inside the caller's box)
-         if (ps->lower && (double) lo[c] < ps->lower[c]) lo[c] = std::nextafter(lo[c], std::numeric_limits<real>::infinity());
-         if (ps->upper && (double) hi[c] > ps->upper[c]) hi[c] = std::nextafter(hi[c], -std::numeric_limits<real>::infinity());
-      }
-      d_lo.reset(dev_alloc<real>(n)); d_hi.reset(dev_alloc<real>(n));
-      hip_check(hipMemcpyAsync(d_lo.as<void>(), lo.data(), n*sizeof(real), hipMemcpyHostToDevice, st), "project lower");
-      hip_check(hipMemcpyAsync(d_hi.as<void>(), hi.data(), n*sizeof(real), hipMemcpyHostToDevice, st), "project upper");
-      v.lower = d_lo.as<const real>(); v.upper = d_hi.as<const real>();
-      d_rows.reset(dev_alloc<double>(count)); d_resid.reset(dev_alloc<double>(n_q));
-      d_steps.reset(dev_alloc<int>(n_q)); d_status.reset(dev_alloc<int>(n_q));
+      up.box(ps->lower, ps->upper, n, v.lower, v.upper);
+      v.rows_out = up.template alloc<double>(count); v.resid_out = up.template alloc<double>(n_q);
+      v.steps_out = up.template alloc<int>(n_q); v.status_out = up.template alloc<int>(n_q);
       // (the answer of a row that never improves on its input is the input: the caller's own doubles)
-      hip_check(hipMemcpyAsync(d_rows.as<void>(), configs, count*sizeof(double), hipMemcpyHostToDevice, st), "project rows out");
-      v.rows_out = d_rows.as<double>(); v.resid_out = d_resid.as<double>(); v.steps_out = d_steps.as<int>(); v.status_out = d_status.as<int>();
+      up.up(v.rows_out, configs, count*sizeof(double), "rows out");
    }
    else
    {
-      d_h.reset(dev_alloc<double>((size_t) n_q * 6)); d_jac.reset(dev_alloc<double>(count * 6));
-      hip_check(hipMemsetAsync(d_h.as<void>(), 0, (size_t) n_q*6*sizeof(double), st), "config tsr h");
-      hip_check(hipMemsetAsync(d_jac.as<void>(), 0, count*6*sizeof(double), st), "config tsr jac");
-      v.h_out = d_h.as<double>(); v.jac_out = d_jac.as<double>();
+      v.h_out = up.template alloc<double>((size_t) n_q * 6); v.jac_out = up.template alloc<double>(count * 6);
+      hip_check(hipMemsetAsync(v.h_out, 0, (size_t) n_q*6*sizeof(double), up.st), "config tsr h");
+      hip_check(hipMemsetAsync(v.jac_out, 0, count*6*sizeof(double), up.st), "config tsr jac");
    }
-   hip_check(orc_launch_project(v, kmax, st), "project_tsr_kernel launch");
-   if (out.h) hip_check(hipMemcpyAsync(out.h, d_h.as<void>(), (size_t) n_q*6*sizeof(double), hipMemcpyDeviceToHost, st), "config tsr h");
-   if (out.jac) hip_check(hipMemcpyAsync(out.jac, d_jac.as<void>(), count*6*sizeof(double), hipMemcpyDeviceToHost, st), "config tsr jac");
-   if (out.rows) hip_check(hipMemcpyAsync(out.rows, d_rows.as<void>(), count*sizeof(double), hipMemcpyDeviceToHost, st), "project rows");
-   if (out.resid) hip_check(hipMemcpyAsync(out.resid, d_resid.as<void>(), (size_t) n_q*sizeof(double), hipMemcpyDeviceToHost, st), "project residuals");
-   if (out.steps) hip_check(hipMemcpyAsync(out.steps, d_steps.as<void>(), (size_t) n_q*sizeof(int), hipMemcpyDeviceToHost, st), "project steps");
-   if (out.status) hip_check(hipMemcpyAsync(out.status, d_status.as<void>(), (size_t) n_q*sizeof(int), hipMemcpyDeviceToHost, st), "project statuses");
-   hip_check(hipStreamSynchronize(st), "project sync");
+   hip_check(orc_launch_project(v, kmax, up.st), "project_tsr_kernel launch");
+   if (out.h) hip_check(hipMemcpyAsync(out.h, v.h_out, (size_t) n_q*6*sizeof(double), hipMemcpyDeviceToHost, up.st), "config tsr h");
+   if (out.jac) hip_check(hipMemcpyAsync(out.jac, v.jac_out, count*6*sizeof(double), hipMemcpyDeviceToHost, up.st), "config tsr jac");
+   up.down(out.rows, v.rows_out, count*sizeof(double), "rows");
+   up.down(out.resid, v.resid_out, (size_t) n_q*sizeof(double), "residuals");
+   up.down(out.steps, v.steps_out, (size_t) n_q*sizeof(int), "steps");
+   up.down(out.status, v.status_out, (size_t) n_q*sizeof(int), "statuses");
+   up.sync();
 }
 
 void BatchShard::project_tsr(const Robot & robot, const std::vector<TsrSpec> & specs, int n_q, const int * tsr_of_q, const double * configs,
@@ -200,8 +156,7 @@ void BatchShard::project_tsr(const Robot & robot, const std::vector<TsrSpec> & s
 // where a lane's state lives for this batch's model and `kmax` enforced rows: 1 in LDS, 0 in the call's workspace
 int BatchShard::project_state_in_lds(int kmax) const
 {
-   const size_t real_size = params.precision == 64 ? sizeof(double) : sizeof(float);
-   return (size_t) ORC_PROJECT_LANES * orc_project_stride(n, kmax) * real_size <= ORC_PROJECT_LDS_BYTES ? 1 : 0;
+   return project_state_fits_lds(n, kmax, params.precision == 64 ? sizeof(double) : sizeof(float)) ? 1 : 0;
 }
 
 } // namespace orc

@@ -12,8 +12,7 @@
 //
 // Within a launch a lane's state -- h, J [KMAX][n], the iterate, the gradient -- is indexed by loop counters and lives in
 // memory, not in registers: in LDS when a workgroup's 64 states fit ORC_PROJECT_LDS_BYTES, else in the call's workspace, as the
-// sibling's.  The Cholesky text is a copy of the sibling's (project_kernels.hip keeps its own, so that its code object is not
-// touched by this file).
+// sibling's.  The residual, the factor, the solve and the clipped move are the sibling's text (project_step.h).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "dev_types.h"
@@ -25,28 +24,7 @@ namespace {
 #include "sdf_lookup.h"
 #include "fk.h"
 #include "tsr_point.h"
-
-// y = (L L^T)^-1 b: L z = b by rows ascending, L^T y = z by rows descending
-template <typename real, int KMAX>
-__device__ __forceinline__ void clear_solve(const real (&L)[KMAX][KMAX], const real (&b)[KMAX], real (&y)[KMAX])
-{
-#pragma unroll
-   for (int i=0; i<KMAX; i++)
-   {
-      real s = b[i];
-#pragma unroll
-      for (int p=0; p<i; p++) s -= L[i][p] * y[p];
-      y[i] = s / L[i][i];
-   }
-#pragma unroll
-   for (int i=KMAX-1; i>=0; i--)
-   {
-      real s = y[i];
-#pragma unroll
-      for (int p=i+1; p<KMAX; p++) s -= L[p][i] * y[p];
-      y[i] = s / L[i][i];
-   }
-}
+#include "project_step.h"
 
 template <typename real>
 __device__ __forceinline__ bool clear_finite(real x) { return M<real>::fabs_(x) < M<real>::inf(); }
@@ -61,8 +39,8 @@ void project_clear_step_kernel(DevProjectClear<real> v)
    if (v.done[q]) return;       // (a frozen row)
    const DevModel<real> & gm = *v.model;
    const int n = v.n, it = v.it;
-   real * st = v.ws ? v.ws + (size_t) q * v.stride : (real *) smem_raw + (size_t) threadIdx.x * v.stride;
-   real * hs = st, * J = st + KMAX, * cur = J + KMAX*n, * g = cur + n;
+   const ProjectLane<real> S = project_lane<real, KMAX>(v.ws, smem_raw, q, v.stride, n);
+   real * hs = S.hs, * J = S.J, * cur = S.cur, * g = S.own;
    const DevTsr<real> & ts = v.tsrs[v.tsr_of_q ? v.tsr_of_q[q] : 0];
    const int k = ts.k;          // (1 .. KMAX: the host chose KMAX by the call's constraints)
    const double nan = __longlong_as_double(0x7ff8000000000000LL);
@@ -90,14 +68,7 @@ void project_clear_step_kernel(DevProjectClear<real> v)
    // ---- the iterate's key
    tsr_eval_point<real>(gm, ts, cur, n, hs, J, v.aws, v.n_q, q);
    real h[KMAX];
-   real r = 0;      // max |h_i|; a NaN entry makes it NaN
-#pragma unroll
-   for (int i=0; i<KMAX; i++)
-   {
-      h[i] = (i < k) ? hs[i] : (real)0;
-      const real a = M<real>::fabs_(h[i]);
-      r = (a > r || a != a) ? a : r;
-   }
+   const real r = project_residual<real, KMAX>(hs, k, h);
    const real U = (real) v.cost[(size_t) q*2] + (real) v.cost[(size_t) q*2 + 1];
    const double clr0 = v.clear[(size_t) q*2], clr1 = v.clear[(size_t) q*2 + 1];
    const bool on = r <= v.tol;
@@ -123,51 +94,10 @@ void project_clear_step_kernel(DevProjectClear<real> v)
    }
    if (cls == ORC_CLEAR_ON_AND_CLEAR) { v.status_out[q] = ORC_PROJECT_DONE; v.done[q] = 1; return; }
    if (it == v.max_steps) { v.done[q] = 1; return; }
-   // ---- the step.  A = J J^T + mu I, the lower triangle, every sum in the order of the columns
-   const real mu = v.mu;
-   real A[KMAX][KMAX];
-#pragma unroll
-   for (int i=0; i<KMAX; i++)
-#pragma unroll
-      for (int j=0; j<KMAX; j++) A[i][j] = 0;
-   for (int c=0; c<n; c++)
-   {
-      real jc[KMAX];
-#pragma unroll
-      for (int i=0; i<KMAX; i++) jc[i] = (i < k) ? J[i*n + c] : (real)0;
-#pragma unroll
-      for (int i=0; i<KMAX; i++)
-#pragma unroll
-         for (int j=0; j<=i; j++) A[i][j] += jc[i] * jc[j];
-   }
-#pragma unroll
-   for (int i=0; i<KMAX; i++) A[i][i] = (i < k) ? A[i][i] + mu : (real)1;
-   // Cholesky row by row: L L^T = A.  A pivot that is not positive and finite ends the row
-   real L[KMAX][KMAX];
-   bool ok = true;
-#pragma unroll
-   for (int i=0; i<KMAX; i++)
-#pragma unroll
-      for (int j=0; j<KMAX; j++) L[i][j] = 0;
-#pragma unroll
-   for (int i=0; i<KMAX; i++)
-#pragma unroll
-      for (int j=0; j<=i; j++)
-      {
-         real s = A[i][j];
-#pragma unroll
-         for (int p=0; p<j; p++) s -= L[i][p] * L[j][p];
-         if (j == i)
-         {
-            const bool good = (s > (real)0) && (s < M<real>::inf());
-            ok = ok && good;
-            L[i][i] = M<real>::sqrt_(good ? s : (real)1);
-         }
-         else L[i][j] = s / L[j][j];
-      }
-   if (!ok) { v.status_out[q] = ORC_PROJECT_STALLED; v.done[q] = 1; return; }
-   real y[KMAX];
-   clear_solve<real, KMAX>(L, h, y);
+   // ---- the step: A = J J^T + mu I, factored once and solved twice
+   real L[KMAX][KMAX], y[KMAX];
+   if (!project_factor<real, KMAX>(J, n, k, v.mu, L)) { v.status_out[q] = ORC_PROJECT_STALLED; v.done[q] = 1; return; }
+   project_solve<real, KMAX>(L, h, y);
    // the push, in the null space of J: only from a cost that is finite and positive and a gradient that is finite
    bool push = clear_finite<real>(U) && (U > (real)0);
    for (int c=0; c<n; c++)
@@ -188,7 +118,7 @@ void project_clear_step_kernel(DevProjectClear<real> v)
 #pragma unroll
          for (int i=0; i<KMAX; i++) w[i] += ((i < k) ? J[i*n + c] : (real)0) * gc;
       }
-      clear_solve<real, KMAX>(L, w, z);
+      project_solve<real, KMAX>(L, w, z);
       real s = 0;
       for (int c=0; c<n; c++)
       {
@@ -214,32 +144,7 @@ void project_clear_step_kernel(DevProjectClear<real> v)
          pscale = (plen > v.push_cap) ? v.push_cap / plen : (real)1;
       }
    }
-   // dq = -J^T y (+ the push), kept in J's first row (column c of J is read before entry c is written, and J is dead after)
-   real nn = 0;
-   for (int c=0; c<n; c++)
-   {
-      real d = 0;
-#pragma unroll
-      for (int i=0; i<KMAX; i++) d += ((i < k) ? J[i*n + c] : (real)0) * y[i];
-      d = -d;
-      if (push) d += g[c] * pscale;
-      J[c] = d;
-      nn += d * d;
-   }
-   const real len = M<real>::sqrt_(nn);
-   const real cap = v.step_cap;
-   const real scale = (len > cap) ? cap / len : (real)1;
-   bool moved = false;
-   for (int c=0; c<n; c++)
-   {
-      const real x = cur[c];
-      real nx = x + J[c] * scale;
-      const real lo = v.lower[c], hi = v.upper[c];
-      nx = (nx < lo) ? lo : nx;
-      nx = (nx > hi) ? hi : nx;
-      moved = moved || (nx != x);
-      cur[c] = nx;
-   }
+   const bool moved = project_move<real, KMAX>(J, cur, n, k, y, push ? g : nullptr, pscale, v.step_cap, v.lower, v.upper);
    if (!moved) { v.status_out[q] = ORC_PROJECT_STALLED; v.done[q] = 1; return; }
    for (int c=0; c<n; c++) v.cur[(size_t) q*n + c] = cur[c];
    v.steps_out[q] += 1;
@@ -251,19 +156,11 @@ void project_clear_step_kernel(DevProjectClear<real> v)
 template <typename real>
 static hipError_t launch_project_clear_t(const DevProjectClear<real> & v, int kmax, hipStream_t stream)
 {
-   if (kmax != 3 && kmax != 6) return hipErrorInvalidValue;
-   if (v.n_q < 1 || v.n_q > ORC_PROJECT_MAX_Q || v.n < 1 || v.max_steps < 0 || v.max_steps > ORC_PROJECT_MAX_STEPS) return hipErrorInvalidValue;
-   if (v.it < 0 || v.it > v.max_steps) return hipErrorInvalidValue;
-   if (v.stride < orc_project_stride(v.n, kmax)) return hipErrorInvalidValue;
-   if (!v.model || !v.tsrs || !v.cur || !v.start || !v.given || !v.lower || !v.upper || !v.cost || !v.grad || !v.clear || !v.aws) return hipErrorInvalidValue;
+   if (v.max_steps < 0 || v.it < 0 || v.it > v.max_steps) return hipErrorInvalidValue;
+   if (!v.cur || !v.start || !v.given || !v.lower || !v.upper || !v.cost || !v.grad || !v.clear) return hipErrorInvalidValue;
    if (!v.done || !v.best_cls || !v.best_val || !v.count || !v.rows_out || !v.resid_out || !v.clear_out || !v.steps_out || !v.status_out)
       return hipErrorInvalidValue;
-   const size_t lds = v.ws ? 0 : (size_t) ORC_PROJECT_LANES * v.stride * sizeof(real);
-   if (lds > ORC_PROJECT_LDS_BYTES) return hipErrorInvalidValue;
-   const int blocks = (v.n_q + ORC_PROJECT_LANES - 1) / ORC_PROJECT_LANES;
-   if (kmax == 3) hipLaunchKernelGGL((project_clear_step_kernel<real, 3>), dim3(blocks), dim3(ORC_PROJECT_LANES), lds, stream, v);
-   else hipLaunchKernelGGL((project_clear_step_kernel<real, 6>), dim3(blocks), dim3(ORC_PROJECT_LANES), lds, stream, v);
-   return hipGetLastError();
+   return launch_project_kernels<DevProjectClear<real>, project_clear_step_kernel<real, 3>, project_clear_step_kernel<real, 6>>(v, kmax, stream);
 }
 hipError_t orc_launch_project_clear_step(const DevProjectClear<double> & v, int kmax, hipStream_t stream) { return launch_project_clear_t<double>(v, kmax, stream); }
 hipError_t orc_launch_project_clear_step(const DevProjectClear<float> & v, int kmax, hipStream_t stream) { return launch_project_clear_t<float>(v, kmax, stream); }

@@ -11,6 +11,7 @@
 // A lane's state -- h, J [KMAX][n], the current row, the best row -- is indexed by loop counters and lives in memory, not in
 // registers: in LDS when a workgroup's 64 states fit ORC_PROJECT_LDS_BYTES, else in the call's workspace (DevProject::ws).
 // tsr_eval_point reaches both through generic pointers; its own workspace of joint axes (aws) is global memory by its text.
+// The step -- residual, factor, solve, clipped move -- is project_step.h, which project_clear_kernels.hip shares.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include "dev_types.h"
@@ -22,6 +23,7 @@ namespace {
 #include "sdf_lookup.h"
 #include "fk.h"
 #include "tsr_point.h"
+#include "project_step.h"
 
 template <typename real>
 __device__ __forceinline__ double project_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
@@ -37,8 +39,8 @@ void project_tsr_kernel(DevProject<real> v)
    if (q >= v.n_q) return;      // (a lane without a query idles: nothing below waits for it)
    const DevModel<real> & gm = *v.model;
    const int n = v.n;
-   real * st = v.ws ? v.ws + (size_t) q * v.stride : (real *) smem_raw + (size_t) threadIdx.x * v.stride;
-   real * hs = st, * J = st + KMAX, * cur = J + KMAX*n, * best = cur + n;
+   const ProjectLane<real> S = project_lane<real, KMAX>(v.ws, smem_raw, q, v.stride, n);
+   real * hs = S.hs, * J = S.J, * cur = S.cur, * best = S.own;
    const DevTsr<real> & ts = v.tsrs[v.tsr_of_q ? v.tsr_of_q[q] : 0];
    const int k = ts.k;          // (1 .. KMAX: the host chose KMAX by the call's constraints)
    const bool evaluate_only = v.max_steps < 0;
@@ -79,14 +81,7 @@ void project_tsr_kernel(DevProject<real> v)
    {
       tsr_eval_point<real>(gm, ts, cur, n, hs, J, v.aws, v.n_q, q);
       real h[KMAX];
-      real r = 0;      // max |h_i|; a NaN entry makes it NaN
-#pragma unroll
-      for (int i=0; i<KMAX; i++)
-      {
-         h[i] = (i < k) ? hs[i] : (real)0;
-         const real a = M<real>::fabs_(h[i]);
-         r = (a > r || a != a) ? a : r;
-      }
+      const real r = project_residual<real, KMAX>(hs, k, h);
       // the visited iterate of smallest r (a NaN is never better, and anything is better than a NaN)
       if (it == 0 || ((r == r) && !(best_r <= r)))
       {
@@ -95,85 +90,10 @@ void project_tsr_kernel(DevProject<real> v)
       }
       if (r <= tol) { status = ORC_PROJECT_DONE; break; }
       if (it == max_steps) break;
-      // A = J J^T + mu I, the lower triangle, every sum in the order of the columns
-      real A[KMAX][KMAX];
-#pragma unroll
-      for (int i=0; i<KMAX; i++)
-#pragma unroll
-         for (int j=0; j<KMAX; j++) A[i][j] = 0;
-      for (int c=0; c<n; c++)
-      {
-         real jc[KMAX];
-#pragma unroll
-         for (int i=0; i<KMAX; i++) jc[i] = (i < k) ? J[i*n + c] : (real)0;
-#pragma unroll
-         for (int i=0; i<KMAX; i++)
-#pragma unroll
-            for (int j=0; j<=i; j++) A[i][j] += jc[i] * jc[j];
-      }
-#pragma unroll
-      for (int i=0; i<KMAX; i++) A[i][i] = (i < k) ? A[i][i] + mu : (real)1;
-      // Cholesky row by row: L L^T = A.  A pivot that is not positive and finite ends the row's projection
-      real L[KMAX][KMAX];
-      bool ok = true;
-#pragma unroll
-      for (int i=0; i<KMAX; i++)
-#pragma unroll
-         for (int j=0; j<=i; j++)
-         {
-            real s = A[i][j];
-#pragma unroll
-            for (int p=0; p<j; p++) s -= L[i][p] * L[j][p];
-            if (j == i)
-            {
-               const bool good = (s > (real)0) && (s < M<real>::inf());
-               ok = ok && good;
-               L[i][i] = M<real>::sqrt_(good ? s : (real)1);
-            }
-            else L[i][j] = s / L[j][j];
-         }
-      if (!ok) { status = ORC_PROJECT_STALLED; break; }
-      real y[KMAX];
-#pragma unroll
-      for (int i=0; i<KMAX; i++)      // L z = h
-      {
-         real s = h[i];
-#pragma unroll
-         for (int p=0; p<i; p++) s -= L[i][p] * y[p];
-         y[i] = s / L[i][i];
-      }
-#pragma unroll
-      for (int i=KMAX-1; i>=0; i--)   // L^T y = z
-      {
-         real s = y[i];
-#pragma unroll
-         for (int p=i+1; p<KMAX; p++) s -= L[p][i] * y[p];
-         y[i] = s / L[i][i];
-      }
-      // dq = -J^T y, kept in J's first row (column c of J is read before entry c is written, and J is dead after the step)
-      real nn = 0;
-      for (int c=0; c<n; c++)
-      {
-         real d = 0;
-#pragma unroll
-         for (int i=0; i<KMAX; i++) d += ((i < k) ? J[i*n + c] : (real)0) * y[i];
-         d = -d;
-         J[c] = d;
-         nn += d * d;
-      }
-      const real len = M<real>::sqrt_(nn);
-      const real scale = (len > cap) ? cap / len : (real)1;
-      bool moved = false;
-      for (int c=0; c<n; c++)
-      {
-         const real x = cur[c];
-         real nx = x + J[c] * scale;
-         const real lo = v.lower[c], hi = v.upper[c];
-         nx = (nx < lo) ? lo : nx;
-         nx = (nx > hi) ? hi : nx;
-         moved = moved || (nx != x);
-         cur[c] = nx;
-      }
+      real L[KMAX][KMAX], y[KMAX];
+      if (!project_factor<real, KMAX>(J, n, k, mu, L)) { status = ORC_PROJECT_STALLED; break; }
+      project_solve<real, KMAX>(L, h, y);
+      const bool moved = project_move<real, KMAX>(J, cur, n, k, y, nullptr, (real)0, cap, v.lower, v.upper);
       if (!moved) { status = ORC_PROJECT_STALLED; break; }
       steps++;
    }
@@ -190,18 +110,10 @@ void project_tsr_kernel(DevProject<real> v)
 template <typename real>
 static hipError_t launch_project_t(const DevProject<real> & v, int kmax, hipStream_t stream)
 {
-   if (kmax != 3 && kmax != 6) return hipErrorInvalidValue;
-   if (v.n_q < 1 || v.n_q > ORC_PROJECT_MAX_Q || v.n < 1 || v.max_steps > ORC_PROJECT_MAX_STEPS) return hipErrorInvalidValue;
-   if (v.stride < orc_project_stride(v.n, kmax)) return hipErrorInvalidValue;
-   if (!v.model || !v.tsrs || !v.configs || !v.aws) return hipErrorInvalidValue;
+   if (!v.configs) return hipErrorInvalidValue;
    if (v.max_steps < 0 ? (!v.h_out || !v.jac_out) : (!v.lower || !v.upper || !v.rows_out || !v.resid_out || !v.steps_out || !v.status_out))
       return hipErrorInvalidValue;
-   const size_t lds = v.ws ? 0 : (size_t) ORC_PROJECT_LANES * v.stride * sizeof(real);
-   if (lds > ORC_PROJECT_LDS_BYTES) return hipErrorInvalidValue;
-   const int blocks = (v.n_q + ORC_PROJECT_LANES - 1) / ORC_PROJECT_LANES;
-   if (kmax == 3) hipLaunchKernelGGL((project_tsr_kernel<real, 3>), dim3(blocks), dim3(ORC_PROJECT_LANES), lds, stream, v);
-   else hipLaunchKernelGGL((project_tsr_kernel<real, 6>), dim3(blocks), dim3(ORC_PROJECT_LANES), lds, stream, v);
-   return hipGetLastError();
+   return launch_project_kernels<DevProject<real>, project_tsr_kernel<real, 3>, project_tsr_kernel<real, 6>>(v, kmax, stream);
 }
 hipError_t orc_launch_project(const DevProject<double> & v, int kmax, hipStream_t stream) { return launch_project_t<double>(v, kmax, stream); }
 hipError_t orc_launch_project(const DevProject<float> & v, int kmax, hipStream_t stream) { return launch_project_t<float>(v, kmax, stream); }

@@ -4,6 +4,7 @@
 // planned walk.
 #include "module.h"
 #include "verdict_device.h"
+#include "query_upload.h"      // walk_chunk
 #include <cstdlib>
 #include <sstream>
 #include <stdexcept>
@@ -251,8 +252,7 @@ void Batch::collision_verdict_planned(const VerdictInputs & in, unsigned long lo
 }
 
 // What the two verdicts share: the tables that the walk reads (verdict_walk.h) go up, the depths are zeroed and `w` is
-// filled, but for key_out.  The chunk: 64 samples per pass, or what the LDS of a CU holds of this robot's rows, positions and
-// joint frames behind what the kernel itself keeps there (lds_bytes(chunk): the kernel's dynamic LDS).
+// filled, but for key_out.  The chunk is walk_chunk's (query_upload.h) for the kernel's dynamic LDS, lds_bytes(chunk).
 template <typename real>
 void BatchShard::verdict_walk_args(const VerdictInputs & in, const std::function<size_t(int)> & lds_bytes, VerdictTables & t, DevVerdictWalk<real> & w)
 {
@@ -262,8 +262,7 @@ void BatchShard::verdict_walk_args(const VerdictInputs & in, const std::function
    hip_check(hipMemcpyAsync(t.pairs.as<void>(), in.pairs.data(), in.pairs.size()*sizeof(int), hipMemcpyHostToDevice, st), "verdict pairs");
    hip_check(hipMemsetAsync(t.depth.as<void>(), 0, n_runs*sizeof(double), st), "verdict depth");
    t.rsum.reset(upload<real>(in.rsum, st)); t.inact.reset(upload<real>(in.inact_pos, st));
-   int chunk = 64;
-   while (chunk > 4 && lds_bytes(chunk) > ORC_VERDICT_LDS_LIMIT) chunk -= 4;
+   const int chunk = walk_chunk(lds_bytes);
    w.model = d_model_.as<const DevModel<real>>(); w.sdfs = d_sdfs_.as<const DevSdf<real>>(); w.n_sdfs = scn_.n_sdfs;
    w.scene_of_run = d_scene_of_run_.as<int>(); w.scene_nsdf = d_scene_nsdf_.as<int>();
    w.n_runs = n_runs; w.n_points = n_points; w.n = n; w.chunk = chunk; w.traj = d_traj_.as<const real>();

@@ -182,6 +182,36 @@ def test_floating_base(oracle):
     mod.close()
 
 
+def test_floating_base_with_a_non_finite_row():
+    """A floating base, one workgroup's worth of queries and one more, the last two with a non-finite entry (one in the pose's
+    quaternion, one in a joint): FK runs on the harmless row with a unit quaternion in their place, they alone report NaN, and
+    every other query answers as in the call without them, in both kernels."""
+    mod = or_cdchomp_amd.Module(0)
+    model, _, dofvals, adofs = common.wam_state()
+    base = PN.floating_base()
+    mod.add_robot(model, transform=list(base), dof_values=dofvals, active_dofs=adofs)
+    scenes.add_tabletop(mod)
+    mod.SendCommand("computedistancefield kinbody table")
+    set_wam_vmax(mod, model)
+    bid = mod.batch_create(model.name, common.wam_goals(1, seed=3), basegoals=base[None, :], **dict(KW4, floating_base=1))
+    pool = CC.floating_configs(base)
+    for chunk, ask in ((mod.batch_penetration_chunk(bid), lambda r: mod.batch_config_penetration(bid, r, margin=PN.MARGINS[2])),
+                       (mod.batch_config_chunk(bid), lambda r: mod.batch_config_clearance(bid, r))):
+        rows = pool[np.arange(chunk + 1) % len(pool)]
+        want = ask(rows)
+        keys = tuple(want)
+        bad = rows.copy(); bad[chunk - 1, 4] = np.nan; bad[chunk, 9] = np.inf      # the last query of a workgroup, the first of the next
+        got = ask(bad)
+        for q in (chunk - 1, chunk):
+            assert all(np.isnan(got[key][q]).all() for key in keys if got[key].dtype == np.float64), q
+            assert (got["sphere"][q] == -1).all() and (got["other"][q] == -1).all(), q
+        keep = np.arange(chunk - 1)
+        assert_same({key: got[key][keep] for key in keys}, {key: want[key][keep] for key in keys}, "beside the non-finite rows", keys=keys)
+        assert np.isfinite(want["clearance"][:, 1]).all()
+    mod.batch_destroy(bid)
+    mod.close()
+
+
 def test_tree_robot(oracle):
     mod = or_cdchomp_amd.Module(0)
     model = common.setup_product_tree30(mod)
@@ -312,6 +342,39 @@ def test_waypoints_and_two_shards(wam):
     for one, other, what in zip(res[0], res[1], ("configurations", "named waypoints", "profile", "starts and goals")):
         assert_same(other, one, "two shards: " + what)
     assert (res[0][2]["cost"][..., 0] > 0).any() and (res[0][2]["cost"][..., 0] == 0).any(), "both outcomes must occur"
+    two.close()
+
+
+def test_a_deal_with_absent_output_columns():
+    """Two shards on one card, 4 runs, the 21 queries of test_waypoints_and_two_shards through the C ABI: an output the caller
+    does not pass (NULL) is not dealt, and every output that is present equals the call with all of them, bit for bit."""
+    pool = np.array(list(PN.wam_rows().values()))
+    cf = np.ascontiguousarray(pool[np.arange(21) % len(pool)])
+    ri = np.array([0, 2, 1, 3] * 6, dtype=np.int32)[:21]      # runs 0, 1: the first shard; 2, 3: the second
+    two = or_cdchomp_amd.Module([0, 0])
+    model = common.setup_product_wam(two)
+    set_wam_vmax(two, model)
+    bid = two.batch_create(model.name, common.wam_goals(4, seed=7), scenes=[[("table", None)], [("table", PN.SHIFT)]],
+                           scene_of_run=np.array([0, 1, 1, 0], dtype=np.int32), **KW4)
+    dp = lambda a: None if a is None else a.ctypes.data_as(_capi.c_double_p)
+    ip = lambda a: None if a is None else a.ctypes.data_as(_capi.c_int_p)
+
+    def call(absent=()):
+        out = dict(cost=np.full((21, 2), -7.0), grad=np.full((21, 7), -7.0), clearance=np.full((21, 2), -7.0),
+                   sphere=np.full((21, 2), -7, dtype=np.int32), other=np.full((21, 2), -7, dtype=np.int32))
+        for key in absent:
+            out[key] = None
+        rc = two._lib.orc_batch_config_penetration(two._h, bid, 21, ip(ri), dp(cf), PN.MARGINS[2][0], PN.MARGINS[2][1], dp(out["cost"]),
+                                                   dp(out["grad"]), dp(out["clearance"]), ip(out["sphere"]), ip(out["other"]))
+        assert rc == 0, two._lib.orc_last_error(two._h).decode()
+        return out
+
+    full = call()
+    assert_same(full, two.batch_config_penetration(bid, cf, runs=ri, margin=PN.MARGINS[2]), "the C call against the wrapper's")
+    assert (full["cost"][:, 0] > 0).any() and (full["grad"] != 0).any() and (full["sphere"] >= 0).any()
+    for absent in (("grad",), ("sphere", "other"), ("cost",), ("sphere",), ("cost", "grad", "clearance")):
+        part = call(absent)
+        assert_same(part, full, "without " + " and ".join(absent), keys=[key for key in OUT if key not in absent])
     two.close()
 
 

@@ -351,7 +351,65 @@ def test_tree_robot(oracle):
     mod.close()
 
 
-# ---- 8. rejections -------------------------------------------------------------------------------------------------------------
+# ---- 8. nothing to clear -------------------------------------------------------------------------------------------------------
+
+# 16 goals of common.wam_goals(48) that are not in contact and whose bent rows the rule keeps clear on their way back to the
+# goal's hand pose (chosen with or_cdchomp_amd/project_clear.py on the host; the test asserts it on the rule's trace)
+CLEAR_16 = [3, 4, 5, 7, 10, 11, 12, 14, 16, 18, 20, 21, 25, 27, 28, 29]
+
+
+@pytest.mark.parametrize("name, precision", [("BW3", 64), ("BW6", 64), ("BW3", 32)])
+def test_nothing_to_clear_is_the_projection(oracle, wam, name, precision):
+    """Rows off their TSRs that no visited iterate brings into contact, margins (0, 0) and slack 0: no cost, no push, every
+    clearance at the margins, so the clear projection is the projection.  The two kernels take their step from one text
+    (project_step.h): the rows, residuals, steps and statuses agree bit for bit."""
+    mod, w = wam["mod"], wam["w"]
+    assert not set(CLEAR_16) & set(PC.CONTACT_48)
+    goals = common.wam_goals(48)[CLEAR_16]
+    rows = np.clip(goals + PC.BENT * np.random.default_rng(21).standard_normal(goals.shape), w["lower"], w["upper"])
+    tsrs = PC.tsrs_of(w, goals, PC.BWS[name])
+    p = dict(tol=PC.PARAMS["tol"] if precision == 64 else 1e-4, mu=PC.PARAMS["mu"], step_cap=PC.PARAMS["step_cap"], max_steps=30)
+    # the premise, on the rule's trace
+    R = PC.Restated(oracle, w, tsrs, np.arange(len(rows)))
+    hist = []
+    rule = R.run(rows, history=hist, dtype=np.float64 if precision == 64 else np.float32, margin=(0.0, 0.0), slack=0.0, **p)
+    R.destroy()
+    lowest = min(float(clr.min()) for _, _, _, _, clr in hist)
+    print("%s, precision %d: the rule visits %d rounds, steps %s; largest cost %g, lowest clearance %.4f"
+          % (name, precision, len(hist), rule[3].tolist(), max(float(U.max()) for _, _, _, U, _ in hist), lowest))
+    assert (rule[3] >= 2).all(), "every row must take steps"
+    for _, _, _, U, clr in hist:
+        assert (U == 0).all() and (clr >= 0).all(), "no visited iterate has a cost, and every clearance is at or above the margins"
+    bid = wam["b64"] if precision == 64 else wam["b32"]
+    want = mod.batch_project_tsr(bid, tsrs, rows, tsr_of=np.arange(len(rows)), **p)
+    got = mod.batch_project_tsr_clear(bid, tsrs, rows, tsr_of=np.arange(len(rows)), margin=(0.0, 0.0), slack=0.0, **p)
+    print("%s, precision %d: steps %s status %s" % (name, precision, got["steps"].tolist(), got["status"].tolist()))
+    assert (want[2] >= 1).all() and (want[3] == project.DONE).all()
+    for key, x in zip(("configs", "resid", "steps", "status"), want):
+        y = got[key]
+        assert x.shape == y.shape and x.dtype == y.dtype and x.tobytes() == y.tobytes(), (name, precision, key, x, y)
+
+
+@pytest.mark.parametrize("name", list(PC.BWS))
+def test_a_pivot_that_is_not_positive_stalls_the_row(wam, name):
+    """A TSR on the robot's base link, which no joint moves, and mu 0: J is zero, A = J J^T is zero, and the first pivot of its
+    factor is not positive.  Both projections stop the row at once: a singular system, no step, the row as it came."""
+    mod, bid = wam["mod"], wam["b64"]
+    rows = wam["rows"][:3]
+    link = wam["model"].link_names[0]
+    tsrs = [robots.Tsr(T0w_d=(0.3, -0.2, 1.5), Bw=PC.BWS[name])]
+    ev = mod.batch_config_tsr(bid, tsrs, rows, link=link)
+    r = np.abs(ev["h"]).max(axis=1)
+    assert (ev["jac"] == 0).all() and (r > 1e-3).all(), "the premise: no joint moves the link, and it is off the TSR"
+    p = dict(link=link, mu=0.0, tol=PC.PARAMS["tol"], step_cap=PC.PARAMS["step_cap"], max_steps=30)
+    out, resid, steps, status = mod.batch_project_tsr(bid, tsrs, rows, **p)
+    got = mod.batch_project_tsr_clear(bid, tsrs, rows, **p)
+    for what, o, rs, st, ss in (("project", out, resid, steps, status), ("clear", got["configs"], got["resid"], got["steps"], got["status"])):
+        assert (ss == project.STALLED).all() and (st == 0).all(), (what, ss, st)
+        assert o.tobytes() == rows.tobytes() and np.array_equal(rs, r), what
+
+
+# ---- 9. rejections -------------------------------------------------------------------------------------------------------------
 
 def test_rejections(wam):
     mod, bid = wam["mod"], wam["b64"]
