@@ -22,6 +22,20 @@
 // the dense m x m products are replaced by the band of A and a structured solve; the per-sphere
 // 3 x n Jacobians are never formed (J^T x is evaluated as axis . ((p - anchor) x force)); a
 // self-collision pair is evaluated once for both of its spheres.
+//
+// The layers, in inclusion order (each a header included inside this file's namespace; this file keeps the kernarg helpers,
+// Env, the convergence state, the phases, the kernel, seed_traj_kernel and the launchers):
+//   sdf_lookup.h     M<real>, the precision's math functions, and the field lookup
+//   fast_math.h      rcp_fast, sqrt_rsq, sqrt_rsq_pos, div_n
+//   wave.h           lane and wavefront primitives: DPP moves, sums, arg-max, scans, lane reads, uni / uni64 / unir / uniform_ptr
+//   metric_solve.h   A^-1 g: cyclic reduction, dense, Toeplitz scans, semiseparable scans; metric_solve
+//   limit_rounds.h   the joint-limit rounds by one wavefront (over limit_regs.h: the register forms); limit_rounds_call*
+//   band.h           A T + B: band_row, smooth_grad, band_gradient_pass, band_cost_pass
+//   cost_gs16.h, cost_pairs.h, self_mfma.h, cost_generic.h      the cost phase by the robot's number of active spheres
+//   fk.h             forward kinematics of a tile's waypoints
+//   tsr.h            the hard constraints (over tsr_point.h, tsr_form.h), behind Env and the convergence state
+// Three minutes of compile time hang on these.  With the host files this one shares dev_types.h, kernel_table.h, launch.h and
+// wave_roles.h and nothing else: a change to a header of the host layer (batch.h, module.h, ...) does not cost the kernel build.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <atomic>
@@ -40,942 +54,11 @@
 namespace {
 
 #include "sdf_lookup.h"
-
-// 1/x and (sqrt(x), 1/sqrt(x)) from the hardware seeds plus Newton/Goldschmidt steps:
-// ~1 ulp, a third of the instructions of the IEEE division / sqrt expansions.
-__device__ __forceinline__ double rcp_fast(double x)
-{
-   double r = __builtin_amdgcn_rcp(x);
-   r = fma(fma(-x, r, 1.0), r, r);
-   r = fma(fma(-x, r, 1.0), r, r);
-   return r;
-}
-__device__ __forceinline__ float rcp_fast(float x) { return 1.0f / x; }
-// returns sqrt(x); *inv = 1/sqrt(x).  x == 0 gives 0 and inf.
-__device__ __forceinline__ double sqrt_rsq(double x, double * inv)
-{
-   double r = __builtin_amdgcn_rsq(x);
-   double g = x * r, h = 0.5 * r;
-#pragma unroll
-   for (int k=0; k<2; k++)
-   {
-      const double e = fma(-h, g, 0.5);
-      g = fma(g, e, g);
-      h = fma(h, e, h);
-   }
-   const double d = fma(-g, g, x);
-   g = fma(d, h, g);
-   const bool zero = !(x > 0.0);
-   *inv = zero ? M<double>::inf() : 2.0 * h;
-   return zero ? 0.0 : g;
-}
-__device__ __forceinline__ float sqrt_rsq(float x, float * inv)
-{
-   const float g = ::sqrtf(x);
-   *inv = 1.0f / g;
-   return g;
-}
-// the same for x > 0 known (pair distances: the caller substitutes 1 where there is no pair), without
-// the guards for x == 0.  (One Goldschmidt step would do for the square root -- 1.1e-16 over 2^20 values,
-// scripts/ubench/rsq_prec.hip -- but leaves its reciprocal at 4e-15, and the three instructions saved per
-// pair evaluation do not show in the throughput: kept at two.)
-__device__ __forceinline__ double sqrt_rsq_pos(double x, double * inv)
-{
-   double r = __builtin_amdgcn_rsq(x);
-   double g = x * r, h = 0.5 * r;
-#pragma unroll
-   for (int k=0; k<2; k++)
-   {
-      const double e = fma(-h, g, 0.5);
-      g = fma(g, e, g);
-      h = fma(h, e, h);
-   }
-   const double d = fma(-g, g, x);
-   g = fma(d, h, g);
-   *inv = 2.0 * h;
-   return g;
-}
-__device__ __forceinline__ float sqrt_rsq_pos(float x, float * inv) { return sqrt_rsq(x, inv); }
-
-// sum over aligned groups of GS lanes (GS a power of two <= 64); every lane of the group
-// receives the total.  Up to 16 lanes stay inside a DPP row (no LDS pipe).
-template <int CTRL>
-__device__ __forceinline__ double dpp_move(double v)
-{
-   int lo = __double2loint(v), hi = __double2hiint(v);
-   lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xF, 0xF, true);
-   hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xF, 0xF, true);
-   return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_move(float v)
-{
-   return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, true));
-}
-template <typename real>
-__device__ __forceinline__ real group_sum(real v, int GS)
-{
-   if (GS >= 2)  v += dpp_move<0xB1>(v);      // quad_perm [1,0,3,2]
-   if (GS >= 4)  v += dpp_move<0x4E>(v);      // quad_perm [2,3,0,1]
-   if (GS >= 8)  v += dpp_move<0x141>(v);     // row_half_mirror
-   if (GS >= 16) v += dpp_move<0x140>(v);     // row_mirror
-   if (GS >= 32) v += __shfl_xor(v, 16, 64);
-   if (GS >= 64) v += __shfl_xor(v, 32, 64);
-   return v;
-}
-
-template <int CTRL>
-__device__ __forceinline__ int dpp_move(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true); }
-
-template <typename real>
-__device__ __forceinline__ real dpp_row_max(real v)
-{
-   real o;
-   o = dpp_move<0xB1>(v);  v = o > v ? o : v;
-   o = dpp_move<0x4E>(v);  v = o > v ? o : v;
-   o = dpp_move<0x141>(v); v = o > v ? o : v;
-   o = dpp_move<0x140>(v); v = o > v ? o : v;
-   return v;
-}
-__device__ __forceinline__ double read_lane(double v, int ln)
-{
-   const int lo = __builtin_amdgcn_readlane(__double2loint(v), ln), hi = __builtin_amdgcn_readlane(__double2hiint(v), ln);
-   return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float read_lane(float v, int ln) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), ln)); }
-template <typename real>
-__device__ __forceinline__ void wave_argmax(real & best, int & best_e)
-{
-   real m = dpp_row_max(best);
-   // the four row maxima (lanes 0, 16, 32, 48 hold them after the row reduction)
-   const real m0 = read_lane(m, 0), m1 = read_lane(m, 16), m2 = read_lane(m, 32), m3 = read_lane(m, 48);
-   const real ma = m0 > m1 ? m0 : m1, mb = m2 > m3 ? m2 : m3;
-   const real mm = ma > mb ? ma : mb;
-   if (!(mm > (real)0)) { best = 0; best_e = 0x7fffffff; return; }      // nothing to find (wave-uniform)
-   unsigned long long cand = __ballot(best == mm);
-   int win = 0x7fffffff;
-   while (cand)                       // one iteration unless two lanes tie exactly
-   {
-      const int ln = __builtin_ctzll(cand);
-      cand &= cand - 1;
-      const int e = __builtin_amdgcn_readlane(best_e, ln);
-      win = e < win ? e : win;
-   }
-   best = mm; best_e = win;
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-   for (int o=32; o>0; o>>=1) v += __shfl_xor(v, o, 64);
-   return v;
-}
-
-// wavefront arg-max of (value >= 0, index), ties to the smallest index; every lane gets the result.
-// Row maxima by DPP, rows combined through readlane; the owner is found with a ballot.
-template <typename real>
-__device__ __forceinline__ real dpp_row_max(real v);   // defined after dpp_move
-template <typename real>
-__device__ __forceinline__ void wave_argmax(real & best, int & best_e);
-
-// the partial sums of a workgroup's wavefronts, added in a fixed pairwise order
-template <int BLOCK>
-__device__ __forceinline__ double sum_partials(const double * r)
-{
-   if (BLOCK == 128) return r[0] + r[1];
-   if (BLOCK == 192) return (r[0] + r[1]) + r[2];
-   if (BLOCK == 256) return (r[0] + r[1]) + (r[2] + r[3]);
-   return ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));      // 512 threads
-}
-// sum over the whole workgroup; every thread receives the result.
-template <int BLOCK>
-__device__ __forceinline__ double block_sum(double v, double * red, int tid)
-{
-   v = wave_sum(v);
-   __syncthreads();
-   if ((tid & 63) == 0) red[tid >> 6] = v;
-   __syncthreads();
-   return sum_partials<BLOCK>(red);
-}
-
-// e / n for 0 <= e < 2^20 without the ~35-instruction integer division: (e + 0.5)/n is at least
-// 0.5/n away from an integer, far more than the rounding of the float product.  rn = 1.0f / n.
-__device__ __forceinline__ int div_n(int e, float rn) { return (int)(((float) e + 0.5f) * rn); }
-
-// ---------------------------------------------------------------------------
-// parallel cyclic reduction with precomputed multipliers: x = A^-1 d for all n
-// columns at once.  src holds d [m][n]; the result ends up in the returned
-// buffer (src or tmp).  Coefficients: pcr[l][0][i] (towards i-s), pcr[l][1][i]
-// (towards i+s), then the inverse of the reduced diagonal.
-template <typename real, int BLOCK, typename BT>
-__device__ __forceinline__ real * pcr_solve(const BT & b, const real * tab, real * src, real * tmp, int tid)
-{
-   const int m = b.m, n = b.n, mn = m*n;
-   const float rn = 1.0f / (float) n;
-   real * cur = src;
-   real * nxt = tmp;
-   int stride = 1;
-   for (int l=0; l<b.pcr_levels; l++)
-   {
-      const real * ka = tab + (size_t)(b.pcr_sym ? l : 2*l) * m;
-      const real * kc = ka + m;
-      for (int e=tid; e<mn; e+=BLOCK)
-      {
-         const int i = div_n(e, rn);
-         real d = cur[e];
-         if (i - stride >= 0) d += ka[i] * cur[e - stride*n];
-         if (i + stride < m)  d += (b.pcr_sym ? ka[m-1-i] : kc[i]) * cur[e + stride*n];
-         nxt[e] = d;
-      }
-      __syncthreads();
-      real * t = cur; cur = nxt; nxt = t;
-      stride <<= 1;
-   }
-   const real * invb = tab + (size_t)(b.pcr_rows - 1) * m;
-   for (int e=tid; e<mn; e+=BLOCK)
-      cur[e] *= invb[div_n(e, rn)];
-   __syncthreads();
-   return cur;
-}
-
-// dense fallback (derivative D >= 2): x = Ainv d
-template <typename real, int BLOCK, typename BT>
-__device__ __forceinline__ real * dense_solve(const BT & b, real * src, real * tmp, int tid)
-{
-   const int m = b.m, n = b.n, mn = m*n;
-   for (int e=tid; e<mn; e+=BLOCK)
-   {
-      const int i = e / n, c = e - i*n;
-      real s = (real)0;
-      for (int k=0; k<m; k++) s += b.Ainv[(size_t) i*m + k] * src[k*n + c];
-      tmp[e] = s;
-   }
-   __syncthreads();
-   return tmp;
-}
-
-// inclusive prefix / suffix sums over the 64 lanes of a wavefront: Kogge-Stone inside the 16-lane
-// DPP rows, then the row totals through v_readlane (no LDS, no barrier)
-template <typename real>
-__device__ __forceinline__ real wave_prefix_incl(real v)
-{
-   v += dpp_move<0x111>(v);      // row_shr:1 (lane i takes lane i-1, 0 before the row)
-   v += dpp_move<0x112>(v);
-   v += dpp_move<0x114>(v);
-   v += dpp_move<0x118>(v);
-   const real t0 = read_lane(v, 15), t1 = read_lane(v, 31), t2 = read_lane(v, 47);
-   const int row = (threadIdx.x & 63) >> 4;
-   real add = (row >= 1) ? t0 : (real)0;
-   add += (row >= 2) ? t1 : (real)0;
-   add += (row >= 3) ? t2 : (real)0;
-   return v + add;
-}
-template <typename real>
-__device__ __forceinline__ real wave_suffix_incl(real v)
-{
-   v += dpp_move<0x101>(v);      // row_shl:1 (lane i takes lane i+1, 0 past the row)
-   v += dpp_move<0x102>(v);
-   v += dpp_move<0x104>(v);
-   v += dpp_move<0x108>(v);
-   const real t1 = read_lane(v, 16), t2 = read_lane(v, 32), t3 = read_lane(v, 48);
-   const int row = (threadIdx.x & 63) >> 4;
-   real add = (row <= 2) ? t3 : (real)0;
-   add += (row <= 1) ? t2 : (real)0;
-   add += (row <= 0) ? t1 : (real)0;
-   return v + add;
-}
-
-// The closed-form scan solve below for trajectories of more than 64 ORC_SCAN_RPL moving waypoints (round 6): the lane's rows read
-// twice instead of held in registers -- a pass for the lane's two partial sums, the wave scans, a pass that forms x row by row
-// (the rows-after sum by taking the lane's own rows off the suffix scan's inclusive value) -- still ONE barrier per solve, where
-// cyclic reduction pays one per level: 300 waypoints ran at 0.6 of the waypoint-iterations/s of 258 (profiles/r06_long_trajectories.txt).
-template <typename real, typename PT>
-__device__ __forceinline__ void toeplitz_scan_column_long(PT buf, int m, int n, int c, int rpl, real kinv)
-{
-   const int lane = threadIdx.x & 63;
-   const int row0 = lane*rpl;
-   real sp = 0, sq = 0;
-   for (int r=0; r<rpl; r++)
-   {
-      const int row = row0 + r;
-      if (row >= m) break;
-      const real g = buf[row*n + c];
-      sp += g * (real)(row + 1); sq += g * (real)(m - row);
-   }
-   const real ip = wave_prefix_incl(sp);
-   real run_p = __shfl_up(ip, 1, 64); if (lane == 0) run_p = 0;      // rows before this lane's
-   real run_q = wave_suffix_incl(sq);                                // rows from this lane's first on
-   for (int r=0; r<rpl; r++)
-   {
-      const int row = row0 + r;
-      if (row >= m) break;
-      const real g = buf[row*n + c];
-      const real wp = (real)(row + 1), wq = (real)(m - row);
-      run_p += g * wp;                                               // rows up to row r
-      run_q -= g * wq;                                               // rows after row r
-      buf[row*n + c] = kinv * (wq * run_p + wp * run_q);
-   }
-}
-// x = A^-1 g in place for the tridiagonal Toeplitz metric A = ca tridiag(-1, 2, -1) (derivative 1),
-// all n columns of buf [m][n].  The inverse is known in closed form,
-//    Ainv[i][v] = (min(i,v)+1) (m - max(i,v)) / ((m+1) ca),
-// so x_i = kinv ( (m-i) sum_{v<=i} (v+1) g_v  +  (i+1) sum_{v>i} (m-v) g_v ): one prefix and one
-// suffix sum per column.  A wavefront owns a column at a time, a lane `rpl` consecutive rows
-// (m <= 64 ORC_SCAN_RPL); the sums across lanes are wave scans, so the whole solve costs one barrier
-// where cyclic reduction costs one per level.  (The reference multiplies by the dense inverse,
-// src/libcd/chomp.c:525-548: the same products, summed in another order.)
-template <typename real, int BLOCK, typename BT>
-__device__ __forceinline__ real * toeplitz_scan_solve(const BT & b, real * buf, int tid)
-{
-   const int m = b.m, n = b.n;
-   const int lane = tid & 63, wave = tid >> 6;
-   const int rpl = (m + 63) >> 6;
-   const real kinv = (real)(-1) / ((real)(m + 1) * b.a_off);      // 1/((m+1) ca), ca = -a_off
-   if (rpl > ORC_SCAN_RPL)      // (more than 256 moving waypoints: the rows are read twice instead of held in registers, below)
-   {
-      for (int c=wave; c<n; c+=BLOCK/64) toeplitz_scan_column_long<real>(buf, m, n, c, rpl, kinv);
-      __syncthreads();
-      return buf;
-   }
-   for (int c=wave; c<n; c+=BLOCK/64)
-   {
-      real g[ORC_SCAN_RPL], wp[ORC_SCAN_RPL], wq[ORC_SCAN_RPL];
-      real sp = 0, sq = 0;
-#pragma unroll
-      for (int r=0; r<ORC_SCAN_RPL; r++)
-      {
-         const int row = lane*rpl + r;
-         const bool valid = (r < rpl) && (row < m);
-         g[r] = valid ? buf[row*n + c] : (real)0;
-         wp[r] = (real)(row + 1); wq[r] = (real)(m - row);
-         sp += g[r] * wp[r];
-         sq += g[r] * wq[r];
-      }
-      // sums over the lanes before / after this one
-      const real ip = wave_prefix_incl(sp), is = wave_suffix_incl(sq);
-      real run_p = __shfl_up(ip, 1, 64);   if (lane == 0) run_p = 0;
-      real run_q = __shfl_down(is, 1, 64); if (lane == 63) run_q = 0;
-      real q[ORC_SCAN_RPL];
-#pragma unroll
-      for (int r=ORC_SCAN_RPL-1; r>=0; r--) { q[r] = run_q; run_q += g[r] * wq[r]; }      // rows after row r
-#pragma unroll
-      for (int r=0; r<ORC_SCAN_RPL; r++)
-      {
-         const int row = lane*rpl + r;
-         run_p += g[r] * wp[r];                                                             // rows up to row r
-         const real x = kinv * (wq[r] * run_p + wp[r] * q[r]);
-         if ((r < rpl) && (row < m)) buf[row*n + c] = x;
-      }
-   }
-   __syncthreads();
-   return buf;
-}
-
-// one column of toeplitz_scan_solve, by the calling wavefront: buf[:, c] <- A^-1 buf[:, c]
-template <typename real, typename PT>
-__device__ __forceinline__ void toeplitz_scan_column(PT buf, int m, int n, int c, int rpl, real kinv)
-{
-   const int lane = threadIdx.x & 63;
-   real g[ORC_SCAN_RPL], wp[ORC_SCAN_RPL], wq[ORC_SCAN_RPL];
-   real sp = 0, sq = 0;
-#pragma unroll
-   for (int r=0; r<ORC_SCAN_RPL; r++)
-   {
-      const int row = lane*rpl + r;
-      const bool valid = (r < rpl) && (row < m);
-      g[r] = valid ? buf[row*n + c] : (real)0;
-      wp[r] = (real)(row + 1); wq[r] = (real)(m - row);
-      sp += g[r] * wp[r];
-      sq += g[r] * wq[r];
-   }
-   const real ip = wave_prefix_incl(sp), is = wave_suffix_incl(sq);
-   real run_p = __shfl_up(ip, 1, 64);   if (lane == 0) run_p = 0;
-   real run_q = __shfl_down(is, 1, 64); if (lane == 63) run_q = 0;
-   real q[ORC_SCAN_RPL];
-#pragma unroll
-   for (int r=ORC_SCAN_RPL-1; r>=0; r--) { q[r] = run_q; run_q += g[r] * wq[r]; }
-#pragma unroll
-   for (int r=0; r<ORC_SCAN_RPL; r++)
-   {
-      const int row = lane*rpl + r;
-      run_p += g[r] * wp[r];
-      const real x = kinv * (wq[r] * run_p + wp[r] * q[r]);
-      if ((r < rpl) && (row < m)) buf[row*n + c] = x;
-   }
-}
-
-// (arguments of a called function arrive in vector registers: these tell the compiler they are wave-uniform)
-__device__ __forceinline__ unsigned long long uni64(unsigned long long v)
-{
-   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned) v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-   return ((unsigned long long) hi << 32) | lo;
-}
-__device__ __forceinline__ double unir(double v) { return __longlong_as_double((long long) uni64((unsigned long long) __double_as_longlong(v))); }
-__device__ __forceinline__ float unir(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
-
-// x = A^-1 g for the band metric of a higher derivative (A = K_D^T K_D / N_D, half-bandwidth D = RANK: penta-diagonal for
-// `derivative 2`, hepta-diagonal for 3; src/libcd/chomp.c:239-340), one column of buf [m][n] in place, by the calling wavefront.
-// The inverse of a band matrix is semiseparable: Ainv[i][j] = sum_k U[k][i] V[k][j] for i <= j (generators from the host,
-// host_math.cpp build_semisep; the mirror image below the diagonal), so
-//    x_i = sum_k U[k][i] S_k(i) + V[k][i] P_k(i),   S_k(i) = sum_{j >= i} V[k][j] g_j,   P_k(i) = sum_{j < i} U[k][j] g_j:
-// RANK prefix and RANK suffix sums per column where the Toeplitz metric of derivative 1 has one of each
-// (toeplitz_scan_column).  A lane owns `rpl` consecutive rows; the sums across lanes are wave scans, in double for either
-// precision of the run.  REGS: the lane's rows and table entries stay in registers (rpl <= 4); else they are read again in the
-// second pass (any rpl).  The reference multiplies by the dense inverse (chomp.c:525-548, dgetrf + dgetri at 393-403).
-template <typename real, int RANK, bool REGS, typename PT>
-__device__ __forceinline__ void semisep_scan_column(PT buf, int m, int n, int c, int rpl, const double * U, const double * V)
-{
-   const int lane = threadIdx.x & 63;
-   const int row0 = lane*rpl;
-   double su[RANK], sv[RANK];
-#pragma unroll
-   for (int k=0; k<RANK; k++) { su[k] = 0.0; sv[k] = 0.0; }
-   if (REGS)
-   {
-      // (reads are unconditional, from a clamped row: a predicated read is a branch around it plus its 64-bit address arithmetic,
-      // and a lone wavefront issues a vector instruction every ~9 cycles; rows past the end take part with g = 0)
-      double g[4], u[RANK][4], v[RANK][4];
-#pragma unroll
-      for (int r=0; r<4; r++)
-      {
-         if (r >= rpl) { g[r] = 0.0; for (int k=0; k<RANK; k++) { u[k][r] = 0.0; v[k][r] = 0.0; } continue; }      // (wave-uniform)
-         const int row = row0 + r, rc = (row < m) ? row : m - 1;
-         const double gv = (double) buf[rc*n + c];
-         g[r] = (row < m) ? gv : 0.0;
-#pragma unroll
-         for (int k=0; k<RANK; k++)
-         {
-            u[k][r] = U[k*m + rc]; v[k][r] = V[k*m + rc];
-            su[k] += u[k][r] * g[r]; sv[k] += v[k][r] * g[r];
-         }
-      }
-      double P[RANK], S[RANK];
-#pragma unroll
-      for (int k=0; k<RANK; k++)
-      {
-         const double ip = wave_prefix_incl(su[k]);
-         P[k] = __shfl_up(ip, 1, 64); if (lane == 0) P[k] = 0.0;      // rows before this lane's
-         S[k] = wave_suffix_incl(sv[k]);                              // rows from this lane's first on
-      }
-#pragma unroll
-      for (int r=0; r<4; r++)
-      {
-         if (r >= rpl) continue;
-         const int row = row0 + r;
-         double x = 0.0;
-#pragma unroll
-         for (int k=0; k<RANK; k++) x += u[k][r] * S[k] + v[k][r] * P[k];
-         if (row < m) buf[row*n + c] = (real) x;
-#pragma unroll
-         for (int k=0; k<RANK; k++) { P[k] += u[k][r] * g[r]; S[k] -= v[k][r] * g[r]; }
-      }
-      return;
-   }
-   for (int r=0; r<rpl; r++)
-   {
-      const int row = row0 + r;
-      if (row >= m) break;
-      const double g = (double) buf[row*n + c];
-#pragma unroll
-      for (int k=0; k<RANK; k++) { su[k] += U[k*m + row] * g; sv[k] += V[k*m + row] * g; }
-   }
-   double P[RANK], S[RANK];
-#pragma unroll
-   for (int k=0; k<RANK; k++)
-   {
-      const double ip = wave_prefix_incl(su[k]);
-      P[k] = __shfl_up(ip, 1, 64); if (lane == 0) P[k] = 0.0;
-      S[k] = wave_suffix_incl(sv[k]);
-   }
-   for (int r=0; r<rpl; r++)
-   {
-      const int row = row0 + r;
-      if (row >= m) break;
-      const double g = (double) buf[row*n + c];
-      double x = 0.0;
-#pragma unroll
-      for (int k=0; k<RANK; k++)
-      {
-         const double uk = U[k*m + row], vk = V[k*m + row];
-         x += uk * S[k] + vk * P[k];
-         P[k] += uk * g; S[k] -= vk * g;
-      }
-      buf[row*n + c] = (real) x;
-   }
-}
-template <typename real, typename PT>
-__device__ __forceinline__ void semisep_scan_column_any(PT buf, int m, int n, int c, int rank, const double * U, const double * V)
-{
-   const int rpl = (m + 63) >> 6;
-   if (rpl <= 4)
-      switch (rank)
-      {
-      case 2: semisep_scan_column<real, 2, true>(buf, m, n, c, rpl, U, V); break;
-      case 3: semisep_scan_column<real, 3, true>(buf, m, n, c, rpl, U, V); break;
-      default: semisep_scan_column<real, 4, true>(buf, m, n, c, rpl, U, V); break;
-      }
-   else
-      switch (rank)
-      {
-      case 2: semisep_scan_column<real, 2, false>(buf, m, n, c, rpl, U, V); break;
-      case 3: semisep_scan_column<real, 3, false>(buf, m, n, c, rpl, U, V); break;
-      default: semisep_scan_column<real, 4, false>(buf, m, n, c, rpl, U, V); break;
-      }
-}
-// all n columns of buf [m][n] in place, a wavefront per column at a time: ONE barrier, like the scan solve of derivative 1.
-// A column that is zero throughout (the joint-limit rounds solve for a Gjlimit with a few non-zero columns) is left alone.
-template <typename real, int BLOCK>
-__device__ __attribute__((noinline)) real * semisep_solve_call(real * buf_in, const real * tab_in, int m_in, int n_in, int rank_in, int tid)
-{
-   // (a function of its own: six instantiations of the column solve, of no interest to a `derivative 1` run's instruction cache)
-   const int m = __builtin_amdgcn_readfirstlane(m_in), n = __builtin_amdgcn_readfirstlane(n_in), rank = __builtin_amdgcn_readfirstlane(rank_in);
-   real * buf = (real *) uni64((unsigned long long) buf_in);
-   const real * tab = (const real *) uni64((unsigned long long) tab_in);
-   const int lane = tid & 63, wave = tid >> 6;
-   const int rpl = (m + 63) >> 6;
-   const double * U = (const double *) tab, * V = U + rank*m;      // (the metric's tables: DevBatch::ss_rank)
-   for (int c=wave; c<n; c+=BLOCK/64)
-   {
-      bool any = false;
-      for (int r=0; r<rpl; r++) { const int row = lane*rpl + r; any = any || ((row < m) && buf[row*n + c] != (real)0); }
-      if (__ballot(any) == 0ull) continue;
-      semisep_scan_column_any<real>(buf, m, n, c, rank, U, V);
-   }
-   __syncthreads();
-   return buf;
-}
-
-
-template <typename real, typename PT>
-__device__ __forceinline__ void toeplitz_scan_column_any(PT buf, int m, int n, int c, real kinv)
-{
-   const int rpl = (m + 63) >> 6;
-   if (rpl <= ORC_SCAN_RPL) toeplitz_scan_column<real>(buf, m, n, c, rpl, kinv);
-   else toeplitz_scan_column_long<real>(buf, m, n, c, rpl, kinv);
-}
-
-// Joint-limit projection rounds (src/libcd/chomp.c:608-655) for the tridiagonal Toeplitz metric,
-// executed by ONE wavefront (the caller's; the others wait at the barrier that follows): a round has
-// no barrier in it.  Lane = `rpl` consecutive waypoints, loop over the columns.  A round is:
-// violations of every entry -> Gjlimit in G (dense) and the largest violation (wave arg-max, ties
-// to the first row-major index) -> GA = A^-1 Gjlimit by the scan solve, only for the columns that
-// have a violation -> T += 1.01 Gjlimit[l]/GA[l] * GA on those columns.
-// Returns the number of rounds made (1000: the caller sets the status).
-// SOLVE: solve_col(c) replaces column c of G_s by A^-1 of it (the calling wavefront's work)
-template <typename real, typename PT, typename PG, typename PJ, typename SOLVE>
-__device__ __forceinline__ int limit_rounds_wave_with(PT T_s, PG G_s, PJ jl_s, int m, int n, SOLVE solve_col, long long * dbg_total)
-{
-   const int lane = threadIdx.x & 63;
-   const int rpl = (m + 63) >> 6;
-   const float rn = 1.0f / (float) n;
-   const int mn = m*n;
-   int rounds;
-   for (rounds=0; rounds<1000; rounds++)
-   {
-      // violations of all entries, in row-major order (lane + 64 k): Gjlimit, the largest one
-      // (first index on ties) and the set of columns that have one
-      real best = 0; int best_e = 0x7fffffff;
-      unsigned long long mycols = 0ull;
-      // four entries of the lane per trip: their reads and short dependent chains overlap (one entry
-      // per trip pays the full latency of each)
-#pragma unroll 1
-      for (int e0=lane; e0<mn; e0+=4*64)
-      {
-         real gk[4]; int ck[4];
-#pragma unroll
-         for (int k=0; k<4; k++)
-         {
-            const int e = e0 + 64*k;
-            const bool ok = (e < mn);
-            const int i = div_n(ok ? e : 0, rn), c = (ok ? e : 0) - i*n;
-            const real t = ok ? T_s[n + e] : (real)0;
-            const real lo = jl_s[c], hi = jl_s[n+c];
-            // lo - t when below, hi - t when above, else 0 (at most one of the two terms is non-zero)
-            real g = M<real>::max_(lo - t, (real)0) + M<real>::min_(hi - t, (real)0);
-            g = ok ? g : (real)0;
-            if (ok) G_s[e] = g;
-            gk[k] = g; ck[k] = c;
-         }
-         // arg-max of the four, then against the running one: a later entry wins only when strictly larger
-         const real a0 = M<real>::fabs_(gk[0]), a1 = M<real>::fabs_(gk[1]), a2 = M<real>::fabs_(gk[2]), a3 = M<real>::fabs_(gk[3]);
-         const bool l01 = (a1 > a0), l23 = (a3 > a2);
-         const real a01 = l01 ? a1 : a0, a23 = l23 ? a3 : a2;
-         const int e01 = l01 ? e0 + 64 : e0, e23 = l23 ? e0 + 192 : e0 + 128;
-         const bool l2 = (a23 > a01);
-         const real a4 = l2 ? a23 : a01; const int e4 = l2 ? e23 : e01;
-         const bool better = (a4 > best);
-         best = better ? a4 : best;
-         best_e = better ? e4 : best_e;
-#pragma unroll
-         for (int k=0; k<4; k++) mycols |= (gk[k] != (real)0) ? (1ull << ck[k]) : 0ull;
-      }
-      wave_argmax(best, best_e);
-      if (!(best > (real)0)) break;                   // nothing violated
-      // columns with a violated entry: OR of the lanes' masks (DPP inside the rows, then the four rows)
-      unsigned int clo = (unsigned int) mycols, chi = (unsigned int)(mycols >> 32);
-      clo |= (unsigned int) dpp_move<0xB1>((int) clo); chi |= (unsigned int) dpp_move<0xB1>((int) chi);     // quad_perm [1,0,3,2]
-      clo |= (unsigned int) dpp_move<0x4E>((int) clo); chi |= (unsigned int) dpp_move<0x4E>((int) chi);     // quad_perm [2,3,0,1]
-      clo |= (unsigned int) dpp_move<0x141>((int) clo); chi |= (unsigned int) dpp_move<0x141>((int) chi);   // row_half_mirror
-      clo |= (unsigned int) dpp_move<0x140>((int) clo); chi |= (unsigned int) dpp_move<0x140>((int) chi);   // row_mirror
-      const unsigned int lo32 = __builtin_amdgcn_readlane((int) clo, 0) | __builtin_amdgcn_readlane((int) clo, 16)
-                              | __builtin_amdgcn_readlane((int) clo, 32) | __builtin_amdgcn_readlane((int) clo, 48);
-      const unsigned int hi32 = __builtin_amdgcn_readlane((int) chi, 0) | __builtin_amdgcn_readlane((int) chi, 16)
-                              | __builtin_amdgcn_readlane((int) chi, 32) | __builtin_amdgcn_readlane((int) chi, 48);
-      const unsigned long long cols = ((unsigned long long) hi32 << 32) | lo32;      // wave-uniform
-      const int ge = best_e;
-      const int gi = div_n(ge, rn), gc = ge - gi*n;
-      const real gl = G_s[ge];                        // Gjlimit[largest]
-      if (dbg_total) *dbg_total += __popcll(cols);
-      for (int c=0; c<n; c++)
-         if ((cols >> c) & 1ull) solve_col(c);
-      const real sc = ((real)1.01 * gl) * rcp_fast(G_s[gi*n + gc]);
-      for (int c=0; c<n; c++)
-         if ((cols >> c) & 1ull)
-         {
-            for (int r=0; r<rpl; r++)      // (any number of rows per lane: trajectories of more than 256 moving waypoints come here)
-            {
-               const int row = lane*rpl + r;
-               if (row < m) T_s[n + row*n + c] += sc * G_s[row*n + c];
-            }
-         }
-   }
-   return rounds;
-}
-template <typename real, typename PT, typename PG, typename PJ>
-__device__ __forceinline__ int limit_rounds_wave(PT T_s, PG G_s, PJ jl_s, int m, int n, real kinv, long long * dbg_total)
-{
-   const int rpl = (m + 63) >> 6;
-   (void) rpl;
-   return limit_rounds_wave_with<real>(T_s, G_s, jl_s, m, n, [&](int c) { toeplitz_scan_column_any<real>(G_s, m, n, c, kinv); }, dbg_total);
-}
-// ... and for the band metric of a higher derivative (solve_mode 3): the same rounds with the band inverse applied through its
-// generators, one wavefront, no barrier inside (m <= 64 ORC_SCAN_RPL: the lane's rows in registers).  A function of its own,
-// like limit_rounds_call: rare, branchy code that should not take part in the update phase's register allocation.
-template <typename real, int SHAPE>
-__device__ __attribute__((noinline)) int limit_rounds_semisep_call(real * T_gen, real * G_gen, const real * jl_gen, int m_in, int n_in, int rank_in,
-   const double * U_in, const double * V_in)
-{
-   const int m = __builtin_amdgcn_readfirstlane(m_in), n = __builtin_amdgcn_readfirstlane(n_in), rank = __builtin_amdgcn_readfirstlane(rank_in);
-   const double * U = (const double *) uni64((unsigned long long) U_in), * V = (const double *) uni64((unsigned long long) V_in);
-   return limit_rounds_wave_with<real>(T_gen, G_gen, jl_gen, m, n, [&](int c) { semisep_scan_column_any<real>(G_gen, m, n, c, rank, U, V); }, nullptr);
-}
-
-
-#include "limit_regs.h"
-// (A forwarding level of its own, on purpose: with the two folded into one function the rounds inline one level less deep, and the
-// compiled limit_rounds_call* functions come out different -- other registers, another schedule.  To be folded by a change that is
-// timed on the card anyway.)
-template <typename real, int NC, int RPL, typename PT, typename PJ>
-__device__ __forceinline__ int limit_rounds_regs(PT T_s, PJ jl_s, int m, int n, real kinv, unsigned long long cols, long long * dbg)
-{
-   return limit_rounds_regs_masks<real, NC, RPL>(T_s, jl_s, m, n, kinv, cols, dbg);
-}
-template <typename real, int NC, typename PT, typename PJ>
-__device__ __forceinline__ int limit_rounds_regs_rpl(PT T_s, PJ jl_s, int m, int n, real kinv, unsigned long long cols, long long * dbg)
-{
-   const int rpl = (m + 63) >> 6;
-   switch (rpl)
-   {
-   case 1: return limit_rounds_regs<real, NC, 1>(T_s, jl_s, m, n, kinv, cols, dbg);
-   case 2: return limit_rounds_regs<real, NC, 2>(T_s, jl_s, m, n, kinv, cols, dbg);
-   case 3: return limit_rounds_regs<real, NC, 3>(T_s, jl_s, m, n, kinv, cols, dbg);
-   default: return limit_rounds_regs<real, NC, 4>(T_s, jl_s, m, n, kinv, cols, dbg);
-   }
-}
-
-// The joint-limit rounds of one iteration as a FUNCTION CALL of the wavefront that makes them: the
-// rounds are long, rare, branchy code with a register appetite of their own; inlined into the
-// iterate kernel they take part in its register allocation and cost the cost phase its registers
-// (measured: +6 % kernel time when the variants for 4..8 columns were added inline).  One copy per
-// precision serves every kernel variant.  T_s / G_s / jl_s are LDS addresses.
-struct LimResult { int rounds; long long kinds; };      // kinds: closed-form | register scans << 20 | general loop << 40
-
-// PART: 1 one or two columns only; 2 three columns and more.  The rounds of one or two columns are a function of their own: its
-// register appetite, and with it the callee-saved registers a call saves and restores, is a third of the large cases'
-template <typename real, int PART, typename PT>
-__device__ __forceinline__ LimResult limit_rounds_body(PT T_s, real * G_gen, const real * jl_gen, int m_in, int n_in, real kinv_in,
-   unsigned long long viol_cols_in)
-{
-   // arguments arrive in vector registers: tell the compiler they are wave-uniform
-   const int m = __builtin_amdgcn_readfirstlane(m_in), n = __builtin_amdgcn_readfirstlane(n_in);
-   const real kinv = unir(kinv_in);
-   const unsigned long long viol_cols = uni64(viol_cols_in);
-   typedef __attribute__((address_space(3))) real * lds_ptr;
-   typedef const __attribute__((address_space(3))) real * lds_cptr;
-   lds_ptr G_s = (lds_ptr) G_gen; lds_cptr jl_s = (lds_cptr) jl_gen;
-   LimResult res; res.rounds = 0; res.kinds = 0;
-   long long * dg = &res.kinds;
-   const int nc = __popcll(viol_cols);
-   if (m > 64*ORC_SCAN_RPL)
-   {
-      // more than 256 moving waypoints: the register forms hold at most four rows per lane; the rounds through G in LDS (still one
-      // wavefront, no barrier inside a round; until round 6 such runs took the workgroup loop with a cyclic-reduction solve per round)
-      res.rounds = limit_rounds_wave<real>(T_s, G_s, jl_s, m, n, kinv, nullptr);
-      res.kinds += (long long) res.rounds << 40;
-      return res;
-   }
-   if (PART == 1)
-   {
-      if (nc == 1) res.rounds = limit_rounds_regs_rpl<real, 1>(T_s, jl_s, m, n, kinv, viol_cols, dg);
-      else res.rounds = limit_rounds_regs_rpl<real, 2>(T_s, jl_s, m, n, kinv, viol_cols, dg);
-      return res;
-   }
-   switch (nc)
-   {
-   case 1: case 2: break;      // (PART 2 is never called with one or two)
-   case 3: res.rounds = limit_rounds_regs_rpl<real, 3>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-   default:
-      // four to eight columns (a trajectory that is leaving its limits for good, the 1000-round
-      // aborts among them): still register-resident when a lane holds at most two waypoints
-      if (m <= 128 && nc <= 8)
-      {
-         switch (nc)
-         {
-         case 4: res.rounds = limit_rounds_regs<real, 4, 2>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         case 5: res.rounds = limit_rounds_regs<real, 5, 2>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         case 6: res.rounds = limit_rounds_regs<real, 6, 2>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         case 7: res.rounds = limit_rounds_regs<real, 7, 2>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         default: res.rounds = limit_rounds_regs<real, 8, 2>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         }
-         break;
-      }
-      if (m <= 256 && nc <= 7)      // 200-waypoint runs (BASELINE configs[3]: seven arm columns can leave their limits)
-      {
-         switch (nc)
-         {
-         case 4: res.rounds = limit_rounds_regs<real, 4, 4>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         case 5: res.rounds = limit_rounds_regs<real, 5, 4>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         case 6: res.rounds = limit_rounds_regs<real, 6, 4>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         default: res.rounds = limit_rounds_regs<real, 7, 4>(T_s, jl_s, m, n, kinv, viol_cols, dg); break;
-         }
-         break;
-      }
-      res.rounds = limit_rounds_wave<real>(T_s, G_s, jl_s, m, n, kinv, nullptr);
-      res.kinds += (long long) res.rounds << 40;
-      break;
-   }
-   return res;
-}
-// the trajectory in LDS (every kernel but the large-robot plans that leave it in global memory)
-template <typename real, int SHAPE>      // SHAPE: a copy per register budget of the calling kernels (the budget follows the callers')
-__device__ __attribute__((noinline)) LimResult limit_rounds_call(real * T_gen, real * G_gen, const real * jl_gen, int m, int n, real kinv,
-   unsigned long long viol_cols)
-{
-   typedef __attribute__((address_space(3))) real * lds_ptr;
-   return limit_rounds_body<real, 2>((lds_ptr) T_gen, G_gen, jl_gen, m, n, kinv, viol_cols);
-}
-template <typename real, int SHAPE>
-__device__ __attribute__((noinline)) LimResult limit_rounds_call_global(real * T_gen, real * G_gen, const real * jl_gen, int m, int n, real kinv,
-   unsigned long long viol_cols)
-{
-   return limit_rounds_body<real, 2>(T_gen, G_gen, jl_gen, m, n, kinv, viol_cols);
-}
-// ... and the same for one or two columns (nearly every call of a 7-dof arm)
-template <typename real, int SHAPE>
-__device__ __attribute__((noinline)) LimResult limit_rounds_call_small(real * T_gen, real * G_gen, const real * jl_gen, int m, int n, real kinv,
-   unsigned long long viol_cols)
-{
-   typedef __attribute__((address_space(3))) real * lds_ptr;
-   return limit_rounds_body<real, 1>((lds_ptr) T_gen, G_gen, jl_gen, m, n, kinv, viol_cols);
-}
-template <typename real, int SHAPE>
-__device__ __attribute__((noinline)) LimResult limit_rounds_call_global_small(real * T_gen, real * G_gen, const real * jl_gen, int m, int n, real kinv,
-   unsigned long long viol_cols)
-{
-   return limit_rounds_body<real, 1>(T_gen, G_gen, jl_gen, m, n, kinv, viol_cols);
-}
-
-template <typename real, int BLOCK, typename BT>
-__device__ __forceinline__ real * metric_solve(const BT & b, const real * tab, real * src, real * tmp, int tid)
-{
-   if (b.solve_mode == 2) return toeplitz_scan_solve<real, BLOCK>(b, src, tid);
-   if (b.solve_mode == 3) return semisep_solve_call<real, BLOCK>(src, tab, b.m, b.n, b.ss_rank, tid);
-   return b.solve_mode == 0 ? pcr_solve<real, BLOCK>(b, tab, src, tmp, tid) : dense_solve<real, BLOCK>(b, src, tmp, tid);
-}
-
-// Row i, column c of A T + B for a higher derivative (|D| >= 2, or derivative 1 without a start boundary), in the
-// accumulation type `acc` (double for fp32 runs: the band's entries are ~1/dt^4, 1e7 for 200 waypoints, and the row's sum is of
-// order one to a hundred -- summed in fp32 the rounding alone is of that order; `tab` is then the band in double).
-// bt_out: the row's term of B alone (beta_s[i] q_start + beta_g[i] q_goal).
-// Away from the D rows at either end the band is Toeplitz and B is zero (DevBatch::band_toeplitz, checked on the host): the
-// 2D+1 coefficients are scalars of the kernarg block.  The end rows read their coefficients from the table -- all loads issued
-// before the first use (a loop over a run-time D made one L2 round trip per coefficient: 4 k cycles per entry, a third of the
-// update phase of a `derivative 2` run).
-template <typename real, typename acc, typename BT>
-__device__ __forceinline__ acc band_row(const BT & b, const real * tab, const real * T_s, int i, int c, acc & bt_out)
-{
-   constexpr int R = ORC_SS_MAX_RANK;
-   const int m = b.m, n = b.n;
-   const int D = (b.D < 0) ? -b.D : b.D;      // (-1: tridiagonal without a start boundary, DevBatch::D)
-   const bool dbl = (sizeof(acc) == 8 && sizeof(real) == 4);
-   // (the Toeplitz row's coefficients first, all of them and before any branch: scalar loads of the kernarg block that are then
-   // certain to execute, so the compiler can move them out of the callers' loops)
-   acc cf[R+1];
-#pragma unroll
-   for (int k=0; k<=R; k++) cf[k] = dbl ? (acc) b.band_c64[k] : (acc) b.band_c[k];
-   const int toep = b.band_toeplitz;      // (set only with solve_mode 3: the end rows are in the metric's table)
-   if (D >= 2 && D <= R && toep && sizeof(acc) == 8)
-   {
-      // Every lane evaluates the Toeplitz row (at a clamped row index, so that all reads are unconditional); the wavefronts that
-      // hold one of the D rows at either end then evaluate that row from the metric's table as well -- 2D+1 coefficients and the two
-      // couplings, contiguous, read unconditionally (a lane that has no end row reads row 0; coefficients of columns outside the
-      // matrix are stored as zeros and meet a clamped trajectory row) -- and the lanes pick.  As predicated reads the end rows
-      // cost ~300 vector instructions of address arithmetic and branches for the two wavefronts that hold them: 4 k cycles per pass.
-      const bool is_end = !(i >= D && i < m - D);
-      const int ic = (i < D) ? D : ((i >= m - D) ? m - D - 1 : i);
-      const real * rowT = T_s + (ic+1)*n + c;
-      acc sum = (acc)0;
-      switch (D)      // (wave-uniform; the sums run from k = -D upwards, the order of the reference's dense row)
-      {
-      case 2:
-#pragma unroll
-         for (int k=-2; k<=2; k++) sum += cf[k < 0 ? -k : k] * (acc) rowT[k*n];
-         break;
-      case 3:
-#pragma unroll
-         for (int k=-3; k<=3; k++) sum += cf[k < 0 ? -k : k] * (acc) rowT[k*n];
-         break;
-      default:
-#pragma unroll
-         for (int k=-4; k<=4; k++) sum += cf[k < 0 ? -k : k] * (acc) rowT[k*n];
-         break;
-      }
-      acc bt = (acc)0;
-#if defined(ORC_ABLATE_BANDEND)      // (timing experiments: the end rows take the Toeplitz row -- wrong results)
-      if (false)
-#else
-      if (__builtin_amdgcn_ballot_w64(is_end) != 0ull)
-#endif
-      {
-         const int er = is_end ? ((i < D) ? i : i - (m - 2*D)) : 0;
-         const double * row = (const double *) tab + 2*D*m + er * (2*D + 3);
-         const acc bte = (acc) row[2*D+1] * (acc) T_s[c] + (acc) row[2*D+2] * (acc) T_s[(b.n_points-1)*n + c];
-         acc se = bte;
-         auto end_row = [&](auto dd) {
-            constexpr int DD = decltype(dd)::value;
-#pragma unroll
-            for (int k=-DD; k<=DD; k++)
-            {
-               const int r = i + k, rc = (r < 0) ? 0 : ((r >= m) ? m - 1 : r);
-               se += (acc) row[k+DD] * (acc) T_s[(rc+1)*n + c];
-            }
-         };
-         switch (D)
-         {
-         case 2: end_row(std::integral_constant<int, 2>{}); break;
-         case 3: end_row(std::integral_constant<int, 3>{}); break;
-         default: end_row(std::integral_constant<int, 4>{}); break;
-         }
-         sum = is_end ? se : sum;
-         bt = is_end ? bte : bt;
-      }
-      bt_out = bt;
-      return sum;
-   }
-   const acc * tabA = dbl ? (const acc *) b.metric64 : (const acc *) b.Aband;
-   const acc * tbs = dbl ? tabA + (size_t)(2*D + 1) * m : (const acc *) b.beta_s;
-   const acc * tbg = dbl ? tbs + m : (const acc *) b.beta_g;
-   const acc bt = tbs[i] * (acc) T_s[c] + tbg[i] * (acc) T_s[(b.n_points-1)*n + c];
-   bt_out = bt;
-   acc sum = bt;
-   if (D <= R)
-   {
-      acc a[2*R+1], t[2*R+1];
-#pragma unroll
-      for (int q=0; q<2*R+1; q++)
-      {
-         const int k = q - R, r = i + k;
-         const bool ok = (k >= -D) && (k <= D) && (r >= 0) && (r < m);
-         a[q] = ok ? tabA[(size_t)(k+D) * m + i] : (acc)0;
-         t[q] = ok ? (acc) T_s[(r+1)*n + c] : (acc)0;
-      }
-#pragma unroll
-      for (int q=0; q<2*R+1; q++)
-      {
-         const int k = q - R, r = i + k;
-         if ((k >= -D) && (k <= D) && (r >= 0) && (r < m)) sum += a[q] * t[q];
-      }
-      return sum;
-   }
-   for (int k=-D; k<=D; k++)
-   {
-      const int r = i + k;
-      if (r < 0 || r >= m) continue;
-      sum += tabA[(size_t)(k+D) * m + i] * (acc) T_s[(r+1)*n + c];
-   }
-   return sum;
-}
-
-// (A T + B)[i][c] of the tridiagonal Toeplitz metric of derivative 1: the end rows couple to the fixed endpoints with a_off.
-// T_s holds all n_points rows (row 0 = start, row n_points-1 = goal).
-template <typename real, typename BT>
-__device__ __forceinline__ real smooth_grad(const BT & b, const real * T_s, int i, int c)
-{
-   const int n = b.n;
-   // In double whatever `real` is (the same bits in fp64; a product of two floats is exact in double), and rounded once: the row is a
-   // second difference, its terms of size a |T|, its value a |T''| dt^2, and float rounds it at a |T| 2^-24.  Of the gradient that is as
-   // much as the waypoints' own float rounding moves it; but A^-1 takes A dT back to dT, while it passes this error on at its full
-   // size: A^-1 G of a 34-waypoint fp32 run was off by 4e-5 of its largest row, 56 x what the float rounding of the waypoints moves it
-   // (NOTES/first-iteration.md).  phase_costs_body forms the row the same way.
-   if (sizeof(real) == 4)
-      return (real)((double) b.a_diag * (double) T_s[(i+1)*n + c] + (double) b.a_off * ((double) T_s[i*n + c] + (double) T_s[(i+2)*n + c]));
-   return b.a_diag * T_s[(i+1)*n + c] + b.a_off * (T_s[i*n + c] + T_s[(i+2)*n + c]);
-}
-// The two passes over the trajectory that need A T + B, for a metric that is not that one (a higher derivative; derivative 1
-// without a start boundary): G = G/m + A T + B of the update phase and 0.5 tr(T^T A T) + tr(B^T T) of the cost pass, as FUNCTIONS of
-// their own -- inlined, band_row tripled the lean update phase of every `derivative 1` kernel (2.1 k -> 5.4 k instructions) and cost
-// BASELINE configs[1] 1 % through the instruction cache alone (profiles/r06_ab_experiments.txt).
-template <typename real, int BLOCK>
-__device__ __attribute__((noinline)) void band_gradient_pass(const void * kp, const real * tab_in, const real * T_in, const real * Gc_in, real * G_in, int tid)
-{
-   // (the kernarg block's address, wave-uniform again; through uni64: readfirstlane returns an int, and OR-ing the low half in as
-   // one sign-extends it -- a launch whose kernarg address has bit 31 set then reads from a wild pointer: the first version did)
-   const __attribute__((address_space(4))) DevBatch<real> & b = *(const __attribute__((address_space(4))) DevBatch<real> *) uni64((unsigned long long) kp);
-   const real * tab = (const real *) uni64((unsigned long long) tab_in), * T_s = (const real *) uni64((unsigned long long) T_in);
-   const real * Gc = (const real *) uni64((unsigned long long) Gc_in);
-   real * G_s = (real *) uni64((unsigned long long) G_in);
-   const int n = b.n, mn = b.m*n;
-   const float rn_f = 1.0f / (float) n;
-   for (int e=tid; e<mn; e+=BLOCK)
-   {
-      const int i = div_n(e, rn_f), c = e - i*n;
-      real g = Gc[e];
-      g *= b.inv_m;
-      if (sizeof(real) == 4 && b.metric64) { double bt; g += (real) band_row<real, double>(b, tab, T_s, i, c, bt); }
-      else { real bt; g += band_row<real, real>(b, tab, T_s, i, c, bt); }
-      G_s[e] = g;
-   }
-}
-template <typename real, int BLOCK>
-__device__ __attribute__((noinline)) double band_cost_pass(const void * kp, const real * tab_in, const real * T_in, int tid)
-{
-   // (the kernarg block's address, wave-uniform again; through uni64: readfirstlane returns an int, and OR-ing the low half in as
-   // one sign-extends it -- a launch whose kernarg address has bit 31 set then reads from a wild pointer: the first version did)
-   const __attribute__((address_space(4))) DevBatch<real> & b = *(const __attribute__((address_space(4))) DevBatch<real> *) uni64((unsigned long long) kp);
-   const real * tab = (const real *) uni64((unsigned long long) tab_in), * T_s = (const real *) uni64((unsigned long long) T_in);
-   const int n = b.n, mn = b.m*n;
-   const float rn_f = 1.0f / (float) n;
-   double acc = 0.0;
-   for (int e=tid; e<mn; e+=BLOCK)
-   {
-      const int i = div_n(e, rn_f), c = e - i*n;
-      if (sizeof(real) == 4 && b.metric64)
-      {
-         // fp32 and a higher derivative: the band's entries are ~1/dt^4 and the sum is of order one, so this one sum is
-         // taken in double from the band in double (the trajectory is what it is: its rounding costs ~1e-5 of the sum)
-         double bt;
-         const double sd = band_row<real, double>(b, tab, T_s, i, c, bt);
-         acc += (double) T_s[n + e] * (0.5 * (sd + bt));
-      }
-      else
-      {
-         real bt;
-         const real sg = band_row<real, real>(b, tab, T_s, i, c, bt);
-         acc += (double) T_s[n + e] * (0.5 * ((double) sg + (double) bt));
-      }
-   }
-   return acc;
-}
+#include "fast_math.h"
+#include "wave.h"
+#include "metric_solve.h"
+#include "limit_rounds.h"
+#include "band.h"
 
 // entries of a thread whose gradient / momentum rows the update phase reads ahead where they live in global memory and a thread has more than four
 constexpr int UPDATE_BATCH = 4;
@@ -999,17 +82,15 @@ constexpr int PRIO_COST_LAST = 2;      // the last round of a tile: it is what t
 // and reloaded in its inner loops, and any change to a rare path moved the spills of the hot one.
 // A phase function receives the address of the kernarg block (DevBatch, read with scalar loads where
 // it is used) and a few wave-uniform scalars, and derives the LDS carve-up again (scalar arithmetic).
+// This file is compiled with -mllvm -enable-ipra=0 (the Makefile's KFLAGS).  With the compiler's inter-procedural register
+// allocation a caller takes every callee-saved SCALAR register its callee touches for lost, although the callee saves and restores
+// it (in VGPR lanes: the target has no scalar spill to memory), and saves its own copy around the call as well: the save is paid
+// twice.  Without it the callers rely on the calling convention (NOTES/call-overhead.md).
 template <typename real> using KArg = const __attribute__((address_space(4))) DevBatch<real>;
 template <typename real> using KModel = const __attribute__((address_space(4))) DevModel<real>;
 
 template <typename real>
-__device__ __forceinline__ KArg<real> * uniform_kernarg(const void * p)
-{
-   const unsigned long long v = (unsigned long long) p;
-   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned) v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-   return (KArg<real> *)(((unsigned long long) hi << 32) | lo);
-}
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ KArg<real> * uniform_kernarg(const void * p) { return (KArg<real> *) uni64((unsigned long long) p); }
 // the kernarg block again, as an address the compiler knows nothing about: what is read through it is read where it is used, by a
 // scalar load, and is not kept in a register from an earlier read (the kernel's loop, between its phase calls)
 template <typename real>
@@ -1032,9 +113,7 @@ template <typename real, typename BT>
 __device__ __forceinline__ const __attribute__((address_space(4))) RunParams<real> * run_params_of(const BT & b)
 {
    typedef const __attribute__((address_space(4))) RunParams<real> * P;
-   const unsigned long long v = b.run_params ? (unsigned long long)(b.run_params + blockIdx.x) : (unsigned long long) &b.shared;
-   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned) v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-   return (P)(((unsigned long long) hi << 32) | lo);
+   return (P) uni64(b.run_params ? (unsigned long long)(b.run_params + blockIdx.x) : (unsigned long long) &b.shared);
 }
 
 // The LOGICAL thread index every phase hands its work out by (wave_roles.h): the hardware index rotated by `rot` whole

@@ -36,6 +36,7 @@ namespace {
 #include "fk.h"
 #include "verdict_walk.h"
 #include "verdict_planned.h"
+#include "wave.h"           // wave_min
 
 // a thread's running minimum of one leg: the items reach a thread in ascending key order, so `<` keeps the lowest key
 template <typename real>
@@ -92,13 +93,6 @@ __device__ __forceinline__ void clearance_tests(const DevVerdictWalk<real> & v, 
       const real rs = v.pair_rsum[pi];
       clearance_offer<real>(slf, dist - rs, sbase + s, v.pairs[pi*4+2], v.pairs[pi*4+3], times, s);
    }
-}
-
-template <typename real>
-__device__ __forceinline__ real wave_min(real x)
-{
-   for (int d=32; d>=1; d>>=1) x = M<real>::min_(x, __shfl_xor(x, d));
-   return x;
 }
 
 // what a run that was not walked reports (tid 0)

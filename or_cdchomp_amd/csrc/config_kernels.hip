@@ -21,6 +21,7 @@ namespace {
 #include "sdf_lookup.h"
 #include "fk.h"
 #include "verdict_walk.h"
+#include "wave.h"           // config_query.h's wave_min
 #include "config_query.h"
 
 template <typename real, bool TREE>

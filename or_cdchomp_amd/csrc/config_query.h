@@ -2,7 +2,7 @@
 // a query's two minima with their keys, the staging of a workgroup's queries from the LDS carve-up to the fence behind FK, and
 // the launcher.  A query is one row, tested against the scene of the run it names, with the batch's model (config_device.h).
 //
-// Included inside the including file's namespace after verdict_walk.h, with the contraction the walk is compiled with in force.
+// Included inside the including file's namespace after verdict_walk.h and wave.h (wave_min), with the contraction the walk is compiled with in force.
 // The minima of the two kernels agree bit for bit because this text is compiled into both: config_tests is one loop, lanes
 // striding over the items, whatever else the including kernel does with the same lookups.
 #pragma once
@@ -37,18 +37,11 @@ __device__ __forceinline__ void config_offer(ConfigMin<real> & m, real gap, int 
    }
 }
 
-template <typename real>
-__device__ __forceinline__ real config_wave_min(real x)
-{
-   for (int d=32; d>=1; d>>=1) x = M<real>::min_(x, __shfl_xor(x, d));
-   return x;
-}
-
 // the wavefront's minimum of a leg and the lowest key at it, written by lane 0
 template <typename real>
 __device__ __forceinline__ void config_report(const ConfigMin<real> & m, int lane, double * clear_out, unsigned int * key_out)
 {
-   const real lowest = config_wave_min<real>(m.val);
+   const real lowest = wave_min<real>(m.val);
    unsigned int key = (m.key != ORC_CONFIG_NONE && m.val == lowest) ? m.key : ORC_CONFIG_NONE;
    for (int d=32; d>=1; d>>=1) { const unsigned int o = __shfl_xor(key, d); key = o < key ? o : key; }
    if (lane == 0)

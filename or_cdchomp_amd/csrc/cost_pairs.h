@@ -23,13 +23,6 @@
 // J^T as in cost_gs16.h: one suffix scan of the wrench over the waypoint's lanes, lane r finishes joint r.
 #pragma once
 
-__device__ __forceinline__ double bperm(int addr4, double v)
-{
-   const int lo = __builtin_amdgcn_ds_bpermute(addr4, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(addr4, __double2hiint(v));
-   return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float bperm(int addr4, float v) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr4, __float_as_int(v))); }
-
 // an entry of the staged pair list { rsum, first | second << 8, pad }: one LDS read (16 bytes in fp64, 8 in fp32)
 template <typename real> struct PairEnt { real rsum; int ab; };
 typedef int orc_v2i __attribute__((ext_vector_type(2)));
@@ -240,8 +233,8 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
             auto operands = [&]()
             {
 #pragma unroll
-               for (int k=0; k<3; k++) { ua[k] = bperm(la4, uvec[k]); ub[k] = bperm(lb4, uvec[k]); }
-               wa = bperm(la4, wself); wb = bperm(lb4, wself);
+               for (int k=0; k<3; k++) { ua[k] = lane_fetch(uvec[k], la4); ub[k] = lane_fetch(uvec[k], lb4); }
+               wa = lane_fetch(wself, la4); wb = lane_fetch(wself, lb4);
             };
             orc_v2i gat = { 0, 0 };
             // a round ahead: the centres; two rounds ahead: the entry (past the last round: the last round's again, unused)
@@ -295,7 +288,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
                      {
                         const int src = gbase4 + ((gat.x >> (8*(q0 + q))) & 255);
 #pragma unroll
-                        for (int k=0; k<3; k++) gv[q][k] = bperm(src, inc[k]);
+                        for (int k=0; k<3; k++) gv[q][k] = lane_fetch(inc[k], src);
                      }
 #pragma unroll
                      for (int q=0; q<GG; q++)
@@ -312,7 +305,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
                      {
                         const int src = gbase4 + ((gat.y >> (8*(q0 + q))) & 255);
 #pragma unroll
-                        for (int k=0; k<3; k++) gv[q][k] = bperm(src, inc[k]);
+                        for (int k=0; k<3; k++) gv[q][k] = lane_fetch(inc[k], src);
                      }
 #pragma unroll
                      for (int q=0; q<GG; q++)
@@ -378,7 +371,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
             real W[6];
             const int src = gbase4 + ((ab & (GSL - 1)) << 2);
 #pragma unroll
-            for (int k=0; k<6; k++) W[k] = bperm(src, w6[k]);
+            for (int k=0; k<6; k++) W[k] = lane_fetch(w6[k], src);
             if (mod.jt_scan == 2)
             {
                // a robot whose joint tree branches (a WAM with its finger dofs active that holds something): the spheres a joint
@@ -389,7 +382,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
 #pragma unroll
                for (int k=0; k<6; k++)
                {
-                  const real lo = bperm(src_e, w6[k]);
+                  const real lo = lane_fetch(w6[k], src_e);
                   W[k] -= (ae < GSL) ? lo : (real)0;
                }
             }

@@ -1,6 +1,6 @@
 // The joint-limit rounds (src/libcd/chomp.c:608-655) with the violated columns held in REGISTERS, the form that
-// looks at lane MASKS first.  Included by chomp_kernel.hip behind its wave helpers (read_lane, wave_argmax,
-// wave_prefix_incl, wave_suffix_incl, M<real>, rcp_fast).
+// looks at lane MASKS first.  Included by limit_rounds.h behind the iterate kernel's wave.h (read_lane, wave_argmax,
+// wave_prefix_incl, wave_suffix_incl), fast_math.h (rcp_fast) and sdf_lookup.h (M<real>).
 //
 // A round only changes the columns that have a violated entry (Gjlimit, and with it A^-1 Gjlimit, is zero in every
 // other column), so no column can join the set found after the step, and the rounds need nothing but those columns:

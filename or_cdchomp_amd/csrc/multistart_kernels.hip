@@ -21,20 +21,7 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_prefix_excl(double v)      // sum over the lanes below
-{
-   const int lane = threadIdx.x & 63;
-   for (int d=1; d<64; d<<=1) { const double t = __shfl_up(v, d); if (lane >= d) v += t; }
-   const double e = __shfl_up(v, 1);
-   return lane ? e : 0.0;
-}
-__device__ __forceinline__ double wave_suffix_excl(double v)      // sum over the lanes above
-{
-   const int lane = threadIdx.x & 63;
-   for (int d=1; d<64; d<<=1) { const double t = __shfl_down(v, d); if (lane + d < 64) v += t; }
-   const double e = __shfl_down(v, 1);
-   return lane < 63 ? e : 0.0;
-}
+#include "wave.h"           // wave_prefix_excl, wave_suffix_excl
 
 // One wavefront (= one workgroup) per run.  xi is staged in LDS ([m][n] doubles in front of the generator's state);
 // lane l owns the rows [l R, (l+1) R), R = ceil(m / 64), of every column: its partial sums go through one prefix and one suffix wave scan per generator, then it walks its rows.

@@ -34,22 +34,8 @@ namespace {
 #include "sdf_lookup.h"
 #include "fk.h"
 #include "verdict_walk.h"
+#include "wave.h"           // wave_sum, read_lane; config_query.h's wave_min
 #include "config_query.h"
-
-// the wavefront's sum in the butterfly's order: every lane ends with the same bits
-template <typename real>
-__device__ __forceinline__ real pen_wave_sum(real x)
-{
-   for (int d=32; d>=1; d>>=1) x += __shfl_xor(x, d);
-   return x;
-}
-
-// lane o's x in every lane, o being wave-uniform: a read through the scalar unit, no LDS round trip as a shuffle makes
-__device__ __forceinline__ float pen_lane(float x, int o) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), o)); }
-__device__ __forceinline__ double pen_lane(double x, int o)
-{
-   return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), o), __builtin_amdgcn_readlane(__double2loint(x), o));
-}
 
 // lane = sphere slot: the slot's items of query s.  f: dU/dp of the sphere, cost [2] the lane's share of U_f and U_s
 template <typename real>
@@ -157,7 +143,7 @@ void penetration_kernel(DevPenetration<real> v)
       for (int leg=0; leg<2; leg++)
       {
          config_report<real>(best[leg], lane, v.clear_out + q*2 + leg, v.ckey_out + q*2 + leg);
-         const real total = pen_wave_sum<real>(cost[leg]);
+         const real total = wave_sum<real>(cost[leg]);
          if (lane == 0) v.cost_out[q*2 + leg] = (double) total;
       }
       // the sphere's wrench about the world's origin: (p x C f, f)
@@ -178,7 +164,7 @@ void penetration_kernel(DevPenetration<real> v)
 #pragma unroll
          for (int k=0; k<6; k++)
          {
-            const real x = pen_lane(w6[k], o);
+            const real x = read_lane(w6[k], o);
             W[k] += mine ? x : (real)0;
          }
       }
@@ -202,7 +188,7 @@ void penetration_kernel(DevPenetration<real> v)
       {
          real T[6];
 #pragma unroll
-         for (int k=0; k<6; k++) T[k] = pen_wave_sum<real>(w6[k]);
+         for (int k=0; k<6; k++) T[k] = wave_sum<real>(w6[k]);
          if (lane == 0)
          {
             const real * row = L.rows_s + s*n;

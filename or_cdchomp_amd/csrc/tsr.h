@@ -172,24 +172,8 @@ __device__ void tsr_block_thomas(const BT & b, const Env<real> & E, const real *
 //   (z_i = r"_i - C"_i z_{i-1}); the two meet in (I - C'_{mid-1} C"_mid) delta_{mid-1} = r'_{mid-1} - C'_{mid-1} r"_mid,
 //   and both substitute outwards from there at the same time.
 // DIR +1: the points i_begin, i_begin + 1, ... < i_end; DIR -1: i_begin, i_begin - 1, ... > i_end.
-// value of `v` in the lane whose byte address (lane * 4) is `addr4`: ds_bpermute, no memory behind it
-__device__ __forceinline__ double lane_fetch(double v, int addr4)
-{
-   const int lo = __builtin_amdgcn_ds_bpermute(addr4, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(addr4, __double2hiint(v));
-   return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ float lane_fetch(float v, int addr4) { return __int_as_float(__builtin_amdgcn_ds_bpermute(addr4, __float_as_int(v))); }
-
-// A function that is called (not inlined) receives its arguments in vector registers: loop bounds, base addresses and the
-// kernarg block then count as "divergent", loops over them are run by lane masks and their address arithmetic by the vector
-// pipe.  These put a wave-uniform value back into scalar registers.
-template <typename T>
-__device__ __forceinline__ T * uniform_ptr(T * p)
-{
-   const unsigned long long v = (unsigned long long) p;
-   const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned) v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-   return (T *)(((unsigned long long) hi << 32) | lo);
-}
+// (lane_fetch, the ds_bpermute read of another lane, and uniform_ptr, which puts a called function's wave-uniform arguments back
+// into scalar registers, are wave.h's)
 
 template <int K> struct PivotIndex { static constexpr int value = K; };
 template <int... Ks, typename F>

@@ -3,6 +3,10 @@
 // of spheres that may collide; the first contact in (sample, XML sphere, field) order, then (sample, pair) order, is kept as
 // a key, which is where the reference's loop stops (src/orcdchomp_mod.cpp:2958-3006).
 //
+// Its steps also serve the clearance of a run (clearance_kernels.hip, through verdict_planned.h) and the kernels over single rows
+// (config_kernels.hip, penetration_kernels.hip, through config_query.h).  Of the iterate kernel's headers it takes the FK and
+// the field lookup, none of the others.
+//
 // Included inside the including file's namespace after dev_types.h, verdict_device.h, sdf_lookup.h and fk.h, with the
 // contraction the walk is compiled with in force.  One kernel walks samples the host planned, the other plans them itself
 // with a fifth wavefront; `depth`, `time` and the key of the two agree bit for bit because this text is compiled into both.

@@ -1,7 +1,7 @@
 """`derivative 2` and `derivative 3` (src/libcd/chomp.c:239-340: K_d = diff K_{d-1} makes the smoothness metric penta- / hepta-diagonal;
 `create ... derivative D`, src/orcdchomp_mod.cpp:1888-2079) on the GPU against the oracle.  The reference multiplies by the dense
 inverse of dgetrf + dgetri (chomp.c:393-403, 525-548, 643-649); the HIP path applies the band inverse through its rank-D generators
-by D prefix and D suffix wave scans per column (csrc/chomp_kernel.hip semisep_scan_column, csrc/host_math.cpp build_semisep), in
+by D prefix and D suffix wave scans per column (csrc/metric_solve.h semisep_scan_column, csrc/host_math.cpp build_semisep), in
 the metric solve and in the joint-limit rounds.  Both are within cond(A) eps of the exact solve and of each other."""
 import numpy as np
 import pytest
