@@ -31,6 +31,7 @@
 //   metric_solve.h   A^-1 g: cyclic reduction, dense, Toeplitz scans, semiseparable scans; metric_solve
 //   limit_rounds.h   the joint-limit rounds by one wavefront (over limit_regs.h: the register forms); limit_rounds_call*
 //   band.h           A T + B: band_row, smooth_grad, band_gradient_pass, band_cost_pass
+//   sdf_cell_lookup.h   the field lookup in cell units of the two cost passes with one lookup per lane
 //   cost_gs16.h, cost_pairs.h, self_mfma.h, cost_generic.h      the cost phase by the robot's number of active spheres
 //   fk.h             forward kinematics of a tile's waypoints
 //   tsr.h            the hard constraints (over tsr_point.h, tsr_form.h), behind Env and the convergence state
@@ -68,6 +69,7 @@ constexpr int GS16_U = 1;
 constexpr int PRIO_FK = 3, PRIO_COST = 0, PRIO_UPDATE = 3;
 constexpr int PRIO_COST_LAST = 2;      // the last round of a tile: it is what the tile's barrier waits for
 
+#include "sdf_cell_lookup.h"
 #include "cost_gs16.h"
 #include "cost_pairs.h"
 #include "self_mfma.h"

@@ -437,7 +437,7 @@ __device__ __forceinline__ void cost_tile_generic(const BT & b, const ModelView<
                else
                {
                   // two waypoints per wavefront: suffix inside the 16-lane rows, then the upper row of each half
-                  v += dpp_move<0x101>(v); v += dpp_move<0x102>(v); v += dpp_move<0x104>(v); v += dpp_move<0x108>(v);
+                  v = row_suffix_incl(v);
                   const real t16 = read_lane(v, 16), t48 = read_lane(v, 48);
                   const int ln = tid & 63;
                   v += (ln < 16) ? t16 : ((ln >= 32 && ln < 48) ? t48 : (real)0);

@@ -351,11 +351,7 @@ __device__ __forceinline__ void cost_tile_pairs(const BT & b, const ModelView<re
 #pragma unroll
             for (int k=0; k<6; k++)
             {
-               real v = w6[k];
-               v += dpp_move<0x101>(v);       // row_shl:1  (lane i takes lane i+1, 0 past the row)
-               v += dpp_move<0x102>(v);       // row_shl:2
-               v += dpp_move<0x104>(v);       // row_shl:4
-               v += dpp_move<0x108>(v);       // row_shl:8
+               real v = row_suffix_incl(w6[k]);
                const real t16 = read_lane(v, 16), t48 = read_lane(v, 48);
                v += lower ? ((ln < 32) ? t16 : t48) : (real)0;
                w6[k] = v;                     // sum over the spheres s .. GSL-1 of this waypoint

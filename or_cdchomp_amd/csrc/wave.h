@@ -142,13 +142,20 @@ __device__ __forceinline__ real wave_prefix_incl(real v)
    add += (row >= 3) ? t2 : (real)0;
    return v + add;
 }
+// (the suffix sums inside the 16-lane rows alone: lane i ends with the sum over the lanes i .. 15 of its row)
+template <typename real>
+__device__ __forceinline__ real row_suffix_incl(real v)
+{
+   v += dpp_move<0x101>(v);      // row_shl:1 (lane i takes lane i+1, 0 past the row)
+   v += dpp_move<0x102>(v);      // row_shl:2
+   v += dpp_move<0x104>(v);      // row_shl:4
+   v += dpp_move<0x108>(v);      // row_shl:8
+   return v;
+}
 template <typename real>
 __device__ __forceinline__ real wave_suffix_incl(real v)
 {
-   v += dpp_move<0x101>(v);      // row_shl:1 (lane i takes lane i+1, 0 past the row)
-   v += dpp_move<0x102>(v);
-   v += dpp_move<0x104>(v);
-   v += dpp_move<0x108>(v);
+   v = row_suffix_incl(v);
    const real t1 = read_lane(v, 16), t2 = read_lane(v, 32), t3 = read_lane(v, 48);
    const int row = (threadIdx.x & 63) >> 4;
    real add = (row <= 2) ? t3 : (real)0;
