@@ -563,6 +563,44 @@ int orc_batch_config_clearance(orc_module * mod, int batch_id, int n_q, const in
    const double * configs /* [n_q][n] */, double * clearance_out /* [n_q][2] */, int * sphere_out, int * other_out /* [n_q][2] each */);
 int orc_batch_waypoint_clearance(orc_module * mod, int batch_id, int n_q, const int * run_of_q, const int * point_of_q,
    double * clearance_out, int * sphere_out, int * other_out);
+/* The clearance of given paths and of segments between waypoints, on the device: what orc_batch_clearance reports for a run
+ * that holds the path as its trajectory, for paths that are no run's.  Query q returns clearance, time, sphere, other and
+ * n_samples of that hypothetical run BIT FOR BIT, the run living in a batch with the same robot, held bodies, live mask, pair
+ * tables and self-check setting, the same precision and velocity limits, and the scene of run run_of_q[q] (NULL: run 0 for
+ * every query).  The batch's own n_points plays no part.
+ * orc_batch_path_clearance uploads paths [n_q][n_rows][n], rows as orc_batch_set_traj takes them and narrowed to float for a
+ * precision-32 batch as it narrows them; n_rows lies in [2, 4096].  Two rows are a segment: its answer is that of a 3-point run
+ * holding [a, b, b], which has the same samples.  orc_batch_waypoint_segment_clearance takes the segment from
+ * T[run_of_q[q]][from_of_q[q]] to T[run_of_q[q]][to_of_q[q]] of the device's trajectories and uploads the three index arrays
+ * only; from > to is the reverse direction, from == to has no sample; it returns what orc_batch_path_clearance returns for
+ * those two rows, bit for bit.
+ * Retiming and samples are orc_batch_clearance's (verdict_samples of or_cdchomp_amd/module.py: a sample every 0.04 of C-space
+ * length, the clock advanced by repeated addition while time < duration).  THE END ROW IS NOT A SAMPLE, exactly as the goal of a
+ * run is not: ask orc_batch_config_clearance about it.  The too-long rule is orc_batch_clearance's with this call's max_samples
+ * (in [1, 2^20]; `clearance_too_long` of module.py): such a query reports NaN, time -1, -1 / -1 and n_samples -2, AND THE CALL
+ * SUCCEEDS.  A path of zero length has no sample: +inf, time -1, -1 / -1, n_samples 0.  Non-finite entries are decided by the
+ * same rules as they stand: a NaN entry leaves one sample (or none) whose NaN gaps are never a minimum -- the spheres the entry
+ * does not move still count --, an infinite entry makes the query too long; no memory is indexed by a value derived from one.
+ * Outputs as orc_batch_clearance's with n_q in place of n_runs; clearance_out and n_samples_out required, the others may be
+ * NULL.
+ * The samples of all queries are packed: a workgroup walks 64 consecutive samples of the call (fewer for a robot whose rows do
+ * not fit the LDS), whichever queries they belong to, so short segments share chunks.  They lie in a workspace of 2^21
+ * samples (96 MiB at most, allocated at the size a call needs and freed at its end); a call with more is cut into rounds of
+ * consecutive queries by the host.  A query's answer depends on its rows and its run only: not on its place in the list, on
+ * n_q, on what shares a chunk with it, on the shard or on the rounds (a sample is reduced by one wavefront with shuffles, a
+ * query by one wavefront over its samples in order; no atomic, ties to the lowest key as in orc_batch_clearance).  The calls
+ * leave no state and are ordered on the shards' streams like orc_batch_clearance; the host waits once in their middle for the
+ * sample counts.  Several devices: every shard takes the queries whose run it owns; a list may interleave shards freely.
+ * Rejected with a nonzero return and a message before any device work, the batch unchanged and the module usable: an unknown
+ * batch; n_q < 1 or n_q > 2^22; n_rows < 2 or n_rows > 4096; paths, clearance_out or n_samples_out NULL; max_samples outside
+ * [1, 2^20]; a run_of_q entry outside [0, n_runs); from_of_q or to_of_q NULL, or an entry of theirs outside [0, n_points). */
+int orc_batch_path_clearance(orc_module * mod, int batch_id, int n_q, const int * run_of_q /* NULL: run 0 */,
+   int n_rows, const double * paths /* [n_q][n_rows][n] */, int max_samples,
+   double * clearance_out /* [n_q][2] */, double * time_out /* [n_q][2] */,
+   int * sphere_out, int * other_out /* [n_q][2] each */, int * n_samples_out /* [n_q] */);
+int orc_batch_waypoint_segment_clearance(orc_module * mod, int batch_id, int n_q, const int * run_of_q,
+   const int * from_of_q, const int * to_of_q, int max_samples,
+   double * clearance_out, double * time_out, int * sphere_out, int * other_out, int * n_samples_out);
 /* Which way is out: the penetration cost of single configurations and its gradient, on the device.  The queries, their rows,
  * runs and waypoints are those of the two clearance calls above, and so are the rules for n_q, run_of_q, point_of_q and configs.
  * With gap the quantity those calls take the minimum of, per query:

@@ -105,6 +105,10 @@ SYMBOLS = [
                                       c_int_p]),
     ("orc_batch_config_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, c_double_p, c_int_p, c_int_p]),
     ("orc_batch_waypoint_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_double_p, c_int_p, c_int_p]),
+    ("orc_batch_path_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, C.c_int, c_double_p, C.c_int, c_double_p, c_double_p,
+                                           c_int_p, c_int_p, c_int_p]),
+    ("orc_batch_waypoint_segment_clearance", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_int_p, C.c_int, c_double_p,
+                                                       c_double_p, c_int_p, c_int_p, c_int_p]),
     ("orc_batch_config_penetration", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_double_p, C.c_double, C.c_double, c_double_p, c_double_p,
                                                c_double_p, c_int_p, c_int_p]),
     ("orc_batch_waypoint_penetration", C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, C.c_double, C.c_double, c_double_p, c_double_p,

@@ -155,6 +155,12 @@ public:
    void config_clearance(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
                          double * clear_out, unsigned int * key_out);
    int config_chunk() const;                 // the queries a workgroup of that kernel takes: the walk's rule for `chunk` with this kernel's LDS
+   // (path_clearance.cpp) the clearance of n_q paths against the scenes of this shard's runs (path_kernels.hip): paths
+   // [n_q][n_rows][n] with run_of_q [n_q] (LOCAL runs, NULL: run 0); or paths NULL and n_rows 2, the segments between the
+   // waypoints from_of_q and to_of_q [n_q] of the device's trajectories.  What of clear, time, key [n_q][2] (path_device.h) and
+   // n_samples [n_q] is not NULL comes back; nothing is kept on the device
+   void path_clearance(const VerdictInputs & in, int n_q, const int * run_of_q, const int * from_of_q, const int * to_of_q, int n_rows,
+                       const double * paths, int max_samples, double * clear_out, double * time_out, unsigned long long * key_out, int * n_samples_out);
    // (penetration.cpp) the penetration cost and its gradient of the same queries (penetration_kernels.hip), with the two minima
    // and keys of config_clearance; nothing is kept on the device
    void config_penetration(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
@@ -207,6 +213,8 @@ private:
       double * time_out, unsigned long long * key_out, int * n_samples_out);
    template <typename real> void config_clearance_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q,
       const double * configs, double * clear_out, unsigned int * key_out);
+   template <typename real> void path_clearance_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * from_of_q, const int * to_of_q,
+      int n_rows, const double * paths, int max_samples, double * clear_out, double * time_out, unsigned long long * key_out, int * n_samples_out);
    template <typename real> void config_penetration_typed(const VerdictInputs & in, int n_q, const int * run_of_q, const int * point_of_q,
       const double * configs, double margin_field, double margin_self, const PenetrationOut & out);
    // what a launch of penetration_kernel needs beside its queries and outputs: the walk's tables (verdict_walk_args) and the
@@ -316,6 +324,15 @@ public:
    void config_clearance_check(bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs) const;
    void config_clearance(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q,
                          const double * configs, double * clear_out, unsigned int * key_out);
+   // (path_clearance.cpp) orc_batch_path_clearance / orc_batch_waypoint_segment_clearance.  path_clearance_check throws for what
+   // those calls reject, before any device work (waypoints: n_rows and paths are not read); `path_clearance`: every shard takes
+   // the queries whose run it owns, in their order, and the results go back to the caller's order; outputs [n_q][2], n_samples
+   // [n_q], or NULL
+   void path_clearance_check(bool waypoints, int n_q, const int * run_of_q, const int * from_of_q, const int * to_of_q, int n_rows,
+                             const double * paths, int max_samples) const;
+   void path_clearance(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * from_of_q, const int * to_of_q,
+                       int n_rows, const double * paths, int max_samples, double * clear_out, double * time_out, unsigned long long * key_out,
+                       int * n_samples_out);
    // (penetration.cpp) orc_batch_config_penetration / orc_batch_waypoint_penetration: the queries dealt by run (the caller has
    // made config_clearance_check and margins_check)
    void config_penetration(const VerdictInputs & in, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q,

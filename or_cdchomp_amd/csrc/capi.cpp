@@ -705,6 +705,28 @@ int orc_batch_waypoint_clearance(orc_module * mod, int id, int n_q, const int * 
    return guarded(mod, [&] { mod->impl->batch_config_clearance(id, true, n_q, run_of_q, point_of_q, nullptr, clearance_out, sphere_out, other_out); });
 }
 
+int orc_batch_path_clearance(orc_module * mod, int id, int n_q, const int * run_of_q, int n_rows, const double * paths, int max_samples,
+   double * clearance_out, double * time_out, int * sphere_out, int * other_out, int * n_samples_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch(id);      // (an unknown batch first)
+      need(clearance_out, "clearance_out"); need(n_samples_out, "n_samples_out");
+      mod->impl->batch_path_clearance(id, false, n_q, run_of_q, nullptr, nullptr, n_rows, paths, max_samples, clearance_out, time_out, sphere_out,
+         other_out, n_samples_out);
+   });
+}
+
+int orc_batch_waypoint_segment_clearance(orc_module * mod, int id, int n_q, const int * run_of_q, const int * from_of_q, const int * to_of_q,
+   int max_samples, double * clearance_out, double * time_out, int * sphere_out, int * other_out, int * n_samples_out)
+{
+   return guarded(mod, [&] {
+      mod->impl->batch(id);      // (an unknown batch first)
+      need(clearance_out, "clearance_out"); need(n_samples_out, "n_samples_out");
+      mod->impl->batch_path_clearance(id, true, n_q, run_of_q, from_of_q, to_of_q, 2, nullptr, max_samples, clearance_out, time_out, sphere_out,
+         other_out, n_samples_out);
+   });
+}
+
 int orc_batch_config_penetration(orc_module * mod, int id, int n_q, const int * run_of_q, const double * configs, double margin_field,
    double margin_self, double * cost_out, double * grad_out, double * clearance_out, int * sphere_out, int * other_out)
 {

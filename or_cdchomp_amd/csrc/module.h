@@ -63,6 +63,11 @@ public:
    // names the run whose scene a query is tested against; outputs [n_q][2], any may be NULL
    void batch_config_clearance(int id, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,
       double * clearance, int * sphere, int * other);
+   // (path_clearance.cpp) orc_batch_path_clearance / orc_batch_waypoint_segment_clearance: what batch_clearance reports for a run
+   // that holds the path, n_q paths that are uploaded (paths [n_q][n_rows][n]) or segments between two waypoints of the device's
+   // trajectories (waypoints: n_rows and paths are not read); outputs [n_q][2] and n_samples [n_q], any may be NULL
+   void batch_path_clearance(int id, bool waypoints, int n_q, const int * run_of_q, const int * from_of_q, const int * to_of_q, int n_rows,
+      const double * paths, int max_samples, double * clearance, double * time, int * sphere, int * other, int * n_samples);
    // (penetration.cpp) orc_batch_config_penetration / orc_batch_waypoint_penetration: the same queries; per query the penetration
    // cost of the two legs at the two margins [n_q][2], its gradient with respect to the row [n_q][n], and the outputs above
    void batch_config_penetration(int id, bool waypoints, int n_q, const int * run_of_q, const int * point_of_q, const double * configs,

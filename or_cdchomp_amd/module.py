@@ -1160,6 +1160,53 @@ class Module:
                                                            None if pq is None else _ip(pq), _dp(clr), _ip(sph), _ip(oth)))
         return dict(clearance=clr, sphere=sph, other=oth)
 
+    def batch_path_clearance(self, bid, paths, runs=None, max_samples=65536):
+        """The clearance of given paths, on the device (orc_batch_path_clearance): per path what batch_clearance reports for
+        a run that holds it as its trajectory, bit for bit, whatever n_points the batch has.  paths [n_q][n_rows][n] (or one
+        path [n_rows][n]), rows as batch_gettraj returns them, n_rows >= 2; [n_q][2][n] are segments.  runs: the run whose
+        scene each is tested against, an int array [n_q], one int for all, or None for run 0.  Returns a dict with the keys
+        of batch_clearance: clearance, time, sphere, other [n_q][2], n_samples [n_q].  The samples are verdict_samples': THE
+        END ROW IS NOT ONE (ask batch_config_clearance about it).  A path of zero length has no sample (+inf, -1, -1 / -1,
+        n_samples 0); one that clearance_too_long(path, vmax, col0, max_samples) marks reports NaN / -1 and n_samples -2."""
+        n_runs, _, n = self.batch_dims(bid)
+        pt = np.ascontiguousarray(paths, dtype=np.float64)
+        if pt.ndim == 2:
+            pt = pt.reshape((1,) + pt.shape)
+        if pt.ndim != 3 or pt.shape[2] != n or pt.shape[0] < 1:
+            raise ValueError("paths is [n_q][n_rows][%d], n_q >= 1" % n)
+        n_q, n_rows = pt.shape[0], pt.shape[1]
+        rq = None
+        if runs is not None:
+            rq = np.asarray(runs)
+            rq = np.full(n_q, int(rq), dtype=np.int32) if rq.ndim == 0 else np.ascontiguousarray(rq, dtype=np.int32).reshape(-1)
+            if rq.size != n_q:
+                raise ValueError("runs has %d entries for %d paths" % (rq.size, n_q))
+        clr = np.zeros((n_q, 2)); tim = np.zeros((n_q, 2))
+        sph = np.zeros((n_q, 2), dtype=np.int32); oth = np.zeros((n_q, 2), dtype=np.int32)
+        cnt = np.zeros(n_q, dtype=np.int32)
+        self._check(self._lib.orc_batch_path_clearance(self._h, bid, n_q, None if rq is None else _ip(rq), n_rows, _dp(pt),
+                                                       int(max_samples), _dp(clr), _dp(tim), _ip(sph), _ip(oth), _ip(cnt)))
+        return dict(clearance=clr, time=tim, sphere=sph, other=oth, n_samples=cnt)
+
+    def batch_waypoint_segment_clearance(self, bid, runs, points_from, points_to, max_samples=65536):
+        """The clearance of the straight segments between waypoints of the batch's trajectories as they stand on the device
+        (orc_batch_waypoint_segment_clearance); nothing is uploaded but indices.  runs, points_from, points_to: int arrays
+        [n_q] (one int stands for all); query q is the segment from T[runs[q]][points_from[q]] to T[runs[q]][points_to[q]],
+        from > to the reverse direction, from == to without a sample.  Returns what batch_path_clearance returns for those
+        two rows, bit for bit."""
+        arrs = [np.asarray(a) for a in (runs, points_from, points_to)]
+        n_q = max([a.size for a in arrs if a.ndim] or [1])
+        arrs = [np.full(n_q, int(a), dtype=np.int32) if a.ndim == 0 else np.ascontiguousarray(a, dtype=np.int32).reshape(-1) for a in arrs]
+        if n_q < 1 or any(a.size != n_q for a in arrs):
+            raise ValueError("runs, points_from and points_to have one entry per segment")
+        rq, fq, tq = arrs
+        clr = np.zeros((n_q, 2)); tim = np.zeros((n_q, 2))
+        sph = np.zeros((n_q, 2), dtype=np.int32); oth = np.zeros((n_q, 2), dtype=np.int32)
+        cnt = np.zeros(n_q, dtype=np.int32)
+        self._check(self._lib.orc_batch_waypoint_segment_clearance(self._h, bid, n_q, _ip(rq), _ip(fq), _ip(tq), int(max_samples),
+                                                                   _dp(clr), _dp(tim), _ip(sph), _ip(oth), _ip(cnt)))
+        return dict(clearance=clr, time=tim, sphere=sph, other=oth, n_samples=cnt)
+
     @staticmethod
     def _margins(margin):
         m = np.asarray(margin, dtype=np.float64).reshape(-1)
